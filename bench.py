@@ -3,15 +3,17 @@
 
 A "step" = one LearnedIndex.search of a whole query batch: MLP forward -> top-n_buckets -> routing -> bucket
 scan -> merge.  The index is resident in HBM before the timed region (it is built once, like the reference's DataFrames).
-EXACTLY K steps are timed twice, each between barrier + synchronize: (i) with the query batches already in HBM and the results left
-there -- `value`, `ms_per_step`, `roofline`, `phases_ms` (`value_loop: "resident"`); (ii) HOST-IN -> HOST-OUT, the reference's own
-boundary: every step takes its batch from pinned host memory and leaves (dists, ids) in pinned host memory, the
-upload of batch i+1 and the MLP of batch i+1 overlap the search of batch i (learnedmetricindex_amd/pipeline.py) -- the PCIe-inclusive
-rate, reported beside it as `host_to_host` (`--value-loop host` makes it `value`, as rounds 1-4 did).
+EXACTLY K steps are timed, between barrier + synchronize, in one of two loops: (i) with the query batches already in HBM and the
+results left there -- `value`, `ms_per_step`, `roofline`, `phases_ms` (`value_loop: "resident"`); (ii) HOST-IN -> HOST-OUT, the
+reference's own boundary: every step takes its batch from pinned host memory and leaves (dists, ids) in pinned
+host memory, the upload of batch i+1 and the MLP of batch i+1 overlap the search of batch i (learnedmetricindex_amd/pipeline.py) -- the
+PCIe-inclusive rate (`--value-loop host` makes it `value`, as rounds 1-4 did).  A plain run times only the loop `value` comes from
+and prints the line; `--full` also times the other loop (`host_to_host`), measures recall, runs the CPU baselines and oracle checks
+and the other legs (hard, all-f32, C1, C5, notebook).  `--dump-outputs DIR` writes what the last timed step returned.
 Default workload = BASELINE.json configs[1]: 10M x 768 synthetic unit-norm vectors (LAION-10M shape),
 120 leaves, MLP-4 (768->512->120), top-4 buckets, 10k queries, 1 x MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: the index is bucket-sharded over the ranks (each rank ingests only the rows it owns), every rank
@@ -45,6 +47,25 @@ CHUNK = 1 << 19  # rows generated / ingested per piece
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, dists, ids, seed):
+    """--dump-outputs: the (dists, ids) the last timed step returned, as DIR/dists.npy (float32) and DIR/ids.npy (float64: ids are
+    exact).  Past DUMP_MAX_BYTES a fixed, seeded sample of query rows is written instead, its row numbers in DIR/rows.npy."""
+    dists, ids = np.asarray(dists, dtype=np.float32), np.asarray(ids).astype(np.float64)
+    arrays = {"dists": dists, "ids": ids}
+    row_bytes = dists[:1].nbytes + ids[:1].nbytes
+    if row_bytes * dists.shape[0] > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)   # (4 KB: the .npy headers)
+        rows = np.sort(np.random.RandomState(seed).choice(dists.shape[0], keep, replace=False))
+        arrays = {"dists": dists[rows], "ids": ids[rows], "rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"[bench] outputs of the last timed step -> {out_dir}: " + ", ".join(f"{n} {a.shape}" for n, a in arrays.items()))
 
 
 def lib_provenance() -> dict:
@@ -108,7 +129,9 @@ class Workload:
             cent = xtr[torch.randperm(ntr, device=dev)[:L]].clone()
             for _ in range(10):  # Lloyd iterations (faiss/sklearn k-means stand-in; offline build step)
                 lab = (xtr @ cent.T).argmax(1)
-                cent = torch.zeros_like(cent).index_add_(0, lab, xtr)
+                # (index_put_ with accumulate sums in a fixed order on the GPU; index_add_'s atomics would make the centres -- and so
+                # the MLP, the index and the answers -- differ from run to run)
+                cent = torch.zeros_like(cent).index_put_((lab,), xtr, accumulate=True)
                 cent = torch.nn.functional.normalize(cent, dim=1)
             lab = (xtr @ cent.T).argmax(1)
             net.train(xtr, lab, epochs=args.epochs)
@@ -168,9 +191,9 @@ class Workload:
                 f"min/median/max = {sizes.min()}/{int(np.median(sizes))}/{sizes.max()}, empty={int((sizes == 0).sum())}")
 
     # ------------------------------------------------------------------------------------------------
-    def run(self, steps, warmup, shard_inference=True, measure_resident=True):
-        """Times `steps` host-in -> host-out searches (pipelined) and, optionally (main() picks `value` from these), as many device-resident ones.
-        Returns a dict of raw measurements."""
+    def run(self, steps, warmup, shard_inference=True, measure_resident=True, measure_host=True):
+        """Times `steps` host-in -> host-out searches (pipelined) and/or as many device-resident ones (main() picks `value` from one
+        of the two; a plain run times only that one).  Returns a dict of raw measurements."""
         import torch
         import torch.distributed as dist
 
@@ -207,57 +230,58 @@ class Workload:
         # the one the checks below (oracle, recall) look at and the last one submitted.
         nrot = max(1, self.args.rotate_batches)
         rot = [self.queries] + [self.gen_rows(7, 100 + i, nq) for i in range(nrot - 1)]
-        q_hosts = [t.cpu().pin_memory() for t in rot]
-        q_host = q_hosts[0]
-        ov = os.environ.get("LMI_PIPE_OVERLAP", "1")
-        pipe = HostPipeline(eng, nq, d, d, nb, k, depth=int(os.environ.get("LMI_PIPE_DEPTH", "2")), same_queries=True,
-                            # (the bucket order is the bench's own need -- roofline, oracle check -- not part of the reference's search() result: on
-                            # one GPU it is fetched from the slot's device buffer AFTER the timed region, not downloaded with every batch)
-                            want_bucket_order=world > 1,
-                            overlap_inference=(ov == "1") if world == 1 else os.environ.get("LMI_PIPE_OVERLAP_SHARDED", "0") == "1",
-                            two_handles=ov == "2", sharded=searcher if world > 1 else None,
-                            use_graph=world == 1 and os.environ.get("LMI_PIPE_GRAPH", "0") == "1",
-                            direct_out=world == 1 and os.environ.get("LMI_PIPE_DIRECT", "1") == "1")   # (dists, ids) stored straight into the pinned host buffers
-        for qh in q_hosts:   # LMI_PIPE_GRAPH=1: hipGraph replay (opt-in: measured SLOWER than eager submission on ROCm 7.2 -- C1 0.27 against 0.22 ms
-            pipe.capture(qh)  # per batch: two graph launches cost more than the dozen eager ones); the graphs are built here, untimed
-        # (world > 1: the rank's MLP slice of batch i+1 beside the scan of batch i is opt-in -- it could only be rehearsed with
-        # gloo on one card, where it was slower; on a single GPU the same overlap is measured: -1.9 %)
-        for i in range(warmup):
-            pipe.submit(q_hosts[(i + 1) % nrot])
-        pipe.drain()
-        sync_all()
-        eng.timings_reset()
-        stamps = []
         # no garbage collection inside the timed region: a collection that finalises an earlier leg's device tensors ends in hipFree, which
         # synchronises the device (seen as one 30-ms step in a tenth of the multi-leg runs' hard legs: 6.1 -> 8.7-10.3 ms per step over 10 steps)
         import gc
-        gc.collect()
-        gc_was = gc.isenabled()
-        gc.disable()
-        t0 = time.perf_counter()
-        for i in range(steps):
-            ticket = pipe.submit(q_hosts[(steps - 1 - i) % nrot])   # ... the last step submits batch 0
-            stamps.append(time.perf_counter() - t0)
-        pipe.drain()
-        sync_all()
-        elapsed = time.perf_counter() - t0
-        if gc_was:
-            gc.enable()
-        if os.environ.get("LMI_BENCH_DEBUG") and rank == 0:
-            log(f"[bench:{self.tag}] submit returned at (ms): {[round(v * 1e3, 2) for v in stamps]}; end {elapsed * 1e3:.2f}")
-        # device clock stamps (or, at --timing-level 3, hipEvents) on the kernels' own stream around every phase of every step; read
-        # once, after the timed region (the handle keeps the newest 128 sets), so the loop itself has no host synchronisation
-        phases, n_timed = eng.timings_mean()
-        calls = searcher.calls_per_search * pipe.calls_per_batch
-        phases = phases * calls
-        out_d, out_i = (a.copy() for a in pipe.result(ticket))
-        bo = pipe.bucket_order(ticket).copy()
-        tm = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        if world > 1:
-            dist.all_reduce(tm, op=dist.ReduceOp.MAX)
-        coll = searcher.collective_ms() if getattr(searcher, "time_collectives", False) else None
-        res = dict(elapsed=float(tm.item()), elapsed_local=elapsed, phases=phases, n_timed=int(n_timed) // calls, collectives_ms=coll,
-                   out_d=out_d, out_i=out_i, bo=bo, calls=calls, overlapped=bool(pipe.overlap or pipe.sh_overlap))
+        res = {}
+        if measure_host:
+            q_hosts = [t.cpu().pin_memory() for t in rot]
+            ov = os.environ.get("LMI_PIPE_OVERLAP", "1")
+            pipe = HostPipeline(eng, nq, d, d, nb, k, depth=int(os.environ.get("LMI_PIPE_DEPTH", "2")), same_queries=True,
+                                # (the bucket order is the bench's own need -- roofline, oracle check -- not part of the reference's search() result: on
+                                # one GPU it is fetched from the slot's device buffer AFTER the timed region, not downloaded with every batch)
+                                want_bucket_order=world > 1,
+                                overlap_inference=(ov == "1") if world == 1 else os.environ.get("LMI_PIPE_OVERLAP_SHARDED", "0") == "1",
+                                two_handles=ov == "2", sharded=searcher if world > 1 else None,
+                                use_graph=world == 1 and os.environ.get("LMI_PIPE_GRAPH", "0") == "1",
+                                direct_out=world == 1 and os.environ.get("LMI_PIPE_DIRECT", "1") == "1")   # (dists, ids) stored straight into the pinned host buffers
+            for qh in q_hosts:   # LMI_PIPE_GRAPH=1: hipGraph replay (opt-in: measured SLOWER than eager submission on ROCm 7.2 -- C1 0.27 against 0.22 ms
+                pipe.capture(qh)  # per batch: two graph launches cost more than the dozen eager ones); the graphs are built here, untimed
+            # (world > 1: the rank's MLP slice of batch i+1 beside the scan of batch i is opt-in -- it could only be rehearsed with
+            # gloo on one card, where it was slower; on a single GPU the same overlap is measured: -1.9 %)
+            for i in range(warmup):
+                pipe.submit(q_hosts[(i + 1) % nrot])
+            pipe.drain()
+            sync_all()
+            eng.timings_reset()
+            stamps = []
+            gc.collect()
+            gc_was = gc.isenabled()
+            gc.disable()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                ticket = pipe.submit(q_hosts[(steps - 1 - i) % nrot])   # ... the last step submits batch 0
+                stamps.append(time.perf_counter() - t0)
+            pipe.drain()
+            sync_all()
+            elapsed = time.perf_counter() - t0
+            if gc_was:
+                gc.enable()
+            if os.environ.get("LMI_BENCH_DEBUG") and rank == 0:
+                log(f"[bench:{self.tag}] submit returned at (ms): {[round(v * 1e3, 2) for v in stamps]}; end {elapsed * 1e3:.2f}")
+            # device clock stamps (or, at --timing-level 3, hipEvents) on the kernels' own stream around every phase of every step; read
+            # once, after the timed region (the handle keeps the newest 128 sets), so the loop itself has no host synchronisation
+            phases, n_timed = eng.timings_mean()
+            calls = searcher.calls_per_search * pipe.calls_per_batch
+            phases = phases * calls
+            out_d, out_i = (a.copy() for a in pipe.result(ticket))
+            bo = pipe.bucket_order(ticket).copy()
+            tm = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            if world > 1:
+                dist.all_reduce(tm, op=dist.ReduceOp.MAX)
+            coll = searcher.collective_ms() if getattr(searcher, "time_collectives", False) else None
+            res = dict(elapsed=float(tm.item()), elapsed_local=elapsed, phases=phases, n_timed=int(n_timed) // calls, collectives_ms=coll,
+                       out_d=out_d, out_i=out_i, bo=bo, calls=calls, overlapped=bool(pipe.overlap or pipe.sh_overlap))
         if measure_resident:
             eng.set_stream(torch.cuda.current_stream().cuda_stream)
             q = self.queries
@@ -270,7 +294,7 @@ class Workload:
             t0 = time.perf_counter()
             for i in range(steps):
                 qi = rot[(steps - 1 - i) % nrot]
-                rd, ri, _ = searcher.search(qi, qi, nb, k)
+                rd, ri, rbo = searcher.search(qi, qi, nb, k)
             sync_all()
             # phases of the SEQUENTIAL loop: in the pipelined one the next batch's MLP runs on a stream of its own, its
             # events span the time it waits for CUs
@@ -283,8 +307,14 @@ class Workload:
                 dist.all_reduce(tr, op=dist.ReduceOp.MAX)
             res["resident_elapsed"] = float(tr.item())
             res["collectives_ms_resident"] = searcher.collective_ms() if getattr(searcher, "time_collectives", False) else None
-            assert np.array_equal(ri.cpu().numpy().view(np.uint32), out_i), "resident and host-boundary results differ"
-            if self.args.timing_level == 2:
+            # what the last step returned (batch 0), copied before any later search reuses the searcher's output buffers
+            res["resident_out"] = (rd.cpu().numpy(), ri.cpu().numpy().view(np.uint32), rbo.cpu().numpy())
+            if "out_i" in res:
+                assert np.array_equal(res["resident_out"][1], res["out_i"]), "resident and host-boundary results differ"
+            else:
+                res.update(out_d=res["resident_out"][0], out_i=res["resident_out"][1], bo=res["resident_out"][2],
+                           calls=searcher.calls_per_search, overlapped=False)
+            if self.args.timing_level == 2 and self.args.full:
                 # cross-check of the device stamps: the same phases from hipEvents recorded between the kernels (timing level 3: each
                 # event is a ~5 us bubble, so this loop is slower than the timed one and not part of it)
                 eng.set_timing(3)
@@ -874,7 +904,16 @@ def main():
     ap.add_argument("--traffic-json", default=None,
                     help="PMC-derived HBM bytes per scan launch (default: profiles/scan_pmc_<config>.json, "
                          "written by profiles/summarize.py from separate rocprofv3 --pmc passes of this bench)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the other of the two timed loops, the hipEvent cross-check of the phases, recall, "
+                         "the CPU baselines and oracle checks, the hard / all-f32 / C1 / C5 / notebook legs and, at N > 1, the other collective "
+                         "layout (each still subject to its --no-* switch).  Without it the run times only the loop `value` comes from")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned -- DIR/dists.npy (float32) and DIR/ids.npy "
+                         "(float64), [nq, k'] each -- for comparing two builds output for output")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_recall = args.no_hard_leg = args.no_other_configs = args.no_exact_leg = True
     cfg = dict(CONFIGS[args.config])
     for key in ("n", "nq", "nb", "leaves", "d"):
         if getattr(args, key) is not None:
@@ -915,16 +954,19 @@ def main():
         wl = Workload(args, cfg, dev, rank, world, local_rank, sigma=args.hard_sigma, zipf=args.hard_zipf, centre_scale=args.hard_centre_scale, tag="hard")
     else:
         wl = Workload(args, cfg, dev, rank, world, local_rank, tag=os.environ.get("LMI_BENCH_TAG", "main"))   # (developer aid: another data seed)
-    res = wl.run(args.steps, args.warmup, shard_inference=True)
+    res = wl.run(args.steps, args.warmup, shard_inference=True, measure_host=args.full or args.value_loop == "host",
+                 measure_resident=args.full or args.value_loop == "resident")
     # `value` is the rate with the inputs already in HBM when the timed region starts (the PCIe-inclusive host-in -> host-out rate is
     # reported beside it, never as `value`): the step's time, phases and the dominant kernel's duration all come from that SAME loop
-    host_loop = {"elapsed": res["elapsed"], "elapsed_local": res["elapsed_local"], "phases": res["phases"], "n_timed": res["n_timed"],
-                 "overlapped": res.get("overlapped")}
+    host_loop = None if "elapsed" not in res else {"elapsed": res["elapsed"], "elapsed_local": res["elapsed_local"], "phases": res["phases"],
+                                                   "n_timed": res["n_timed"], "overlapped": res.get("overlapped")}
     value_loop = "resident" if (args.value_loop == "resident" and "resident_elapsed" in res) else "host"
     if value_loop == "resident":
         res = dict(res, elapsed=res["resident_elapsed"], elapsed_local=res["resident_elapsed_local"], phases=res["phases_resident"],
                    n_timed=res.get("n_timed_resident", args.steps), collectives_ms=res.get("collectives_ms_resident"))
     elapsed, phases, out_d, out_i, bo = res["elapsed"], res["phases"], res["out_d"], res["out_i"], res["bo"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *(res["resident_out"][:2] if value_loop == "resident" else (out_d, out_i)), seed=args.seed)
     flops, pairs, items = res["scan_stats"]
     pf_active, pf_survivors, pf_fallbacks = res["pf_stats"]
     sizes, owner = wl.sizes, wl.owner
@@ -938,7 +980,7 @@ def main():
                      m=np.bincount(bo_h, minlength=L))
     # N > 1: the other collective layout (every rank routes the whole batch: ONE all-gather, as north_star words it)
     alt = None
-    if world > 1 and not wl.replica:
+    if world > 1 and not wl.replica and args.full:
         r2 = wl.run(args.steps, args.warmup, shard_inference=False, measure_resident=False)
         assert np.array_equal(r2["out_i"], out_i), "the two sharded modes disagree"
         alt = {"mode": "replicated MLP on every rank, ONE all-gather (per-rank top-k)",
@@ -1163,7 +1205,7 @@ def main():
             "value_loop": value_loop,
             "boundary": ("`value` / `ms_per_step` / `roofline` / `phases_ms`: the query batches are in HBM when the timed region starts and the "
                          "results stay in HBM (one lmi_search per batch on one stream, MLP included, nothing overlapped between batches); "
-                         "`host_to_host` is the PCIe-inclusive rate of the same steps (pinned host buffers in and out, pipelined)"
+                         "`host_to_host` (--full) is the PCIe-inclusive rate of the same steps (pinned host buffers in and out, pipelined)"
                          if value_loop == "resident" else
                          "host-in -> host-out: every step uploads its query batch from pinned host memory and downloads "
                          "(dists, ids) to pinned host memory; transfers of neighbouring batches overlap the search"
@@ -1187,10 +1229,11 @@ def main():
             "resident": resident,
             # the PCIe-inclusive rate: every step uploads its batch from pinned host memory and stores (dists, ids) into pinned host memory;
             # uploads / downloads of neighbouring batches and the next batch's MLP (a stream of its own) overlap the search
-            "host_to_host": {"value": round(nq * args.steps / host_loop["elapsed"], 2), "unit": "queries/s",
-                             "ms_per_step": round(host_loop["elapsed"] / args.steps * 1e3, 4),
-                             "dominant_kernel_ms": round(float(host_loop["phases"][_capi.T_SCAN if args.exact else _capi.T_PF_EMIT]), 4),
-                             "mlp_of_next_batch_overlapped": bool(host_loop["overlapped"])},
+            "host_to_host": None if host_loop is None else {
+                "value": round(nq * args.steps / host_loop["elapsed"], 2), "unit": "queries/s",
+                "ms_per_step": round(host_loop["elapsed"] / args.steps * 1e3, 4),
+                "dominant_kernel_ms": round(float(host_loop["phases"][_capi.T_SCAN if args.exact else _capi.T_PF_EMIT]), 4),
+                "mlp_of_next_batch_overlapped": bool(host_loop["overlapped"])},
             "sharded_alt_mode": alt,
             "rccl_ranks_seen": None if up is None else up["rccl_ranks_seen"],
             "rccl_version": None if up is None else up["rccl_version"],
@@ -1225,7 +1268,7 @@ def main():
             out.update(extra)
             return out
         legs = {"c2": leg(result["value"], result["ms_per_step"], roof, cpu is not None, recall=result["recall_at_10"])}
-        if value_loop == "resident":   # `value`: inputs and results in HBM; beside it the PCIe-inclusive host -> host rate of the same steps
+        if value_loop == "resident" and result["host_to_host"]:   # `value`: inputs and results in HBM; beside it the PCIe-inclusive host -> host rate
             legs["c2"]["host_to_host_qps"] = round(result["host_to_host"]["value"])
         elif isinstance(result.get("resident"), dict):
             legs["c2"]["hbm_resident_qps"] = round(result["resident"]["value"])

@@ -6,7 +6,7 @@ out="$1"; R="$2"; shift 2
 mkdir -p "$(dirname "$out")"; : > "$out"
 for r in $(seq 1 "$R"); do
   for lib in "$@"; do
-    LMI_LIB="$PWD/$lib" timeout -k 10 240 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-recall --no-other-configs ${BENCH_AB_FLAGS:-} 2> /tmp/bench_ab.err | python3 -c "
+    LMI_LIB="$PWD/$lib" timeout -k 10 240 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-recall --no-other-configs ${BENCH_AB_FLAGS:-} 2> /tmp/bench_ab.err | python3 -c "
 import sys, json
 for ln in sys.stdin:
     ln = ln.strip()

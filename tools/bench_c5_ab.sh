@@ -5,7 +5,7 @@ out="$1"; R="$2"; shift 2
 mkdir -p "$(dirname "$out")"; : > "$out"
 for r in $(seq 1 "$R"); do
   for lib in "$@"; do
-    LMI_LIB="$PWD/$lib" timeout -k 10 200 python3 bench.py --config c5 --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_AB_FLAGS:-} 2>/dev/null | python3 -c "
+    LMI_LIB="$PWD/$lib" timeout -k 10 200 python3 bench.py --full --config c5 --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_AB_FLAGS:-} 2>/dev/null | python3 -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

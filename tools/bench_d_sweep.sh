@@ -5,7 +5,7 @@ set -uo pipefail
 out="$1"; cfg="$2"; n="$3"; ds="$4"; shift 4
 mkdir -p "$(dirname "$out")"; : > "$out"
 for D in $ds; do
-  timeout -k 10 300 python3 bench.py --config "$cfg" --n "$n" --d "$D" --steps 10 --warmup 2 --no-cpu-baseline --no-recall --no-hard-leg --no-exact-leg --no-other-configs "$@" 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --config "$cfg" --n "$n" --d "$D" --steps 10 --warmup 2 --no-cpu-baseline --no-recall --no-hard-leg --no-exact-leg --no-other-configs "$@" 2>/dev/null | python3 -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -6,7 +6,7 @@ out="$1"; R="$2"; shift 2
 mkdir -p "$(dirname "$out")"; : > "$out"
 for r in $(seq 1 "$R"); do
   for lib in "$@"; do
-    LMI_LIB="$PWD/$lib" timeout -k 10 400 python3 bench.py --no-cpu-baseline --no-exact-leg --no-recall 2>/dev/null | python3 -c "
+    LMI_LIB="$PWD/$lib" timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --no-exact-leg --no-recall 2>/dev/null | python3 -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

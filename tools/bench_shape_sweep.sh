@@ -6,7 +6,7 @@ out="$1"; shapes="$2"; shift 2
 mkdir -p "$(dirname "$out")"; : > "$out"
 for sh in $shapes; do
   IFS=: read -r n d leaves nb nq <<< "$sh"
-  timeout -k 10 300 python3 bench.py --config c2 --n "$n" --d "$d" --leaves "$leaves" --nb "$nb" --nq "$nq" --steps 10 --warmup 2 --no-cpu-baseline --no-recall --no-hard-leg --no-exact-leg --no-other-configs "$@" 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --config c2 --n "$n" --d "$d" --leaves "$leaves" --nb "$nb" --nq "$nq" --steps 10 --warmup 2 --no-cpu-baseline --no-recall --no-hard-leg --no-exact-leg --no-other-configs "$@" 2>/dev/null | python3 -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

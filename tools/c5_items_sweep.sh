@@ -2,7 +2,7 @@
 # Developer aid (GPU box): pass 2's item lengths at 10M x 45 (bench.py --config c5).  run NAME [VAR=value ...]
 run() {
   name=$1; shift
-  env "$@" timeout -k 10 200 python3 bench.py --config c5 --steps 60 --warmup 10 --no-cpu-baseline --no-recall --no-hard-leg --no-other-configs --no-exact-leg 2>/dev/null | python3 -c "
+  env "$@" timeout -k 10 200 python3 bench.py --full --config c5 --steps 60 --warmup 10 --no-cpu-baseline --no-recall --no-hard-leg --no-other-configs --no-exact-leg 2>/dev/null | python3 -c "
 import json,sys;j=json.loads(sys.stdin.read().strip().splitlines()[-1]);p=j['phases_ms'];print('$name','step',j['ms_per_step'],'p1',p['pf_sample'],'p2',p['pf_emit'],'tail',p['rescore'])"
 }
 run off LMI_P2_GRADED=0 &&

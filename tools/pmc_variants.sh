@@ -5,7 +5,7 @@ set -uo pipefail
 export TMPDIR=/tmp
 out="$1"; shift
 mkdir -p "$out"
-B="python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-recall"
+B="python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-recall"
 K="pass2_kernel<false"
 for lib in "$@"; do
   tag=$(basename "$lib" .so)

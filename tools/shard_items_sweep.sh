@@ -2,7 +2,7 @@
 # Developer aid (GPU box): pass 2's item lengths on an emulated 1/8 shard (bench.py --emulate-shard).  run NAME SHARD [VAR=value ...]
 run() {
   name=$1; sh=$2; shift 2
-  env "$@" timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --emulate-shard $sh/8 --no-cpu-baseline --no-recall --no-hard-leg 2> gpurun_out/shs_$name.err | python3 -c "
+  env "$@" timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --emulate-shard $sh/8 --no-cpu-baseline --no-recall --no-hard-leg 2> "${TMPDIR:-/tmp}/shs_$name.err" | python3 -c "
 import json,sys;j=json.loads(sys.stdin.read().strip().splitlines()[-1]);p=j['phases_ms'];print('$name shard $sh','step',j['ms_per_step'],'resident',j['resident']['ms_per_step'],'p1',p['pf_sample'],'p2',p['pf_emit'],'tail',p['rescore'])"
 }
 for sh in 0 7; do

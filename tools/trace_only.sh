@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 tag="$1"; shift
 root="$PWD"; out="$root/gpurun_out/trace_$tag"
 mkdir -p "$out"
-B="python3 $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-recall --no-hard-leg $*"
+B="python3 $root/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-recall --no-hard-leg $*"
 cd /tmp
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- $B > "$out/bench.json" 2> "$out/trace.err" || { echo "trace pass failed"; tail -5 "$out/trace.err"; exit 1; }
 cd "$root"

@@ -8,7 +8,7 @@ root="$PWD"; out="$root/gpurun_out/steps_$tag"
 mkdir -p "$out"
 for spec in "$@"; do
   set -- $spec; cfg="$1"; lvl="$2"
-  B="python3 $root/bench.py --config $cfg --steps 12 --warmup 3 --timing-level $lvl --no-cpu-baseline --no-recall --no-hard-leg --no-other-configs --no-exact-leg"
+  B="python3 $root/bench.py --full --config $cfg --steps 12 --warmup 3 --timing-level $lvl --no-cpu-baseline --no-recall --no-hard-leg --no-other-configs --no-exact-leg"
   d="$out/${cfg}_t${lvl}"
   (cd /tmp && timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d "$d" -- $B > "$d.json" 2> "$d.err") || { echo "trace $spec failed"; tail -5 "$d.err"; exit 1; }
   python3 tools/trace_gaps.py "$d" > "$out/${cfg}_t${lvl}_timeline.txt" 2>&1 || true
