@@ -136,7 +136,7 @@ LMI_API int lmi_set_metric(lmi_index *h, int metric);
  *        L < 2^20 (any fan-out the reference's n_categories can name in practice, e.g. [100, 100]).
  * add_rows: rows [nrows][d] are the original objects row0 .. row0+nrows-1 (any order of calls, each
  *        object exactly once); they are scattered to their bucket-contiguous position on device.
- * end:   finishes the build; the index is immutable afterwards. */
+ * end:   finishes the build.  The built index can then be changed in place by lmi_buckets_insert / lmi_buckets_delete. */
 LMI_API int lmi_buckets_begin(lmi_index *h, int64_t N, int d, int L, const int64_t *labels,
                       const uint32_t *ids, const uint8_t *owned);
 LMI_API int lmi_buckets_add_rows(lmi_index *h, const float *rows, int64_t row0, int64_t nrows, int on_device);
@@ -147,6 +147,21 @@ LMI_API int lmi_buckets_add_rows(lmi_index *h, const float *rows, int64_t row0, 
 LMI_API int lmi_buckets_add_owned_rows(lmi_index *h, const float *rows, const int64_t *index, int64_t nrows,
                                int on_device);
 LMI_API int lmi_buckets_end(lmi_index *h);
+/* Mutation of a built index (no reference counterpart: the reference rebuilds).  rows [nrows][d] (host, or device with
+ * on_device), labels [nrows] bucket ids in [0, L) (host), ids [nrows] (host; NULL -> an error, ids are the caller's).
+ * Objects of buckets this handle does not own (lmi_buckets_begin's `owned`) are skipped; *n_stored (nullable) <- stored.
+ * Each inserted object goes after the last object of its bucket. */
+LMI_API int lmi_buckets_insert(lmi_index *h, const float *rows, const int64_t *labels, const uint32_t *ids, int64_t nrows,
+                               int on_device, int64_t *n_stored);
+/* Removes every object whose id is in ids[n] (host); the survivors keep their order.  *n_removed (nullable) <- removed
+ * (ids not present are not an error).
+ * Both calls: searches then return exactly what a fresh lmi_buckets_begin / add_rows / end of the equivalent object list
+ * returns (the survivors in the order the index held them, then the inserted objects in call order).  They synchronise
+ * the handle's stream first (a search enqueued before reads the index as it was) and return when the index is updated.
+ * Refused, with the index unchanged, when the index is not built, when a lmi_clone_view of the handle is alive (or the
+ * handle is one), when a label is outside [0, L) or when rows, spare row-blocks and holes would pass the 32-bit positions
+ * of the slab; a slab that must grow is copied into new allocations, so a failed allocation leaves the old index. */
+LMI_API int lmi_buckets_delete(lmi_index *h, const uint32_t *ids, int64_t n, int64_t *n_removed);
 /* sizes[L] <- number of objects per bucket (0 for buckets not owned). */
 LMI_API int lmi_bucket_sizes(lmi_index *h, int64_t *sizes);
 /* Reads one bucket back to the host in bucket order (what `data_search.loc[g.index].to_numpy()`

@@ -46,6 +46,8 @@ SIGNATURES = {
     "lmi_buckets_add_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "lmi_buckets_add_owned_rows": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
     "lmi_buckets_end": (ctypes.c_int, [_vp]),
+    "lmi_buckets_insert": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _i64p]),
+    "lmi_buckets_delete": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _i64p]),
     "lmi_bucket_sizes": (ctypes.c_int, [_vp, _vp]),
     "lmi_mlp_topk": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_mlp_proba": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -323,6 +325,34 @@ class Index:
         for r0 in range(0, data.shape[0], piece):
             self.add_rows(data[r0: r0 + piece], r0)
         self.buckets_end()
+
+    def insert(self, rows, labels, ids) -> int:
+        """Adds objects to the built index (`lmi_buckets_insert`): rows numpy [n,d] float32 (host) or a CUDA torch tensor,
+        labels int64 [n] bucket ids, ids uint32 [n].  Each goes after the last object of its bucket.  Returns how many
+        were stored (objects of buckets this handle does not own are skipped)."""
+        labels = _np(labels, np.int64).reshape(-1)
+        ids_a = _np(ids, np.uint32).reshape(-1)
+        if isinstance(rows, np.ndarray):
+            rows = _np(rows, np.float32).reshape(-1, self.d)
+            on_device = 0
+        else:
+            assert rows.is_cuda and rows.is_contiguous() and rows.dtype.is_floating_point and rows.element_size() == 4
+            on_device = 1
+        assert rows.shape[1] == self.d and labels.shape[0] == ids_a.shape[0] == rows.shape[0]
+        out = ctypes.c_int64(0)
+        _check(lib().lmi_buckets_insert(self._h, _ptr(rows), _ptr(labels), _ptr(ids_a), int(rows.shape[0]), on_device,
+                                        ctypes.byref(out)))
+        self.N = getattr(self, "N", 0) + int(rows.shape[0])
+        return out.value
+
+    def delete(self, ids) -> int:
+        """Removes every object whose id is in `ids` (`lmi_buckets_delete`); the others keep their order.  Returns how
+        many were removed (ids not present are not an error)."""
+        ids_a = _np(ids, np.uint32).reshape(-1)
+        out = ctypes.c_int64(0)
+        _check(lib().lmi_buckets_delete(self._h, _ptr(ids_a), int(ids_a.shape[0]), ctypes.byref(out)))
+        self.N = getattr(self, "N", 0) - out.value
+        return out.value
 
     def bucket_sizes(self) -> np.ndarray:
         out = np.zeros(self.L, dtype=np.int64)

@@ -88,14 +88,9 @@ __global__ void make_scale_kernel(const unsigned* __restrict__ maxbits, float* _
 //   K  > 128 (lmi_pass2.h, v_mfma_f32_16x16x32_f16):        H[rb][k/32][r >> 4][lane = 16 ((k >> 3) & 3) + (r & 15)][k & 7]  (16 rows x 32 k)
 // (r = row in its 32-row block.)  Either way a row-block's fragments of 32 consecutive k are 2 KiB side by side.
 // One thread per (slab row p, k16-group, half).
-__global__ void convert16_kernel(const float* __restrict__ rows, int d, int pitch, long long n_rows, int KG16,
-                                 const float* __restrict__ scale, uint4* __restrict__ dst, int f16x16 /* 1: the K > 128 shape */) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n_rows * KG16 * 2) return;
-    const int hh = (int)(idx & 1);
-    const int g = (int)((idx >> 1) % KG16);
-    const long long p = (idx >> 1) / KG16;
-    const float s = scale[0];
+// one (slab row p, k16-group g, half hh) of convert16_kernel (also lmi_mutate.h's range-list form)
+__device__ __forceinline__ void convert16_one(const float* __restrict__ rows, int d, int pitch, long long p, int g, int hh, int KG16,
+                                              float s, uint4* __restrict__ dst, int f16x16) {
     const float* x = rows + p * pitch;
     half8 h;
 #pragma unroll
@@ -111,11 +106,30 @@ __global__ void convert16_kernel(const float* __restrict__ rows, int d, int pitc
         dst[((size_t)(p >> 5) * KG16 + g) * 64 + hh * 32 + r] = *reinterpret_cast<uint4*>(&h);
     }
 }
+__global__ void convert16_kernel(const float* __restrict__ rows, int d, int pitch, long long n_rows, int KG16,
+                                 const float* __restrict__ scale, uint4* __restrict__ dst, int f16x16 /* 1: the K > 128 shape */) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_rows * KG16 * 2) return;
+    convert16_one(rows, d, pitch, (idx >> 1) / KG16, (int)((idx >> 1) % KG16), (int)(idx & 1), KG16, scale[0], dst, f16x16);
+}
 
 // Rounding-up factor of a binary32 norm: a sum of d non-negative squares accumulated in ANY order errs by at
 // most d 2^-24 relative, its square root by half that (+ one rounding); the factor covers twice the bound for
 // every d (a fixed 1.0002 only did up to d ~ 6 000).
 __device__ __forceinline__ float norm_guard(int d) { return 1.0001f + (float)d * 5.96046448e-8f; }
+
+// one row of bucket_norm_kernel (also lmi_mutate.h's range-list form): best / bestd <- max(., ||x'|| / ||x^ - x'|| rounded up)
+__device__ __forceinline__ void row_norms(const float* __restrict__ x, int d, float s, float guard, float& best, float& bestd) {
+    float acc = 0.0f, dl = 0.0f;
+    for (int k = 0; k < d; ++k) {
+        const float xs = x[k] * s;
+        const float e = (float)(_Float16)xs - xs;
+        acc += xs * xs;
+        dl += e * e;
+    }
+    best = fmaxf(best, sqrtf(acc) * guard);
+    bestd = fmaxf(bestd, sqrtf(dl) * guard);
+}
 
 // per-bucket max of the scaled row norm ||x'|| and of the norm of the row's fp16 rounding error
 // ||x^ - x'|| (x' = x * scale exactly, x^ = the _Float16 image convert16_kernel stores; the difference of
@@ -129,16 +143,7 @@ __global__ void bucket_norm_kernel(const float* __restrict__ rows, int d, int pi
     const float guard = norm_guard(d);
     float best = 0.0f, bestd = 0.0f;
     for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n_b; row += gridDim.x * blockDim.x) {
-        const float* x = rows + ((size_t)rb_start[b] * 32 + row) * pitch;
-        float acc = 0.0f, dl = 0.0f;
-        for (int k = 0; k < d; ++k) {
-            const float xs = x[k] * s;
-            const float e = (float)(_Float16)xs - xs;
-            acc += xs * xs;
-            dl += e * e;
-        }
-        best = fmaxf(best, sqrtf(acc) * guard);
-        bestd = fmaxf(bestd, sqrtf(dl) * guard);
+        row_norms(rows + ((size_t)rb_start[b] * 32 + row) * pitch, d, s, guard, best, bestd);
     }
     if (best > 0.0f) atomicMax(bnorm_bits + b, __float_as_uint(best));
     if (bestd > 0.0f) atomicMax(bdelta_bits + b, __float_as_uint(bestd));

@@ -255,6 +255,69 @@ class LearnedIndex(Logger):
                                  time.time())
 
     # ------------------------------------------------------------------------------------------
+    def insert(self, data_navigation_new: pd.DataFrame, data_search_new: Optional[pd.DataFrame] = None,
+               ids=None) -> npt.NDArray[np.int64]:
+        """Adds objects to the HBM-resident index (an extension: the reference rebuilds).  Each object is placed the way
+        `LearnedIndexBuilder.build` places it -- argmax of the root model, then argmax of each internal node's model down the
+        tree, through the HIP MLP -- and goes after the last object of its bucket (`lmi_buckets_insert`).  `data_search_new`
+        (default: `data_navigation_new`) holds the scan vectors, `ids` (default: `data_navigation_new.index`) the labels.
+        Returns the objects' `data_prediction` rows (int64 [n, n_levels]) for the caller to append to their own frames.
+        A multi-level placement onto a leaf path that holds no bucket would need a new bucket: the whole call is refused
+        with ValueError before anything changes.  Afterwards `search_resident` answers from the mutated index; `search`
+        keeps answering from the frames it is given (they no longer match the resident copy, which it rebuilds)."""
+        eng = self._resident("insert")
+        nav = data_navigation_new
+        srch = nav if data_search_new is None else data_search_new
+        labels = nav.index.to_numpy() if ids is None else np.asarray(ids).reshape(-1)
+        assert labels.shape[0] == nav.shape[0], "one id per object"
+        assert labels.min(initial=0) >= 0 and labels.max(initial=0) < 2 ** 32, "ids must fit uint32"
+        x_nav = np.ascontiguousarray(nav[_feature_columns(nav)].to_numpy(dtype=np.float32))
+        n_levels = 1 if self._path_ids is None else len(next(iter(self._path_ids)))
+        dp = np.full((nav.shape[0], n_levels), EMPTY_VALUE, dtype=np.int64)
+        if nav.shape[0]:
+            dp[:, 0] = self.root_model.predict(x_nav)
+        for level in range(1, n_levels):   # every node's objects by its own model (LearnedIndexBuilder.build)
+            prefixes, which = np.unique(dp[:, :level], axis=0, return_inverse=True)
+            which = np.asarray(which).reshape(-1)
+            for j, prefix in enumerate(prefixes):
+                net = self.internal_models.get(tuple(int(v) for v in prefix) + (EMPTY_VALUE,) * (n_levels - level))
+                if net is not None and (prefix != EMPTY_VALUE).all():
+                    sel = np.flatnonzero(which == j)
+                    dp[sel, level] = net.predict(x_nav[sel])
+        if n_levels == 1:
+            bucket_of = dp[:, 0]
+        else:
+            bucket_of = np.asarray([self._path_ids.get(tuple(int(v) for v in p), -1) for p in dp], dtype=np.int64)
+            missing = int((bucket_of < 0).sum())
+            if missing:
+                raise ValueError(f"{missing} of {dp.shape[0]} object(s) fall on a leaf path that holds no bucket; creating buckets "
+                                 "is not supported (rebuild the index): nothing was inserted")
+        cols = _feature_columns(srch)
+        frame = srch if srch.index.equals(nav.index) else srch.loc[nav.index]
+        rows = np.ascontiguousarray(frame[cols].to_numpy(dtype=np.float32))
+        eng.insert(rows, bucket_of, labels.astype(np.uint32))
+        self._engine_key = self._mutated_key()
+        return dp
+
+    def delete(self, ids) -> int:
+        """Removes every object whose id (DataFrame index label) is in `ids` from the HBM-resident index (an extension;
+        `lmi_buckets_delete`); the others keep their order.  Returns how many were removed.  Afterwards `search_resident`
+        answers from the mutated index; `search` keeps answering from the frames it is given."""
+        eng = self._resident("delete")
+        n = eng.delete(np.asarray(ids).reshape(-1).astype(np.uint32))
+        self._engine_key = self._mutated_key()
+        return n
+
+    def _resident(self, what: str):
+        assert self._engine is not None, f"{what}: no resident index: call prepare()/search() or index_io.load_index()"
+        return self._engine
+
+    @staticmethod
+    def _mutated_key():
+        """An `_engine_key` no `prepare` key equals: the resident index no longer holds what any frames it was built from
+        hold, so a later `search(frames)` must not be answered from it."""
+        return ("mutated", object())
+
     def search(
         self,
         data_navigation: pd.DataFrame,

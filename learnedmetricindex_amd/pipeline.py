@@ -38,6 +38,10 @@ _STREAMS: dict = {}   # device index -> the four streams every pipeline of this 
 
 
 class HostPipeline:
+    """With `two_handles` the pipeline holds a clone view of the index (`lmi_clone_view`): `lmi_buckets_insert` /
+    `lmi_buckets_delete` (`Index.insert` / `Index.delete`, `LearnedIndex.insert` / `.delete`) are refused while it lives.
+    Call `close()` before mutating the index."""
+
     def __init__(self, index, nq: int, d_nav: int, d_search: int, nb: int, k: int = 10, depth: int = 2,
                  device: Optional[int] = None, same_queries: bool = False, want_bucket_order: bool = False,
                  search_fn=None, overlap_inference: bool = True, two_handles: bool = False, sharded=None, use_graph: bool = False,
@@ -281,6 +285,16 @@ class HostPipeline:
             return s["bo_h"].numpy()
         assert self.search_fn is None and self.sharded is None, "bucket order on demand: single-GPU forms only (pass want_bucket_order=True)"
         return s["bo_d"].cpu().numpy()
+
+    def close(self) -> None:
+        """Waits for the batches in flight and destroys the clone view of `two_handles` (the index itself stays open)."""
+        self.drain()
+        for h, _ in self.handles[1:]:
+            h.close()
+            views = getattr(self.index, "_views", [])
+            if h in views:
+                views.remove(h)
+        self.handles = self.handles[:1]
 
     def drain(self) -> None:
         for s in self.slots:
