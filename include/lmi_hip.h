@@ -288,6 +288,14 @@ LMI_API int lmi_workspace_bytes(lmi_index *h, int nq, int n_buckets, int64_t *by
 LMI_API int lmi_debug_emit_all(lmi_index *h, int on);
 LMI_API int lmi_debug_read_candidates(lmi_index *h, int64_t slot, int cap, uint32_t *rows, float *shat,
                               int *count, float *eps2, float *qscale, float *xscale);
+/* Test hook for the mutation layout (tests/test_gpu_mutate_fuzz.py; no reference counterpart).  Copies the host tables
+ * of a built index: rb_start[L + 1] (bucket b's first row-block; [L] = the row-blocks the layout spans), cap_rb[L]
+ * (row-blocks reserved per bucket), n_rb_total, alloc_rb (row-blocks every allocation of the slab holds) and counters[4]:
+ * buckets that took inserted rows in their slack, buckets relocated behind the last row-block, re-packs that grew the
+ * allocations and re-packs whose layout fit the allocations they replaced (forced by holes), summed over the handle's
+ * lmi_buckets_insert calls.  Any pointer may be NULL.  Launches nothing and reads no device memory. */
+LMI_API int lmi_debug_layout(lmi_index *h, int32_t *rb_start, int32_t *cap_rb, int64_t *n_rb_total, int64_t *alloc_rb,
+                             int64_t *counters);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,7 @@ SIGNATURES = {
     "lmi_debug_emit_all": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_debug_read_candidates": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp,
                                                  ctypes.POINTER(ctypes.c_int), _f32p, _f32p, _f32p]),
+    "lmi_debug_layout": (ctypes.c_int, [_vp, _vp, _vp, _i64p, _i64p, _vp]),
 }
 
 
@@ -211,6 +212,17 @@ class Index:
                                                ctypes.byref(e2), ctypes.byref(qs), ctypes.byref(xs)))
         n = max(0, min(cnt.value, cap))
         return rows[:n], shat[:n], cnt.value, e2.value, qs.value, xs.value
+
+    def debug_layout(self) -> dict:
+        """Test hook (`lmi_debug_layout`, host tables only): rb_start i32[L+1], cap_rb i32[L], n_rb_total, alloc_rb and
+        counters i64[4] = (slack fills, relocations, growth re-packs, hole re-packs) of this handle's inserts."""
+        rb_start = np.empty(self.L + 1, dtype=np.int32)
+        cap_rb = np.empty(self.L, dtype=np.int32)
+        counters = np.empty(4, dtype=np.int64)
+        n_rb, alloc = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(lib().lmi_debug_layout(self._h, _ptr(rb_start), _ptr(cap_rb), ctypes.byref(n_rb), ctypes.byref(alloc),
+                                      _ptr(counters)))
+        return dict(rb_start=rb_start, cap_rb=cap_rb, n_rb_total=n_rb.value, alloc_rb=alloc.value, counters=counters)
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(lib().lmi_set_stream(self._h, _vp(stream_ptr)))

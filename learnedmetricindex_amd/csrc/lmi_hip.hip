@@ -203,6 +203,7 @@ struct lmi_index {
     std::vector<unsigned char> h_any;    // per bucket: holds rows on some rank (n_nonempty)
     lmi_index* parent = nullptr;         // a clone view: the handle whose memory it borrows
     int live_clones = 0;                 // clone views of this handle that are alive (a mutation is refused while any is)
+    int64_t mut_paths[4] = {0, 0, 0, 0}; // lmi_debug_layout: buckets filled in their slack, buckets relocated, growth re-packs, hole re-packs
     DevBuf mut_pos, mut_ids, mut_list, mut_keep, mut_src, mut_stage, mut_word;
 };
 
@@ -983,6 +984,14 @@ extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const
         for (int b = 0; b < L; ++b) { start[b] = (int)std::min<int64_t>(total, INT32_MAX); total += cap[b]; }
         alloc_new = std::min(total + total / 8, max_slab_rb(h));
     }
+    // which layout path ran (lmi_debug_layout).  A re-pack whose packed layout fits the allocations it replaces was forced by the
+    // holes, not by the rows: with 1/8 headroom, holes never pass a quarter of the slab before the tail reaches the allocation's end
+    int64_t paths[4] = {0, 0, 0, 0};
+    if (pack) {
+        paths[total > have ? 2 : 3] = 1;
+    } else {
+        for (int b = 0; b < L; ++b) paths[moved[b] ? 1 : 0] += add[b] > 0;
+    }
     if (total > max_slab_rb(h))
         return fail("lmi_buckets_insert: %lld row-blocks of rows, spare row-blocks and holes exceed the 32-bit positions of the slab", (long long)total);
     CHK(set_dev(h));
@@ -1090,6 +1099,7 @@ extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 4; ++i) h->mut_paths[i] += paths[i];
     if (n_stored) *n_stored = stored;
     return 0;
 }
@@ -2687,6 +2697,19 @@ extern "C" LMI_API int lmi_search_tree(lmi_index* h, const float* queries_nav, c
 extern "C" LMI_API int lmi_debug_emit_all(lmi_index* h, int on) {
     if (!h) return fail("lmi_debug_emit_all: NULL handle");
     h->debug_emit_all = on != 0;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_debug_layout(lmi_index* h, int32_t* rb_start, int32_t* cap_rb, int64_t* n_rb_total, int64_t* alloc,
+                                        int64_t* counters) {
+    if (!h) return fail("lmi_debug_layout: NULL handle");
+    if (!h->built) return fail("lmi_debug_layout: the bucket index is not built (lmi_buckets_end has not run)");
+    const int L = h->L;
+    if (rb_start) std::copy(h->h_rb_start.begin(), h->h_rb_start.begin() + L + 1, rb_start);
+    if (cap_rb) std::copy(h->h_cap_rb.begin(), h->h_cap_rb.end(), cap_rb);
+    if (n_rb_total) *n_rb_total = h->n_rb_total;
+    if (alloc) *alloc = alloc_rb(h);
+    if (counters) std::copy(h->mut_paths, h->mut_paths + 4, counters);
     return 0;
 }
 

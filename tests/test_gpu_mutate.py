@@ -382,3 +382,224 @@ def test_li_insert_two_levels(oracle):
     after = li3.search_resident(Qn, Qs, ncat, nb, k)
     assert np.array_equal(before[1], after[1]) and np.array_equal(before[0], after[0])
     li3.close()
+
+
+# ---- directed edges the random sequences of test_gpu_mutate_fuzz.py cannot afford or might not reach ------------------------
+@pytest.mark.parametrize("prefilter", [True, False])
+def test_delete_in_several_staging_groups(capi, oracle, prefilter):
+    """d = 9000: a delete stages the hit buckets' rows in groups of ~1 GiB (29 826 rows of 36 kB); three buckets of ~11 500
+    rows need two groups in both modes."""
+    rng = np.random.default_rng(47)
+    L, d, per = 3, 9000, 11_500
+    X = rng.standard_normal((L * per, d), dtype=np.float32)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    lab = rng.permutation(np.repeat(np.arange(L), per))
+    ids = np.arange(1, X.shape[0] + 1, dtype=np.uint32)
+    layers = mlp(np.random.RandomState(47), d, L)
+    Q = X[rng.choice(X.shape[0], 16, replace=False)] + 0.1 * rng.standard_normal((16, d), dtype=np.float32)
+    m = Mirror(X, lab, ids)
+    idx = fresh(capi, layers, m, L, prefilter=prefilter)
+    gone = np.concatenate([ids[rng.random(ids.size) < 0.05], ids[lab == 1][-40:]])
+    assert idx.delete(gone) == m.delete(gone)
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10)], prefilter=prefilter)
+    idx.close()
+
+
+def test_chunk_rows_grow_past_1024_chunks(capi, oracle):
+    """chunk_rows = 256 and 270 000 rows inserted into one bucket: it passes 1 024 chunks, so the chunk length grows."""
+    rs = np.random.RandomState(53)
+    L, N, d = 4, 4000, 8
+    X = dataset(rs, N + 270_000, d)
+    lab = np.r_[rs.randint(0, L, N), np.full(270_000, 2)]
+    ids = np.arange(1, X.shape[0] + 1, dtype=np.uint32)
+    layers = mlp(rs, d, L)
+    Q = dataset(rs, 64, d)
+    m = Mirror(X[:N], lab[:N], ids[:N])
+    idx = capi.Index(0, chunk_rows=256)
+    idx.set_mlp(layers)
+    idx.set_buckets(m.X, m.lab, L, ids=m.ids)
+    assert idx.insert(X[N:], lab[N:], ids[N:]) == 270_000
+    m.insert(X[N:], lab[N:], ids[N:])
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (2, 10), (4, 20)])
+    idx.close()
+
+
+@pytest.mark.parametrize("prefilter", [True, False])
+def test_more_than_65535_buckets(capi, oracle, prefilter):
+    """L = 70 000: the build's per-bucket maxima, the delete's marking and the range lists of an insert and of a delete that
+    touch every bucket each cover more buckets than a grid's y dimension of 65 535."""
+    rs = np.random.RandomState(59)
+    L, N, d = 70_000, 160_000, 32
+    X = dataset(rs, N + L, d)
+    lab = np.r_[rs.randint(0, L, N), rs.permutation(L)]
+    ids = np.arange(1, X.shape[0] + 1, dtype=np.uint32)
+    layers = mlp(rs, d, L)
+    Q = dataset(rs, 32, d)
+    m = Mirror(X[:N], lab[:N], ids[:N])
+    idx = fresh(capi, layers, m, L, prefilter=prefilter)
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10)], prefilter=prefilter)
+    assert idx.insert(X[N:], lab[N:], ids[N:]) == L      # one row into every bucket
+    m.insert(X[N:], lab[N:], ids[N:])
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10)], prefilter=prefilter)
+    gone = ids[N:]                                        # ... and out of every bucket again, with some of the build's rows
+    gone = np.r_[gone, ids[:N:7]]
+    assert idx.delete(gone) == m.delete(gone)
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10)], prefilter=prefilter)
+    idx.close()
+
+
+@pytest.mark.parametrize("prefilter", [True, False])
+def test_device_insert_l2(capi, oracle, prefilter):
+    """Rows inserted from a CUDA tensor under L2 (the norm column is added on the device)."""
+    rs = np.random.RandomState(61)
+    L, N, d = 6, 3000, 100
+    X = dataset(rs, N, d) * rs.uniform(0.2, 3.0, (N, 1)).astype(np.float32)
+    lab = rs.randint(0, L, N)
+    ids = np.arange(1, N + 1, dtype=np.uint32)
+    layers = mlp(rs, d, L)
+    Q = dataset(rs, 64, d)
+    m = Mirror(X[:2000], lab[:2000], ids[:2000])
+    idx = fresh(capi, layers, m, L, metric="l2", prefilter=prefilter)
+    dev = torch.device("cuda", 0)
+    for s in (slice(2000, 2050), slice(2050, 3000)):   # the second one relocates or re-packs
+        lb = np.where(np.arange(s.stop - s.start) % 2 == 0, 4, lab[s])
+        assert idx.insert(torch.from_numpy(X[s]).to(dev), lb, ids[s]) == s.stop - s.start
+        m.insert(X[s], lb, ids[s])
+    for b in range(L):
+        rows, bid = idx.read_bucket(b)
+        np.testing.assert_array_equal(rows, m.X[m.lab == b])
+        np.testing.assert_array_equal(bid, m.ids[m.lab == b])
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10), (6, 20)], metric="l2", prefilter=prefilter)
+    idx.close()
+
+
+def test_delete_everything_then_insert(capi, oracle):
+    rs = np.random.RandomState(67)
+    L, N, d = 5, 2000, 64
+    X = dataset(rs, N, d)
+    lab = rs.randint(0, L, N)
+    ids = np.arange(1, N + 1, dtype=np.uint32)
+    layers = mlp(rs, d, L)
+    Q = dataset(rs, 32, d)
+    m = Mirror(X[:1200], lab[:1200], ids[:1200])
+    idx = fresh(capi, layers, m, L)
+    assert idx.delete(ids) == 1200 == m.delete(ids)
+    assert idx.bucket_sizes().sum() == 0
+    assert idx.delete(ids) == 0
+    for nb, k in ((1, 10), (3, 10)):   # an index of no objects: the oracle's empty answer (inf, id 0)
+        d1, i1, _ = idx.search(Q, Q, nb, k)
+        do, no, _ = oracle.search(layers, Q, m.X, Q, m.lab, nb, k, ids=m.ids, nthreads=8)
+        assert np.array_equal(i1, no) and np.array_equal(d1.astype(np.float64), do), (nb, k)
+    small = X[1200:] * np.float32(0.25)   # rows below the old scale's range: the scale stays, the answers must not care
+    assert idx.insert(small, lab[1200:], ids[1200:]) == N - 1200
+    m.insert(small, lab[1200:], ids[1200:])
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10), (5, 20)])
+    idx.close()
+
+
+def test_rank_that_stores_no_row(capi, oracle):
+    """Two ranks; an insert that lands only in rank 0's buckets stores nothing on rank 1 (its early return)."""
+    rs = np.random.RandomState(71)
+    L, N, d, world = 6, 3000, 48, 2
+    X = dataset(rs, N, d)
+    lab = rs.randint(0, L, N)
+    ids = np.arange(1, N + 1, dtype=np.uint32)
+    layers = mlp(rs, d, L)
+    Q = dataset(rs, 64, d)
+    m = Mirror(X[:2000], lab[:2000], ids[:2000])
+    owned = [(np.arange(L) % world == r).astype(np.uint8) for r in range(world)]
+    ranks = []
+    for r in range(world):
+        h = capi.Index(0)
+        h.set_mlp(layers)
+        h.set_buckets(m.X, m.lab, L, ids=m.ids, owned=owned[r])
+        ranks.append(h)
+    lb = np.where(lab[2000:] % 2 == 0, lab[2000:], 0)   # rank 0's buckets only
+    assert [h.insert(X[2000:], lb, ids[2000:]) for h in ranks] == [N - 2000, 0]
+    m.insert(X[2000:], lb, ids[2000:])
+    gone = ids[::5]
+    assert sum(h.delete(gone) for h in ranks) == m.delete(gone)
+    ref = fresh(capi, layers, m, L)
+    for nb, k in ((1, 10), (3, 10), (6, 20)):
+        outs = [h.search(Q, Q, nb, k, want_keys=True) for h in ranks]
+        kout = outs[0][0].shape[1]
+        gd = np.ascontiguousarray(np.stack([o[0] for o in outs]))
+        gi = np.ascontiguousarray(np.stack([o[1] for o in outs]))
+        gk = np.ascontiguousarray(np.stack([o[3] for o in outs]))
+        hd = np.empty((Q.shape[0], kout), np.float32)
+        hi = np.empty((Q.shape[0], kout), np.uint32)
+        ranks[0].merge_gathered(gd, gi, gk, world, Q.shape[0], kout, hd, hi)
+        d2, i2, _ = ref.search(Q, Q, nb, k)
+        assert np.array_equal(hi, i2) and np.array_equal(hd, d2), (nb, k)
+    for h in ranks + [ref]:
+        h.close()
+
+
+def test_clone_view_after_mutations(capi, oracle):
+    rs = np.random.RandomState(73)
+    L, N, d = 7, 3000, 128
+    X = dataset(rs, N, d)
+    lab = rs.randint(0, L, N)
+    ids = np.arange(1, N + 1, dtype=np.uint32)
+    layers = mlp(rs, d, L)
+    Q = dataset(rs, 64, d)
+    m = Mirror(X[:2000], lab[:2000], ids[:2000])
+    idx = fresh(capi, layers, m, L)
+    idx.insert(X[2000:], np.full(N - 2000, 3), ids[2000:])   # a relocation or re-pack: the view must see the new tables
+    m.insert(X[2000:], np.full(N - 2000, 3), ids[2000:])
+    gone = ids[::3]
+    assert idx.delete(gone) == m.delete(gone)
+    view = idx.clone_view()
+    ref = fresh(capi, layers, m, L)
+    for nb, k in ((1, 10), (3, 10), (7, 20)):
+        d1, i1, _, k1 = view.search(Q, Q, nb, k, want_keys=True)
+        d2, i2, _, k2 = ref.search(Q, Q, nb, k, want_keys=True)
+        assert np.array_equal(i1, i2) and np.array_equal(d1, d2) and np.array_equal(k1, k2), (nb, k)
+    ref.close()
+    view.close()
+    idx._views.remove(view)
+    idx.insert(X[:10] * 0.5, np.arange(10) % L, ids[:10] + 10 * N)   # mutable again once the view is gone
+    m.insert(X[:10] * 0.5, np.arange(10) % L, ids[:10] + 10 * N)
+    assert_same(capi, oracle, idx, layers, m, L, Q, [(1, 10), (3, 10)])
+    idx.close()
+
+
+def test_save_load_mutated_exact_l2(oracle, tmp_path, monkeypatch):
+    """A mutated all-f32 L2 index: read_bucket (the f32 fragments unpacked, no norm column) and save -> load."""
+    from learnedmetricindex_amd import index_io
+    from learnedmetricindex_amd.li.LearnedIndex import LearnedIndex
+
+    monkeypatch.setenv("LMI_PREFILTER", "0")
+    rs = np.random.RandomState(79)
+    L, N, d = 6, 3000, 40
+    X = dataset(rs, N, d) * rs.uniform(0.2, 3.0, (N, 1)).astype(np.float32)
+    layers = mlp(rs, d, L, hidden=128)   # NeuralNetwork's "MLP": in -> 128 -> out
+    Q = dataset(rs, 64, d)
+    li = LearnedIndex(net_from(layers), {}, [(i,) for i in range(L)])
+    nav = frame(X[:2000])
+    dp = oracle.predict(layers, X[:2000]).astype(np.int64).reshape(-1, 1)
+    li.prepare(nav, nav, dp, [L], metric="l2")
+    assert not li._engine.prefilter_stats()[0]
+    new_df = frame(X[2000:], first_id=2001)
+    dp_new = li.insert(new_df)
+    gone = np.r_[np.arange(1, 2001, 4), np.arange(2001, N + 1, 9)]
+    assert li.delete(gone) == gone.size
+    all_df = pd.concat([nav, new_df])
+    all_dp = np.concatenate([dp, dp_new])
+    keep = ~np.isin(all_df.index.to_numpy(), gone)
+    eq_X, eq_dp, eq_ids = all_df.to_numpy(dtype=np.float32)[keep], all_dp[keep], all_df.index.to_numpy()[keep]
+    for b in range(L):
+        rows, bid = li._engine.read_bucket(b)
+        sel = eq_dp[:, 0] == b
+        np.testing.assert_array_equal(rows, eq_X[sel])
+        np.testing.assert_array_equal(bid, eq_ids[sel])
+    d_res, n_res, _ = li.search_resident(Q, Q, [L], 3, 10)
+    do, no, _ = oracle.search(layers, Q, eq_X, Q, eq_dp, 3, 10, ids=eq_ids, nthreads=8, metric="l2")
+    assert np.array_equal(n_res, no) and np.array_equal(d_res, do)
+    index_io.save_index(str(tmp_path / "mut"), li, [L])
+    li2, ncat = index_io.load_index(str(tmp_path / "mut"))
+    assert li2._engine.metric == "l2" and not li2._engine.prefilter_stats()[0]
+    d_l, n_l, _ = li2.search_resident(Q, Q, ncat, 3, 10)
+    assert np.array_equal(n_l, n_res) and np.array_equal(d_l, d_res)
+    li2.close()
+    li.close()
