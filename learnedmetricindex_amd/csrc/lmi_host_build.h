@@ -1,0 +1,261 @@
+// lmi_host_build.h -- building the bucket index (lmi_buckets_begin / add_rows / end), the prefilter's images of the slab, and reading
+// a bucket back.
+#pragma once
+#include "lmi_host.h"
+
+extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, const int64_t* labels,
+                                 const uint32_t* ids, const uint8_t* owned) {
+    if (!h) return fail("lmi_buckets_begin: NULL handle");
+    if (N < 0 || d < 1 || L < 1 || (N > 0 && !labels)) return fail("lmi_buckets_begin: bad arguments");
+    if (N >= (1ll << 31) - 64ll * L) return fail("lmi_buckets_begin: N too large for 32-bit positions");
+    if (L >= (1 << ROUTE_ID_BITS)) return fail("lmi_buckets_begin: %d buckets, the routing kernels take fewer than %d", L, 1 << ROUTE_ID_BITS);
+    CHK(set_dev(h));
+    h->N = N;
+    h->d_user = d;
+    h->d = h->metric == LMI_METRIC_L2 ? (int)rup(d + 1, 4) : d;  // L2: + the -|x|^2/2 column (sim_to_dist, lmi_kernels.h)
+    d = h->d;
+    h->dp = (int)rup(d, 4);   // floats per row of the row-major f32 copy: 16-byte rows for the streamed re-rank (d = 45: 48, zero-filled)
+    h->L = L;
+    h->KGs = (int)rup(cdiv(d, 8), STAGE_G);
+    h->built = false;
+    h->h_nb_rows.assign(L, 0);
+    std::vector<unsigned char> seen(owned ? L : 0, 0);   // (a sharded rank: which buckets hold rows on ANY rank)
+    for (int64_t i = 0; i < N; ++i) {
+        int64_t b = labels[i];
+        if (b < 0 || b >= L) return fail("lmi_buckets_begin: labels[%lld] = %lld outside [0,%d)", (long long)i, (long long)b, L);
+        if (!owned || owned[b]) h->h_nb_rows[b]++;
+        if (owned) seen[b] = 1;
+    }
+    h->h_rb_start.assign(L + 1, 0);
+    h->h_nch.assign(L, 0);
+    // Chunk rows not set by the caller: small indexes (or small shards) get smaller chunks so that a scan has
+    // many more work items than the 256 blocks that share them (100 000 rows x 1 000 queries: pass 2 0.169 ms
+    // with 2048-row chunks, 0.089 ms with 256; the 1.25M-row shard of an 8-way split that holds the largest
+    // bucket: 0.90 ms with 2048, 0.69 ms with 512); 10M rows keep 2048.
+    // A bucket is scanned in at most 1024 chunks: very large buckets get larger chunks than that.
+    {
+        int max_rows = 0;
+        long long owned_rows = 0;
+        // buckets with rows on any rank: the queries of a batch spread over all of them, whoever owns them
+        int nonempty = 0;
+        for (int b = 0; b < L; ++b) { max_rows = std::max(max_rows, h->h_nb_rows[b]); owned_rows += h->h_nb_rows[b]; nonempty += owned ? seen[b] : h->h_nb_rows[b] > 0; }
+        h->n_nonempty = std::max(1, nonempty);
+        if (h->chunk_rows_auto) {
+            h->chunk_rows = (int)std::min<long long>(2048, std::max<long long>(P2_TILE_ROWS, rup(owned_rows / 4096, P2_TILE_ROWS)));
+            // d <= 128 (lmi_pass2_small.h): a 2048-row item is ~5 us of work there, about what taking it from the queue and
+            // staging its query fragments costs, while 8192-row items are too few to share out evenly (10M x 45, pass 2 at
+            // 1024 / 2048 / 4096 / 8192 rows per item: 0.590 / 0.441 / 0.385 / 0.412 ms): up to 4096
+            if (low_d_form(h, cdiv(d, 16)))
+                h->chunk_rows = (int)std::min<long long>(4096, std::max<long long>(P2_TILE_ROWS, rup(owned_rows / 1024, P2_TILE_ROWS)));
+            // all-f32 scan (scan_kernel: 128-query tiles, so a bucket's chunk is read by several items): the chunk's 4 d-byte rows should
+            // stay in an XCD's 4-MiB L2 until the bucket's last query tile has come by -- 10M x 768: 2 048-row chunks (6 MB) 35.28 ms,
+            // 1 024-row chunks 34.76 (profiles/r05_exact_chunks.txt)
+            if (!h->prefilter)
+                h->chunk_rows = (int)std::max<long long>(P2_TILE_ROWS, std::min<long long>(h->chunk_rows, (3ll << 20) / (4ll * d) / P2_TILE_ROWS * P2_TILE_ROWS));
+        }
+        const int need = (int)rup(cdiv(max_rows, 1024), 256);
+        if (need > h->chunk_rows) h->chunk_rows = need;
+    }
+    const int chunk_rb = h->chunk_rows / 32;
+    for (int b = 0; b < L; ++b) {
+        int nrb = cdiv(h->h_nb_rows[b], 32);
+        h->h_rb_start[b + 1] = h->h_rb_start[b] + nrb;
+        h->h_nch[b] = cdiv(nrb, chunk_rb);
+    }
+    h->n_rb_total = h->h_rb_start[L];
+    h->h_cap_rb.assign(L, 0);
+    h->h_any.assign(L, 0);
+    for (int b = 0; b < L; ++b) {
+        h->h_cap_rb[b] = h->h_rb_start[b + 1] - h->h_rb_start[b];
+        h->h_any[b] = owned ? seen[b] : h->h_nb_rows[b] > 0;
+    }
+    if (owned) h->h_owned.assign(owned, owned + L);
+    else h->h_owned.clear();
+    // bucket-contiguous position of every object (stable: ascending original row inside a bucket,
+    // the order pandas groupby yields) and the id of every slab row
+    std::vector<int> pos((size_t)N);
+    std::vector<uint32_t> ids_slab((size_t)std::max<int64_t>(h->n_rb_total, 1) * 32, 0u);
+    std::vector<int> fill(L, 0);
+    for (int64_t i = 0; i < N; ++i) {
+        int b = (int)labels[i];
+        if (owned && !owned[b]) { pos[i] = -1; continue; }
+        int p = h->h_rb_start[b] * 32 + fill[b]++;
+        pos[i] = p;
+        ids_slab[p] = ids ? ids[i] : (uint32_t)(i + 1);  // search.py:190-191: 1-based labels
+    }
+    const size_t slab_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KGs * 1024;
+    if (h->prefilter) {  // row-major f32 (exact re-rank / fallback / read-back); fp16 fragments at buckets_end
+        const size_t rm_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * 32 * h->dp * 4;
+        h->slab.release();
+        CHK(h->rowmajor.reserve(rm_bytes));
+        HIPCHK(hipMemsetAsync(h->rowmajor.p, 0, rm_bytes, h->stream));
+    } else {             // f32 fragments for the all-f32 scan
+        h->rowmajor.release();
+        h->slab16.release();
+        CHK(h->slab.reserve(slab_bytes));
+        HIPCHK(hipMemsetAsync(h->slab.p, 0, slab_bytes, h->stream));
+    }
+    CHK(h->ids_slab.reserve(ids_slab.size() * 4));
+    HIPCHK(hipMemcpy(h->ids_slab.p, ids_slab.data(), ids_slab.size() * 4, hipMemcpyHostToDevice));
+    CHK(h->pos.reserve(std::max<size_t>(pos.size(), 1) * 4));
+    if (N) HIPCHK(hipMemcpy(h->pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    CHK(h->d_nb_rows.reserve(L * 4));
+    CHK(h->d_rb_start.reserve((L + 1) * 4));
+    CHK(h->d_nch.reserve(L * 4));
+    HIPCHK(hipMemcpy(h->d_nb_rows.p, h->h_nb_rows.data(), L * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_rb_start.p, h->h_rb_start.data(), (L + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_nch.p, h->h_nch.data(), L * 4, hipMemcpyHostToDevice));
+    h->rows_added = 0;
+    h->indexed_ingest = false;
+    h->owned_total = 0;
+    for (int b = 0; b < L; ++b) h->owned_total += h->h_nb_rows[b];
+    h->building = true;
+    return 0;
+}
+
+// rows [nrows][d] are objects row0.. (index == NULL) or objects index[0..nrows) (host or device like `rows`)
+// pos: slab row of every object (-1: not stored), n_total: its length (lmi_buckets_insert passes the batch's)
+static int add_rows_impl(lmi_index* h, const float* rows, int64_t row0, const int64_t* index, int64_t nrows, int on_device,
+                         const int* pos, int64_t n_total) {
+    CHK(set_dev(h));
+    const int64_t piece = std::max<int64_t>(1, (256ll << 20) / ((int64_t)h->d * 4));
+    for (int64_t off = 0; off < nrows; off += piece) {
+        const int64_t n = std::min(piece, nrows - off);
+        const float* src = rows + off * h->d_user;
+        const long long* idx = index ? reinterpret_cast<const long long*>(index + off) : nullptr;
+        if (!on_device) {
+            const size_t row_bytes = (size_t)n * h->d_user * 4;
+            CHK(h->stage.reserve(row_bytes + (index ? (size_t)n * 8 : 0)));
+            HIPCHK(hipMemcpyAsync(h->stage.p, src, row_bytes, hipMemcpyHostToDevice, h->stream));
+            src = h->stage.as<float>();
+            if (index) {
+                HIPCHK(hipMemcpyAsync(h->stage.as<char>() + row_bytes, index + off, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+                idx = reinterpret_cast<const long long*>(h->stage.as<char>() + row_bytes);
+            }
+        }
+        if (h->metric == LMI_METRIC_L2) {  // the piece with its norm column, then ingested like any d-column piece
+            CHK(h->aug_rows.reserve((size_t)n * h->d * 4));
+            augment_copy_kernel<<<cdiv((long long)n * h->d, 256), 256, 0, h->stream>>>(src, h->d_user, h->d, n, h->aug_rows.as<float>());
+            HIPCHK(hipGetLastError());
+            augment_norm_kernel<<<cdiv(n, 256), 256, 0, h->stream>>>(src, h->d_user, h->d, n, h->aug_rows.as<float>(), nullptr);
+            HIPCHK(hipGetLastError());
+            src = h->aug_rows.as<float>();
+        }
+        if (h->prefilter) {
+            long long total = (long long)n * h->d;
+            scatter_rows_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
+                                                                        h->rowmajor.as<float>(), h->dp);
+        } else {
+            long long total = (long long)n * h->KGs;
+            pack_scatter_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
+                                                                        h->KGs, h->slab.as<float4>());
+        }
+        HIPCHK(hipGetLastError());
+        if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+extern "C" LMI_API int lmi_buckets_add_rows(lmi_index* h, const float* rows, int64_t row0, int64_t nrows, int on_device) {
+    if (!h || !h->building) return fail("lmi_buckets_add_rows: call lmi_buckets_begin first");
+    if (h->indexed_ingest) return fail("lmi_buckets_add_rows: this build already uses lmi_buckets_add_owned_rows");
+    if (row0 < 0 || nrows < 0 || row0 + nrows > h->N) return fail("lmi_buckets_add_rows: rows [%lld,%lld) outside [0,%lld)", (long long)row0, (long long)(row0 + nrows), (long long)h->N);
+    if (nrows == 0) return 0;
+    CHK(add_rows_impl(h, rows, row0, nullptr, nrows, on_device, h->pos.as<int>(), h->N));
+    h->rows_added += nrows;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_buckets_add_owned_rows(lmi_index* h, const float* rows, const int64_t* index, int64_t nrows,
+                                          int on_device) {
+    if (!h || !h->building) return fail("lmi_buckets_add_owned_rows: call lmi_buckets_begin first");
+    if (h->rows_added > 0 && !h->indexed_ingest) return fail("lmi_buckets_add_owned_rows: this build already uses lmi_buckets_add_rows");
+    if (nrows < 0 || (nrows > 0 && (!rows || !index))) return fail("lmi_buckets_add_owned_rows: bad arguments");
+    if (!on_device)
+        for (int64_t i = 0; i < nrows; ++i)
+            if (index[i] < 0 || index[i] >= h->N) return fail("lmi_buckets_add_owned_rows: index[%lld] = %lld outside [0,%lld)", (long long)i, (long long)index[i], (long long)h->N);
+    h->indexed_ingest = true;
+    if (nrows == 0) return 0;
+    CHK(add_rows_impl(h, rows, 0, index, nrows, on_device, h->pos.as<int>(), h->N));
+    h->rows_added += nrows;
+    return 0;
+}
+
+// The prefilter's images of the whole slab: one power-of-two scale from the absmax of every stored value (holes and spare
+// row-blocks hold zeros), the fp16 fragments and every bucket's norm maxima.  lmi_buckets_end, and lmi_buckets_insert when
+// new rows break max|x'| < 1 under the current scale.
+static int prefilter_images(lmi_index* h) {
+    // fp16 copy of the slab for the prefilter: one power-of-two scale for the whole index
+    // (pass2_kernel's stages hold two k16-groups; the low-dimensional form has no stages: d = 45 is 48 wide, not 64)
+    h->KG16 = low_d_form(h, cdiv(h->d, 16)) ? (int)cdiv(h->d, 16) : (int)rup(cdiv(h->d, 16), PF_STAGE_G);
+    const long long n_rows = (long long)h->n_rb_total * 32;
+    CHK(h->xmaxbits.reserve(16));
+    CHK(h->xscale.reserve(16));
+    CHK(h->bnorm.reserve((size_t)h->L * 4));
+    CHK(h->bdelta.reserve((size_t)h->L * 4));
+    // (+ 8 KiB: pass2_kernel's look-ahead requests up to two stages = 4 KiB past the last row-block's fragments before it learns that
+    // the item is over; the data is never used, the addresses must be the allocation's)
+    CHK(h->slab16.reserve((size_t)h->n_rb_total * h->KG16 * 1024 + 8192));
+    HIPCHK(hipMemsetAsync(h->xmaxbits.p, 0, 16, h->stream));
+    HIPCHK(hipMemsetAsync(h->bnorm.p, 0, (size_t)h->L * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->bdelta.p, 0, (size_t)h->L * 4, h->stream));
+    absmax_kernel<<<h->num_cus * 8, 256, 0, h->stream>>>(h->rowmajor.as<float>(), n_rows * h->dp, h->xmaxbits.as<unsigned>());
+    HIPCHK(hipGetLastError());
+    make_scale_kernel<<<1, 1, 0, h->stream>>>(h->xmaxbits.as<unsigned>(), h->xscale.as<float>());
+    HIPCHK(hipGetLastError());
+    const long long total = n_rows * h->KG16 * 2;
+    convert16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->rowmajor.as<float>(), h->d, h->dp, n_rows, h->KG16,
+                                                             h->xscale.as<float>(), h->slab16.as<uint4>(), frag16x16(h));
+    HIPCHK(hipGetLastError());
+    dim3 g(64, h->L);
+    bucket_norm_kernel<<<g, 256, 0, h->stream>>>(h->rowmajor.as<float>(), h->d, h->dp, h->d_rb_start.as<int>(),
+                                                h->d_nb_rows.as<int>(), h->xscale.as<float>(), h->bnorm.as<unsigned>(),
+                                                h->bdelta.as<unsigned>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->have16 = true;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_buckets_end(lmi_index* h) {
+    if (!h || !h->building) return fail("lmi_buckets_end: call lmi_buckets_begin first");
+    const int64_t expect = h->indexed_ingest ? h->owned_total : h->N;
+    if (h->rows_added != expect) return fail("lmi_buckets_end: %lld of %lld rows were added", (long long)h->rows_added, (long long)expect);
+    CHK(set_dev(h));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->pos.release();
+    h->have16 = false;
+    if (h->prefilter && h->n_rb_total > 0) CHK(prefilter_images(h));
+    h->building = false;
+    h->built = true;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_bucket_sizes(lmi_index* h, int64_t* sizes) {
+    if (!h || !(h->built || h->building)) return fail("lmi_bucket_sizes: no buckets");
+    for (int b = 0; b < h->L; ++b) sizes[b] = h->h_nb_rows[b];
+    return 0;
+}
+
+extern "C" LMI_API int lmi_bucket_read(lmi_index* h, int bucket, float* rows, uint32_t* ids) {
+    if (!h || !h->built) return fail("lmi_bucket_read: the bucket index is not built");
+    if (bucket < 0 || bucket >= h->L) return fail("lmi_bucket_read: bucket %d outside [0,%d)", bucket, h->L);
+    const int64_t n = h->h_nb_rows[bucket];
+    if (n == 0) return 0;
+    CHK(set_dev(h));
+    const int64_t p0 = (int64_t)h->h_rb_start[bucket] * 32;
+    const int du = h->d_user;  // the caller's columns (the L2 norm column is not returned)
+    if (rows && h->prefilter) {
+        HIPCHK(hipMemcpy2DAsync(rows, (size_t)du * 4, h->rowmajor.as<float>() + (size_t)p0 * h->dp, (size_t)h->dp * 4, (size_t)du * 4, (size_t)n,
+                                hipMemcpyDeviceToHost, h->stream));
+    } else if (rows) {
+        CHK(h->stage.reserve((size_t)n * du * 4));
+        long long total = n * cdiv(du, 8);
+        unpack_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab.as<float4>(), h->KGs, p0, n, du, h->stage.as<float>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rows, h->stage.p, (size_t)n * du * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (ids) HIPCHK(hipMemcpyAsync(ids, h->ids_slab.as<uint32_t>() + p0, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}

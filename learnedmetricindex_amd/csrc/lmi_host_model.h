@@ -1,0 +1,449 @@
+// lmi_host_model.h -- the navigation models on the host side: packing of the Linear stacks, the tree, the MLP forward in its fused
+// and per-layer forms (lmi_mlp_topk / lmi_mlp_proba) and the multi-level walk (nav_enqueue, lmi_nav_order).
+#pragma once
+#include "lmi_host.h"
+
+// upload a row-major host matrix and pack it fragment-major (rows padded to 32, K to 8*KG)
+static int pack_from_host(lmi_index* h, const float* src, int rows, int cols, int n_rb, int KG, DevBuf& dst) {
+    CHK(h->stage.reserve((size_t)rows * cols * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(h->stage.p, src, (size_t)rows * cols * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    CHK(dst.reserve((size_t)n_rb * KG * 1024));
+    long long total = (long long)n_rb * 32 * KG;
+    pack_gather_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->stage.as<float>(), cols, nullptr, rows,
+                                                               (long long)n_rb * 32, KG, dst.as<float4>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));  // staging buffer is reused by the next call
+    return 0;
+}
+
+// packs one Linear stack (torch layout W[out][in]) fragment-major: shared by lmi_set_mlp and lmi_nav_set_model
+static int pack_model(lmi_index* h, const char* who, int n_layers, const int* dims, const float* const* W, const float* const* b,
+                      std::vector<int>& o_dims, std::vector<int>& o_nrb, std::vector<int>& o_KG, std::vector<DevBuf>& o_W,
+                      std::vector<DevBuf>& o_b) {
+    if (n_layers < 1 || n_layers > LMI_MAX_LAYERS) return fail("%s: n_layers %d out of range", who, n_layers);
+    for (int i = 0; i <= n_layers; ++i)
+        if (dims[i] < 1) return fail("%s: dims[%d] = %d", who, i, dims[i]);
+    for (auto& x : o_W) x.release();
+    for (auto& x : o_b) x.release();
+    o_dims.assign(dims, dims + n_layers + 1);
+    o_nrb.assign(n_layers, 0);
+    o_KG.assign(n_layers, 0);
+    o_W.assign(n_layers, DevBuf());
+    o_b.assign(n_layers, DevBuf());
+    for (int i = 0; i < n_layers; ++i) {
+        o_nrb[i] = cdiv(dims[i + 1], 32);
+        o_KG[i] = (i == 0) ? cdiv(dims[0], 8) : o_nrb[i - 1] * 4;  // hidden K = padded features
+        if (!W[i] || !b[i]) return fail("%s: NULL weight/bias for layer %d", who, i);
+        CHK(pack_from_host(h, W[i], dims[i + 1], dims[i], o_nrb[i], o_KG[i], o_W[i]));
+        std::vector<float> bp((size_t)o_nrb[i] * 32, 0.0f);
+        std::copy(b[i], b[i] + dims[i + 1], bp.begin());
+        CHK(o_b[i].reserve(bp.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(o_b[i].p, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+extern "C" LMI_API int lmi_set_mlp(lmi_index* h, int n_layers, const int* dims, const float* const* W,
+                           const float* const* b) {
+    if (!h) return fail("lmi_set_mlp: NULL handle");
+    CHK(set_dev(h));
+    h->desc_dirty = true;
+    h->n_layers = 0;
+    CHK(pack_model(h, "lmi_set_mlp", n_layers, dims, W, b, h->dims, h->n_rb, h->KG, h->Wf, h->bias));
+    h->n_layers = n_layers;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_set_fused_mlp(lmi_index* h, int on) {
+    if (!h) return fail("lmi_set_fused_mlp: NULL handle");
+    if (on < 0 || on > 2) return fail("lmi_set_fused_mlp: mode %d outside 0..2", on);
+    h->fused_mlp = on;
+    return 0;
+}
+
+// ---- multi-level index: the internal nodes' models and the tree (lmi_mlp_fused.h) ----
+extern "C" LMI_API int lmi_nav_set_model(lmi_index* h, int model_id, int n_layers, const int* dims, const float* const* W,
+                                 const float* const* b) {
+    if (!h) return fail("lmi_nav_set_model: NULL handle");
+    if (model_id < 1 || model_id > 1 << 20) return fail("lmi_nav_set_model: model_id %d (the root, model 0, is lmi_set_mlp)", model_id);
+    CHK(set_dev(h));
+    if ((size_t)model_id > h->node_models.size()) h->node_models.resize(model_id);
+    auto& m = h->node_models[model_id - 1];
+    h->desc_dirty = true;
+    h->tree_set = false;
+    m.n_layers = 0;
+    CHK(pack_model(h, "lmi_nav_set_model", n_layers, dims, W, b, m.dims, m.n_rb, m.KG, m.Wf, m.bias));
+    m.n_layers = n_layers;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_nav_set_tree(lmi_index* h, int n_models, const int32_t* child_offset, const int32_t* child_model,
+                                const int32_t* child_bucket) {
+    if (!h) return fail("lmi_nav_set_tree: NULL handle");
+    if (h->n_layers == 0) return fail("lmi_nav_set_tree: no root model (lmi_set_mlp)");
+    if (n_models != 1 + (int)h->node_models.size()) return fail("lmi_nav_set_tree: %d models, %d set (root + lmi_nav_set_model)", n_models, 1 + (int)h->node_models.size());
+    if (!child_offset || !child_model || !child_bucket || child_offset[0] != 0) return fail("lmi_nav_set_tree: bad arguments");
+    for (int m = 0; m < n_models; ++m) {
+        const int classes = m == 0 ? h->dims[h->n_layers] : (h->node_models[m - 1].n_layers ? h->node_models[m - 1].dims.back() : -1);
+        if (classes < 0) return fail("lmi_nav_set_tree: model %d has no weights (lmi_nav_set_model)", m);
+        if (child_offset[m + 1] - child_offset[m] != classes) return fail("lmi_nav_set_tree: model %d has %d classes, %d children listed", m, classes, child_offset[m + 1] - child_offset[m]);
+    }
+    const int total = child_offset[n_models];
+    for (int e = 0; e < total; ++e) {
+        if (child_model[e] < -1 || child_model[e] == 0 || child_model[e] >= n_models) return fail("lmi_nav_set_tree: child_model[%d] = %d", e, child_model[e]);
+        if (child_bucket[e] < -2) return fail("lmi_nav_set_tree: child_bucket[%d] = %d", e, child_bucket[e]);
+    }
+    CHK(set_dev(h));
+    h->h_child_offset.assign(child_offset, child_offset + n_models + 1);
+    h->h_child_model.assign(child_model, child_model + total);
+    h->h_child_bucket.assign(child_bucket, child_bucket + total);
+    CHK(h->d_child_offset.reserve((size_t)(n_models + 1) * 4));
+    CHK(h->d_child_model.reserve((size_t)std::max(total, 1) * 4));
+    CHK(h->d_child_bucket.reserve((size_t)std::max(total, 1) * 4));
+    HIPCHK(hipMemcpy(h->d_child_offset.p, child_offset, (size_t)(n_models + 1) * 4, hipMemcpyHostToDevice));
+    if (total) {
+        HIPCHK(hipMemcpy(h->d_child_model.p, child_model, (size_t)total * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_child_bucket.p, child_bucket, (size_t)total * 4, hipMemcpyHostToDevice));
+    }
+    h->tree_set = true;
+    return 0;
+}
+
+// device descriptors of every model + the LDS plan of mlp_fused_kernel for the current model set
+static int build_descs(lmi_index* h) {
+    if (!h->desc_dirty) return 0;
+    const int nm = 1 + (int)h->node_models.size();
+    std::vector<ModelDesc> D(nm);
+    bool ok = h->n_layers > 0, logits_lds = true;
+    int w0 = 0, w1 = 0;
+    auto add = [&](ModelDesc& d, int n_layers, const std::vector<int>& dims, const std::vector<int>& n_rb, const std::vector<int>& KG,
+                   const std::vector<DevBuf>& Wf, const std::vector<DevBuf>& bias) {
+        memset(&d, 0, sizeof(d));
+        d.n_layers = n_layers;
+        if (n_layers == 0) { ok = false; return; }
+        for (int i = 0; i <= n_layers; ++i) d.dims[i] = dims[i];
+        for (int i = 0; i < n_layers; ++i) {
+            d.KG[i] = KG[i];
+            d.W[i] = Wf[i].as<float4>();
+            d.b[i] = bias[i].as<float>();
+            const int padded = n_rb[i] * 32;
+            const bool last = i + 1 == n_layers;
+            if (padded > FM_MAXH) { if (last) logits_lds = false; else ok = false; continue; }
+            int& wref = (i & 1) ? w1 : w0;
+            wref = std::max(wref, padded);
+        }
+    };
+    add(D[0], h->n_layers, h->dims, h->n_rb, h->KG, h->Wf, h->bias);
+    for (int m = 1; m < nm; ++m) {
+        const auto& M = h->node_models[m - 1];
+        add(D[m], M.n_layers, M.dims, M.n_rb, M.KG, M.Wf, M.bias);
+    }
+    h->fm_s0 = w0 + 1;
+    h->fm_s1 = w1 + 1;
+    h->fm_act0 = FM_COLS * h->fm_s0;
+    h->fm_lds = (2 * FM_COLS * FM_CHUNK_S + FM_COLS * h->fm_s0 + FM_COLS * h->fm_s1) * 4;
+    if (h->fm_lds > 160 * 1024 - 1024) ok = false;
+    h->fm_ok = ok;
+    h->fm_logits_lds = logits_lds ? 1 : 0;
+    CHK(h->d_models.reserve(sizeof(ModelDesc) * nm));
+    HIPCHK(hipMemcpy(h->d_models.p, D.data(), sizeof(ModelDesc) * nm, hipMemcpyHostToDevice));
+    if (ok) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_TOPK>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_PROBA>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_NAV>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
+    }
+    h->desc_dirty = false;
+    return 0;
+}
+
+static void fused_base(lmi_index* h, const float* d_q, int nq, FusedParams& P) {
+    memset(&P, 0, sizeof(P));
+    P.models = h->d_models.as<ModelDesc>();
+    P.n_models = 1 + (int)h->node_models.size();
+    P.x = d_q;
+    P.d = h->dims[0];
+    P.nq = nq;
+    P.s0 = h->fm_s0;
+    P.s1 = h->fm_s1;
+    P.act0_floats = h->fm_act0;
+    P.logits_in_lds = h->fm_logits_lds;
+}
+
+// MLP forward + class ranking (+ softmax when d_probs: then nb == L and d_order receives the full class order)
+// the per-layer form: one mlp_layer_kernel launch per Linear, then the ranking (and softmax) kernels, on stream `st`
+static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs) {
+    const int L = h->dims[h->n_layers];
+    const int ncb = cdiv(nq, 32);
+    // pack the queries as the B operand of layer 0
+    CHK(h->xfrag.reserve((size_t)ncb * h->KG[0] * 1024));
+    {
+        long long total = (long long)ncb * 32 * h->KG[0];
+        pack_gather_kernel<<<cdiv(total, 256), 256, 0, st>>>(d_q, h->dims[0], nullptr, nq, (long long)ncb * 32,
+                                                            h->KG[0], h->xfrag.as<float4>(), st == h->stream ? tsp(h, ST_MLP0) : nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    int maxrb = 0;
+    for (int i = 0; i + 1 < h->n_layers; ++i) maxrb = std::max(maxrb, h->n_rb[i]);
+    for (int i = 0; i < 2; ++i) CHK(h->act[i].reserve((size_t)std::max(1, ncb) * std::max(1, maxrb) * 4 * 1024));
+    float* d_logits = d_logits_out;
+    if (!d_logits) {
+        CHK(h->logits.reserve((size_t)nq * L * 4));
+        d_logits = h->logits.as<float>();
+    }
+    const float4* in = h->xfrag.as<float4>();
+    for (int i = 0; i < h->n_layers; ++i) {
+        const bool last = i + 1 == h->n_layers;
+        // col-blocks per wave: 4 when that already gives every CU two blocks, else 2, else 1 (e.g. the
+        // 120-class output layer has 4 feature blocks = one block row; 768->512 on 10 000 queries had 316
+        // blocks of CBW 4 on 256 CUs)
+        const int rows = cdiv(h->n_rb[i], 4);
+        const int cbw = rows * cdiv(ncb, 4) >= 2 * h->num_cus ? 4 : rows * cdiv(ncb, 2) >= 2 * h->num_cus ? 2 : 1;
+        dim3 grid(cdiv(ncb, cbw), rows);
+        float* o = last ? d_logits : h->act[i & 1].as<float>();
+        const int KGn = last ? 0 : h->n_rb[i] * 4;
+#define LMI_MLP_LAUNCH(LASTV, CBWV)                                                                        \
+        mlp_layer_kernel<LASTV, CBWV><<<grid, 256, 0, st>>>(h->Wf[i].as<float4>(), h->bias[i].as<float>(), in, \
+                                                           h->KG[i], h->n_rb[i], ncb, o, KGn, nq, L)
+        if (last) {
+            if (cbw == 4) LMI_MLP_LAUNCH(true, 4); else if (cbw == 2) LMI_MLP_LAUNCH(true, 2); else LMI_MLP_LAUNCH(true, 1);
+        } else {
+            if (cbw == 4) LMI_MLP_LAUNCH(false, 4); else if (cbw == 2) LMI_MLP_LAUNCH(false, 2); else LMI_MLP_LAUNCH(false, 1);
+            in = reinterpret_cast<const float4*>(o);
+        }
+#undef LMI_MLP_LAUNCH
+        HIPCHK(hipGetLastError());
+    }
+    rank_classes_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, d_order);
+    HIPCHK(hipGetLastError());
+    if (d_probs) {
+        softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, st>>>(d_logits, d_order, nq, L, d_probs);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs = nullptr) {
+    if (h->n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
+    const int L = h->dims[h->n_layers];
+    if (nb < 1 || nb > L) return fail("lmi_mlp_topk: n_buckets %d outside [1,%d]", nb, L);
+    CHK(build_descs(h));
+    // One launch for every layer + ranking when the batch fills the chip (a block = 32 queries, one per CU for the wide
+    // models: 8 192 queries 100 us against 138 us for the per-layer kernels); small batches (a rank's slice of a
+    // sharded batch, single queries) have too few 32-query blocks for that and take the per-layer kernels, whose grids
+    // also split the features (2 048 queries: 79 us against 88 us).  predict_proba always takes the fused kernel.
+    const bool fill = cdiv(nq, FM_COLS) * 2 >= h->num_cus || d_probs != nullptr || h->fused_mlp == 2;
+    if (h->fused_mlp && h->fm_ok && fill) {
+        // every layer, the ranking and the softmax in ONE launch (lmi_mlp_fused.h)
+        // A batch whose last round of 32-query blocks would fill under 30 % of the CUs (10 000 queries: 313 blocks = 256 + 57)
+        // pays a whole second round for it.  The tail's queries go through the per-layer kernels on a side stream instead,
+        // beside the fused kernel's one full round (the fused blocks leave wave slots and half of the MFMA pipe): 182 ->
+        // ~125 us at 10 000 queries; identical results (both forms are the canonical chain).
+        int grid = cdiv(nq, FM_COLS);
+        int nq_head = nq;
+        const int rem = grid % h->num_cus;
+        if (h->fused_mlp == 1 && !d_probs && !d_logits_out && h->fm_logits_lds && grid > h->num_cus && rem > 0 && rem * 10 < h->num_cus * 3) {
+            nq_head = (grid - rem) * FM_COLS;
+            grid -= rem;
+        }
+        FusedParams P;
+        fused_base(h, d_q, nq_head, P);
+        float* d_logits = d_logits_out;
+        if (!h->fm_logits_lds && !d_logits) {  // wide output layer: logits through global memory, ranked below
+            CHK(h->logits.reserve((size_t)nq * L * 4));
+            d_logits = h->logits.as<float>();
+        }
+        P.logits_out = d_logits;
+        P.nb = nb;
+        P.order = d_order;
+        P.probs = d_probs;
+        P.classes = d_order;
+        P.ts = tsp(h, ST_MLP0);
+        if (nq_head < nq) CHK(side_fork(h));
+        if (d_probs) mlp_fused_kernel<FM_PROBA><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        else mlp_fused_kernel<FM_TOPK><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        HIPCHK(hipGetLastError());
+        if (nq_head < nq) {
+            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr));
+            CHK(side_join(h));
+        }
+        if (!h->fm_logits_lds) {
+            rank_classes_kernel<<<nq, 64, 0, h->stream>>>(d_logits, nq, L, nb, d_order);
+            HIPCHK(hipGetLastError());
+            if (d_probs) {
+                softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, h->stream>>>(d_logits, d_order, nq, L, d_probs);
+                HIPCHK(hipGetLastError());
+            }
+        }
+        return 0;
+    }
+    return mlp_layers_enqueue(h, h->stream, d_q, nq, nb, d_order, d_logits_out, d_probs);
+}
+
+extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int nq, int nb, int32_t* bucket_order,
+                            float* logits, int on_device) {
+    if (!h) return fail("lmi_mlp_topk: NULL handle");
+    if (nq < 0) return fail("lmi_mlp_topk: nq < 0");
+    if (nq == 0) return 0;
+    CHK(set_dev(h));
+    if (h->n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
+    const int L = h->dims[h->n_layers];
+    const void* d_q = nullptr;
+    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_q));
+    int* d_order = bucket_order;
+    float* d_logits = logits;
+    if (!on_device) {
+        CHK(h->order.reserve((size_t)nq * nb * 4));
+        d_order = h->order.as<int>();
+        if (logits) { CHK(h->logits.reserve((size_t)nq * L * 4)); d_logits = h->logits.as<float>(); }
+    }
+    begin_call(h);
+    CHK(record(h, 0));
+    CHK(mlp_enqueue(h, static_cast<const float*>(d_q), nq, nb, d_order, d_logits));
+    CHK(record(h, 1));
+    CHK(stamp_end(h, ST_MLP1));
+    if (!on_device) CHK(copy_back(h, {{bucket_order, d_order, (size_t)nq * nb * 4}, {logits, d_logits, (size_t)nq * L * 4}}));
+    return 0;
+}
+
+extern "C" LMI_API int lmi_mlp_proba(lmi_index* h, const float* queries_nav, int nq, float* probs, int32_t* classes,
+                             int on_device) {
+    if (!h) return fail("lmi_mlp_proba: NULL handle");
+    if (nq < 0) return fail("lmi_mlp_proba: nq < 0");
+    if (nq == 0) return 0;
+    CHK(set_dev(h));
+    if (h->n_layers == 0) return fail("lmi_mlp_proba: no MLP set (lmi_set_mlp)");
+    const int L = h->dims[h->n_layers];
+    const void* d_q = nullptr;
+    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_q));
+    int* d_order = classes;
+    float* d_probs = probs;
+    if (!on_device) {
+        CHK(h->order.reserve((size_t)nq * L * 4));
+        CHK(h->out_d.reserve((size_t)nq * L * 4));
+        d_order = h->order.as<int>();
+        d_probs = h->out_d.as<float>();
+    }
+    begin_call(h);
+    CHK(record(h, 0));
+    CHK(mlp_enqueue(h, static_cast<const float*>(d_q), nq, L, d_order, nullptr, d_probs));
+    CHK(record(h, 1));
+    CHK(stamp_end(h, ST_MLP1));
+    if (!on_device) CHK(copy_back(h, {{classes, d_order, (size_t)nq * L * 4}, {probs, d_probs, (size_t)nq * L * 4}}));
+    return 0;
+}
+
+// Multi-level navigation on the device: LearnedIndex._precompute_bucket_order for len(n_categories) > 1
+// (LearnedIndex.py:216-252) -- the batched priority-queue walk.  slab_ids[nq][nb] <- slab bucket id of the
+// j-th visited bucket (-1: listed bucket without objects or queue exhausted), entries[nq][nb] <- its flat child
+// index (child_offset[parent model] + class; -1: none) from which the caller rebuilds the path.
+// The multi-level walk of one batch, enqueued on h->stream: d_slab / d_ent [nq][nb] receive the visited buckets in visiting order.
+// Trees of up to NAV_ENQUEUE_ALL models: EVERY possible step is enqueued up front and a step whose predecessor left no query waiting
+// returns at once (nav_pop_kernel: prev_active) -- no host round trip inside the walk, the call is asynchronous like every other
+// enqueue.  Larger trees: steps in batches of 4 with the count read back after each (one small synchronisation).
+constexpr int NAV_ENQUEUE_ALL = 16;
+static int nav_check(lmi_index* h, int nq, int nb, const char* who) {
+    if (!h->tree_set) return fail("%s: no tree (lmi_nav_set_model / lmi_nav_set_tree)", who);
+    CHK(set_dev(h));
+    CHK(build_descs(h));
+    if (!h->fm_ok || !h->fm_logits_lds)
+        return fail("%s: a model of the tree does not fit the fused kernel (layer outputs <= %d, LDS plan %d bytes)", who, FM_MAXH, h->fm_lds);
+    const int nm = 1 + (int)h->node_models.size();
+    const int cap = h->h_child_offset[nm];
+    if ((long long)nq * cap >= (1ll << 31) || (long long)nq * nb >= (1ll << 31)) return fail("%s: nq too large for this tree", who);
+    if (cap == 0) return fail("%s: empty tree", who);
+    return 0;
+}
+static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_slab, int* d_ent) {
+    const int nm = 1 + (int)h->node_models.size();
+    const int cap = h->h_child_offset[nm];
+    CHK(h->pq_prob.reserve((size_t)nq * cap * 4));
+    CHK(h->pq_ent.reserve((size_t)nq * cap * 4));
+    CHK(h->pq_len.reserve((size_t)nq * 4));
+    CHK(h->nav_len.reserve((size_t)nq * 4));
+    CHK(h->nav_count.reserve((size_t)2 * (nm + 1) * 4));  // [2][nm + 1]: per-model counters + the step's active-query count
+    CHK(h->nav_colq.reserve((size_t)nm * nq * 4));
+    FillRanges Z;
+    Z.count = 0;
+    bool fill_ok = true;
+    auto fill = [&](void* ptr, long long words, unsigned value) { fill_ok = Z.add(ptr, words, value) && fill_ok; };
+    fill(h->pq_len.p, nq, 0u);
+    fill(h->nav_len.p, nq, 0u);
+    fill(d_slab, (long long)nq * nb, 0xFFFFFFFFu);
+    fill(d_ent, (long long)nq * nb, 0xFFFFFFFFu);
+    fill(h->nav_count.p, 2 * (nm + 1), 0u);
+    if (!fill_ok) return fail("internal: more than %d fill ranges queued (%s:%d)", FillRanges::MAXR, __FILE__, __LINE__);
+    Z.ts = tsp(h, ST_MLP0);
+    fill_ranges_kernel<<<h->num_cus * 2, 256, 0, h->stream>>>(Z);
+    HIPCHK(hipGetLastError());
+    FusedParams P;
+    fused_base(h, d_q, nq, P);
+    P.pq_prob = h->pq_prob.as<float>();
+    P.pq_ent = h->pq_ent.as<int>();
+    P.pq_len = h->pq_len.as<int>();
+    P.cap = cap;
+    P.child_offset = h->d_child_offset.as<int>();
+    P.reverse = 1;  // root children: least probable first (LearnedIndex.py:220-227)
+    mlp_fused_kernel<FM_NAV><<<cdiv(nq, FM_COLS), 256, h->fm_lds, h->stream>>>(P);
+    HIPCHK(hipGetLastError());
+    P.reverse = 0;
+    P.col_query = h->nav_colq.as<int>();
+    NavParams N;
+    N.nq = nq; N.nb = nb; N.cap = cap;
+    N.pq_prob = P.pq_prob; N.pq_ent = P.pq_ent; N.pq_len = P.pq_len;
+    N.child_model = h->d_child_model.as<int>();
+    N.child_bucket = h->d_child_bucket.as<int>();
+    N.out_len = h->nav_len.as<int>();
+    N.out_slab = d_slab;
+    N.out_ent = d_ent;
+    N.col_query = h->nav_colq.as<int>();
+    int* counts = h->nav_count.as<int>();
+    // A step pops entries until the query hits an internal node; a query expands each node at most once, so there are
+    // at most (models) steps.
+    const int max_steps = nm + 1;
+    const bool all = nm <= NAV_ENQUEUE_ALL;
+    const bool pop_lds = cap <= NAV_LDS_CAP;
+    int h_active = 1;
+    for (int it = 0; it < max_steps && h_active > 0;) {
+        int last_par = 0;
+        for (int k4 = 0; (all || k4 < 4) && it < max_steps; ++k4, ++it) {
+            const int par = it & 1;
+            N.node_count = counts + par * (nm + 1);
+            N.active = counts + par * (nm + 1) + nm;
+            N.prev_active = (all && it > 0) ? counts + (1 - par) * (nm + 1) + nm : nullptr;
+            if (pop_lds) nav_pop_lds_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N);
+            else nav_pop_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N);
+            HIPCHK(hipGetLastError());
+            P.node_count = N.node_count;
+            P.zero_counts = counts + (1 - par) * (nm + 1);
+            P.n_zero = nm + 1;
+            mlp_fused_kernel<FM_NAV><<<cdiv(nq, FM_COLS) + nm, 256, h->fm_lds, h->stream>>>(P);
+            HIPCHK(hipGetLastError());
+            last_par = par;
+        }
+        if (all) break;
+        HIPCHK(hipMemcpyAsync(&h_active, counts + last_par * (nm + 1) + nm, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+extern "C" LMI_API int lmi_nav_order(lmi_index* h, const float* queries_nav, int nq, int nb, int32_t* slab_ids, int32_t* entries,
+                             int on_device) {
+    if (!h) return fail("lmi_nav_order: NULL handle");
+    if (nq < 0 || nb < 1) return fail("lmi_nav_order: bad nq/n_buckets");
+    if (nq == 0) return 0;
+    CHK(nav_check(h, nq, nb, "lmi_nav_order"));
+    const void* d_q = nullptr;
+    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_q));
+    CHK(h->nav_slab.reserve((size_t)nq * nb * 4));
+    CHK(h->nav_ent.reserve((size_t)nq * nb * 4));
+    int* d_slab = on_device ? slab_ids : h->nav_slab.as<int>();
+    int* d_ent = on_device ? entries : h->nav_ent.as<int>();
+    begin_call(h);
+    CHK(record(h, 0));
+    CHK(nav_enqueue(h, static_cast<const float*>(d_q), nq, nb, d_slab, d_ent));
+    CHK(record(h, 1));
+    CHK(stamp_end(h, ST_MLP1));
+    if (!on_device) CHK(copy_back(h, {{slab_ids, d_slab, (size_t)nq * nb * 4}, {entries, d_ent, (size_t)nq * nb * 4}}));
+    return 0;
+}

@@ -213,7 +213,7 @@ def test_multi_level_index(oracle, name):
                                        ([12, 12], "13 models: every step enqueued up front; 156-entry queues stay in global memory"),
                                        ([5, 4], "small: everything up front, queues in LDS")])
 def test_walk_forms_against_the_oracle(oracle, ncat, what):
-    """The walk's launch forms (lmi_hip.hip nav_enqueue: NAV_ENQUEUE_ALL, NAV_LDS_CAP) on synthetic two-level trees with random models:
+    """The walk's launch forms (lmi_host_model.h nav_enqueue: NAV_ENQUEUE_ALL, NAV_LDS_CAP) on synthetic two-level trees with random models:
     bucket order and results equal the oracle's restatement of LearnedIndex.py:216-325."""
     from learnedmetricindex_amd.li.LearnedIndex import LearnedIndex
     from learnedmetricindex_amd.li.model import NeuralNetwork
