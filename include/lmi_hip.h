@@ -94,6 +94,20 @@ LMI_API int lmi_set_mlp(lmi_index *h, int n_layers, const int *dims, const float
  * and probabilities. */
 LMI_API int lmi_set_fused_mlp(lmi_index *h, int mode);
 
+/* Probability-mass stop of the 1-level navigation (no reference counterpart: the reference visits exactly n_buckets buckets
+ * per query).  mass == 0 (default): off, every call behaves as without it.  0 < mass <= 1: in the bucket order that
+ * lmi_mlp_topk, lmi_search and lmi_pipeline_submit compute, rank 0 is always visited and rank t >= 1 is visited iff
+ * c_{t-1} < mass, where p_t is the probability lmi_mlp_proba returns at rank t (same maximum, same expf, row sum in class
+ * order, one division), c_0 = p_0 and c_t = c_{t-1} + p_t, each a binary32 add with one rounding, taken in rank order;
+ * the compare is binary32 and false on NaN.  A rank that is not visited gets bucket_order[q][t] = -1, which the scan and
+ * the merge treat as an unvisited slot (dist = +inf, id = 0): kout and the output shapes do not change, n_buckets == 1
+ * is unaffected.  Any other value (NaN included) is an error that leaves the setting as it was.  Per handle; a
+ * lmi_clone_view copies its parent's value when it is made; may be changed between any two calls, the index is not
+ * rebuilt.  lmi_mlp_proba and the multi-level calls (lmi_nav_order, lmi_search_tree: the walk ranks by LOCAL
+ * probabilities, whose sum has no such meaning) ignore it.  All three ranking paths (lmi_set_fused_mlp) give
+ * bit-identical orders. */
+LMI_API int lmi_set_stop_mass(lmi_index *h, float mass);
+
 /* Multi-level index (len(n_categories) > 1; LearnedIndex.py:216-325, PriorityQueue.py:18-94): the models of
  * the internal nodes and the tree.  Model 0 is the root (lmi_set_mlp); lmi_nav_set_model sets model_id >= 1
  * (arguments as lmi_set_mlp).  lmi_nav_set_tree: child e = child_offset[m] + c is class c of model m:

@@ -37,6 +37,7 @@ SIGNATURES = {
     "lmi_set_stream": (ctypes.c_int, [_vp, _vp]),
     "lmi_set_mlp": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "lmi_set_fused_mlp": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lmi_set_stop_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
     "lmi_set_metric": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_nav_set_model": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "lmi_nav_set_tree": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
@@ -143,6 +144,7 @@ class Index:
         self.d_nav = None
         self.d = None
         self.L = None
+        self.stop_mass = 0.0
         if chunk_rows is not None:
             _check(lib().lmi_set_chunk_rows(self._h, int(chunk_rows)))
         if prefilter is None and os.environ.get("LMI_PREFILTER") is not None:
@@ -167,7 +169,7 @@ class Index:
         v = Index.__new__(Index)
         v._h = _vp()
         _check(lib().lmi_clone_view(self._h, ctypes.byref(v._h)))
-        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric"):
+        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric", "stop_mass"):
             setattr(v, a, getattr(self, a, None))
         v._views = []
         v._parent = self
@@ -245,6 +247,14 @@ class Index:
     def set_fused_mlp(self, mode: int) -> None:
         """2: always the one-launch MLP kernel, 0: always the per-layer kernels, 1 (default): by batch size; identical outputs."""
         _check(lib().lmi_set_fused_mlp(self._h, int(mode)))
+
+    def set_stop_mass(self, mass: float) -> None:
+        """Probability-mass stop of the 1-level navigation (`lmi_set_stop_mass`): 0 = off (default); 0 < mass <= 1: a
+        query's bucket order keeps rank t >= 1 only while the probabilities of the ranks before it sum to less than
+        `mass` (binary32, in rank order); the ranks cut are -1 = unvisited.  Anything else raises and changes nothing.
+        `self.stop_mass` holds the value in force (a clone view starts with its parent's)."""
+        _check(lib().lmi_set_stop_mass(self._h, ctypes.c_float(mass)))
+        self.stop_mass = float(np.float32(mass))
 
     # ---- multi-level navigation ---------------------------------------------------------------
     @staticmethod

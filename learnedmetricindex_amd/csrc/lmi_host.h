@@ -108,6 +108,7 @@ struct lmi_index {
     };
     std::vector<NodeModel> node_models;   // index = model id - 1
     int fused_mlp = 1;                    // lmi_set_fused_mlp: 0 never, 1 when the batch fills the chip, 2 always
+    float stop_mass = 0.0f;               // lmi_set_stop_mass: 0 off; (0, 1]: a query's bucket order ends once this much probability is covered
     bool desc_dirty = true;
     DevBuf d_models;                      // ModelDesc[1 + node_models.size()]
     int fm_s0 = 0, fm_s1 = 0, fm_act0 = 0, fm_lds = 0, fm_logits_lds = 0;  // LDS plan of the current model set

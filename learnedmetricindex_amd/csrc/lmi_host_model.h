@@ -54,6 +54,22 @@ extern "C" LMI_API int lmi_set_mlp(lmi_index* h, int n_layers, const int* dims, 
     return 0;
 }
 
+extern "C" LMI_API int lmi_set_stop_mass(lmi_index* h, float mass) {
+    if (!h) return fail("lmi_set_stop_mass: NULL handle");
+    if (!(mass >= 0.0f && mass <= 1.0f)) return fail("lmi_set_stop_mass: mass %g outside [0, 1] (0: off)", (double)mass);
+    h->stop_mass = mass;
+    return 0;
+}
+
+// the class ranking behind the per-layer kernels and behind a fused launch whose logits went through global memory: with the stop
+// on (mass > 0) rank_classes_stop_kernel takes rank_classes_kernel's place
+static int rank_enqueue(hipStream_t st, const float* d_logits, int nq, int L, int nb, float mass, int* d_order) {
+    if (mass > 0.0f) rank_classes_stop_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, d_order);
+    else rank_classes_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, d_order);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" LMI_API int lmi_set_fused_mlp(lmi_index* h, int on) {
     if (!h) return fail("lmi_set_fused_mlp: NULL handle");
     if (on < 0 || on > 2) return fail("lmi_set_fused_mlp: mode %d outside 0..2", on);
@@ -151,6 +167,7 @@ static int build_descs(lmi_index* h) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_TOPK>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_PROBA>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_NAV>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_TOPK_STOP>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
     }
     h->desc_dirty = false;
     return 0;
@@ -171,7 +188,9 @@ static void fused_base(lmi_index* h, const float* d_q, int nq, FusedParams& P) {
 
 // MLP forward + class ranking (+ softmax when d_probs: then nb == L and d_order receives the full class order)
 // the per-layer form: one mlp_layer_kernel launch per Linear, then the ranking (and softmax) kernels, on stream `st`
-static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs) {
+// mass > 0: the order is cut by the probability-mass stop (never together with d_probs)
+static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs,
+                              float mass) {
     const int L = h->dims[h->n_layers];
     const int ncb = cdiv(nq, 32);
     // pack the queries as the B operand of layer 0
@@ -213,8 +232,7 @@ static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, in
 #undef LMI_MLP_LAUNCH
         HIPCHK(hipGetLastError());
     }
-    rank_classes_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, d_order);
-    HIPCHK(hipGetLastError());
+    CHK(rank_enqueue(st, d_logits, nq, L, nb, mass, d_order));
     if (d_probs) {
         softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, st>>>(d_logits, d_order, nq, L, d_probs);
         HIPCHK(hipGetLastError());
@@ -227,6 +245,8 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
     const int L = h->dims[h->n_layers];
     if (nb < 1 || nb > L) return fail("lmi_mlp_topk: n_buckets %d outside [1,%d]", nb, L);
     CHK(build_descs(h));
+    // the probability-mass stop (lmi_set_stop_mass) cuts a bucket order; predict_proba's full class order and a single rank are never cut
+    const float mass = (!d_probs && nb > 1) ? h->stop_mass : 0.0f;
     // One launch for every layer + ranking when the batch fills the chip (a block = 32 queries, one per CU for the wide
     // models: 8 192 queries 100 us against 138 us for the per-layer kernels); small batches (a rank's slice of a
     // sharded batch, single queries) have too few 32-query blocks for that and take the per-layer kernels, whose grids
@@ -258,17 +278,18 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
         P.probs = d_probs;
         P.classes = d_order;
         P.ts = tsp(h, ST_MLP0);
+        P.stop_mass = mass;
         if (nq_head < nq) CHK(side_fork(h));
         if (d_probs) mlp_fused_kernel<FM_PROBA><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        else if (mass > 0.0f) mlp_fused_kernel<FM_TOPK_STOP><<<grid, 256, h->fm_lds, h->stream>>>(P);
         else mlp_fused_kernel<FM_TOPK><<<grid, 256, h->fm_lds, h->stream>>>(P);
         HIPCHK(hipGetLastError());
         if (nq_head < nq) {
-            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr));
+            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr, mass));
             CHK(side_join(h));
         }
         if (!h->fm_logits_lds) {
-            rank_classes_kernel<<<nq, 64, 0, h->stream>>>(d_logits, nq, L, nb, d_order);
-            HIPCHK(hipGetLastError());
+            CHK(rank_enqueue(h->stream, d_logits, nq, L, nb, mass, d_order));
             if (d_probs) {
                 softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, h->stream>>>(d_logits, d_order, nq, L, d_probs);
                 HIPCHK(hipGetLastError());
@@ -276,7 +297,7 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
         }
         return 0;
     }
-    return mlp_layers_enqueue(h, h->stream, d_q, nq, nb, d_order, d_logits_out, d_probs);
+    return mlp_layers_enqueue(h, h->stream, d_q, nq, nb, d_order, d_logits_out, d_probs, mass);
 }
 
 extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int nq, int nb, int32_t* bucket_order,

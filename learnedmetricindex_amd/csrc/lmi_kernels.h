@@ -339,6 +339,67 @@ __global__ void softmax_ranked_kernel(const float* __restrict__ logits, const in
 }
 
 // ------------------------------------------------------------------------------------------------
+// Class ranking with the probability-mass stop (lmi_set_stop_mass; no reference counterpart): rank_classes_kernel's
+// selection passes, and rank t >= 1 is kept only while the probabilities of the ranks before it sum to less than
+// `mass`; a rank that is not kept gets -1 (an unvisited slot of the scan).  One wave per query, launched IN PLACE of
+// rank_classes_kernel.  The probabilities are predict_proba's bit for bit: row maximum, lmi_expf -- computed 64 classes
+// at a time, one per lane -- summed in class order (the lanes' values are read back one by one into ONE chain of adds;
+// a tree reduction would round differently), one division per rank.  The cumulative sum c_t = c_{t-1} + p_t is a
+// chain of binary32 adds in rank order and the test `c_{t-1} < mass` is false on NaN.  As p_t >= 0 the sum never
+// decreases, so the first rank that is cut ends the selection passes.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void rank_classes_stop_kernel(const float* __restrict__ logits, int nq, int L, int nb,
+                                                              float mass, int* __restrict__ order) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    if (q >= nq) return;
+    const float* l = logits + (size_t)q * L;
+    // row maximum by softmax_ranked_kernel's rule (`v > m ? v : m` from l[0]): the largest comparable logit, NaN iff l[0] is
+    float m = l[0];
+    for (int j = lane; j < L; j += 64) {
+        const float v = l[j];
+        m = v > m ? v : m;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(m, o);
+        m = ov > m ? ov : m;
+    }
+    float s = 0.0f;
+    for (int j0 = 0; j0 < L; j0 += 64) {
+        const int j = j0 + lane;
+        const float e = j < L ? lmi_expf(l[j] - m) : 0.0f;   // past L: +0, which leaves the non-negative sum as it is
+#pragma unroll
+        for (int k = 0; k < 64; ++k) s += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), k));
+    }
+    float pv = INFINITY, c = 0.0f;
+    int pi = -1;
+    int t = 0;
+    for (; t < nb; ++t) {
+        if (t > 0 && !(c < mass)) break;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int j = lane; j < L; j += 64) {
+            float v = l[j];
+            bool after = (v < pv) || (v == pv && j > pi);
+            if (after && (v > bv || (v == bv && j < bi))) { bv = v; bi = j; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            float ov = __shfl_xor(bv, o);
+            int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        const bool none = bi == 0x7fffffff;   // ran out of comparable logits (NaN): class -1, probability NaN
+        if (lane == 0) order[(size_t)q * nb + t] = none ? -1 : bi;
+        const float p = none ? __builtin_nanf("") : lmi_expf(bv - m) / s;   // bv is l[bi]
+        c = t == 0 ? p : c + p;
+        pv = bv;
+        pi = bi;
+    }
+    for (int u = t + lane; u < nb; u += 64) order[(size_t)q * nb + u] = -1;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Routing: the GPU twin of the `for bucket: filter_path_idxs(bucket_path, path)` loop
 // (LearnedIndex.py:350-353, utils.py:61-65): queries grouped bucket-major (CSR).
 // ------------------------------------------------------------------------------------------------

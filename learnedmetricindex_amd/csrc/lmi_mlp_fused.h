@@ -14,6 +14,8 @@
 //   * epilogue per column, from the logits in LDS: class ranking by selection passes (ties -> lower class index),
 //     the canonical softmax (same expf, row sum in class order) and, by mode,
 //       FM_TOPK   bucket_order[q][0..nb)                                        (LearnedIndex.py:197-214)
+//       FM_TOPK_STOP  the same, cut by the probability-mass stop: -1 from the first rank whose predecessors' probabilities
+//                 sum to `stop_mass` or more (lmi_set_stop_mass; no reference counterpart)
 //       FM_PROBA  probs[q][L] descending + classes[q][L]                        (model.py:238-241)
 //       FM_NAV    the node's children pushed into the query's priority queue    (LearnedIndex.py:220-227, 289-299)
 //     Final layers wider than FM_MAXH keep their logits in global memory and the host runs the separate ranking
@@ -28,7 +30,7 @@ constexpr int FM_COLS = 32;     // columns per block = one MFMA column block
 constexpr int FM_CHUNK = 96;    // input features staged per step of layer 0 (12 k-groups: a multiple of the 3-deep weight prefetch)
 constexpr int FM_CHUNK_S = FM_CHUNK + 1;
 constexpr int FM_MAXH = 512;    // widest layer whose outputs stay in LDS
-enum { FM_TOPK = 0, FM_PROBA = 1, FM_NAV = 2 };
+enum { FM_TOPK = 0, FM_PROBA = 1, FM_NAV = 2, FM_TOPK_STOP = 3 };
 
 struct ModelDesc {  // device copy of one model's shape and weights (root = model 0, internal nodes 1..)
     int n_layers;
@@ -50,8 +52,8 @@ struct FusedParams {
     // step of the walk, model m's queries at col_query[m * nq ..)
     const int* node_count;
     const int* col_query;
-    int nb;                      // FM_TOPK
-    int* order;                  // FM_TOPK [nq][nb]
+    int nb;                      // FM_TOPK, FM_TOPK_STOP
+    int* order;                  // FM_TOPK, FM_TOPK_STOP [nq][nb]
     float* logits_out;           // nullable [nq][L] (model 0 only)
     float* probs;                // FM_PROBA [nq][L]
     int* classes;                // FM_PROBA [nq][L]
@@ -65,6 +67,7 @@ struct FusedParams {
     int* zero_counts;            // block 0 clears the NEXT step's counters
     int n_zero;
     unsigned long long* ts;      // nullable: device stamp of the launch's start (lmi_kernels.h)
+    float stop_mass;             // FM_TOPK_STOP: in (0, 1]
 };
 
 template <int MODE>
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
     if (!P.logits_in_lds) return;  // wide output layer: the host runs rank_classes_kernel / softmax_ranked_kernel
     const float* lg = ((n_layers - 1) & 1) ? act1 : act0;
     const int SL = ((n_layers - 1) & 1) ? P.s1 : P.s0;
-    if (MODE != FM_TOPK) {
+    if (MODE == FM_PROBA || MODE == FM_NAV) {
         // canonical softmax terms: row max, then the sum of expf(l - max) in class order (softmax_ranked_kernel)
         if (tid < ncols) {
             const float* l = lg + tid * SL;
@@ -277,11 +280,32 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
     // Ranking: 8 lanes per column, all 8 columns of a wave side by side (a wave per column, one column after the
     // other, took 27 us of a 106-us block: 32 sequential passes of 12 dependent shuffles each).  Selection pass t
     // finds the t-th class of the descending order, ties -> lower class index (rank_classes_kernel's rule).
-    const int T = MODE == FM_TOPK ? P.nb : L;
+    const int T = (MODE == FM_TOPK || MODE == FM_TOPK_STOP) ? P.nb : L;
     const int col = w * 8 + (lane >> 3), sub = lane & 7;
     const bool live = col < ncols;
     const int q = s_q[live ? col : 0];
     const float* l = lg + (live ? col : 0) * SL;
+    // FM_TOPK_STOP: the column's softmax terms by its 8 lanes (rank_classes_stop_kernel's arithmetic: the row maximum, then the
+    // exponentials 8 classes at a time, one per lane, added in class order into one chain that every lane of the group carries)
+    float sm = 0.0f, ss = 0.0f, cum = 0.0f;
+    if (MODE == FM_TOPK_STOP) {
+        sm = l[0];
+        for (int j = sub; j < L; j += 8) {
+            const float v = l[j];
+            sm = v > sm ? v : sm;
+        }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(sm, o);
+            sm = ov > sm ? ov : sm;
+        }
+        for (int j0 = 0; j0 < L; j0 += 8) {
+            const int j = j0 + sub;
+            const float e = j < L ? lmi_expf(l[min(j, L - 1)] - sm) : 0.0f;   // past L: +0, which leaves the non-negative sum as it is
+#pragma unroll
+            for (int k = 0; k < 8; ++k) ss += __shfl(e, k, 8);
+        }
+    }
     int base = 0;
     if (MODE == FM_NAV) base = P.pq_len[q];
     float pv = INFINITY;
@@ -304,6 +328,13 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
             const int cls = bi == 0x7fffffff ? -1 : bi;
             if (MODE == FM_TOPK) {
                 P.order[(size_t)q * P.nb + t] = cls;
+            } else if (MODE == FM_TOPK_STOP) {
+                // rank t >= 1 is visited iff c_{t-1} < mass (false on NaN); c_t = c_{t-1} + p_t, one binary32 add per rank
+                // (a column that is cut keeps running the selection passes, unlike rank_classes_stop_kernel's early exit: the 8
+                // columns of a wave go through the passes in lockstep, so stopping one of them would save nothing)
+                P.order[(size_t)q * P.nb + t] = (t == 0 || cum < P.stop_mass) ? cls : -1;
+                const float pr = cls >= 0 ? lmi_expf(l[cls] - sm) / ss : __builtin_nanf("");
+                cum = t == 0 ? pr : cum + pr;
             } else {
                 const float pr = cls >= 0 ? lmi_expf(l[cls] - s_max[col]) / s_sum[col] : __builtin_nanf("");
                 if (MODE == FM_PROBA) {

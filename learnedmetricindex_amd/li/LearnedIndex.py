@@ -247,12 +247,20 @@ class LearnedIndex(Logger):
         return eng
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
-                        k: int = 10):
+                        k: int = 10, stop_mass: Optional[float] = None):
         """`search` against the index already resident in HBM (after `prepare`, a previous `search`
-        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`."""
+        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass` as there."""
+        self._check_stop_mass(stop_mass, n_categories)
         assert self._engine is not None, "no resident index: call prepare()/search() or index_io.load_index()"
         return self._search_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, k,
-                                 time.time())
+                                 time.time(), stop_mass)
+
+    @staticmethod
+    def _check_stop_mass(stop_mass, n_categories) -> None:
+        """`stop_mass` is defined on the root model's probabilities of a 1-level index; the multi-level walk ranks by local
+        probabilities, so it is refused there before any work is done."""
+        if stop_mass is not None and len(n_categories) > 1:
+            raise ValueError("stop_mass is not supported on a multi-level index (the walk ranks buckets by local probabilities)")
 
     # ------------------------------------------------------------------------------------------
     def insert(self, data_navigation_new: pd.DataFrame, data_search_new: Optional[pd.DataFrame] = None,
@@ -330,17 +338,32 @@ class LearnedIndex(Logger):
         k: int = 10,
         metric: str = "ip",
         assume_unchanged: bool = False,
+        stop_mass: Optional[float] = None,
     ) -> Tuple[npt.NDArray, npt.NDArray[np.uint32], Dict[str, float]]:
         """Searches for `k` nearest neighbors of every query in its `n_buckets` most probable buckets.
         Parameters and return values as the reference (LearnedIndex.py:41-83).  `metric` (an extension; the
         reference scans with `1 - inner product` only): "ip" (default) or "l2" -- squared Euclidean distances.
         `assume_unchanged` (an extension): the caller vouches that `data_search` still holds what the HBM-resident copy was
-        built from, so its bytes are not fingerprinted again (see `prepare`); the default re-checks them on every call."""
+        built from, so its bytes are not fingerprinted again (see `prepare`); the default re-checks them on every call.
+        `stop_mass` (an extension, 1-level indexes only; `lmi_set_stop_mass`): None = off; 0 < stop_mass <= 1: a query stops
+        visiting buckets once the probabilities of the ranks it has visited sum to `stop_mass` or more -- the ranks it skips
+        stay unvisited, the result shapes do not change.  It holds for this call only.  ValueError on a multi-level index."""
+        self._check_stop_mass(stop_mass, n_categories)
         s = time.time()
         eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged)
-        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
+        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass)
 
-    def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
+    def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None):
+        if stop_mass is None:
+            return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
+        before = eng.stop_mass   # the engine's own setting comes back afterwards: a later call without the argument is as before
+        eng.set_stop_mass(stop_mass)
+        try:
+            return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
+        finally:
+            eng.set_stop_mass(before)
+
+    def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
         measured_time = defaultdict(float)
         qn = np.ascontiguousarray(queries_navigation, dtype=np.float32)
         qs = qn if queries_search is queries_navigation else np.ascontiguousarray(queries_search, dtype=np.float32)

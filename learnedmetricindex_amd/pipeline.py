@@ -45,10 +45,12 @@ class HostPipeline:
     def __init__(self, index, nq: int, d_nav: int, d_search: int, nb: int, k: int = 10, depth: int = 2,
                  device: Optional[int] = None, same_queries: bool = False, want_bucket_order: bool = False,
                  search_fn=None, overlap_inference: bool = True, two_handles: bool = False, sharded=None, use_graph: bool = False,
-                 direct_out: bool = False, native_submit: bool = True, share_streams: bool = True):
+                 direct_out: bool = False, native_submit: bool = True, share_streams: bool = True, stop_mass: Optional[float] = None):
         """`search_fn(qn_dev, qs_dev) -> (dists_t, ids_t, bucket_order_t)`: optional replacement of the single-GPU
         `lmi_search` call, run on the compute stream (the bucket-sharded searcher of sharded.py, whose collectives
-        then run on that stream too); its output tensors may be reused by its next call."""
+        then run on that stream too); its output tensors may be reused by its next call.
+        `stop_mass`: the probability-mass stop (`Index.set_stop_mass`) for every batch, set on every handle the pipeline
+        alternates between; `close()` gives the index its earlier value back.  None leaves the handles' own setting."""
         import torch
 
         self.index, self.nq, self.nb, self.k, self.depth = index, int(nq), int(nb), int(k), int(depth)
@@ -87,6 +89,11 @@ class HostPipeline:
             self.s_in, self.s_run, self.s_nav, s2 = (torch.cuda.Stream(dev) for _ in range(4))
         index.set_stream(self.s_run.cuda_stream)
         self.handles = [(index, self.s_run)]
+        self._mass_before = None
+        if stop_mass is not None:   # before the clone view is made: an invalid value raises here with nothing to undo, and the clone inherits it
+            before = index.stop_mass
+            index.set_stop_mass(stop_mass)
+            self._mass_before = before
         if self.two:
             twin = index.clone_view()
             twin.set_stream(s2.cuda_stream)
@@ -289,6 +296,9 @@ class HostPipeline:
     def close(self) -> None:
         """Waits for the batches in flight and destroys the clone view of `two_handles` (the index itself stays open)."""
         self.drain()
+        if self._mass_before is not None:   # the constructor's stop_mass ends with the pipeline
+            self.index.set_stop_mass(self._mass_before)
+            self._mass_before = None
         for h, _ in self.handles[1:]:
             h.close()
             views = getattr(self.index, "_views", [])

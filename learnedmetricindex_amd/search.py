@@ -73,6 +73,7 @@ class Experiment:
     synthetic: bool = False
     evaluate: bool = False
     job: str = "unknown"
+    stop_mass: Optional[float] = None
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -93,9 +94,16 @@ class Experiment:
         p.add_argument("--synthetic", action="store_true",
                        help="generate stand-in vectors when the dataset files are missing (results are stamped synthetic)")
         p.add_argument("--eval", dest="evaluate", action="store_true", help="report recall@k against GPU brute force")
+        p.add_argument("--stop-mass", type=float, default=None,
+                       help="1-level indexes: a query stops visiting buckets once the visited ranks' probabilities sum to this "
+                            "(0 < mass <= 1); default: every query visits its whole budget")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
+        if a["stop_mass"] is not None and levels > 1:
+            p.error("--stop-mass needs a 1-level index (one value for --n-categories)")
+        if a["stop_mass"] is not None and not 0.0 < a["stop_mass"] <= 1.0:
+            p.error("--stop-mass must lie in (0, 1]")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -248,13 +256,13 @@ def run(exp: Experiment) -> Dict:
     index.prepare(nav, scan, placement, exp.n_categories)  # one upload; every budget below reuses the resident slab
     sink, out = ResultSink(), {}
     for budget in bucket_budgets(exp.buckets_perc, n_buckets_in_index):
-        dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k)
+        dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass)
         LOG.info("%d buckets: search %.4fs (inference %.4fs, within buckets %.4fs, scan %.4fs, merge %.4fs)", budget,
                  clock["search"], clock["inference"], clock["search_within_buckets"], clock["seq_search"], clock["sort"])
         if exp.evaluate:
             out[f"recall_{budget}"] = recall_against_bruteforce(scan_q, scan, knns, exp.k)
             LOG.info("%d buckets: recall@%d = %.5f", budget, exp.k, out[f"recall_{budget}"])
-        stem = exp.tag(f"learned-index-{exp.dataset}-{exp.size}", buck=budget)
+        stem = exp.tag(f"learned-index-{exp.dataset}-{exp.size}", buck=budget, **({} if exp.stop_mass is None else {"stop": exp.stop_mass}))
         sink.write(exp.dataset, exp.size, stem, dists, knns, algo="Learned-index", data=src.stamp(exp.dataset),
                    buildtime=build_s, querytime=clock["search"], size=exp.size, params=stem)
         out[budget] = (dists, knns, clock)

@@ -52,7 +52,8 @@ def estimate_bucket_work(index, sample_nav_t, nb: int, sizes) -> np.ndarray:
     probe = torch.empty((sample_nav_t.shape[0], nb), dtype=torch.int32, device=sample_nav_t.device)
     index.mlp_topk_device(sample_nav_t.contiguous(), nb, probe)
     torch.cuda.synchronize(sample_nav_t.device)
-    routed = np.bincount(probe.cpu().numpy().ravel(), minlength=sizes.shape[0]).astype(np.float64)
+    visited = probe.cpu().numpy().ravel()
+    routed = np.bincount(visited[visited >= 0], minlength=sizes.shape[0]).astype(np.float64)   # (-1: cut by the index's stop mass)
     return sizes * (routed[: sizes.shape[0]] + 1.0)
 
 
@@ -128,9 +129,17 @@ class ShardedSearcher:
     (at 8 ranks the replicated MLP was a sixth of a rank's step).  `calls_per_search` tells a caller that
     averages `Index.timings_mean()` how many C-ABI calls one search makes."""
 
-    def __init__(self, index, rank: int, world: int, group=None, shard_inference: bool = True, lib_comm=None):
+    def __init__(self, index, rank: int, world: int, group=None, shard_inference: bool = True, lib_comm=None,
+                 stop_mass: Optional[float] = None):
         """`lib_comm`: an ncclComm_t from `Index.comm_init` -- the result exchange then runs inside the library
-        (`lmi_allgather_merge`: ncclAllGather + merge kernel on the handle's stream) instead of torch.distributed."""
+        (`lmi_allgather_merge`: ncclAllGather + merge kernel on the handle's stream) instead of torch.distributed.
+        `stop_mass`: the probability-mass stop (`Index.set_stop_mass`), set on the rank's handle until `close()` gives
+        the handle its earlier value back; None leaves the handle's own setting.  Every rank cuts the order of the queries
+        it routes (its slice, or the whole batch), so the gathered order carries the -1s and every rank skips the same slots."""
+        self._mass_before = None
+        if stop_mass is not None:
+            self._mass_before = index.stop_mass
+            index.set_stop_mass(stop_mass)
         self.index, self.rank, self.world, self.group = index, rank, world, group
         self.lib_comm = lib_comm
         self.shard_inference = bool(shard_inference) and world > 1
@@ -141,6 +150,12 @@ class ShardedSearcher:
         # rank really WAITS for each exchange, the other ranks' lateness included; read with collective_ms() after a synchronize
         self.time_collectives = False
         self._coll = {"bucket_order_allgather": [], "result_allgather_merge": []}
+
+    def close(self) -> None:
+        """Ends the constructor's `stop_mass`: the handle gets the value it had before (the index itself stays open)."""
+        if self._mass_before is not None:
+            self.index.set_stop_mass(self._mass_before)
+            self._mass_before = None
 
     def _timed(self, name, fn, on_cuda: bool):
         if not self.time_collectives or self.world == 1:
@@ -247,9 +262,16 @@ class ReplicaSearcher:
     shard_inference = False   # (HostPipeline: nothing to route ahead of the search call)
     lib_comm = None
 
-    def __init__(self, index, rank: int, world: int, group=None):
+    def __init__(self, index, rank: int, world: int, group=None, stop_mass: Optional[float] = None):
+        """`stop_mass`: as `ShardedSearcher` (a rank's slice of the batch is cut by its own search call; `close()` ends it)."""
         self.index, self.rank, self.world, self.group = index, rank, world, group
         self._buf = None
+        self._mass_before = None
+        if stop_mass is not None:
+            self._mass_before = index.stop_mass
+            index.set_stop_mass(stop_mass)
+
+    close = ShardedSearcher.close
 
     def _buffers(self, per: int, nb: int, kout: int, dev):
         import torch
