@@ -103,10 +103,28 @@ LMI_API int lmi_set_fused_mlp(lmi_index *h, int mode);
  * the merge treat as an unvisited slot (dist = +inf, id = 0): kout and the output shapes do not change, n_buckets == 1
  * is unaffected.  Any other value (NaN included) is an error that leaves the setting as it was.  Per handle; a
  * lmi_clone_view copies its parent's value when it is made; may be changed between any two calls, the index is not
- * rebuilt.  lmi_mlp_proba and the multi-level calls (lmi_nav_order, lmi_search_tree: the walk ranks by LOCAL
- * probabilities, whose sum has no such meaning) ignore it.  All three ranking paths (lmi_set_fused_mlp) give
- * bit-identical orders. */
+ * rebuilt.  lmi_mlp_proba and the multi-level calls (lmi_nav_order, lmi_search_tree) ignore it: the walk ranks by LOCAL
+ * probabilities, whose running sum is not a covered probability; the walk's own stop is lmi_set_path_mass below, which
+ * accounts in path probabilities.  All three ranking paths (lmi_set_fused_mlp) give bit-identical orders. */
 LMI_API int lmi_set_stop_mass(lmi_index *h, float mass);
+
+/* Probability-mass stop of the multi-level walk (lmi_nav_order, lmi_search_tree; no reference counterpart).  The product of
+ * the local probabilities along a path is a distribution over the leaves, so the walk can account for how much of it the
+ * buckets it has recorded cover -- without changing its order: priorities (the local probability), pop order and tie rule
+ * (the later-pushed entry wins; the root's children are pushed least probable first) stay the reference's.
+ * Every queue entry carries a path mass m beside its priority: a root child has m = p, the probability lmi_mlp_proba
+ * returns for it; a child pushed when an internal entry of mass M is expanded has m = M * p_local, one binary32 multiply,
+ * rounded before anything is added to it.  When the walk records a bucket of mass m -- a listed bucket without objects
+ * (child_bucket -1) included; a dropped path (-2) is not recorded and adds nothing -- c_0 = m_0 and c_j = c_{j-1} + m_j in
+ * recording order, each a binary32 add.  The first bucket is always recorded; after j recorded buckets the query goes on
+ * popping only while c_{j-1} < mass (a binary32 compare, false on NaN).  A stopped query pops nothing more and never
+ * queues for a model again; its remaining slab_ids / entries slots stay -1, which lmi_scan_topk treats as unvisited
+ * (dist = +inf, id = 0): kout and the output shapes do not change, n_buckets == 1 is unaffected.
+ * mass == 0 (default): off, the walk runs the same kernels as without the setting.  Any value outside [0, 1] (NaN
+ * included) is an error that leaves the setting as it was.  Per handle; a lmi_clone_view copies its parent's value when it
+ * is made; may be changed between any two calls.  Independent of lmi_set_stop_mass: the 1-level calls (lmi_mlp_topk,
+ * lmi_search, lmi_pipeline_submit, lmi_mlp_proba) ignore this setting, the walk ignores that one. */
+LMI_API int lmi_set_path_mass(lmi_index *h, float mass);
 
 /* Multi-level index (len(n_categories) > 1; LearnedIndex.py:216-325, PriorityQueue.py:18-94): the models of
  * the internal nodes and the tree.  Model 0 is the root (lmi_set_mlp); lmi_nav_set_model sets model_id >= 1

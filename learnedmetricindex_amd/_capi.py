@@ -38,6 +38,7 @@ SIGNATURES = {
     "lmi_set_mlp": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "lmi_set_fused_mlp": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_set_stop_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
+    "lmi_set_path_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
     "lmi_set_metric": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_nav_set_model": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "lmi_nav_set_tree": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
@@ -145,6 +146,7 @@ class Index:
         self.d = None
         self.L = None
         self.stop_mass = 0.0
+        self.path_mass = 0.0
         if chunk_rows is not None:
             _check(lib().lmi_set_chunk_rows(self._h, int(chunk_rows)))
         if prefilter is None and os.environ.get("LMI_PREFILTER") is not None:
@@ -169,7 +171,7 @@ class Index:
         v = Index.__new__(Index)
         v._h = _vp()
         _check(lib().lmi_clone_view(self._h, ctypes.byref(v._h)))
-        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric", "stop_mass"):
+        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric", "stop_mass", "path_mass"):
             setattr(v, a, getattr(self, a, None))
         v._views = []
         v._parent = self
@@ -255,6 +257,16 @@ class Index:
         `self.stop_mass` holds the value in force (a clone view starts with its parent's)."""
         _check(lib().lmi_set_stop_mass(self._h, ctypes.c_float(mass)))
         self.stop_mass = float(np.float32(mass))
+
+    def set_path_mass(self, mass: float) -> None:
+        """Probability-mass stop of the multi-level walk (`lmi_set_path_mass`; `nav_order`, `search_tree`): 0 = off
+        (default); 0 < mass <= 1: a query's walk ends once the path probabilities (the product of the local probabilities
+        along a bucket's path) of the buckets it has recorded sum to `mass` or more (binary32, in recording order); the
+        slots behind the stop are -1 = unvisited.  The walk's order does not change.  Anything else raises and changes
+        nothing.  `self.path_mass` holds the value in force (a clone view starts with its parent's); the 1-level calls
+        ignore it, as the walk ignores `stop_mass`."""
+        _check(lib().lmi_set_path_mass(self._h, ctypes.c_float(mass)))
+        self.path_mass = float(np.float32(mass))
 
     # ---- multi-level navigation ---------------------------------------------------------------
     @staticmethod

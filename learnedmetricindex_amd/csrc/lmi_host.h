@@ -109,6 +109,7 @@ struct lmi_index {
     std::vector<NodeModel> node_models;   // index = model id - 1
     int fused_mlp = 1;                    // lmi_set_fused_mlp: 0 never, 1 when the batch fills the chip, 2 always
     float stop_mass = 0.0f;               // lmi_set_stop_mass: 0 off; (0, 1]: a query's bucket order ends once this much probability is covered
+    float path_mass = 0.0f;               // lmi_set_path_mass: 0 off; (0, 1]: a query's walk ends once its recorded buckets cover this much path probability
     bool desc_dirty = true;
     DevBuf d_models;                      // ModelDesc[1 + node_models.size()]
     int fm_s0 = 0, fm_s1 = 0, fm_act0 = 0, fm_lds = 0, fm_logits_lds = 0;  // LDS plan of the current model set
@@ -119,6 +120,7 @@ struct lmi_index {
     bool tree_set = false;
     DevBuf gather_send, gather_recv;      // lmi_allgather_merge
     DevBuf pq_prob, pq_ent, pq_len, nav_len, nav_slab, nav_ent, nav_count, nav_colq, nav_active;
+    DevBuf pq_mass, nav_parent_mass, nav_cum;   // the path-mass stop: reserved only while it is on
 
     // ---- buckets ----
     bool building = false, built = false;
@@ -216,7 +218,7 @@ static void each_index_buf(lmi_index* h, F f) {
 template <class F>
 static void each_call_buf(lmi_index* h, F f) {
     DevBuf* b[] = {&h->gather_send, &h->gather_recv, &h->pq_prob, &h->pq_ent, &h->pq_len, &h->nav_len, &h->nav_slab, &h->nav_ent, &h->nav_count,
-                   &h->nav_colq, &h->nav_active, &h->aug_rows, &h->q_aug, &h->qn2, &h->stage, &h->qdelta, &h->qnorm, &h->qscale, &h->qfrag16,
+                   &h->nav_colq, &h->nav_active, &h->pq_mass, &h->nav_parent_mass, &h->nav_cum, &h->aug_rows, &h->q_aug, &h->qn2, &h->stage, &h->qdelta, &h->qnorm, &h->qscale, &h->qfrag16,
                    &h->eps2, &h->cand_cnt, &h->cand_row, &h->cand_s, &h->fallback, &h->pf_bound, &h->nkeep, &h->redo, &h->surv_row, &h->rs_flag,
                    &h->rs_active, &h->act[0], &h->act[1], &h->xfrag, &h->logits, &h->order, &h->q_nav, &h->q_srch, &h->m, &h->cb_start,
                    &h->item_base, &h->part_base, &h->stats, &h->head, &h->slot_local, &h->slot_col, &h->colmap, &h->qfrag, &h->grp, &h->col_thr,

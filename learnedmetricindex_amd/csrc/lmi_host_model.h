@@ -70,6 +70,13 @@ static int rank_enqueue(hipStream_t st, const float* d_logits, int nq, int L, in
     return 0;
 }
 
+extern "C" LMI_API int lmi_set_path_mass(lmi_index* h, float mass) {
+    if (!h) return fail("lmi_set_path_mass: NULL handle");
+    if (!(mass >= 0.0f && mass <= 1.0f)) return fail("lmi_set_path_mass: mass %g outside [0, 1] (0: off)", (double)mass);
+    h->path_mass = mass;
+    return 0;
+}
+
 extern "C" LMI_API int lmi_set_fused_mlp(lmi_index* h, int on) {
     if (!h) return fail("lmi_set_fused_mlp: NULL handle");
     if (on < 0 || on > 2) return fail("lmi_set_fused_mlp: mode %d outside 0..2", on);
@@ -168,6 +175,7 @@ static int build_descs(lmi_index* h) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_PROBA>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_NAV>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_TOPK_STOP>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_NAV_MASS>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
     }
     h->desc_dirty = false;
     return 0;
@@ -361,6 +369,8 @@ extern "C" LMI_API int lmi_mlp_proba(lmi_index* h, const float* queries_nav, int
 // Trees of up to NAV_ENQUEUE_ALL models: EVERY possible step is enqueued up front and a step whose predecessor left no query waiting
 // returns at once (nav_pop_kernel: prev_active) -- no host round trip inside the walk, the call is asynchronous like every other
 // enqueue.  Larger trees: steps in batches of 4 with the count read back after each (one small synchronisation).
+// The path-mass stop (lmi_set_path_mass > 0): the same launches in their mass forms (mlp_fused_kernel<FM_NAV_MASS>, nav_pop_mass_kernel /
+// nav_pop_lds_mass_kernel) with three more buffers; a single bucket per query (nb == 1) is never cut, so it takes the plain forms.
 constexpr int NAV_ENQUEUE_ALL = 16;
 static int nav_check(lmi_index* h, int nq, int nb, const char* who) {
     if (!h->tree_set) return fail("%s: no tree (lmi_nav_set_model / lmi_nav_set_tree)", who);
@@ -383,6 +393,12 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
     CHK(h->nav_len.reserve((size_t)nq * 4));
     CHK(h->nav_count.reserve((size_t)2 * (nm + 1) * 4));  // [2][nm + 1]: per-model counters + the step's active-query count
     CHK(h->nav_colq.reserve((size_t)nm * nq * 4));
+    const bool with_mass = h->path_mass > 0.0f && nb > 1;
+    if (with_mass) {
+        CHK(h->pq_mass.reserve((size_t)nq * cap * 4));
+        CHK(h->nav_parent_mass.reserve((size_t)nq * 4));
+        CHK(h->nav_cum.reserve((size_t)nq * 4));
+    }
     FillRanges Z;
     Z.count = 0;
     bool fill_ok = true;
@@ -392,6 +408,10 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
     fill(d_slab, (long long)nq * nb, 0xFFFFFFFFu);
     fill(d_ent, (long long)nq * nb, 0xFFFFFFFFu);
     fill(h->nav_count.p, 2 * (nm + 1), 0u);
+    if (with_mass) {
+        fill(h->nav_cum.p, nq, 0u);
+        fill(h->nav_parent_mass.p, nq, 0x3F800000u);  // 1.0f: the root's children get their own probability as their mass
+    }
     if (!fill_ok) return fail("internal: more than %d fill ranges queued (%s:%d)", FillRanges::MAXR, __FILE__, __LINE__);
     Z.ts = tsp(h, ST_MLP0);
     fill_ranges_kernel<<<h->num_cus * 2, 256, 0, h->stream>>>(Z);
@@ -404,7 +424,13 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
     P.cap = cap;
     P.child_offset = h->d_child_offset.as<int>();
     P.reverse = 1;  // root children: least probable first (LearnedIndex.py:220-227)
-    mlp_fused_kernel<FM_NAV><<<cdiv(nq, FM_COLS), 256, h->fm_lds, h->stream>>>(P);
+    if (with_mass) {
+        P.pq_mass = h->pq_mass.as<float>();
+        P.parent_mass = h->nav_parent_mass.as<float>();
+        mlp_fused_kernel<FM_NAV_MASS><<<cdiv(nq, FM_COLS), 256, h->fm_lds, h->stream>>>(P);
+    } else {
+        mlp_fused_kernel<FM_NAV><<<cdiv(nq, FM_COLS), 256, h->fm_lds, h->stream>>>(P);
+    }
     HIPCHK(hipGetLastError());
     P.reverse = 0;
     P.col_query = h->nav_colq.as<int>();
@@ -417,6 +443,14 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
     N.out_slab = d_slab;
     N.out_ent = d_ent;
     N.col_query = h->nav_colq.as<int>();
+    NavMass S;
+    memset(&S, 0, sizeof(S));
+    if (with_mass) {
+        S.pq_mass = h->pq_mass.as<float>();
+        S.cum = h->nav_cum.as<float>();
+        S.parent_mass = h->nav_parent_mass.as<float>();
+        S.mass = h->path_mass;
+    }
     int* counts = h->nav_count.as<int>();
     // A step pops entries until the query hits an internal node; a query expands each node at most once, so there are
     // at most (models) steps.
@@ -431,13 +465,19 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
             N.node_count = counts + par * (nm + 1);
             N.active = counts + par * (nm + 1) + nm;
             N.prev_active = (all && it > 0) ? counts + (1 - par) * (nm + 1) + nm : nullptr;
-            if (pop_lds) nav_pop_lds_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N);
-            else nav_pop_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N);
+            if (with_mass) {
+                if (pop_lds) nav_pop_lds_mass_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N, S);
+                else nav_pop_mass_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N, S);
+            } else {
+                if (pop_lds) nav_pop_lds_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N);
+                else nav_pop_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N);
+            }
             HIPCHK(hipGetLastError());
             P.node_count = N.node_count;
             P.zero_counts = counts + (1 - par) * (nm + 1);
             P.n_zero = nm + 1;
-            mlp_fused_kernel<FM_NAV><<<cdiv(nq, FM_COLS) + nm, 256, h->fm_lds, h->stream>>>(P);
+            if (with_mass) mlp_fused_kernel<FM_NAV_MASS><<<cdiv(nq, FM_COLS) + nm, 256, h->fm_lds, h->stream>>>(P);
+            else mlp_fused_kernel<FM_NAV><<<cdiv(nq, FM_COLS) + nm, 256, h->fm_lds, h->stream>>>(P);
             HIPCHK(hipGetLastError());
             last_par = par;
         }

@@ -18,6 +18,8 @@
 //                 sum to `stop_mass` or more (lmi_set_stop_mass; no reference counterpart)
 //       FM_PROBA  probs[q][L] descending + classes[q][L]                        (model.py:238-241)
 //       FM_NAV    the node's children pushed into the query's priority queue    (LearnedIndex.py:220-227, 289-299)
+//       FM_NAV_MASS  the same, and every pushed child's path mass = its parent's path mass * its local probability, one binary32
+//                 multiply (lmi_set_path_mass; no reference counterpart)
 //     Final layers wider than FM_MAXH keep their logits in global memory and the host runs the separate ranking
 //     kernels afterwards.
 #pragma once
@@ -30,7 +32,7 @@ constexpr int FM_COLS = 32;     // columns per block = one MFMA column block
 constexpr int FM_CHUNK = 96;    // input features staged per step of layer 0 (12 k-groups: a multiple of the 3-deep weight prefetch)
 constexpr int FM_CHUNK_S = FM_CHUNK + 1;
 constexpr int FM_MAXH = 512;    // widest layer whose outputs stay in LDS
-enum { FM_TOPK = 0, FM_PROBA = 1, FM_NAV = 2, FM_TOPK_STOP = 3 };
+enum { FM_TOPK = 0, FM_PROBA = 1, FM_NAV = 2, FM_TOPK_STOP = 3, FM_NAV_MASS = 4 };
 
 struct ModelDesc {  // device copy of one model's shape and weights (root = model 0, internal nodes 1..)
     int n_layers;
@@ -68,6 +70,9 @@ struct FusedParams {
     int n_zero;
     unsigned long long* ts;      // nullable: device stamp of the launch's start (lmi_kernels.h)
     float stop_mass;             // FM_TOPK_STOP: in (0, 1]
+    // FM_NAV_MASS: the path masses beside the priorities
+    float* pq_mass;              // [cap][nq] like pq_prob
+    const float* parent_mass;    // [nq] path mass of the entry whose children this launch pushes (1 before the root launch)
 };
 
 template <int MODE>
@@ -113,6 +118,7 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
     float* act0 = fm_smem + 2 * FM_COLS * FM_CHUNK_S;
     float* act1 = act0 + P.act0_floats;
     const int L = M.dims[n_layers];
+    constexpr bool NAV = MODE == FM_NAV || MODE == FM_NAV_MASS;
 
     for (int li = 0; li < n_layers; ++li) {
         const int J = M.dims[li + 1];
@@ -264,7 +270,7 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
     if (!P.logits_in_lds) return;  // wide output layer: the host runs rank_classes_kernel / softmax_ranked_kernel
     const float* lg = ((n_layers - 1) & 1) ? act1 : act0;
     const int SL = ((n_layers - 1) & 1) ? P.s1 : P.s0;
-    if (MODE == FM_PROBA || MODE == FM_NAV) {
+    if (MODE == FM_PROBA || NAV) {
         // canonical softmax terms: row max, then the sum of expf(l - max) in class order (softmax_ranked_kernel)
         if (tid < ncols) {
             const float* l = lg + tid * SL;
@@ -307,7 +313,9 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
         }
     }
     int base = 0;
-    if (MODE == FM_NAV) base = P.pq_len[q];
+    if (NAV) base = P.pq_len[q];
+    float pmass = 1.0f;
+    if (MODE == FM_NAV_MASS) pmass = P.parent_mass[q];
     float pv = INFINITY;
     int pi = -1;
     for (int t = 0; t < T; ++t) {
@@ -345,6 +353,9 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
                     if (pos < P.cap) {  // entry-major: the pop kernel's threads (one per query) read coalesced
                         P.pq_prob[(size_t)pos * P.nq + q] = pr;
                         P.pq_ent[(size_t)pos * P.nq + q] = cls >= 0 ? P.child_offset[model] + cls : -1;
+                        // the product is rounded and stored here; the pop kernel adds it up (the root's parent mass is 1: the child's mass
+                        // is its probability, exactly)
+                        if (MODE == FM_NAV_MASS) P.pq_mass[(size_t)pos * P.nq + q] = __fmul_rn(pmass, pr);
                     }
                 }
             }
@@ -352,7 +363,7 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
         pv = bv;
         pi = bi;
     }
-    if (MODE == FM_NAV && sub == 0 && live) P.pq_len[q] = min(P.cap, base + L);
+    if (NAV && sub == 0 && live) P.pq_len[q] = min(P.cap, base + L);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -379,6 +390,14 @@ struct NavParams {
     const int* prev_active;   // nullable: the same count of the step before -- 0: the walk is over, this launch returns (the host then
                               // enqueues every possible step up front instead of reading the count back)
 };
+// the path-mass stop (lmi_set_path_mass): what the *_mass_kernel forms take beside NavParams (a struct of its own: the plain forms keep
+// their kernel arguments, and with them their code, as they are)
+struct NavMass {
+    const float* pq_mass;     // [cap][nq] path mass of every queue entry (mlp_fused_kernel<FM_NAV_MASS>)
+    float* cum;               // [nq] path mass of the buckets recorded so far (0 before the walk)
+    float* parent_mass;       // [nq] path mass of the internal entry the query popped in this step
+    float mass;               // in (0, 1]
+};
 
 // The queries of a wave that stopped at an internal node queue up for its model: ONE counter atomic per (wave, model) and one for the
 // step's count of waiting queries (round 5: 2 atomics per query on 1 + n_models addresses were most of the step -- 10 000 queries: 40-100 us).
@@ -403,95 +422,16 @@ __device__ __forceinline__ void nav_push(const NavParams& P, int q, int my_cm) {
     if (lane == first) atomicAdd(P.active, total);
 }
 
-__global__ __launch_bounds__(256) void nav_pop_kernel(NavParams P) {
-    if (P.prev_active && *P.prev_active == 0) return;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = q < P.nq;
-    int have = live ? P.out_len[q] : P.nb;
-    const float* pp = P.pq_prob + (live ? q : 0);   // entry i at [i * nq]
-    int* pe = P.pq_ent + (live ? q : 0);
-    const int len = (live && have < P.nb) ? P.pq_len[q] : 0;
-    // Bucket pops change nothing but the queue, so they continue within this step; the walk pauses at the first
-    // internal node (its children's probabilities come from this step's grouped MLP launch) -- the same sequence
-    // of pops as the reference's one-pop-per-iteration loop, in fewer launches.
-    int my_cm = -1;
-    while (len > 0) {
-        float best = 0.0f;
-        int bi = -1;
-        for (int i = 0; i < len; ++i) {
-            if (pe[(size_t)i * P.nq] < 0) continue;
-            const float v = pp[(size_t)i * P.nq];
-            if (bi < 0 || v >= best) { best = v; bi = i; }  // >=: the later entry wins a tie
-        }
-        if (bi < 0) break;  // queue exhausted: the remaining slots stay EMPTY (the reference would fail here)
-        const int ent = pe[(size_t)bi * P.nq];
-        pe[(size_t)bi * P.nq] = -1;
-        const int cm = P.child_model[ent], cb = P.child_bucket[ent];
-        if (cm >= 0) { my_cm = cm; break; }
-        if (cb >= -1) {
-            P.out_slab[(size_t)q * P.nb + have] = cb;
-            P.out_ent[(size_t)q * P.nb + have] = ent;
-            P.out_len[q] = ++have;
-            if (have >= P.nb) break;
-        }
-    }
-    nav_push(P, q, my_cm);
-}
-
-// The same step for trees whose queues fit LDS (cap <= NAV_LDS_CAP entries: [10, 10] has 110): a wave per 64 queries reads their queues
-// ONCE (entry-major: a 256-byte row per entry) and every pop scans LDS instead of global memory -- a step's ~10 pops x up to 110
-// entries per query took 43-101 us of a 0.96-ms walk at 10 000 queries (round 5 trace, profiles/r05_nav.txt); same pops, same order.
-constexpr int NAV_LDS_CAP = 128;
-__global__ __launch_bounds__(64) void nav_pop_lds_kernel(NavParams P) {
-    extern __shared__ __attribute__((aligned(16))) char nav_smem[];
-    if (P.prev_active && *P.prev_active == 0) return;
-    float* sp = reinterpret_cast<float*>(nav_smem) + threadIdx.x;      // [cap][64]: this lane's column
-    int* se = reinterpret_cast<int*>(nav_smem) + P.cap * 64 + threadIdx.x;
-    const int q = blockIdx.x * 64 + threadIdx.x;
-    const bool live = q < P.nq;
-    int have = live ? P.out_len[q] : P.nb;
-    const int len = (live && have < P.nb) ? P.pq_len[q] : 0;
-    const float* pp = P.pq_prob + (live ? q : 0);
-    int* pe = P.pq_ent + (live ? q : 0);
-    int mx = len;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
-    for (int i0 = 0; i0 < mx; i0 += 16) {   // 32 loads in flight per lane, then their LDS stores (clamped addresses: no branch per load)
-        float v[16];
-        int e[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const size_t o = (size_t)min(i0 + j, max(len - 1, 0)) * P.nq;
-            v[j] = pp[o];
-            e[j] = pe[o];
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (i0 + j < len) { sp[(i0 + j) * 64] = v[j]; se[(i0 + j) * 64] = e[j]; }
-    }
-    int my_cm = -1;
-    while (len > 0) {
-        float best = 0.0f;
-        int bi = -1;
-        for (int i = 0; i < len; ++i) {
-            const int e = se[i * 64];
-            const float v = sp[i * 64];
-            if (e >= 0 && (bi < 0 || v >= best)) { best = v; bi = i; }  // >=: the later entry wins a tie
-        }
-        if (bi < 0) break;
-        const int ent = se[bi * 64];
-        se[bi * 64] = -1;
-        pe[(size_t)bi * P.nq] = -1;
-        const int cm = P.child_model[ent], cb = P.child_bucket[ent];
-        if (cm >= 0) { my_cm = cm; break; }
-        if (cb >= -1) {
-            P.out_slab[(size_t)q * P.nb + have] = cb;
-            P.out_ent[(size_t)q * P.nb + have] = ent;
-            P.out_len[q] = ++have;
-            if (have >= P.nb) break;
-        }
-    }
-    nav_push(P, q, my_cm);
-}
+// The two pop kernels (lmi_nav_pop.h), compiled twice: as they were, and in their mass forms for the path-mass stop.  Two compilations
+// of one text rather than a `template <bool MASS>` body behind the named kernels: inlined from such a body (by reference or by value),
+// hipcc laid the plain kernels out differently (tools/isa_diff.py), and the walk without the stop is to keep its code instruction for
+// instruction.
+constexpr int NAV_LDS_CAP = 128;   // queues of up to this many entries are popped from LDS (nav_pop_lds_kernel)
+#define LMI_NAV_MASS 0
+#include "lmi_nav_pop.h"
+#undef LMI_NAV_MASS
+#define LMI_NAV_MASS 1
+#include "lmi_nav_pop.h"
+#undef LMI_NAV_MASS
 
 }  // namespace lmi

@@ -114,7 +114,8 @@ def _frame_fingerprint(df: pd.DataFrame, full: bool) -> int:
 class LearnedIndex(Logger):
     _WORKSPACE_BYTES = 6 << 30  # per-call device workspace budget of one search chunk
     _NAV_QUEUE_BYTES = 4 << 30  # multi-level walk: per-query priority queues hold one 8-byte entry per child of every node
-                                # (lmi_nav_order refuses 2^31 entries); larger batches are walked in query chunks
+                                # (12 bytes with the path-mass stop on; lmi_nav_order refuses 2^31 entries); larger batches
+                                # are walked in query chunks
 
     def __init__(self, root_model: NeuralNetwork, internal_models: Dict[Tuple, NeuralNetwork],
                  bucket_paths: List[Tuple]):
@@ -247,13 +248,14 @@ class LearnedIndex(Logger):
         return eng
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
-                        k: int = 10, stop_mass: Optional[float] = None):
+                        k: int = 10, stop_mass: Optional[float] = None, path_mass: Optional[float] = None):
         """`search` against the index already resident in HBM (after `prepare`, a previous `search`
-        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass` as there."""
+        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass` and `path_mass` as there."""
         self._check_stop_mass(stop_mass, n_categories)
+        self._check_path_mass(path_mass, n_categories)
         assert self._engine is not None, "no resident index: call prepare()/search() or index_io.load_index()"
         return self._search_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, k,
-                                 time.time(), stop_mass)
+                                 time.time(), stop_mass, path_mass)
 
     @staticmethod
     def _check_stop_mass(stop_mass, n_categories) -> None:
@@ -261,6 +263,13 @@ class LearnedIndex(Logger):
         probabilities, so it is refused there before any work is done."""
         if stop_mass is not None and len(n_categories) > 1:
             raise ValueError("stop_mass is not supported on a multi-level index (the walk ranks buckets by local probabilities)")
+
+    @staticmethod
+    def _check_path_mass(path_mass, n_categories) -> None:
+        """`path_mass` is the stop of the multi-level walk; a 1-level index has `stop_mass` for the same purpose.  Refused
+        before any work is done."""
+        if path_mass is not None and len(n_categories) == 1:
+            raise ValueError("path_mass is the stop of the multi-level walk; on a 1-level index use stop_mass")
 
     # ------------------------------------------------------------------------------------------
     def insert(self, data_navigation_new: pd.DataFrame, data_search_new: Optional[pd.DataFrame] = None,
@@ -339,6 +348,7 @@ class LearnedIndex(Logger):
         metric: str = "ip",
         assume_unchanged: bool = False,
         stop_mass: Optional[float] = None,
+        path_mass: Optional[float] = None,
     ) -> Tuple[npt.NDArray, npt.NDArray[np.uint32], Dict[str, float]]:
         """Searches for `k` nearest neighbors of every query in its `n_buckets` most probable buckets.
         Parameters and return values as the reference (LearnedIndex.py:41-83).  `metric` (an extension; the
@@ -347,21 +357,31 @@ class LearnedIndex(Logger):
         built from, so its bytes are not fingerprinted again (see `prepare`); the default re-checks them on every call.
         `stop_mass` (an extension, 1-level indexes only; `lmi_set_stop_mass`): None = off; 0 < stop_mass <= 1: a query stops
         visiting buckets once the probabilities of the ranks it has visited sum to `stop_mass` or more -- the ranks it skips
-        stay unvisited, the result shapes do not change.  It holds for this call only.  ValueError on a multi-level index."""
+        stay unvisited, the result shapes do not change.  It holds for this call only.  ValueError on a multi-level index.
+        `path_mass` (an extension, multi-level indexes only; `lmi_set_path_mass`): None = off; 0 < path_mass <= 1: the walk keeps
+        its order, and a query stops once the path probabilities (the product of the local probabilities along a bucket's path)
+        of the buckets it has recorded sum to `path_mass` or more -- the slots behind the stop stay unvisited, the result shapes
+        do not change.  It holds for this call only.  ValueError on a 1-level index (use `stop_mass` there)."""
         self._check_stop_mass(stop_mass, n_categories)
+        self._check_path_mass(path_mass, n_categories)
         s = time.time()
         eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged)
-        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass)
+        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass)
 
-    def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None):
-        if stop_mass is None:
+    def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None):
+        if stop_mass is None and path_mass is None:
             return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
-        before = eng.stop_mass   # the engine's own setting comes back afterwards: a later call without the argument is as before
-        eng.set_stop_mass(stop_mass)
+        # the engine's own settings come back afterwards: a later call without the arguments is as before
+        before = eng.stop_mass, eng.path_mass
         try:
+            if stop_mass is not None:
+                eng.set_stop_mass(stop_mass)
+            if path_mass is not None:
+                eng.set_path_mass(path_mass)
             return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         finally:
-            eng.set_stop_mass(before)
+            eng.set_stop_mass(before[0])
+            eng.set_path_mass(before[1])
 
     def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
         measured_time = defaultdict(float)
@@ -444,7 +464,8 @@ class LearnedIndex(Logger):
     def _nav_chunk(self) -> int:
         """Queries per lmi_nav_order call: queue memory under _NAV_QUEUE_BYTES and under the call's 2^31-entry limit."""
         cap = max(1, getattr(self, "_nav_cap", 0) or len(self._entry_paths))
-        return max(1, min(self._NAV_QUEUE_BYTES // (8 * cap), ((1 << 31) - 1) // cap))
+        entry_bytes = 12 if self._engine is not None and self._engine.path_mass > 0 else 8   # priority + child index (+ path mass)
+        return max(1, min(self._NAV_QUEUE_BYTES // (entry_bytes * cap), ((1 << 31) - 1) // cap))
 
     @log_runtime(INFO, "Precomputed bucket order time: {}")
     def _precompute_bucket_order(self, queries_navigation: npt.NDArray[np.float32], n_buckets: int,
@@ -452,7 +473,8 @@ class LearnedIndex(Logger):
         """(bucket_order int32[nq, n_buckets, n_levels], inference seconds) -- LearnedIndex.py:163-252.
 
         1 level: lmi_mlp_topk on the root model.  More levels: lmi_nav_order on the resident index (`prepare`
-        uploaded the tree); the visited buckets' flat child indices are mapped back to their paths."""
+        uploaded the tree); the visited buckets' flat child indices are mapped back to their paths.  With the path-mass stop on
+        (`Index.set_path_mass` on the resident engine) the slots behind a query's stop are EMPTY_VALUE paths."""
         assert self.root_model is not None, "Model is not trained, call `build` first."
         qn = np.ascontiguousarray(queries_navigation, dtype=np.float32)
         n_queries, n_levels = qn.shape[0], len(n_categories)

@@ -74,6 +74,7 @@ class Experiment:
     evaluate: bool = False
     job: str = "unknown"
     stop_mass: Optional[float] = None
+    path_mass: Optional[float] = None
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -97,6 +98,9 @@ class Experiment:
         p.add_argument("--stop-mass", type=float, default=None,
                        help="1-level indexes: a query stops visiting buckets once the visited ranks' probabilities sum to this "
                             "(0 < mass <= 1); default: every query visits its whole budget")
+        p.add_argument("--path-mass", type=float, default=None,
+                       help="multi-level indexes: a query's walk stops once the path probabilities of the buckets it has recorded "
+                            "sum to this (0 < mass <= 1); default: every query visits its whole budget")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -104,6 +108,10 @@ class Experiment:
             p.error("--stop-mass needs a 1-level index (one value for --n-categories)")
         if a["stop_mass"] is not None and not 0.0 < a["stop_mass"] <= 1.0:
             p.error("--stop-mass must lie in (0, 1]")
+        if a["path_mass"] is not None and levels == 1:
+            p.error("--path-mass needs a multi-level index (on a 1-level index use --stop-mass)")
+        if a["path_mass"] is not None and not 0.0 < a["path_mass"] <= 1.0:
+            p.error("--path-mass must lie in (0, 1]")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -256,13 +264,15 @@ def run(exp: Experiment) -> Dict:
     index.prepare(nav, scan, placement, exp.n_categories)  # one upload; every budget below reuses the resident slab
     sink, out = ResultSink(), {}
     for budget in bucket_budgets(exp.buckets_perc, n_buckets_in_index):
-        dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass)
+        dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass,
+                                                     path_mass=exp.path_mass)
         LOG.info("%d buckets: search %.4fs (inference %.4fs, within buckets %.4fs, scan %.4fs, merge %.4fs)", budget,
                  clock["search"], clock["inference"], clock["search_within_buckets"], clock["seq_search"], clock["sort"])
         if exp.evaluate:
             out[f"recall_{budget}"] = recall_against_bruteforce(scan_q, scan, knns, exp.k)
             LOG.info("%d buckets: recall@%d = %.5f", budget, exp.k, out[f"recall_{budget}"])
-        stem = exp.tag(f"learned-index-{exp.dataset}-{exp.size}", buck=budget, **({} if exp.stop_mass is None else {"stop": exp.stop_mass}))
+        stem = exp.tag(f"learned-index-{exp.dataset}-{exp.size}", buck=budget, **({} if exp.stop_mass is None else {"stop": exp.stop_mass}),
+                       **({} if exp.path_mass is None else {"pathmass": exp.path_mass}))
         sink.write(exp.dataset, exp.size, stem, dists, knns, algo="Learned-index", data=src.stamp(exp.dataset),
                    buildtime=build_s, querytime=clock["search"], size=exp.size, params=stem)
         out[budget] = (dists, knns, clock)
