@@ -161,6 +161,30 @@ LMI_API int lmi_search_tree(lmi_index *h, const float *queries_nav, const float 
  * FLT_MAX.  Internally every stored vector carries the column -xn/2 (lmi_bucket_read does not return it). */
 LMI_API int lmi_set_metric(lmi_index *h, int metric);
 
+/* How a built index keeps its scan vectors (call before lmi_buckets_begin, like lmi_set_metric: the value takes effect at the next
+ * lmi_buckets_begin; default LMI_STORAGE_F32).  No reference counterpart (the reference keeps the DataFrame).
+ *   LMI_STORAGE_F32  a row-major f32 image (exact re-rank, fallback, read-back, mutation) + the prefilter's fp16 fragments.
+ *   LMI_STORAGE_F16  the fp16 fragments ONLY: a third of the device memory, for vectors that are binary16-exact (data distributed
+ *                    as 16-bit floats).  lmi_buckets_add_rows / _add_owned_rows still take f32 rows; each piece is converted as it
+ *                    arrives and no f32 image of more than the staged piece ever exists.  The LIBRARY decides, on the device, whether
+ *                    the data is admissible: every stored x is finite and exactly representable in binary16 (subnormals included),
+ *                    and so is x * s for the index scale s (the power of two with max|x| * s in [0.5, 1); only a scale below 1, i.e.
+ *                    max|x| >= 1, can lose bits).  Inadmissible data: lmi_buckets_end fails, the message names the condition, and the
+ *                    handle is left without an index (lmi_buckets_begin may be called again) -- nothing approximate is ever served.
+ *                    Widening a half and undoing a power-of-two scale are exact, so every search returns bit for bit what
+ *                    LMI_STORAGE_F32 returns for the same rows, and lmi_bucket_read returns the original f32 rows.  The exact
+ *                    re-rank gathers a survivor's row from 16-byte fragment pieces instead of one contiguous row: that is the price.
+ *                    Refused with LMI_STORAGE_F16 (the handle stays as it was): LMI_METRIC_L2 (the -|x|^2/2 column is not
+ *                    fp16-exact), lmi_set_prefilter(0) (the all-f32 scan needs f32 fragments), a device whose fp16 self-test
+ *                    failed, and lmi_buckets_insert / lmi_buckets_delete -- mutation of a compact index is a follow-up.
+ * Any other value is an error.  lmi_knn_ip keeps an LMI_STORAGE_F32 index of its own. */
+#define LMI_STORAGE_F32 0
+#define LMI_STORAGE_F16 1
+LMI_API int lmi_set_storage(lmi_index *h, int storage);
+/* Device bytes of the index images the handle holds at this moment: the vector images, the ids and the per-bucket tables -- not the
+ * per-call workspaces, not the ingest staging.  Valid from lmi_buckets_begin on (a clone view reports its parent's images). */
+LMI_API int lmi_index_bytes(lmi_index *h, int64_t *bytes);
+
 /* Bucket-contiguous index in HBM.
  * begin: labels[N] = data_prediction[:,0] (bucket of every object, 0 <= label < L), ids[N] = the
  *        DataFrame index labels (NULL -> 1..N, search.py:190-191), owned[L] = which buckets this

@@ -40,6 +40,8 @@ SIGNATURES = {
     "lmi_set_stop_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
     "lmi_set_path_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
     "lmi_set_metric": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lmi_set_storage": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lmi_index_bytes": (ctypes.c_int, [_vp, _i64p]),
     "lmi_nav_set_model": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "lmi_nav_set_tree": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     "lmi_nav_order": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -131,15 +133,44 @@ def _np(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def f16_admissible(x):
+    """(ok, reason): whether `storage="f16"` (LMI_STORAGE_F16) would accept the scan vectors `x` -- the library's rule
+    (include/lmi_hip.h, decided there on the device) in numpy, for callers who want to know before they upload.  Every value
+    must be finite and exactly representable in binary16, and so must the value times the index scale: the power of two `s`
+    with max|x| * s in [0.5, 1)."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.size == 0:
+        return True, "admissible"
+    if not np.isfinite(x).all():
+        return False, "a value is not finite (inf or NaN)"
+    with np.errstate(over="ignore"):
+        if not np.array_equal(x.astype(np.float16).astype(np.float32), x):
+            return False, "a value is not exactly representable in binary16"
+    m = float(np.abs(x).max())
+    s = np.float32(1.0) if m == 0.0 else np.float32(np.ldexp(1.0, -int(np.frexp(m)[1])))
+    xs = x * s   # a power of two: exact in binary32
+    if not np.array_equal(xs.astype(np.float16).astype(np.float32), xs):
+        return False, f"a value times the index scale {float(s):g} is not exactly representable in binary16"
+    return True, "admissible"
+
+
 class Index:
     """One device-resident index: thin, typed wrapper over an `lmi_index*`."""
 
     METRICS = {"ip": 0, "l2": 1}
+    STORAGES = {"f32": 0, "f16": 1}
 
     def __init__(self, device: int = 0, chunk_rows: Optional[int] = None, prefilter: Optional[bool] = None,
-                 metric: str = "ip"):
+                 metric: str = "ip", storage: str = "f32"):
         self._h = _vp()
         _check(lib().lmi_create(int(device), ctypes.byref(self._h)))
+        try:
+            self._configure(device, chunk_rows, prefilter, metric, storage)
+        except BaseException:
+            self.close()   # a refused setting leaves no handle behind
+            raise
+
+    def _configure(self, device, chunk_rows, prefilter, metric, storage) -> None:
         self.device = int(device)
         self.n_classes = None
         self.d_nav = None
@@ -156,6 +187,25 @@ class Index:
         if metric != "ip":  # "l2": squared Euclidean distances instead of 1 - inner product
             _check(lib().lmi_set_metric(self._h, self.METRICS[metric]))
         self.metric = metric
+        self.storage = "f32"
+        if storage != "f32":  # "f16": the fp16 fragments only, for binary16-exact vectors (lmi_set_storage)
+            self.set_storage(storage)
+
+    def set_storage(self, storage: str) -> None:
+        """"f32" (default) or "f16" (`lmi_set_storage`): how the next `buckets_begin` stores the scan vectors.  "f16" keeps the
+        prefilter's fp16 fragments only -- a third of the memory, same results bit for bit -- and `buckets_end` refuses data
+        that is not binary16-exact (`f16_admissible`).  Not with metric "l2", `prefilter=False`, `insert` or `delete`."""
+        if storage not in self.STORAGES:
+            raise ValueError(f"storage must be one of {sorted(self.STORAGES)}, not {storage!r}")
+        _check(lib().lmi_set_storage(self._h, self.STORAGES[storage]))
+        self.storage = storage
+
+    def index_bytes(self) -> int:
+        """Device bytes of the index images held right now: vector images, ids, per-bucket tables (`lmi_index_bytes`; valid from
+        `buckets_begin` on)."""
+        out = ctypes.c_int64(0)
+        _check(lib().lmi_index_bytes(self._h, ctypes.byref(out)))
+        return out.value
 
     def close(self) -> None:
         for c in getattr(self, "_views", []):   # clones borrow this handle's memory: they go first
@@ -171,7 +221,7 @@ class Index:
         v = Index.__new__(Index)
         v._h = _vp()
         _check(lib().lmi_clone_view(self._h, ctypes.byref(v._h)))
-        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric", "stop_mass", "path_mass"):
+        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric", "storage", "stop_mass", "path_mass"):
             setattr(v, a, getattr(self, a, None))
         v._views = []
         v._parent = self

@@ -185,6 +185,30 @@ extern "C" LMI_API int lmi_set_metric(lmi_index* h, int metric) {
     return 0;
 }
 
+extern "C" LMI_API int lmi_set_storage(lmi_index* h, int storage) {
+    if (!h) return fail("lmi_set_storage: NULL handle");
+    if (storage != LMI_STORAGE_F32 && storage != LMI_STORAGE_F16)
+        return fail("lmi_set_storage: unknown storage %d (LMI_STORAGE_F32 = 0, LMI_STORAGE_F16 = 1)", storage);
+    if (h->building) return fail("lmi_set_storage: an index is being built; the storage is chosen before lmi_buckets_begin");
+    if (h->parent) return fail("lmi_set_storage: a clone view builds no index");
+    if (storage == LMI_STORAGE_F16)
+        if (const char* why = storage16_conflict(h)) return fail("lmi_set_storage: LMI_STORAGE_F16: %s", why);
+    h->storage_req = storage;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_index_bytes(lmi_index* h, int64_t* bytes) {
+    if (!h || !bytes) return fail("lmi_index_bytes: NULL argument");
+    if (!h->building && !h->built) return fail("lmi_index_bytes: no index (valid from lmi_buckets_begin on)");
+    // what the handle holds for the index right now: the vector images, the ids, the per-bucket tables (a clone view: its parent's)
+    const DevBuf* b[] = {&h->slab, &h->slab16, &h->rowmajor, &h->ids_slab, &h->d_nb_rows, &h->d_rb_start, &h->d_nch,
+                         &h->xscale, &h->xmaxbits, &h->bnorm, &h->bdelta};
+    int64_t t = 0;
+    for (const DevBuf* x : b) t += x->p ? (int64_t)x->cap : 0;
+    *bytes = t;
+    return 0;
+}
+
 extern "C" LMI_API int lmi_set_prefilter(lmi_index* h, int on) {
     if (!h) return fail("lmi_set_prefilter: NULL handle");
     if ((h->built || h->building) && (on != 0) != h->prefilter)

@@ -10,6 +10,7 @@
 #include "lmi_front.h"
 #include "lmi_tail.h"
 #include "lmi_mutate.h"
+#include "lmi_store16.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -141,7 +142,10 @@ struct lmi_index {
     bool pf_hw_ok = false;   // fp16 subnormal self-test passed on this device
     bool have16 = false;     // slab16 built by lmi_buckets_end
     int KG16 = 0;
-    int dp = 0;   // row pitch (floats) of `rowmajor`
+    int dp = 0;   // row pitch (floats) of `rowmajor` (LMI_STORAGE_F16: no such image; d rounded up to 8, the floats of a query the re-rank stages)
+    int storage = LMI_STORAGE_F32;       // of the index being built / built: LMI_STORAGE_F16 keeps slab16 only (lmi_store16.h)
+    int storage_req = LMI_STORAGE_F32;   // lmi_set_storage: what the next lmi_buckets_begin builds
+    bool attrs16_done = false;           // storage16_kernel_attrs ran for this handle's device
     DevBuf slab16, rowmajor, xscale, xmaxbits, bnorm, bdelta, qdelta;
     DevBuf qnorm, qscale, qfrag16, eps2, cand_cnt, cand_row, cand_s, fallback, pf_bound, nkeep, surv_row, rs_flag, rs_active;
     DevBuf grp_scratch;      // route_group_kernel<true>: the bucket sort of fan-outs past ROUTE_MAX_BUCKETS
@@ -232,6 +236,28 @@ static void each_call_buf(lmi_index* h, F f) {
 static bool low_d_form(const lmi_index* h, int kg16) { return h->pf_small && kg16 <= PS_MAXKG; }
 // which fp16 fragment shape the index and the queries are packed in: 16 x 32 for pass2_kernel, 32 x 16 for the low-dimensional kernels
 static int frag16x16(const lmi_index* h) { return low_d_form(h, h->KG16) ? 0 : 1; }
+
+// why an LMI_STORAGE_F16 build cannot go with the handle's other settings (nullptr: it can)
+static const char* storage16_conflict(const lmi_index* h) {
+    if (!h->pf_hw_ok) return "the fp16 subnormal self-test failed on this device: the fp16 fragments cannot be trusted to hold the vectors";
+    if (h->metric == LMI_METRIC_L2) return "LMI_METRIC_L2 is not supported (the -|x|^2/2 column of a stored vector is not fp16-exact)";
+    if (!h->prefilter) return "lmi_set_prefilter(0) is not supported (the all-f32 scan needs f32 fragments)";
+    return nullptr;
+}
+
+// the dynamic-LDS limits of the re-rank kernels' LMI_STORAGE_F16 forms: set when a handle first builds such an index (per device;
+// handles that never do -- lmi_knn_ip's among them -- do not pay for it)
+static int storage16_kernel_attrs(lmi_index* h) {
+    if (h->attrs16_done) return 0;
+#define LMI_RC16_ATTR(GV) \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rescore_kernel<GV, false, true, Frag16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rescore_kernel<GV, true, true, Frag16>), hipFuncAttributeMaxDynamicSharedMemorySize, RC_SMALL_LDS_CAP)); \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_kernel<GV, true, Frag16>), hipFuncAttributeMaxDynamicSharedMemorySize, RC_SMALL_LDS_CAP));
+    LMI_RC16_ATTR(1) LMI_RC16_ATTR(2) LMI_RC16_ATTR(3) LMI_RC16_ATTR(4)
+#undef LMI_RC16_ATTR
+    h->attrs16_done = true;
+    return 0;
+}
 
 static int set_dev(lmi_index* h) {
     HIPCHK(hipSetDevice(h->device));

@@ -3,18 +3,33 @@
 #pragma once
 #include "lmi_host.h"
 
+// k16-groups of the fp16 fragments of d-column vectors (pass2_kernel's stages hold two k16-groups; the low-dimensional form has no
+// stages: d = 45 is 48 wide, not 64)
+static int kg16_for(const lmi_index* h, int d) {
+    return low_d_form(h, cdiv(d, 16)) ? (int)cdiv(d, 16) : (int)rup(cdiv(d, 16), PF_STAGE_G);
+}
+// bytes of the fp16 fragments (+ 8 KiB: pass2_kernel's look-ahead requests up to two stages = 4 KiB past the last row-block's fragments
+// before it learns that the item is over; the data is never used, the addresses must be the allocation's)
+static size_t slab16_bytes(const lmi_index* h) { return (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KG16 * 1024 + 8192; }
+
 extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, const int64_t* labels,
                                  const uint32_t* ids, const uint8_t* owned) {
     if (!h) return fail("lmi_buckets_begin: NULL handle");
     if (N < 0 || d < 1 || L < 1 || (N > 0 && !labels)) return fail("lmi_buckets_begin: bad arguments");
+    if (h->storage_req == LMI_STORAGE_F16)
+        if (const char* why = storage16_conflict(h)) return fail("lmi_buckets_begin: LMI_STORAGE_F16: %s", why);
     if (N >= (1ll << 31) - 64ll * L) return fail("lmi_buckets_begin: N too large for 32-bit positions");
     if (L >= (1 << ROUTE_ID_BITS)) return fail("lmi_buckets_begin: %d buckets, the routing kernels take fewer than %d", L, 1 << ROUTE_ID_BITS);
     CHK(set_dev(h));
+    if (h->storage_req == LMI_STORAGE_F16) CHK(storage16_kernel_attrs(h));
     h->N = N;
     h->d_user = d;
     h->d = h->metric == LMI_METRIC_L2 ? (int)rup(d + 1, 4) : d;  // L2: + the -|x|^2/2 column (sim_to_dist, lmi_kernels.h)
     d = h->d;
     h->dp = (int)rup(d, 4);   // floats per row of the row-major f32 copy: 16-byte rows for the streamed re-rank (d = 45: 48, zero-filled)
+    h->storage = h->storage_req;
+    if (h->storage == LMI_STORAGE_F16) h->dp = (int)rup(d, 8);   // no such copy: the floats of a query the re-rank stages (whole 8-k pieces)
+    h->have16 = false;
     h->L = L;
     h->KGs = (int)rup(cdiv(d, 8), STAGE_G);
     h->built = false;
@@ -84,11 +99,22 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
         ids_slab[p] = ids ? ids[i] : (uint32_t)(i + 1);  // search.py:190-191: 1-based labels
     }
     const size_t slab_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KGs * 1024;
-    if (h->prefilter) {  // row-major f32 (exact re-rank / fallback / read-back); fp16 fragments at buckets_end
+    if (h->prefilter) h->KG16 = kg16_for(h, d);
+    if (h->storage == LMI_STORAGE_F16) {   // fp16 fragments only (lmi_store16.h): filled piece by piece, unscaled until buckets_end
+        h->slab.release();
+        h->rowmajor.release();
+        CHK(h->slab16.reserve(slab16_bytes(h)));
+        HIPCHK(hipMemsetAsync(h->slab16.p, 0, slab16_bytes(h), h->stream));
+        CHK(h->xmaxbits.reserve(16));   // [0] max |x| (bits), [1] S16_* flags
+        HIPCHK(hipMemsetAsync(h->xmaxbits.p, 0, 16, h->stream));
+    } else if (h->prefilter) {  // row-major f32 (exact re-rank / fallback / read-back); fp16 fragments at buckets_end
         const size_t rm_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * 32 * h->dp * 4;
         h->slab.release();
         CHK(h->rowmajor.reserve(rm_bytes));
         HIPCHK(hipMemsetAsync(h->rowmajor.p, 0, rm_bytes, h->stream));
+        // (reserved with the build's other images, so that a build that cannot fit fails before the rows are uploaded and
+        // lmi_index_bytes reports the index's size from here on; lmi_buckets_end fills them)
+        CHK(h->slab16.reserve(slab16_bytes(h)));
     } else {             // f32 fragments for the all-f32 scan
         h->rowmajor.release();
         h->slab16.release();
@@ -141,7 +167,11 @@ static int add_rows_impl(lmi_index* h, const float* rows, int64_t row0, const in
             HIPCHK(hipGetLastError());
             src = h->aug_rows.as<float>();
         }
-        if (h->prefilter) {
+        if (h->storage == LMI_STORAGE_F16) {   // the piece -> halves -> its rows' fragments; the exactness flags and the absmax
+            long long total = (long long)n * 2 * h->KG16;
+            ingest16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n, h->KG16,
+                                                                    frag16x16(h), h->slab16.as<uint4>(), h->xmaxbits.as<unsigned>());
+        } else if (h->prefilter) {
             long long total = (long long)n * h->d;
             scatter_rows_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
                                                                         h->rowmajor.as<float>(), h->dp);
@@ -187,15 +217,13 @@ extern "C" LMI_API int lmi_buckets_add_owned_rows(lmi_index* h, const float* row
 static int prefilter_images(lmi_index* h) {
     // fp16 copy of the slab for the prefilter: one power-of-two scale for the whole index
     // (pass2_kernel's stages hold two k16-groups; the low-dimensional form has no stages: d = 45 is 48 wide, not 64)
-    h->KG16 = low_d_form(h, cdiv(h->d, 16)) ? (int)cdiv(h->d, 16) : (int)rup(cdiv(h->d, 16), PF_STAGE_G);
+    h->KG16 = kg16_for(h, h->d);
     const long long n_rows = (long long)h->n_rb_total * 32;
     CHK(h->xmaxbits.reserve(16));
     CHK(h->xscale.reserve(16));
     CHK(h->bnorm.reserve((size_t)h->L * 4));
     CHK(h->bdelta.reserve((size_t)h->L * 4));
-    // (+ 8 KiB: pass2_kernel's look-ahead requests up to two stages = 4 KiB past the last row-block's fragments before it learns that
-    // the item is over; the data is never used, the addresses must be the allocation's)
-    CHK(h->slab16.reserve((size_t)h->n_rb_total * h->KG16 * 1024 + 8192));
+    CHK(h->slab16.reserve(slab16_bytes(h)));
     HIPCHK(hipMemsetAsync(h->xmaxbits.p, 0, 16, h->stream));
     HIPCHK(hipMemsetAsync(h->bnorm.p, 0, (size_t)h->L * 4, h->stream));
     HIPCHK(hipMemsetAsync(h->bdelta.p, 0, (size_t)h->L * 4, h->stream));
@@ -217,6 +245,41 @@ static int prefilter_images(lmi_index* h) {
     return 0;
 }
 
+// LMI_STORAGE_F16: the fragments were filled unscaled by lmi_buckets_add_*rows; the scale from their absmax, the slab times the scale
+// in place, the buckets' norms from the stored halves -- and the verdict: the flags are read after the synchronisation, a refused
+// build launches nothing more and leaves the handle without an index.
+static int storage16_finish(lmi_index* h) {
+    unsigned* state = h->xmaxbits.as<unsigned>();
+    CHK(h->xscale.reserve(16));
+    CHK(h->bnorm.reserve((size_t)h->L * 4));
+    CHK(h->bdelta.reserve((size_t)h->L * 4));
+    HIPCHK(hipMemsetAsync(h->bnorm.p, 0, (size_t)h->L * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->bdelta.p, 0, (size_t)h->L * 4, h->stream));   // ||x^ - x'|| = 0: the stored value IS x'
+    make_scale_kernel<<<1, 1, 0, h->stream>>>(state, h->xscale.as<float>());
+    HIPCHK(hipGetLastError());
+    rescale16_kernel<<<h->num_cus * 8, 256, 0, h->stream>>>(h->slab16.as<uint4>(), (long long)h->n_rb_total * h->KG16 * 64, h->xscale.as<float>(), state);
+    HIPCHK(hipGetLastError());
+    dim3 g(64, h->L);
+    bucket_norm16_kernel<<<g, 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->d, h->KG16, frag16x16(h), h->d_rb_start.as<int>(),
+                                                  h->d_nb_rows.as<int>(), h->bnorm.as<unsigned>());
+    HIPCHK(hipGetLastError());
+    unsigned st[4] = {0, 0, 0, 0};
+    float sc[2] = {1.0f, 1.0f};
+    HIPCHK(hipMemcpyAsync(st, state, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(sc, h->xscale.p, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (st[1] & S16_NONFINITE) return fail("lmi_buckets_end: LMI_STORAGE_F16 refused: a stored value is not finite (inf or NaN)");
+    if (st[1] & S16_INEXACT) return fail("lmi_buckets_end: LMI_STORAGE_F16 refused: a stored value is not exactly representable in binary16");
+    if (st[1] & S16_SCALE_LOSS) {
+        float mx;
+        memcpy(&mx, &st[0], 4);
+        return fail("lmi_buckets_end: LMI_STORAGE_F16 refused: every value is binary16-exact, but not once multiplied by the index scale %g "
+                    "(max|x| = %g; a small value falls below the binary16 subnormals)", (double)sc[0], (double)mx);
+    }
+    h->have16 = true;
+    return 0;
+}
+
 extern "C" LMI_API int lmi_buckets_end(lmi_index* h) {
     if (!h || !h->building) return fail("lmi_buckets_end: call lmi_buckets_begin first");
     const int64_t expect = h->indexed_ingest ? h->owned_total : h->N;
@@ -225,7 +288,13 @@ extern "C" LMI_API int lmi_buckets_end(lmi_index* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     h->pos.release();
     h->have16 = false;
-    if (h->prefilter && h->n_rb_total > 0) CHK(prefilter_images(h));
+    if (h->storage == LMI_STORAGE_F16 && h->n_rb_total > 0) {
+        if (storage16_finish(h) != 0) {   // inadmissible data (or a failed call): no index; lmi_buckets_begin may be called again
+            h->building = false;
+            h->slab16.release();
+            return -1;
+        }
+    } else if (h->prefilter && h->n_rb_total > 0) CHK(prefilter_images(h));
     h->building = false;
     h->built = true;
     return 0;
@@ -245,7 +314,14 @@ extern "C" LMI_API int lmi_bucket_read(lmi_index* h, int bucket, float* rows, ui
     CHK(set_dev(h));
     const int64_t p0 = (int64_t)h->h_rb_start[bucket] * 32;
     const int du = h->d_user;  // the caller's columns (the L2 norm column is not returned)
-    if (rows && h->prefilter) {
+    if (rows && h->storage == LMI_STORAGE_F16) {   // the rows out of the fp16 fragments, widened and unscaled (exact: lmi_store16.h)
+        CHK(h->stage.reserve((size_t)n * du * 4));
+        long long total = n * cdiv(du, 8);
+        unpack16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->KG16, frag16x16(h), p0, n, du, h->xscale.as<float>(),
+                                                                h->stage.as<float>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rows, h->stage.p, (size_t)n * du * 4, hipMemcpyDeviceToHost, h->stream));
+    } else if (rows && h->prefilter) {
         HIPCHK(hipMemcpy2DAsync(rows, (size_t)du * 4, h->rowmajor.as<float>() + (size_t)p0 * h->dp, (size_t)h->dp * 4, (size_t)du * 4, (size_t)n,
                                 hipMemcpyDeviceToHost, h->stream));
     } else if (rows) {

@@ -33,6 +33,8 @@ int64_t max_slab_rb(const lmi_index* h) { return ((1ll << 31) - 64ll * h->L) / 3
 int mut_check(lmi_index* h, const char* who) {
     if (!h) return fail("%s: NULL handle", who);
     if (!h->built) return fail("%s: the bucket index is not built (lmi_buckets_end has not run)", who);
+    if (h->storage == LMI_STORAGE_F16)
+        return fail("%s: an LMI_STORAGE_F16 index cannot be changed in place yet (mutation of a compact index is not implemented); rebuild it, or use LMI_STORAGE_F32", who);
     if (h->parent) return fail("%s: a clone view cannot change the index it borrows", who);
     if (h->live_clones > 0) return fail("%s: %d clone view(s) of this handle are alive (they hold copies of the bucket tables); destroy them first", who, h->live_clones);
     return 0;

@@ -549,13 +549,21 @@ static void rescore_params(lmi_index* h, const ScanCall& C, const PrefilterParam
 #endif
     Q.host_oflag = P.use_tail ? h->h_oflag : nullptr;
 }
+// LMI_STORAGE_F16: where the *16 kernels read the rows (RescoreParams::rows is null: no f32 image exists)
+static Frag16 frag16_of(const lmi_index* h) {
+    Frag16 F;
+    F.frag = h->slab16.as<uint4>(); F.scale = h->xscale.as<float>(); F.KG16 = h->KG16; F.f16x16 = frag16x16(h);
+    return F;
+}
 
 // stage 8 -- the exact re-rank of the candidates: tail_kernel | select_kernel + rescore_kernel x 2 | select_rescore_kernel
 static int rerank(lmi_index* h, const ScanCall& C, const RescoreParams& Q) {
     const ScanPlan& P = C.P;
     const int nslots = (int)P.nslots, G = P.G, groups = P.groups;
+    const bool f16 = h->storage == LMI_STORAGE_F16;
     if (!P.streamed) {
-        select_rescore_kernel<<<cdiv(nslots, RS_WAVES), 64 * RS_WAVES, 0, h->stream>>>(Q);
+        if (f16) select_rescore_kernel<true><<<cdiv(nslots, RS_WAVES), 64 * RS_WAVES, 0, h->stream>>>(Q, frag16_of(h));
+        else select_rescore_kernel<false><<<cdiv(nslots, RS_WAVES), 64 * RS_WAVES, 0, h->stream>>>(Q);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -574,7 +582,8 @@ static int rerank(lmi_index* h, const ScanCall& C, const RescoreParams& Q) {
         T.pending = h->rs_flag.as<int>();   // [groups] (used as [nq] when the tail merges: then groups == nq)
         const int lds_s = RC_WAVES * tail_wave_lds(h->dp, G, true);
         const int blocks = cdiv(groups, RC_WAVES);
-#define LMI_TL_LAUNCH(GV) { tail_kernel<GV><<<blocks, 64 * RC_WAVES, lds_s, h->stream>>>(Q, O, T); }
+#define LMI_TL_LAUNCH(GV) { if (f16) tail_kernel<GV, true><<<blocks, 64 * RC_WAVES, lds_s, h->stream>>>(Q, O, T, frag16_of(h)); \
+                           else tail_kernel<GV><<<blocks, 64 * RC_WAVES, lds_s, h->stream>>>(Q, O, T); }
         if (G == 4) LMI_TL_LAUNCH(4) else if (G == 3) LMI_TL_LAUNCH(3) else if (G == 2) LMI_TL_LAUNCH(2) else LMI_TL_LAUNCH(1)
 #undef LMI_TL_LAUNCH
         HIPCHK(hipGetLastError());
@@ -589,8 +598,10 @@ static int rerank(lmi_index* h, const ScanCall& C, const RescoreParams& Q) {
     const int blocks = cdiv(groups, ws);
     const int lds = wb * rc_wave_lds(h->dp, G), lds_s = ws * rc_wave_lds(h->dp, G, true);
     // first every group in the small-LDS form (three blocks per CU), then the groups it passed on (more survivors than it holds)
-#define LMI_RC_LAUNCH(GV) { rescore_kernel<GV, true><<<blocks, 64 * ws, lds_s, h->stream>>>(Q, O); \
-                            rescore_kernel<GV, false><<<std::min(cdiv(groups, wb), h->num_cus), 64 * wb, lds, h->stream>>>(Q, O); }
+#define LMI_RC_LAUNCH(GV) { if (f16) { rescore_kernel<GV, true, true><<<blocks, 64 * ws, lds_s, h->stream>>>(Q, O, frag16_of(h)); \
+                                       rescore_kernel<GV, false, true><<<std::min(cdiv(groups, wb), h->num_cus), 64 * wb, lds, h->stream>>>(Q, O, frag16_of(h)); } \
+                            else { rescore_kernel<GV, true><<<blocks, 64 * ws, lds_s, h->stream>>>(Q, O); \
+                                   rescore_kernel<GV, false><<<std::min(cdiv(groups, wb), h->num_cus), 64 * wb, lds, h->stream>>>(Q, O); } }
     if (G == 4) LMI_RC_LAUNCH(4) else if (G == 3) LMI_RC_LAUNCH(3) else if (G == 2) LMI_RC_LAUNCH(2) else LMI_RC_LAUNCH(1)
 #undef LMI_RC_LAUNCH
     HIPCHK(hipGetLastError());
@@ -599,7 +610,8 @@ static int rerank(lmi_index* h, const ScanCall& C, const RescoreParams& Q) {
 
 // stage 9 -- the slots the re-rank flagged (overflowed candidate buffers, failed bounds): exact, from the log or the whole bucket
 static int scan_fallback(lmi_index* h, const ScanCall& C, const RescoreParams& Q) {
-    fallback_kernel<<<std::min(cdiv(C.P.nslots, 4), h->num_cus * 4), 256, 0, h->stream>>>(Q);
+    if (h->storage == LMI_STORAGE_F16) fallback_kernel<true><<<std::min(cdiv(C.P.nslots, 4), h->num_cus * 4), 256, 0, h->stream>>>(Q, frag16_of(h));
+    else fallback_kernel<false><<<std::min(cdiv(C.P.nslots, 4), h->num_cus * 4), 256, 0, h->stream>>>(Q);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -113,6 +113,18 @@ __global__ void convert16_kernel(const float* __restrict__ rows, int d, int pitc
     convert16_one(rows, d, pitch, (idx >> 1) / KG16, (int)((idx >> 1) % KG16), (int)(idx & 1), KG16, scale[0], dst, f16x16);
 }
 
+// ---- LMI_STORAGE_F16 (lmi_store16.h): the index keeps the fp16 fragments ONLY; whoever needs a stored row reads it out of them.
+//      uint4 index of the 16-byte piece that holds k = 8 k8 .. 8 k8 + 7 of slab row p (the two shapes of convert16_one) ----
+__device__ __forceinline__ size_t frag16_piece(long long p, int k8, int KG16, int f16x16) {
+    const int r = (int)(p & 31);
+    if (f16x16) return (((size_t)(p >> 5) * (KG16 / 2) + (k8 >> 2)) * 2 + (r >> 4)) * 64 + 16 * (k8 & 3) + (r & 15);
+    return ((size_t)(p >> 5) * KG16 + (k8 >> 1)) * 64 + (k8 & 1) * 32 + r;
+}
+// uint4s between piece 0 and piece j (< 8) of one 64-k chunk of a row; a row's consecutive chunks are 256 uint4s (4 KiB) apart in both shapes
+__device__ __forceinline__ int frag16_piece_off(int j, int f16x16) {
+    return f16x16 ? (j >> 2) * 128 + 16 * (j & 3) : (j >> 1) * 64 + (j & 1) * 32;
+}
+
 // Rounding-up factor of a binary32 norm: a sum of d non-negative squares accumulated in ANY order errs by at
 // most d 2^-24 relative, its square root by half that (+ one rounding); the factor covers twice the bound for
 // every d (a fixed 1.0002 only did up to d ~ 6 000).
@@ -433,6 +445,17 @@ struct RescoreParams {
     unsigned* m_out_id;
     unsigned* m_out_key;                  // nullable
 };
+// LMI_STORAGE_F16: where the *16 kernels find the rows (their last argument; RescoreParams::rows is null there and ::dp is d rounded up
+// to 8, the floats of a query staged in LDS).  The kernels of an LMI_STORAGE_F32 index take no such argument.
+struct Frag16 {
+    const uint4* frag;     // the index's fp16 fragments (PrefilterParams::slab16)
+    const float* scale;    // [0] the index scale s, [1] 1 / s: a stored half widens to x = (float)h * (1 / s), exactly
+    int KG16, f16x16;      // the fragments' shape (convert16_one)
+};
+// The kernels that read stored rows are templates <.., bool H = false, class... FR>: H = false, no FR -- an LMI_STORAGE_F32 index, the
+// kernel's arguments and code are what they were before LMI_STORAGE_F16 existed; H = true, FR = Frag16 -- the rows come out of the fragments.
+__device__ __forceinline__ Frag16 frag16_arg() { return Frag16{}; }
+__device__ __forceinline__ Frag16 frag16_arg(const Frag16& f) { return f; }
 // the first workgroup of the selection launch: its own start + pass 2's end (known now: the stream ran pass 2 to completion)
 __device__ __forceinline__ void select_stamps(const RescoreParams& P) {
     if (P.ts && threadIdx.x == 0 && blockIdx.x == 0) {
@@ -478,6 +501,28 @@ __device__ __forceinline__ float exact_score(const float* __restrict__ rows, siz
     return acc;
 }
 
+// the same chain over a row of an LMI_STORAGE_F16 index: x[k] = the stored half widened and unscaled (both exact), 16 bytes = 8 k per load
+__device__ __forceinline__ float exact_score16(const RescoreParams& P, const Frag16& F, float inv, size_t p, const float* __restrict__ qv) {
+    float acc = 0.0f;
+    const int d = P.d, n8 = (d + 7) >> 3;
+    for (int k8 = 0; k8 < n8; ++k8) {
+        const uint4 w = F.frag[frag16_piece((long long)p, k8, F.KG16, F.f16x16)];
+        const half8 hv = __builtin_bit_cast(half8, w);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 8 * k8 + j;
+            if (k < d) acc = __builtin_fmaf(qv[k], (float)hv[j] * inv, acc);
+        }
+    }
+    return acc;
+}
+// a stored row's score for either storage (H: LMI_STORAGE_F16)
+template <bool H>
+__device__ __forceinline__ float stored_score(const RescoreParams& P, const Frag16& F, float inv, size_t p, const float* __restrict__ qv) {
+    if constexpr (H) return exact_score16(P, F, inv, p, qv);
+    else return exact_score(P.rows, p, qv, P.d, P.dp);
+}
+
 // lanes 0..9 hold the sorted (score, row) results; writes the slot's rank list (merge phase A form)
 __device__ __forceinline__ void write_rank_list(int lane, float my_s, unsigned my_r, int n_b, int rb0, int raw,
                                                 const unsigned* __restrict__ ids_slab, float* rd, unsigned* ri,
@@ -507,7 +552,9 @@ constexpr int RS_WAVES = 4;
 #endif
 constexpr int RS_MAXD = 1024;  // queries up to this many dims are staged in LDS (else read from L2)
 
-__global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(LMI_RS_WAVES_PER_EU))) void select_rescore_kernel(RescoreParams P) {
+template <bool H = false, class... FR>
+__global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(LMI_RS_WAVES_PER_EU))) void select_rescore_kernel(RescoreParams P, FR... frag) {
+    const Frag16 F = frag16_arg(frag...);
     select_stamps(P);
     pf_x_scatter(P, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     __shared__ unsigned keep_row[RS_WAVES][PF_KEEP];
@@ -601,69 +648,73 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(L
     unsigned row = NOROW;
     if (lane < (int)nk) {
         row = keep_row[wv][lane];
-        const float* x = P.rows + ((size_t)rb0 * 32 + row) * P.dp;
         const float* qv = q_lds ? qs[wv] : qg;
-        float acc = 0.0f;
-        int k = 0;
-        if (q_lds && (P.d & 31) == 0) {
-            // One 128-byte line of the row per step and lane.  With only that line outstanding the DRAM
-            // sees 24 isolated accesses per 3-KiB row (2.1 TB/s measured).  Registers for more lines cost
-            // occupancy, so the lines RS_AHEAD steps ahead are pulled into L2/MALL by 4-byte-per-lane
-            // LDS-DMA loads into a sink (no VGPRs; issued AFTER the step's own loads, since vmcnt returns in
-            // order).  The query is read from LDS by inline asm: hipcc would order a visible ds_read
-            // behind every pending LDS-DMA.
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            const unsigned qaddr = (unsigned)reinterpret_cast<uintptr_t>(&qs[wv][0]);
-            constexpr int RS_AHEAD = LMI_RS_AHEAD;
+        if constexpr (H) {
+            s = exact_score16(P, F, F.scale[1], (size_t)rb0 * 32 + row, qv);
+        } else {
+            const float* x = P.rows + ((size_t)rb0 * 32 + row) * P.dp;
+            float acc = 0.0f;
+            int k = 0;
+            if (q_lds && (P.d & 31) == 0) {
+                // One 128-byte line of the row per step and lane.  With only that line outstanding the DRAM
+                // sees 24 isolated accesses per 3-KiB row (2.1 TB/s measured).  Registers for more lines cost
+                // occupancy, so the lines RS_AHEAD steps ahead are pulled into L2/MALL by 4-byte-per-lane
+                // LDS-DMA loads into a sink (no VGPRs; issued AFTER the step's own loads, since vmcnt returns in
+                // order).  The query is read from LDS by inline asm: hipcc would order a visible ds_read
+                // behind every pending LDS-DMA.
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                const unsigned qaddr = (unsigned)reinterpret_cast<uintptr_t>(&qs[wv][0]);
+                constexpr int RS_AHEAD = LMI_RS_AHEAD;
 #pragma unroll
-            for (int j = 1; j <= RS_AHEAD; ++j)
-                if (j * 32 < P.d)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(x + j * 32),
+                for (int j = 1; j <= RS_AHEAD; ++j)
+                    if (j * 32 < P.d)
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(x + j * 32),
+                                                         (__attribute__((address_space(3))) void*)&sink[wv][0], 4, 0, 0);
+                for (; k < P.d; k += 32) {
+                    // the step's line by inline asm, then exactly one prefetch (past the end: the last line again),
+                    // then `vmcnt(1)`: the line has landed, the prefetch may still be out (hipcc waits for vmcnt(0))
+                    f32x4 xv[8];
+                    const float* xk = x + k;
+                    asm volatile("global_load_dwordx4 %0, %8, off\n\tglobal_load_dwordx4 %1, %8, off offset:16\n\t"
+                                 "global_load_dwordx4 %2, %8, off offset:32\n\tglobal_load_dwordx4 %3, %8, off offset:48\n\t"
+                                 "global_load_dwordx4 %4, %8, off offset:64\n\tglobal_load_dwordx4 %5, %8, off offset:80\n\t"
+                                 "global_load_dwordx4 %6, %8, off offset:96\n\tglobal_load_dwordx4 %7, %8, off offset:112"
+                                 : "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]), "=&v"(xv[4]), "=&v"(xv[5]), "=&v"(xv[6]), "=&v"(xv[7])
+                                 : "v"(xk) : "memory");
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(x + min(k + (RS_AHEAD + 1) * 32, P.d - 32)),
                                                      (__attribute__((address_space(3))) void*)&sink[wv][0], 4, 0, 0);
-            for (; k < P.d; k += 32) {
-                // the step's line by inline asm, then exactly one prefetch (past the end: the last line again),
-                // then `vmcnt(1)`: the line has landed, the prefetch may still be out (hipcc waits for vmcnt(0))
-                f32x4 xv[8];
-                const float* xk = x + k;
-                asm volatile("global_load_dwordx4 %0, %8, off\n\tglobal_load_dwordx4 %1, %8, off offset:16\n\t"
-                             "global_load_dwordx4 %2, %8, off offset:32\n\tglobal_load_dwordx4 %3, %8, off offset:48\n\t"
-                             "global_load_dwordx4 %4, %8, off offset:64\n\tglobal_load_dwordx4 %5, %8, off offset:80\n\t"
-                             "global_load_dwordx4 %6, %8, off offset:96\n\tglobal_load_dwordx4 %7, %8, off offset:112"
-                             : "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]), "=&v"(xv[4]), "=&v"(xv[5]), "=&v"(xv[6]), "=&v"(xv[7])
-                             : "v"(xk) : "memory");
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(x + min(k + (RS_AHEAD + 1) * 32, P.d - 32)),
-                                                 (__attribute__((address_space(3))) void*)&sink[wv][0], 4, 0, 0);
-                asm volatile("s_waitcnt vmcnt(1)"
-                             : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7])
-                             :: "memory");
-                f32x4 qq[8];
-                const unsigned qa = qaddr + (unsigned)k * 4u;
-                asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:16\n\tds_read_b128 %2, %8 offset:32\n\t"
-                             "ds_read_b128 %3, %8 offset:48\n\tds_read_b128 %4, %8 offset:64\n\tds_read_b128 %5, %8 offset:80\n\t"
-                             "ds_read_b128 %6, %8 offset:96\n\tds_read_b128 %7, %8 offset:112\n\ts_waitcnt lgkmcnt(0)"
-                             : "=&v"(qq[0]), "=&v"(qq[1]), "=&v"(qq[2]), "=&v"(qq[3]), "=&v"(qq[4]), "=&v"(qq[5]), "=&v"(qq[6]), "=&v"(qq[7])
-                             : "v"(qa) : "memory");
+                    asm volatile("s_waitcnt vmcnt(1)"
+                                 : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7])
+                                 :: "memory");
+                    f32x4 qq[8];
+                    const unsigned qa = qaddr + (unsigned)k * 4u;
+                    asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:16\n\tds_read_b128 %2, %8 offset:32\n\t"
+                                 "ds_read_b128 %3, %8 offset:48\n\tds_read_b128 %4, %8 offset:64\n\tds_read_b128 %5, %8 offset:80\n\t"
+                                 "ds_read_b128 %6, %8 offset:96\n\tds_read_b128 %7, %8 offset:112\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&v"(qq[0]), "=&v"(qq[1]), "=&v"(qq[2]), "=&v"(qq[3]), "=&v"(qq[4]), "=&v"(qq[5]), "=&v"(qq[6]), "=&v"(qq[7])
+                                 : "v"(qa) : "memory");
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    acc = __builtin_fmaf(qq[i].x, xv[i].x, acc); acc = __builtin_fmaf(qq[i].y, xv[i].y, acc);
-                    acc = __builtin_fmaf(qq[i].z, xv[i].z, acc); acc = __builtin_fmaf(qq[i].w, xv[i].w, acc);
+                    for (int i = 0; i < 8; ++i) {
+                        acc = __builtin_fmaf(qq[i].x, xv[i].x, acc); acc = __builtin_fmaf(qq[i].y, xv[i].y, acc);
+                        acc = __builtin_fmaf(qq[i].z, xv[i].z, acc); acc = __builtin_fmaf(qq[i].w, xv[i].w, acc);
+                    }
+                }
+            } else if ((P.d & 3) == 0) {
+                for (; k + 32 <= P.d; k += 32) {  // 8 independent 16-byte loads in flight, then 32 chained fmas
+                    float4 xv[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) xv[i] = *reinterpret_cast<const float4*>(x + k + 4 * i);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const float4 qq = *reinterpret_cast<const float4*>(qv + k + 4 * i);
+                        acc = __builtin_fmaf(qq.x, xv[i].x, acc); acc = __builtin_fmaf(qq.y, xv[i].y, acc);
+                        acc = __builtin_fmaf(qq.z, xv[i].z, acc); acc = __builtin_fmaf(qq.w, xv[i].w, acc);
+                    }
                 }
             }
-        } else if ((P.d & 3) == 0) {
-            for (; k + 32 <= P.d; k += 32) {  // 8 independent 16-byte loads in flight, then 32 chained fmas
-                float4 xv[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) xv[i] = *reinterpret_cast<const float4*>(x + k + 4 * i);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float4 qq = *reinterpret_cast<const float4*>(qv + k + 4 * i);
-                    acc = __builtin_fmaf(qq.x, xv[i].x, acc); acc = __builtin_fmaf(qq.y, xv[i].y, acc);
-                    acc = __builtin_fmaf(qq.z, xv[i].z, acc); acc = __builtin_fmaf(qq.w, xv[i].w, acc);
-                }
-            }
+            for (; k < P.d; ++k) acc = __builtin_fmaf(qv[k], x[k], acc);
+            s = acc;
         }
-        for (; k < P.d; ++k) acc = __builtin_fmaf(qv[k], x[k], acc);
-        s = acc;
     }
     // 10 best by (score desc, row asc): a survivor's output position is the number of survivors that beat
     // it (rows are distinct, so positions are too); the owner lane writes the entry itself.
@@ -768,7 +819,9 @@ __device__ __forceinline__ void merge_entries(float dv, unsigned iv, int lane, i
 
 // Exact fallback for overflowed slots: one block per slot, brute force over the whole bucket with the
 // canonical chain on the VALU (slow, rare, always correct).
-__global__ __launch_bounds__(256) void fallback_kernel(RescoreParams P) {
+template <bool H = false, class... FR>
+__global__ __launch_bounds__(256) void fallback_kernel(RescoreParams P, FR... frag) {
+    const Frag16 F = frag16_arg(frag...);
     __shared__ float fs[256 * KPB];
     __shared__ unsigned fr[256 * KPB];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -778,6 +831,8 @@ __global__ __launch_bounds__(256) void fallback_kernel(RescoreParams P) {
     // time, every block of the grid busy when thousands of slots are flagged (duplicate-heavy data); an empty list costs one
     // round of blocks reading the count
     const int nt = *P.fb_count;
+    float inv = 1.0f;
+    if constexpr (H) inv = F.scale[1];
     for (int ti = blockIdx.x; ti < nt; ti += gridDim.x) {
     const int p = P.fb_list[ti];
     const int b = P.bucket_order[p];
@@ -799,7 +854,7 @@ __global__ __launch_bounds__(256) void fallback_kernel(RescoreParams P) {
     // entries are picked out of the log as it lies -- complete as long as the log did not run full; every flagged slot reads the whole log.
     const bool in_log = ccol >= 0 && ccnt > (unsigned)PF_CAP && P.x_off == nullptr && P.x_log != nullptr && P.x_cap != 0u && P.x_fail[0] == 0u;
     auto consider = [&](unsigned row) {
-        const float s = exact_score(P.rows, (size_t)rb0 * 32 + row, qv, P.d, P.dp);
+        const float s = stored_score<H>(P, F, inv, (size_t)rb0 * 32 + row, qv);
         if (better(s, row, v[KPB - 1], id[KPB - 1])) {  // candidates come in no order: ties by row here
 #pragma unroll
             for (int t = KPB - 1; t > 0; --t) {   // list_insert with the (score desc, row asc) order
@@ -827,7 +882,7 @@ __global__ __launch_bounds__(256) void fallback_kernel(RescoreParams P) {
     } else {
     if (tid == 0) atomicAdd(P.fb_count + 5, 1);   // (statistics: slots that scan their whole bucket)
     for (unsigned row = tid; row < (unsigned)n_b; row += 256) {
-        const float s = exact_score(P.rows, (size_t)rb0 * 32 + row, qv, P.d, P.dp);
+        const float s = stored_score<H>(P, F, inv, (size_t)rb0 * 32 + row, qv);
         if (s > v[KPB - 1]) list_insert(v, id, s, row);  // rows ascend per thread: strict > keeps the earlier
     }
     }

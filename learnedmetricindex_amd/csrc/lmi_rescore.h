@@ -225,11 +225,19 @@ struct RcWave {
 // canonical chain of row base + r against the query at LDS byte address `qaddr`; scores -> ksc[base ..].  NP = LDS-DMA pieces per chunk that
 // hold rows of THIS batch (a wave re-scores ~13 rows since the bound is per query: 2 pieces instead of the 9 that cover 64 rows -- issuing the
 // unused ones was most of the kernel's time).  RINGB: bytes of the ring.
-template <int NP, int RINGB>
-__device__ __forceinline__ void rc_run_batch(const RescoreParams& P, unsigned char* mine, const unsigned* krow, float* ksc, unsigned qaddr,
+// H (LMI_STORAGE_F16): the rows come out of the fp16 fragments.  The LDS picture is the same -- a row's 128-byte chunk is now 64 k = eight
+// 16-byte fragment pieces, lane (row, 16-byte column j) fetches piece 8 c + j of its row (frag16_piece; consecutive chunks of a row are
+// 4 KiB apart in both fragment shapes) -- and the chain step takes the chunk's 64 halves, widened and multiplied by 1 / s (both exact),
+// against 64 query floats.  The chain ends with the piece that holds k = d - 1: its halves past d are the +0 padding of the fragments, the
+// query's floats there the +0 padding of stage_query (P.dp = d rounded up to 8).
+template <int NP, int RINGB, bool H = false>
+__device__ __forceinline__ void rc_run_batch(const RescoreParams& P, const Frag16& F, unsigned char* mine, const unsigned* krow, float* ksc, unsigned qaddr,
                                              int base, int total, int lane) {
     const int d = P.dp;
-    const int nchunks = (d + RC_CHUNK - 1) / RC_CHUNK;
+    const int n8 = (P.d + 7) >> 3;   // (H) 16-byte pieces of a row that hold data
+    const int nchunks = H ? (n8 + 7) >> 3 : (d + RC_CHUNK - 1) / RC_CHUNK;
+    float inv = 1.0f;
+    if constexpr (H) inv = F.scale[1];
         // the wave's RC_DEPTH x RC_BUF bytes of chunk buffers, cut into buffers of NP pieces: fewer rows -> MORE chunks in flight
         // (13 instead of 3 at NP = 2).  A wave of ~13 rows waited 24 x for a 2-deep pipeline of 128-byte row segments: latency,
         // not bandwidth (profiles/r03_pass2_experiments.txt, section 12).
@@ -244,6 +252,7 @@ __device__ __forceinline__ void rc_run_batch(const RescoreParams& P, unsigned ch
         // first row's segment again (an L2 hit nobody uses).
         const float* src[NP];
         unsigned colb[NP];
+        int poff[H ? NP : 1];
 #pragma unroll
         for (int pc = 0; pc < NP; ++pc) {
             const int o = pc * 1024 + lane * 16;
@@ -251,15 +260,23 @@ __device__ __forceinline__ void rc_run_batch(const RescoreParams& P, unsigned ch
             const int cb = o - r * RC_PITCH;
             const bool okl = r < nrows && cb < RC_CHUNK * 4;
             const int i = base + (okl ? r : 0);
-            src[pc] = P.rows + (size_t)krow[i] * d + (okl ? cb / 4 : 0);
+            if constexpr (H) {
+                poff[pc] = okl ? 4 * frag16_piece_off(cb / 16, F.f16x16) : 0;   // floats between the chunk's piece 0 and this lane's piece
+                src[pc] = reinterpret_cast<const float*>(F.frag + frag16_piece((long long)krow[i], 0, F.KG16, F.f16x16)) + poff[pc];
+            } else {
+                src[pc] = P.rows + (size_t)krow[i] * d + (okl ? cb / 4 : 0);
+            }
             colb[pc] = okl ? (unsigned)cb : 0u;
         }
         auto issue = [&](int c, unsigned char* buf) {
-            const int cbytes = min(RC_CHUNK, d - c * RC_CHUNK) * 4;  // the last chunk of a row may be short
+            // the last chunk of a row may be short (H: pieces with data, 16 bytes each)
+            const int cbytes = H ? min(8, n8 - c * 8) * 16 : min(RC_CHUNK, d - c * RC_CHUNK) * 4;
 #pragma unroll
             for (int pc = 0; pc < NP; ++pc) {
                 // a lane past the row's end re-reads the row's first bytes of this chunk (kept inside the row)
-                const float* s_ = src[pc] + c * RC_CHUNK - ((int)colb[pc] < cbytes ? 0 : (int)colb[pc] / 4);
+                const float* s_;
+                if constexpr (H) s_ = src[pc] + c * 1024 - ((int)colb[pc] < cbytes ? 0 : poff[pc]);
+                else s_ = src[pc] + c * RC_CHUNK - ((int)colb[pc] < cbytes ? 0 : (int)colb[pc] / 4);
                 glds16(reinterpret_cast<const float4*>(s_), reinterpret_cast<float4*>(buf + pc * 1024));
             }
         };
@@ -277,7 +294,38 @@ __device__ __forceinline__ void rc_run_batch(const RescoreParams& P, unsigned ch
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             slot = slot + 1 == DEPTH ? 0 : slot + 1;
-            if (lane < nrows) {
+            if constexpr (H) {
+              if (lane < nrows) {
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                const unsigned xa = (unsigned)reinterpret_cast<uintptr_t>(cur) + (unsigned)lane * RC_PITCH;
+                const unsigned qa = qaddr + (unsigned)c * 256u;   // 64 query floats per chunk
+                const int np8 = min(8, n8 - c * 8);                // pieces of this chunk that hold data (wave-uniform)
+                for (int st = 0; st * 4 < np8; ++st) {             // 4 pieces = 32 k per step
+                    f32x4 xv[4], qq[8];
+                    const unsigned xo = xa + st * 64u, qo = qa + st * 128u;
+                    // asm reads: hipcc would order a visible ds_read behind every pending LDS-DMA (vmcnt(0))
+                    asm volatile("ds_read_b128 %0, %12\n\tds_read_b128 %1, %12 offset:16\n\tds_read_b128 %2, %12 offset:32\n\t"
+                                 "ds_read_b128 %3, %12 offset:48\n\t"
+                                 "ds_read_b128 %4, %13\n\tds_read_b128 %5, %13 offset:16\n\tds_read_b128 %6, %13 offset:32\n\t"
+                                 "ds_read_b128 %7, %13 offset:48\n\tds_read_b128 %8, %13 offset:64\n\tds_read_b128 %9, %13 offset:80\n\t"
+                                 "ds_read_b128 %10, %13 offset:96\n\tds_read_b128 %11, %13 offset:112\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]),
+                                   "=&v"(qq[0]), "=&v"(qq[1]), "=&v"(qq[2]), "=&v"(qq[3]), "=&v"(qq[4]), "=&v"(qq[5]), "=&v"(qq[6]), "=&v"(qq[7])
+                                 : "v"(xo), "v"(qo) : "memory");
+                    const int nv = min(4, np8 - st * 4);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        if (t < nv) {
+                            const half8 hv = __builtin_bit_cast(half8, xv[t]);
+                            acc = __builtin_fmaf(qq[2 * t].x, (float)hv[0] * inv, acc); acc = __builtin_fmaf(qq[2 * t].y, (float)hv[1] * inv, acc);
+                            acc = __builtin_fmaf(qq[2 * t].z, (float)hv[2] * inv, acc); acc = __builtin_fmaf(qq[2 * t].w, (float)hv[3] * inv, acc);
+                            acc = __builtin_fmaf(qq[2 * t + 1].x, (float)hv[4] * inv, acc); acc = __builtin_fmaf(qq[2 * t + 1].y, (float)hv[5] * inv, acc);
+                            acc = __builtin_fmaf(qq[2 * t + 1].z, (float)hv[6] * inv, acc); acc = __builtin_fmaf(qq[2 * t + 1].w, (float)hv[7] * inv, acc);
+                        }
+                    }
+                }
+              }
+            } else if (lane < nrows) {
                 typedef float f32x4 __attribute__((ext_vector_type(4)));
                 const unsigned xa = (unsigned)reinterpret_cast<uintptr_t>(cur) + (unsigned)lane * RC_PITCH;
                 const unsigned qa = qaddr + (unsigned)c * RC_CHUNK * 4u;
@@ -310,14 +358,14 @@ __device__ __forceinline__ void rc_run_batch(const RescoreParams& P, unsigned ch
         if (lane < nrows) ksc[base + lane] = acc;
 }
 // the batch at `base`, with as few pieces per chunk as its rows need (wave-uniform choice)
-template <bool SMALL>
-__device__ __forceinline__ void rc_stream_batch(const RescoreParams& P, unsigned char* mine, const unsigned* krow, float* ksc, unsigned qaddr,
+template <bool SMALL, bool H = false>
+__device__ __forceinline__ void rc_stream_batch(const RescoreParams& P, const Frag16& F, unsigned char* mine, const unsigned* krow, float* ksc, unsigned qaddr,
                                                 int base, int total, int lane) {
     constexpr int RINGB = SMALL ? RC_SMALL_RING : RC_DEPTH * RC_BUF;
     const int np = (min(RC_ROWS, total - base) * RC_PITCH + 1023) / 1024;   // wave-uniform
-    if (np <= 2) rc_run_batch<2, RINGB>(P, mine, krow, ksc, qaddr, base, total, lane);
-    else if (SMALL || (np <= 4 && RC_PIECES > 4)) rc_run_batch<(RC_PIECES > 4 ? 4 : RC_PIECES), RINGB>(P, mine, krow, ksc, qaddr, base, total, lane);
-    else { if constexpr (!SMALL) rc_run_batch<RC_PIECES, RINGB>(P, mine, krow, ksc, qaddr, base, total, lane); }
+    if (np <= 2) rc_run_batch<2, RINGB, H>(P, F, mine, krow, ksc, qaddr, base, total, lane);
+    else if (SMALL || (np <= 4 && RC_PIECES > 4)) rc_run_batch<(RC_PIECES > 4 ? 4 : RC_PIECES), RINGB, H>(P, F, mine, krow, ksc, qaddr, base, total, lane);
+    else { if constexpr (!SMALL) rc_run_batch<RC_PIECES, RINGB, H>(P, F, mine, krow, ksc, qaddr, base, total, lane); }
 }
 
 // The re-rank proper, shared by rescore_kernel and tail_kernel (lmi_tail.h): the wave's survivors krow[0, off[G]) (absolute slab rows, slot after
@@ -326,8 +374,8 @@ __device__ __forceinline__ void rc_stream_batch(const RescoreParams& P, unsigned
 // PRE (tail_kernel, round 5): what the rank lists need from global memory was requested by the caller BEFORE the rows were streamed -- the id of
 // survivor `lane` (my_id), and per slot the bucket's first slab row, its row count and the id of its last row (the padding) -- instead of
 // three more dependent round trips at the wave's end (a tail wave is parked on memory two thirds of its life: profiles/r05_tail_ring.txt).
-template <int G, bool SMALL, bool LCOPY, bool PRE = false>
-__device__ __forceinline__ void rescore_core(const RescoreParams& P, const RcWave<G, SMALL>& W, const int (&off)[G + 1], int p0, int lane,
+template <int G, bool SMALL, bool LCOPY, bool PRE = false, bool H = false>
+__device__ __forceinline__ void rescore_core(const RescoreParams& P, const Frag16& F, const RcWave<G, SMALL>& W, const int (&off)[G + 1], int p0, int lane,
                                              const int (&colv)[G], const int (&fbv)[G], float* rl_d, unsigned* rl_i,
                                              unsigned my_id = 0u, const unsigned* row_base = nullptr, const int* nbr = nullptr, const unsigned* pad_id = nullptr) {
     unsigned char* mine = W.mine;   // (rows of pitch P.dp: the chain runs over the zero padding too -- +0 * +0 added to the sum changes nothing)
@@ -336,7 +384,7 @@ __device__ __forceinline__ void rescore_core(const RescoreParams& P, const RcWav
     const float FMAXV = 3.402823466e+38f;
     const int total = off[G];
     const unsigned qaddr = (unsigned)reinterpret_cast<uintptr_t>(W.qs);
-    for (int base = 0; base < total; base += RC_ROWS) rc_stream_batch<SMALL>(P, mine, krow, ksc, qaddr, base, total, lane);
+    for (int base = 0; base < total; base += RC_ROWS) rc_stream_batch<SMALL, H>(P, F, mine, krow, ksc, qaddr, base, total, lane);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // rank lists: a survivor's position = the number of survivors of ITS slot that beat it by (score desc, row asc)
@@ -401,8 +449,8 @@ __device__ __forceinline__ void rescore_core(const RescoreParams& P, const RcWav
     }
 }
 
-template <int G, bool SMALL>
-__device__ __forceinline__ void rescore_group(const RescoreParams& P, const SelectOut& O, unsigned char* rc_smem, int wv, int lane, int p0) {
+template <int G, bool SMALL, bool H = false>
+__device__ __forceinline__ void rescore_group(const RescoreParams& P, const Frag16& F, const SelectOut& O, unsigned char* rc_smem, int wv, int lane, int p0) {
     const int d = P.dp;
     const RcWave<G, SMALL> W(rc_smem + (size_t)wv * rc_wave_lds(d, G, SMALL), d);
     // the survivor lists of the wave's slots, slot after slot, and the wave's query (G divides nb: one query per wave)
@@ -425,12 +473,13 @@ __device__ __forceinline__ void rescore_group(const RescoreParams& P, const Sele
     W.stage_query(P, p0 / P.nb, lane);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    rescore_core<G, SMALL, false>(P, W, off, p0, lane, colv, fbv, nullptr, nullptr);
+    rescore_core<G, SMALL, false, false, H>(P, F, W, off, p0, lane, colv, fbv, nullptr, nullptr);
 }
 
-template <int G, bool SMALL>
-__global__ __launch_bounds__(64 * RC_WAVES, SMALL ? 3 : 1) void rescore_kernel(RescoreParams P, SelectOut O) {
+template <int G, bool SMALL, bool H = false, class... FR>
+__global__ __launch_bounds__(64 * RC_WAVES, SMALL ? 3 : 1) void rescore_kernel(RescoreParams P, SelectOut O, FR... frag) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const Frag16 F = frag16_arg(frag...);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int nwv = (int)(blockDim.x >> 6);   // waves of the block: RC_WAVES, fewer for rows so wide that four waves' buffers pass 160 KiB
     const int wid = blockIdx.x * nwv + wv;
@@ -445,13 +494,13 @@ __global__ __launch_bounds__(64 * RC_WAVES, SMALL ? 3 : 1) void rescore_kernel(R
         const int sub = (int)__popcll(__ballot(incl <= wid));  // sub-lists that end at or before entry wid
         if (sub >= RC_SUB) return;                             // wid >= total
         const int before = sub ? __shfl(incl, sub - 1, 64) : 0;
-        rescore_group<G, true>(P, O, rc_smem, wv, lane, O.active[RC_SUB + sub * O.sub_cap + (wid - before)] * G);
+        rescore_group<G, true, H>(P, F, O, rc_smem, wv, lane, O.active[RC_SUB + sub * O.sub_cap + (wid - before)] * G);
     } else {
         // the passed-on groups are few (none on most batches): a grid of one block per CU walks the list, so that an empty list
         // costs one launch of 256 blocks and not one block (148 KiB of LDS each, one per CU at a time) per four groups
         const int nbig = __builtin_amdgcn_readfirstlane(O.big[0]);
         for (int i = wid; i < nbig; i += (int)gridDim.x * nwv) {
-            rescore_group<G, false>(P, O, rc_smem, wv, lane, O.big[1 + i] * G);
+            rescore_group<G, false, H>(P, F, O, rc_smem, wv, lane, O.big[1 + i] * G);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the wave's LDS lists are rewritten by its next group
             __builtin_amdgcn_wave_barrier();
         }

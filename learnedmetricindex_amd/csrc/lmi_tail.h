@@ -87,11 +87,12 @@ __device__ __forceinline__ unsigned tail_select(int lane, unsigned cnt, float e2
     return nk;
 }
 
-template <int G>
-__global__ __launch_bounds__(64 * RC_WAVES, 3) void tail_kernel(RescoreParams P, SelectOut O, TailParams T) {
+template <int G, bool H = false, class... FR>   // H: the rows of an LMI_STORAGE_F16 index, streamed out of the fp16 fragments (FR = Frag16)
+__global__ __launch_bounds__(64 * RC_WAVES, 3) void tail_kernel(RescoreParams P, SelectOut O, TailParams T, FR... frag) {
     select_stamps(P);
     pf_x_scatter(P, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     extern __shared__ __attribute__((aligned(16))) unsigned char tl_smem[];
+    const Frag16 F = frag16_arg(frag...);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int nwv = (int)(blockDim.x >> 6);
     const int grp = blockIdx.x * nwv + wv;
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(64 * RC_WAVES, 3) void tail_kernel(RescoreParams P,
     if (total <= RC_SMALL_ROWS) {
         // the survivors' ids: requested now, used behind the chains
         const unsigned my_id = (lane < total && !P.raw) ? P.ids_slab[W.krow[lane]] : 0u;
-        rescore_core<G, true, true, true>(P, W, off, p0, lane, colv, fbv, rl_d, rl_i, my_id, row_base, nbr, pad_id);
+        rescore_core<G, true, true, true, H>(P, F, W, off, p0, lane, colv, fbv, rl_d, rl_i, my_id, row_base, nbr, pad_id);
     } else {
         // More survivors than the small ring holds at once (a few per cent of the queries at C2, none at most shapes; round 4 and the
         // first form of this file passed them on to a second launch with a big ring -- 16-35 us per search, most of it the launch's
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(64 * RC_WAVES, 3) void tail_kernel(RescoreParams P,
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            rc_stream_batch<true>(P, W.mine, W.krow, W.ksc, qaddr, 0, nrows, lane);
+            rc_stream_batch<true, H>(P, F, W.mine, W.krow, W.ksc, qaddr, 0, nrows, lane);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             // fold: per slot, its old best (<= 10) and its rows of this batch (<= 28) ranked by (score desc, row asc); the ten best stay

@@ -2,7 +2,8 @@
 DataFrames -- replaces the reference's whole-object pickle (search.py:234-241, utils.py:14-29),
 which stores the models only and drops `data_prediction` and the vectors.
 
-    <dir>/meta.json      format/version, N, d, metric ("ip" | "l2"), n_categories, bucket paths, model descriptions
+    <dir>/meta.json      format/version, N, d, metric ("ip" | "l2"), storage ("f32" | "f16"; optional, absent = "f32"),
+                         n_categories, bucket paths, model descriptions
     <dir>/weights.npz    Linear weights/biases of the root and internal models (float32)
     <dir>/sizes.npy      int64 [B]    objects per bucket, in bucket-id order
     <dir>/ids.npy        uint32 [N]   object labels, bucket-contiguous
@@ -45,6 +46,8 @@ def save_index(path: str, li: LearnedIndex, n_categories: List[int]) -> None:
     meta = {"format": FORMAT, "version": VERSION, "N": N, "d": d, "metric": eng.metric, "n_categories": [int(v) for v in n_categories],
             "bucket_paths": [[int(v) for v in p] for p in li.bucket_paths],
             "root_layers": _put(weights, "root_", li.root_model), "internal": []}
+    if getattr(eng, "storage", "f32") != "f32":   # how the index was resident (the vectors on disk are f32 either way); a reader
+        meta["storage"] = eng.storage             # that does not know the key loads an f32-resident index: same results
     for i, (p, net) in enumerate(li.internal_models.items()):
         meta["internal"].append({"path": [int(v) for v in p], "layers": _put(weights, f"int{i}_", net)})
     if li._path_ids is not None:  # multi-level: bucket id -> path
@@ -66,8 +69,9 @@ def save_index(path: str, li: LearnedIndex, n_categories: List[int]) -> None:
         json.dump(meta, fh, indent=1)
 
 
-def load_index(path: str, device: int = 0) -> Tuple[LearnedIndex, List[int]]:
-    """(LearnedIndex with the index resident on `device`, n_categories); use `li.search_resident`."""
+def load_index(path: str, device: int = 0, storage=None) -> Tuple[LearnedIndex, List[int]]:
+    """(LearnedIndex with the index resident on `device`, n_categories); use `li.search_resident`.  `storage`: None = as the
+    directory says (its "storage" key; absent: "f32"), or "f32" / "f16" to override it."""
     meta = json.load(open(os.path.join(path, "meta.json")))
     assert meta["format"] == FORMAT and meta["version"] in (1, VERSION), f"unknown index format {meta.get('format')} v{meta.get('version')}"
     metric = meta.get("metric", "ip")
@@ -80,7 +84,10 @@ def load_index(path: str, device: int = 0) -> Tuple[LearnedIndex, List[int]]:
     sizes = np.load(os.path.join(path, "sizes.npy"))
     ids = np.load(os.path.join(path, "ids.npy"))
     vec = np.load(os.path.join(path, "vectors.f32.npy"), mmap_mode="r")
-    eng = _capi.Index(device, metric=metric)
+    if storage is None:
+        storage = meta.get("storage", "f32")
+    assert storage in _capi.Index.STORAGES, f"unknown storage {storage!r}"
+    eng = _capi.Index(device, metric=metric, storage=storage)
     if len(meta["n_categories"]) == 1:
         eng.set_mlp(linear_layers(root.model))
     else:

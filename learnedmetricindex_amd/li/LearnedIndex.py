@@ -171,9 +171,12 @@ class LearnedIndex(Logger):
 
     def prepare(self, data_navigation: pd.DataFrame, data_search: pd.DataFrame,
                 data_prediction: npt.NDArray[np.int64], n_categories: List[int], device: int = 0, metric: str = "ip",
-                assume_unchanged: bool = False):
+                assume_unchanged: bool = False, storage: str = "f32"):
         """Uploads the scan vectors bucket-contiguously (the one-time replacement of the
-        reference's per-call groupby + `.loc` gather).  Called by `search` when needed."""
+        reference's per-call groupby + `.loc` gather).  Called by `search` when needed.
+        `storage` (an extension; `lmi_set_storage`): "f32" (default) or "f16" -- the resident copy keeps the fp16 fragments
+        only, a third of the device memory, for scan vectors that are binary16-exact (`_capi.f16_admissible`); the library
+        checks that on the device and its refusal surfaces as `_capi.LmiError`.  Same results bit for bit."""
         assert self.root_model is not None, "Model is not trained, call `build` first."
         dp = np.asarray(data_prediction)
         if dp.ndim == 1:
@@ -210,13 +213,22 @@ class LearnedIndex(Logger):
                 w_h.update(W)
                 w_h.update(b)
         key = (content, tuple(data_search.shape), _array_fingerprint(data_navigation.index.to_numpy()), dp.shape, _array_fingerprint(dp),
-               w_h.digest(), tuple(tuple(int(v) for v in p) for p in self.internal_models), tuple(n_categories), device, metric)
+               w_h.digest(), tuple(tuple(int(v) for v in p) for p in self.internal_models), tuple(n_categories), device, metric, storage)
         if self._engine is not None and key == self._engine_key:
             return self._engine
         self.close()
         n_levels = len(n_categories)
         assert dp.shape[1] == n_levels
-        eng = _capi.Index(device, metric=metric)
+        eng = _capi.Index(device, metric=metric, storage=storage)
+        try:
+            self._build_engine(eng, dp, n_levels, n_categories, data_navigation, data_search)
+        except BaseException:
+            eng.close()   # (a refused build -- storage="f16" on data that is not binary16-exact -- leaves nothing resident)
+            raise
+        self._engine, self._engine_key = eng, key
+        return eng
+
+    def _build_engine(self, eng, dp, n_levels, n_categories, data_navigation, data_search) -> None:
         if n_levels == 1:
             # bucket id == class id: lmi_search can run MLP -> scan without leaving the device
             eng.set_mlp(linear_layers(self.root_model.model))
@@ -244,8 +256,6 @@ class LearnedIndex(Logger):
             block = frame.iloc[r0: r0 + piece]
             eng.add_rows(np.ascontiguousarray(block[cols].to_numpy(dtype=np.float32)), r0)
         eng.buckets_end()
-        self._engine, self._engine_key = eng, key
-        return eng
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
                         k: int = 10, stop_mass: Optional[float] = None, path_mass: Optional[float] = None):
@@ -276,7 +286,8 @@ class LearnedIndex(Logger):
                ids=None) -> npt.NDArray[np.int64]:
         """Adds objects to the HBM-resident index (an extension: the reference rebuilds).  Each object is placed the way
         `LearnedIndexBuilder.build` places it -- argmax of the root model, then argmax of each internal node's model down the
-        tree, through the HIP MLP -- and goes after the last object of its bucket (`lmi_buckets_insert`).  `data_search_new`
+        tree, through the HIP MLP -- and goes after the last object of its bucket (`lmi_buckets_insert`; refused by the library,
+        `_capi.LmiError`, on a `storage="f16"` index, which cannot be changed in place yet).  `data_search_new`
         (default: `data_navigation_new`) holds the scan vectors, `ids` (default: `data_navigation_new.index`) the labels.
         Returns the objects' `data_prediction` rows (int64 [n, n_levels]) for the caller to append to their own frames.
         A multi-level placement onto a leaf path that holds no bucket would need a new bucket: the whole call is refused
@@ -318,7 +329,8 @@ class LearnedIndex(Logger):
 
     def delete(self, ids) -> int:
         """Removes every object whose id (DataFrame index label) is in `ids` from the HBM-resident index (an extension;
-        `lmi_buckets_delete`); the others keep their order.  Returns how many were removed.  Afterwards `search_resident`
+        `lmi_buckets_delete`; refused by the library on a `storage="f16"` index); the others keep their order.  Returns how many
+        were removed.  Afterwards `search_resident`
         answers from the mutated index; `search` keeps answering from the frames it is given."""
         eng = self._resident("delete")
         n = eng.delete(np.asarray(ids).reshape(-1).astype(np.uint32))
@@ -349,6 +361,7 @@ class LearnedIndex(Logger):
         assume_unchanged: bool = False,
         stop_mass: Optional[float] = None,
         path_mass: Optional[float] = None,
+        storage: str = "f32",
     ) -> Tuple[npt.NDArray, npt.NDArray[np.uint32], Dict[str, float]]:
         """Searches for `k` nearest neighbors of every query in its `n_buckets` most probable buckets.
         Parameters and return values as the reference (LearnedIndex.py:41-83).  `metric` (an extension; the
@@ -361,11 +374,13 @@ class LearnedIndex(Logger):
         `path_mass` (an extension, multi-level indexes only; `lmi_set_path_mass`): None = off; 0 < path_mass <= 1: the walk keeps
         its order, and a query stops once the path probabilities (the product of the local probabilities along a bucket's path)
         of the buckets it has recorded sum to `path_mass` or more -- the slots behind the stop stay unvisited, the result shapes
-        do not change.  It holds for this call only.  ValueError on a 1-level index (use `stop_mass` there)."""
+        do not change.  It holds for this call only.  ValueError on a 1-level index (use `stop_mass` there).
+        `storage` (an extension): "f32" (default) or "f16", how the HBM-resident copy keeps the scan vectors (see `prepare`)."""
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         s = time.time()
-        eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged)
+        eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged,
+                           storage=storage)
         return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass)
 
     def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None):

@@ -75,6 +75,7 @@ class Experiment:
     job: str = "unknown"
     stop_mass: Optional[float] = None
     path_mass: Optional[float] = None
+    storage: str = "f32"
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -101,6 +102,9 @@ class Experiment:
         p.add_argument("--path-mass", type=float, default=None,
                        help="multi-level indexes: a query's walk stops once the path probabilities of the buckets it has recorded "
                             "sum to this (0 < mass <= 1); default: every query visits its whole budget")
+        p.add_argument("--storage", choices=("f32", "f16"), default="f32",
+                       help="how the resident index keeps the scan vectors: f16 = the fp16 fragments only, a third of the device memory, "
+                            "for vectors that are binary16-exact (refused otherwise); same results")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -261,7 +265,7 @@ def run(exp: Experiment) -> Dict:
         os.makedirs("models", exist_ok=True)
         save_as_pickle(os.path.join("models", exp.tag(f"{exp.dataset}-{exp.size}", prep=exp.preprocess) + ".pkl"), index)
 
-    index.prepare(nav, scan, placement, exp.n_categories)  # one upload; every budget below reuses the resident slab
+    index.prepare(nav, scan, placement, exp.n_categories, storage=exp.storage)  # one upload; every budget below reuses the resident slab
     sink, out = ResultSink(), {}
     for budget in bucket_budgets(exp.buckets_perc, n_buckets_in_index):
         dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass,
