@@ -165,8 +165,8 @@ LMI_API int lmi_set_metric(lmi_index *h, int metric);
  * lmi_buckets_begin; default LMI_STORAGE_F32).  No reference counterpart (the reference keeps the DataFrame).
  *   LMI_STORAGE_F32  a row-major f32 image (exact re-rank, fallback, read-back, mutation) + the prefilter's fp16 fragments.
  *   LMI_STORAGE_F16  the fp16 fragments ONLY: a third of the device memory, for vectors that are binary16-exact (data distributed
- *                    as 16-bit floats).  lmi_buckets_add_rows / _add_owned_rows still take f32 rows; each piece is converted as it
- *                    arrives and no f32 image of more than the staged piece ever exists.  The LIBRARY decides, on the device, whether
+ *                    as 16-bit floats; lmi_buckets_add_rows_f16 takes it as such).  lmi_buckets_add_rows / _add_owned_rows take f32
+ *                    rows; each piece is converted as it arrives and no f32 image of more than the staged piece ever exists.  The LIBRARY decides, on the device, whether
  *                    the data is admissible: every stored x is finite and exactly representable in binary16 (subnormals included),
  *                    and so is x * s for the index scale s (the power of two with max|x| * s in [0.5, 1); only a scale below 1, i.e.
  *                    max|x| >= 1, can lose bits).  Inadmissible data: lmi_buckets_end fails, the message names the condition, and the
@@ -225,6 +225,30 @@ LMI_API int lmi_bucket_sizes(lmi_index *h, int64_t *sizes);
  * be NULL. */
 LMI_API int lmi_bucket_read(lmi_index *h, int bucket, float *rows, uint32_t *ids);
 
+/* Binary16 rows as they are distributed (no reference counterpart: the reference holds float32 DataFrames).  "Half" is IEEE
+ * binary16, passed as its uint16_t bit pattern -- an includer needs no _Float16.  One contract for every *_f16 entry point of this
+ * header: the call returns bit for bit what its namesake returns for the same values widened to binary32 (widening is exact).
+ * A half pointer need only be 2-byte aligned, on the host and -- with on_device -- on the device: the kernels read 16 bytes at a
+ * time only where d % 8 == 0 and the piece's base is 16-byte aligned, element by element otherwise.
+ * lmi_buckets_add_rows_f16 / lmi_buckets_add_owned_rows_f16: as lmi_buckets_add_rows / _add_owned_rows (same checks, same piece size
+ *        in rows, so half the staging and half the upload).  LMI_STORAGE_F16: the halves go into the fragments as they are -- no
+ *        binary32 copy of any piece exists; LMI_STORAGE_F32 (prefilter on or off, either metric): the staged piece is widened on the
+ *        device and ingested like a float piece.  Half and float pieces may be mixed freely within one build, piece by piece; the
+ *        rule that add_rows and add_owned_rows are not mixed covers all four calls.  lmi_buckets_end's verdict is unchanged (a half
+ *        piece can only fail it by inf / NaN or by the scale).
+ * lmi_buckets_insert_f16: as lmi_buckets_insert, its checks and refusals included (an LMI_STORAGE_F16 index is refused). */
+LMI_API int lmi_buckets_add_rows_f16(lmi_index *h, const uint16_t *rows, int64_t row0, int64_t nrows, int on_device);
+LMI_API int lmi_buckets_add_owned_rows_f16(lmi_index *h, const uint16_t *rows, const int64_t *index, int64_t nrows,
+                                   int on_device);
+LMI_API int lmi_buckets_insert_f16(lmi_index *h, const uint16_t *rows, const int64_t *labels, const uint32_t *ids, int64_t nrows,
+                                   int on_device, int64_t *n_stored);
+/* lmi_bucket_read with the rows as halves [n_b][d] (no reference counterpart).  LMI_STORAGE_F16: the halves that were ingested
+ * (undoing the index scale and narrowing are exact by the admissibility rule).  LMI_STORAGE_F32, prefilter on or off: narrowed on the
+ * device; if any value of the bucket is not finite or not exactly representable in binary16 the call fails, says so, and writes
+ * no row -- nothing approximate is ever served, as with lmi_buckets_end.  The index is unchanged either way; the L2 norm column is
+ * not returned. */
+LMI_API int lmi_bucket_read_f16(lmi_index *h, int bucket, uint16_t *rows, uint32_t *ids);
+
 /* Navigation: bucket_order[nq][nb] <- the nb most probable classes per query, most probable first.
  * logits (nullable) [nq][L] <- raw outputs of the last Linear layer. */
 LMI_API int lmi_mlp_topk(lmi_index *h, const float *queries_nav, int nq, int nb, int32_t *bucket_order,
@@ -247,6 +271,19 @@ LMI_API int lmi_scan_topk(lmi_index *h, const float *queries_search, int nq, con
 LMI_API int lmi_search(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb,
                int k, float *dists, uint32_t *ids, uint32_t *keys, int32_t *bucket_order,
                int on_device);
+
+/* lmi_scan_topk / lmi_search / lmi_search_tree with every query array as halves (no reference counterpart; the contract of
+ * lmi_buckets_add_rows_f16 above: the results of the namesake on the widened queries, bit for bit).  Host pointers: the halves are
+ * uploaded -- half the bytes -- and widened on the device into the handle's query buffers (lmi_search_tree_f16 uploads the scan
+ * vectors beside the walk, like its namesake, and widens them behind the join).  on_device: the halves are widened into the handle's
+ * buffers; the caller's memory is only read.  queries_search == queries_nav keeps its meaning: one array.  Everything else --
+ * arguments, outputs, settings, timings -- as the namesakes.  lmi_pipeline_submit takes binary32 queries only. */
+LMI_API int lmi_scan_topk_f16(lmi_index *h, const uint16_t *queries_search, int nq, const int32_t *bucket_order,
+                      int nb, int k, float *dists, uint32_t *ids, uint32_t *keys, int on_device);
+LMI_API int lmi_search_f16(lmi_index *h, const uint16_t *queries_nav, const uint16_t *queries_search, int nq, int nb,
+                   int k, float *dists, uint32_t *ids, uint32_t *keys, int32_t *bucket_order, int on_device);
+LMI_API int lmi_search_tree_f16(lmi_index *h, const uint16_t *queries_nav, const uint16_t *queries_search, int nq, int nb, int k,
+                        float *dists, uint32_t *ids, uint32_t *keys, int32_t *slab_ids, int32_t *entries, int on_device);
 
 /* Multi-GPU: gathered_{dists,ids,keys}[w] is rank w's lmi_scan_topk output [nq][kout], found
  * world_stride elements after rank w-1's (0 -> dense, nq*kout; a packed all-gather of

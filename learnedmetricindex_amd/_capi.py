@@ -87,6 +87,17 @@ SIGNATURES = {
     "lmi_debug_read_candidates": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp,
                                                  ctypes.POINTER(ctypes.c_int), _f32p, _f32p, _f32p]),
     "lmi_debug_layout": (ctypes.c_int, [_vp, _vp, _vp, _i64p, _i64p, _vp]),
+    # binary16 rows and queries as they are distributed (uint16 bit patterns; arguments as the namesakes')
+    "lmi_buckets_add_rows_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "lmi_buckets_add_owned_rows_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
+    "lmi_buckets_insert_f16": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _i64p]),
+    "lmi_bucket_read_f16": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    "lmi_scan_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                         ctypes.c_int]),
+    "lmi_search_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                      ctypes.c_int]),
+    "lmi_search_tree_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
+                                           ctypes.c_int]),
 }
 
 
@@ -131,6 +142,46 @@ def _ptr(a) -> int:
 
 def _np(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _is_f16(a) -> bool:
+    """A numpy float16 array or a torch.float16 tensor: data the `_f16` entry points take as it is."""
+    if isinstance(a, np.ndarray):
+        return a.dtype == np.float16
+    return getattr(a, "dtype", None) is not None and str(a.dtype) == "torch.float16"
+
+
+def _rows_arg(rows):
+    """(rows, on_device, f16) of an ingest call: numpy -> C-contiguous float16 (kept) or float32 (anything else is
+    converted, as before); a CUDA torch tensor -> as it is, float16 or a 4-byte float."""
+    f16 = _is_f16(rows)
+    if isinstance(rows, np.ndarray):
+        return _np(rows, np.float16 if f16 else np.float32), 0, f16
+    assert rows.is_cuda and rows.is_contiguous() and rows.dtype.is_floating_point and rows.element_size() == (2 if f16 else 4)
+    return rows, 1, f16
+
+
+def _device_f16(qn_t, qs_t) -> bool:
+    """Whether a device search call takes its `_f16` form: both query tensors are torch.float16 (contiguous).  A half tensor
+    beside a float one is an error: nothing is converted on the device on the caller's behalf."""
+    f16 = _is_f16(qn_t), _is_f16(qs_t)
+    assert f16[0] == f16[1], "device query tensors must both be float16 or both float32"
+    assert not f16[0] or (qn_t.is_contiguous() and qs_t.is_contiguous())
+    return f16[0]
+
+
+def _nbytes(a) -> int:
+    return int(a.nbytes) if isinstance(a, np.ndarray) else int(a.numel() * a.element_size())
+
+
+def _queries(queries_nav, queries_search):
+    """(qn, qs, f16) of a search call: both arrays float16 -> kept as halves for the `_f16` call; otherwise float32 (a
+    half array beside a float one is widened on the host).  `qs is qn` where the caller passed one array twice."""
+    same = queries_search is queries_nav
+    f16 = _is_f16(queries_nav) and (same or _is_f16(queries_search))
+    dt = np.float16 if f16 else np.float32
+    qn = _np(queries_nav, dt)
+    return qn, (qn if same else _np(queries_search, dt)), f16
 
 
 def f16_admissible(x):
@@ -178,6 +229,7 @@ class Index:
         self.L = None
         self.stop_mass = 0.0
         self.path_mass = 0.0
+        self.bytes_in = 0   # bytes handed to add_rows / add_owned_rows / insert since the last buckets_begin (counted here, not in the library)
         if chunk_rows is not None:
             _check(lib().lmi_set_chunk_rows(self._h, int(chunk_rows)))
         if prefilter is None and os.environ.get("LMI_PREFILTER") is not None:
@@ -350,8 +402,7 @@ class Index:
     def search_tree(self, queries_nav, queries_search, nb: int, k: int = 10, want_keys: bool = False, want_order: bool = False):
         """The multi-level walk + the scan of its buckets in one call (lmi_search_tree): (dists f32[nq,kout], ids u32[nq,kout]
         [, keys] [, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb]])."""
-        qn = _np(queries_nav, np.float32)
-        qs = qn if queries_search is queries_nav else _np(queries_search, np.float32)
+        qn, qs, f16 = _queries(queries_nav, queries_search)   # both float16: uploaded as halves (lmi_search_tree_f16)
         nq = qn.shape[0]
         ko = self.kout(nb, k)
         d = np.empty((nq, ko), dtype=np.float32)
@@ -359,12 +410,15 @@ class Index:
         keys = np.empty((nq, ko), dtype=np.uint32) if want_keys else None
         slab = np.empty((nq, nb), dtype=np.int32) if want_order else None
         ent = np.empty((nq, nb), dtype=np.int32) if want_order else None
-        _check(lib().lmi_search_tree(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(keys), _ptr(slab), _ptr(ent), 0))
+        fn = lib().lmi_search_tree_f16 if f16 else lib().lmi_search_tree
+        _check(fn(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(keys), _ptr(slab), _ptr(ent), 0))
         out = (d, i) + ((keys,) if want_keys else ()) + ((slab, ent) if want_order else ())
         return out
 
     def search_tree_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, keys_t=None, slab_t=None, ent_t=None) -> None:
-        _check(lib().lmi_search_tree(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
+        """Device tensors; both query tensors torch.float16 -> `lmi_search_tree_f16` (any 2-byte-aligned address)."""
+        fn = lib().lmi_search_tree_f16 if _device_f16(qn_t, qs_t) else lib().lmi_search_tree
+        _check(fn(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
                                      _ptr(keys_t), _ptr(slab_t), _ptr(ent_t), 1))
 
     # ---- buckets ---------------------------------------------------------------------------
@@ -377,55 +431,56 @@ class Index:
         _check(lib().lmi_buckets_begin(self._h, labels.shape[0], int(d), int(L), _ptr(labels), _ptr(ids_a),
                                        _ptr(owned_a)))
         self.N, self.d, self.L = labels.shape[0], int(d), int(L)
+        self.bytes_in = 0
 
     def add_rows(self, rows, row0: int) -> None:
-        """rows: numpy [n,d] float32 (host) or a CUDA torch tensor (device)."""
-        if isinstance(rows, np.ndarray):
-            rows = _np(rows, np.float32)
-            on_device = 0
-        else:
-            assert rows.is_cuda and rows.is_contiguous() and rows.dtype.is_floating_point and rows.element_size() == 4
-            on_device = 1
+        """rows: numpy [n,d] (host) or a CUDA torch tensor (device), float32 or float16.  Halves go to
+        `lmi_buckets_add_rows_f16` as they are -- no host widening, half the bytes; the index is the one their widened
+        values build.  Pieces of either type may be mixed within a build."""
+        rows, on_device, f16 = _rows_arg(rows)
         assert rows.shape[1] == self.d
-        _check(lib().lmi_buckets_add_rows(self._h, _ptr(rows), int(row0), int(rows.shape[0]), on_device))
+        fn = lib().lmi_buckets_add_rows_f16 if f16 else lib().lmi_buckets_add_rows
+        _check(fn(self._h, _ptr(rows), int(row0), int(rows.shape[0]), on_device))
+        self.bytes_in += _nbytes(rows)
 
     def add_owned_rows(self, rows, index) -> None:
-        """Owned-only ingest: rows[i] is object index[i] (int64 original row numbers); both numpy or both CUDA tensors."""
-        if isinstance(rows, np.ndarray):
-            rows, index, on_device = _np(rows, np.float32), _np(index, np.int64).reshape(-1), 0
-        else:
-            assert rows.is_cuda and rows.is_contiguous() and rows.element_size() == 4 and rows.dtype.is_floating_point
+        """Owned-only ingest: rows[i] is object index[i] (int64 original row numbers); both numpy or both CUDA tensors.
+        float32 or float16 rows, as `add_rows`."""
+        rows, on_device, f16 = _rows_arg(rows)
+        if on_device:
             assert index.is_cuda and index.is_contiguous() and index.element_size() == 8
-            on_device = 1
+        else:
+            index = _np(index, np.int64).reshape(-1)
         assert rows.shape[1] == self.d and index.shape[0] == rows.shape[0]
-        _check(lib().lmi_buckets_add_owned_rows(self._h, _ptr(rows), _ptr(index), int(rows.shape[0]), on_device))
+        fn = lib().lmi_buckets_add_owned_rows_f16 if f16 else lib().lmi_buckets_add_owned_rows
+        _check(fn(self._h, _ptr(rows), _ptr(index), int(rows.shape[0]), on_device))
+        self.bytes_in += _nbytes(rows)
 
     def buckets_end(self) -> None:
         _check(lib().lmi_buckets_end(self._h))
 
     def set_buckets(self, data, labels, L: int, ids=None, owned=None, piece: int = 1 << 18) -> None:
-        data = data if not isinstance(data, np.ndarray) else _np(data, np.float32)
+        data = data if not isinstance(data, np.ndarray) or data.dtype == np.float16 else _np(data, np.float32)   # halves stay halves
         self.buckets_begin(labels, data.shape[1], L, ids, owned)
         for r0 in range(0, data.shape[0], piece):
             self.add_rows(data[r0: r0 + piece], r0)
         self.buckets_end()
 
     def insert(self, rows, labels, ids) -> int:
-        """Adds objects to the built index (`lmi_buckets_insert`): rows numpy [n,d] float32 (host) or a CUDA torch tensor,
-        labels int64 [n] bucket ids, ids uint32 [n].  Each goes after the last object of its bucket.  Returns how many
-        were stored (objects of buckets this handle does not own are skipped)."""
+        """Adds objects to the built index (`lmi_buckets_insert`): rows numpy [n,d] (host) or a CUDA torch tensor, float32
+        or float16 (`lmi_buckets_insert_f16`: the halves as they are), labels int64 [n] bucket ids, ids uint32 [n].  Each goes
+        after the last object of its bucket.  Returns how many were stored (objects of buckets this handle does not own are
+        skipped)."""
         labels = _np(labels, np.int64).reshape(-1)
         ids_a = _np(ids, np.uint32).reshape(-1)
-        if isinstance(rows, np.ndarray):
-            rows = _np(rows, np.float32).reshape(-1, self.d)
-            on_device = 0
-        else:
-            assert rows.is_cuda and rows.is_contiguous() and rows.dtype.is_floating_point and rows.element_size() == 4
-            on_device = 1
+        rows, on_device, f16 = _rows_arg(rows)
+        if not on_device:
+            rows = rows.reshape(-1, self.d)
         assert rows.shape[1] == self.d and labels.shape[0] == ids_a.shape[0] == rows.shape[0]
         out = ctypes.c_int64(0)
-        _check(lib().lmi_buckets_insert(self._h, _ptr(rows), _ptr(labels), _ptr(ids_a), int(rows.shape[0]), on_device,
-                                        ctypes.byref(out)))
+        fn = lib().lmi_buckets_insert_f16 if f16 else lib().lmi_buckets_insert
+        _check(fn(self._h, _ptr(rows), _ptr(labels), _ptr(ids_a), int(rows.shape[0]), on_device, ctypes.byref(out)))
+        self.bytes_in += _nbytes(rows)
         self.N = getattr(self, "N", 0) + int(rows.shape[0])
         return out.value
 
@@ -464,39 +519,43 @@ class Index:
         return K_PER_BUCKET if nb == 1 else k
 
     def scan_topk(self, queries_search, bucket_order, k: int = 10, want_keys: bool = False):
-        q = _np(queries_search, np.float32)
+        f16 = _is_f16(queries_search)   # float16 queries are uploaded as halves (lmi_scan_topk_f16) and widened on the device
+        q = _np(queries_search, np.float16 if f16 else np.float32)
         bo = _np(bucket_order, np.int32).reshape(q.shape[0], -1)
         nb = bo.shape[1]
         ko = self.kout(nb, k)
         d = np.empty((q.shape[0], ko), dtype=np.float32)
         i = np.empty((q.shape[0], ko), dtype=np.uint32)
         keys = np.empty((q.shape[0], ko), dtype=np.uint32) if want_keys else None
-        _check(lib().lmi_scan_topk(self._h, _ptr(q), q.shape[0], _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(keys), 0))
+        fn = lib().lmi_scan_topk_f16 if f16 else lib().lmi_scan_topk
+        _check(fn(self._h, _ptr(q), q.shape[0], _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(keys), 0))
         return (d, i, keys) if want_keys else (d, i)
 
     def search(self, queries_nav, queries_search, nb: int, k: int = 10, want_keys: bool = False):
-        qn = _np(queries_nav, np.float32)
-        qs = qn if queries_search is queries_nav else _np(queries_search, np.float32)
+        qn, qs, f16 = _queries(queries_nav, queries_search)   # both float16: uploaded as halves (lmi_search_f16)
         nq = qn.shape[0]
         ko = self.kout(nb, k)
         d = np.empty((nq, ko), dtype=np.float32)
         i = np.empty((nq, ko), dtype=np.uint32)
         bo = np.empty((nq, nb), dtype=np.int32)
         keys = np.empty((nq, ko), dtype=np.uint32) if want_keys else None
-        _check(lib().lmi_search(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(keys),
-                                _ptr(bo), 0))
+        fn = lib().lmi_search_f16 if f16 else lib().lmi_search
+        _check(fn(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(keys), _ptr(bo), 0))
         return (d, i, bo, keys) if want_keys else (d, i, bo)
 
     # ---- query path, device tensors (torch), asynchronous on the handle's stream --------------
     def search_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, keys_t=None, bo_t=None) -> None:
-        _check(lib().lmi_search(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t),
+        """Device tensors; both query tensors torch.float16 -> `lmi_search_f16`: they are widened into the handle's buffers."""
+        fn = lib().lmi_search_f16 if _device_f16(qn_t, qs_t) else lib().lmi_search
+        _check(fn(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t),
                                 _ptr(i_t), _ptr(keys_t), _ptr(bo_t), 1))
 
     def mlp_topk_device(self, qn_t, nb: int, bo_t, logits_t=None) -> None:
         _check(lib().lmi_mlp_topk(self._h, _ptr(qn_t), int(qn_t.shape[0]), int(nb), _ptr(bo_t), _ptr(logits_t), 1))
 
     def scan_topk_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, keys_t=None) -> None:
-        _check(lib().lmi_scan_topk(self._h, _ptr(qs_t), int(qs_t.shape[0]), _ptr(bo_t), int(nb), int(k), _ptr(d_t),
+        fn = lib().lmi_scan_topk_f16 if _device_f16(qs_t, qs_t) else lib().lmi_scan_topk
+        _check(fn(self._h, _ptr(qs_t), int(qs_t.shape[0]), _ptr(bo_t), int(nb), int(k), _ptr(d_t),
                                    _ptr(i_t), _ptr(keys_t), 1))
 
     def merge_gathered(self, gd, gi, gk, world: int, nq: int, kout: int, out_d, out_i, world_stride: int = 0) -> None:
@@ -552,15 +611,21 @@ class Index:
         _check(lib().lmi_allgather_merge(self._h, comm, int(rank), int(world), _ptr(d_t), _ptr(i_t), _ptr(k_t), nq, kout,
                                          _ptr(out_d_t), _ptr(out_i_t)))
 
-    def read_bucket(self, b: int, rows_out=None, ids_out=None):
-        """(rows f32[n_b,d], ids u32[n_b]) of bucket b, in bucket order; `rows_out` / `ids_out`: C-contiguous
-        numpy arrays of exactly that shape to fill instead of fresh ones (e.g. slices of one host slab)."""
+    def read_bucket(self, b: int, rows_out=None, ids_out=None, dtype=np.float32):
+        """(rows [n_b,d], ids u32[n_b]) of bucket b, in bucket order; `rows_out` / `ids_out`: C-contiguous
+        numpy arrays of exactly that shape to fill instead of fresh ones (e.g. slices of one host slab).
+        `dtype`: np.float32 (default) or np.float16 (`lmi_bucket_read_f16`): the rows as halves -- the stored halves of a
+        `storage="f16"` index; an f32 index narrows on the device and raises `LmiError` when a value of the bucket is not
+        exactly representable in binary16 (nothing approximate is returned)."""
+        dtype = np.dtype(dtype)
+        assert dtype in (np.dtype(np.float32), np.dtype(np.float16)), "read_bucket: dtype is np.float32 or np.float16"
         n = int(self.bucket_sizes()[b])
-        rows = np.empty((n, self.d), dtype=np.float32) if rows_out is None else rows_out
+        rows = np.empty((n, self.d), dtype=dtype) if rows_out is None else rows_out
         ids = np.empty(n, dtype=np.uint32) if ids_out is None else ids_out
-        assert rows.shape == (n, self.d) and rows.dtype == np.float32 and rows.flags.c_contiguous
+        assert rows.shape == (n, self.d) and rows.dtype == dtype and rows.flags.c_contiguous
         assert ids.shape == (n,) and ids.dtype == np.uint32 and ids.flags.c_contiguous
-        _check(lib().lmi_bucket_read(self._h, int(b), _ptr(rows), _ptr(ids)))
+        fn = lib().lmi_bucket_read_f16 if dtype == np.float16 else lib().lmi_bucket_read
+        _check(fn(self._h, int(b), _ptr(rows), _ptr(ids)))
         return rows, ids
 
     def workspace_bytes(self, nq: int, nb: int) -> int:

@@ -137,6 +137,11 @@ struct lmi_index {
     int64_t rows_added = 0, owned_total = 0;
     bool indexed_ingest = false;  // lmi_buckets_add_owned_rows: only the owned objects are passed in
     DevBuf stage;  // H2D staging for add_rows / host query uploads
+    DevBuf wide;   // a piece of half rows widened to binary32 for an LMI_STORAGE_F32 build (the *_f16 ingest calls; widen16_kernel)
+    DevBuf q16_nav, q16_srch;   // the uploaded halves of a host-pointer *_f16 search call, widened into q_nav / q_srch
+    bool q_srch_async = false;  // an on_device *_f16 call widened into q_srch and did not synchronise: a later side-stream upload into
+                                // q_srch (lmi_search_tree, host pointers) must wait for that call's scan first
+    DevBuf rd_flag;             // lmi_bucket_read_f16 on an LMI_STORAGE_F32 index: [0] != 0 -> a value was not binary16-exact
     // ---- fp16 prefilter (lmi_prefilter.h) ----
     bool prefilter = true;   // lmi_set_prefilter
     bool pf_hw_ok = false;   // fp16 subnormal self-test passed on this device
@@ -222,7 +227,7 @@ static void each_index_buf(lmi_index* h, F f) {
 template <class F>
 static void each_call_buf(lmi_index* h, F f) {
     DevBuf* b[] = {&h->gather_send, &h->gather_recv, &h->pq_prob, &h->pq_ent, &h->pq_len, &h->nav_len, &h->nav_slab, &h->nav_ent, &h->nav_count,
-                   &h->nav_colq, &h->nav_active, &h->pq_mass, &h->nav_parent_mass, &h->nav_cum, &h->aug_rows, &h->q_aug, &h->qn2, &h->stage, &h->qdelta, &h->qnorm, &h->qscale, &h->qfrag16,
+                   &h->nav_colq, &h->nav_active, &h->pq_mass, &h->nav_parent_mass, &h->nav_cum, &h->aug_rows, &h->q_aug, &h->qn2, &h->stage, &h->wide, &h->q16_nav, &h->q16_srch, &h->rd_flag, &h->qdelta, &h->qnorm, &h->qscale, &h->qfrag16,
                    &h->eps2, &h->cand_cnt, &h->cand_row, &h->cand_s, &h->fallback, &h->pf_bound, &h->nkeep, &h->redo, &h->surv_row, &h->rs_flag,
                    &h->rs_active, &h->act[0], &h->act[1], &h->xfrag, &h->logits, &h->order, &h->q_nav, &h->q_srch, &h->m, &h->cb_start,
                    &h->item_base, &h->part_base, &h->stats, &h->head, &h->slot_local, &h->slot_col, &h->colmap, &h->qfrag, &h->grp, &h->col_thr,
@@ -308,6 +313,33 @@ static int input_ptr(lmi_index* h, const void* src, size_t bytes, int on_device,
     if (on_device) { *out = src; return 0; }
     CHK(buf.reserve(bytes));
     HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    *out = buf.p;
+    return 0;
+}
+
+// Binary16 sources (halves as uint16 bit patterns; a caller's pointer is only 2-byte aligned): a kernel may read 8 halves with one
+// 16-byte load only where d % 8 == 0 and the base is 16-byte aligned -- then every row starts on a 16-byte boundary.  Per launch.
+static bool half_src_vec(const void* src, int d) { return d % 8 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0; }
+// n rows of d halves at `src` (device) -> binary32 at `dst` (a buffer of the library's: 16-byte aligned), on stream s
+static int widen16_enqueue(const void* src, long long n, int d, float* dst, hipStream_t s) {
+    const long long total = n * d;
+    if (total == 0) return 0;
+    if (half_src_vec(src, d)) widen16_kernel<true><<<cdiv(total >> 3, 256), 256, 0, s>>>(static_cast<const unsigned short*>(src), total, dst);
+    else widen16_kernel<false><<<cdiv(total, 256), 256, 0, s>>>(static_cast<const unsigned short*>(src), total, dst);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// device pointer to the binary32 form of a half input of n rows x d: the halves are uploaded (host data; half the bytes) into `raw` and
+// widened into `buf`, the handle's buffer for that input; a device pointer is widened from where it lies (the caller's memory is only read)
+static int input_ptr16(lmi_index* h, const void* src, long long n, int d, int on_device, DevBuf& raw, DevBuf& buf, const void** out) {
+    CHK(buf.reserve((size_t)n * d * 4));
+    if (!on_device) {
+        CHK(raw.reserve((size_t)n * d * 2));
+        HIPCHK(hipMemcpyAsync(raw.p, src, (size_t)n * d * 2, hipMemcpyHostToDevice, h->stream));
+        src = raw.p;
+    }
+    else if (&buf == &h->q_srch) h->q_srch_async = true;
+    CHK(widen16_enqueue(src, n, d, buf.as<float>(), h->stream));
     *out = buf.p;
     return 0;
 }

@@ -141,23 +141,34 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
 
 // rows [nrows][d] are objects row0.. (index == NULL) or objects index[0..nrows) (host or device like `rows`)
 // pos: slab row of every object (-1: not stored), n_total: its length (lmi_buckets_insert passes the batch's)
-static int add_rows_impl(lmi_index* h, const float* rows, int64_t row0, const int64_t* index, int64_t nrows, int on_device,
+// src16: the rows are halves (uint16 bit patterns; the *_f16 entry points).  The piece size in ROWS is the same for both types, so a
+// half piece stages half the bytes.  LMI_STORAGE_F16 takes the staged halves as they are (ingest16_half_kernel: no binary32 copy of
+// the piece exists); LMI_STORAGE_F32 widens the piece once (widen16_kernel -> h->wide) and goes on as if it had arrived as floats.
+static int add_rows_impl(lmi_index* h, const void* rows, int src16, int64_t row0, const int64_t* index, int64_t nrows, int on_device,
                          const int* pos, int64_t n_total) {
     CHK(set_dev(h));
+    const size_t esz = src16 ? 2 : 4;
     const int64_t piece = std::max<int64_t>(1, (256ll << 20) / ((int64_t)h->d * 4));
     for (int64_t off = 0; off < nrows; off += piece) {
         const int64_t n = std::min(piece, nrows - off);
-        const float* src = rows + off * h->d_user;
+        const void* raw = static_cast<const char*>(rows) + (size_t)off * h->d_user * esz;
         const long long* idx = index ? reinterpret_cast<const long long*>(index + off) : nullptr;
         if (!on_device) {
-            const size_t row_bytes = (size_t)n * h->d_user * 4;
-            CHK(h->stage.reserve(row_bytes + (index ? (size_t)n * 8 : 0)));
-            HIPCHK(hipMemcpyAsync(h->stage.p, src, row_bytes, hipMemcpyHostToDevice, h->stream));
-            src = h->stage.as<float>();
+            const size_t row_bytes = (size_t)n * h->d_user * esz;
+            const size_t idx_off = src16 ? (size_t)rup((long long)row_bytes, 8) : row_bytes;
+            CHK(h->stage.reserve(idx_off + (index ? (size_t)n * 8 : 0)));
+            HIPCHK(hipMemcpyAsync(h->stage.p, raw, row_bytes, hipMemcpyHostToDevice, h->stream));
+            raw = h->stage.p;
             if (index) {
-                HIPCHK(hipMemcpyAsync(h->stage.as<char>() + row_bytes, index + off, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
-                idx = reinterpret_cast<const long long*>(h->stage.as<char>() + row_bytes);
+                HIPCHK(hipMemcpyAsync(h->stage.as<char>() + idx_off, index + off, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+                idx = reinterpret_cast<const long long*>(h->stage.as<char>() + idx_off);
             }
+        }
+        const float* src = static_cast<const float*>(raw);
+        if (src16 && h->storage != LMI_STORAGE_F16) {   // halves -> the binary32 piece the kernels below were written for
+            CHK(h->wide.reserve((size_t)n * h->d_user * 4));
+            CHK(widen16_enqueue(raw, n, h->d_user, h->wide.as<float>(), h->stream));
+            src = h->wide.as<float>();
         }
         if (h->metric == LMI_METRIC_L2) {  // the piece with its norm column, then ingested like any d-column piece
             CHK(h->aug_rows.reserve((size_t)n * h->d * 4));
@@ -169,8 +180,17 @@ static int add_rows_impl(lmi_index* h, const float* rows, int64_t row0, const in
         }
         if (h->storage == LMI_STORAGE_F16) {   // the piece -> halves -> its rows' fragments; the exactness flags and the absmax
             long long total = (long long)n * 2 * h->KG16;
-            ingest16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n, h->KG16,
-                                                                    frag16x16(h), h->slab16.as<uint4>(), h->xmaxbits.as<unsigned>());
+            if (!src16)
+                ingest16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n, h->KG16,
+                                                                        frag16x16(h), h->slab16.as<uint4>(), h->xmaxbits.as<unsigned>());
+            else if (half_src_vec(raw, h->d))
+                ingest16_half_kernel<true><<<cdiv(total, 256), 256, 0, h->stream>>>(static_cast<const unsigned short*>(raw), h->d, pos, row0 + off, idx,
+                                                                                   (long long)n_total, n, h->KG16, frag16x16(h), h->slab16.as<uint4>(),
+                                                                                   h->xmaxbits.as<unsigned>());
+            else
+                ingest16_half_kernel<false><<<cdiv(total, 256), 256, 0, h->stream>>>(static_cast<const unsigned short*>(raw), h->d, pos, row0 + off, idx,
+                                                                                    (long long)n_total, n, h->KG16, frag16x16(h), h->slab16.as<uint4>(),
+                                                                                    h->xmaxbits.as<unsigned>());
         } else if (h->prefilter) {
             long long total = (long long)n * h->d;
             scatter_rows_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
@@ -186,29 +206,42 @@ static int add_rows_impl(lmi_index* h, const float* rows, int64_t row0, const in
     return 0;
 }
 
-extern "C" LMI_API int lmi_buckets_add_rows(lmi_index* h, const float* rows, int64_t row0, int64_t nrows, int on_device) {
-    if (!h || !h->building) return fail("lmi_buckets_add_rows: call lmi_buckets_begin first");
-    if (h->indexed_ingest) return fail("lmi_buckets_add_rows: this build already uses lmi_buckets_add_owned_rows");
-    if (row0 < 0 || nrows < 0 || row0 + nrows > h->N) return fail("lmi_buckets_add_rows: rows [%lld,%lld) outside [0,%lld)", (long long)row0, (long long)(row0 + nrows), (long long)h->N);
+static int add_rows_checked(lmi_index* h, const void* rows, int src16, int64_t row0, int64_t nrows, int on_device, const char* who) {
+    if (!h || !h->building) return fail("%s: call lmi_buckets_begin first", who);
+    if (h->indexed_ingest) return fail("%s: this build already uses lmi_buckets_add_owned_rows", who);
+    if (row0 < 0 || nrows < 0 || row0 + nrows > h->N) return fail("%s: rows [%lld,%lld) outside [0,%lld)", who, (long long)row0, (long long)(row0 + nrows), (long long)h->N);
     if (nrows == 0) return 0;
-    CHK(add_rows_impl(h, rows, row0, nullptr, nrows, on_device, h->pos.as<int>(), h->N));
+    CHK(add_rows_impl(h, rows, src16, row0, nullptr, nrows, on_device, h->pos.as<int>(), h->N));
     h->rows_added += nrows;
     return 0;
 }
+extern "C" LMI_API int lmi_buckets_add_rows(lmi_index* h, const float* rows, int64_t row0, int64_t nrows, int on_device) {
+    return add_rows_checked(h, rows, 0, row0, nrows, on_device, "lmi_buckets_add_rows");
+}
+extern "C" LMI_API int lmi_buckets_add_rows_f16(lmi_index* h, const uint16_t* rows, int64_t row0, int64_t nrows, int on_device) {
+    return add_rows_checked(h, rows, 1, row0, nrows, on_device, "lmi_buckets_add_rows_f16");
+}
 
-extern "C" LMI_API int lmi_buckets_add_owned_rows(lmi_index* h, const float* rows, const int64_t* index, int64_t nrows,
-                                          int on_device) {
-    if (!h || !h->building) return fail("lmi_buckets_add_owned_rows: call lmi_buckets_begin first");
-    if (h->rows_added > 0 && !h->indexed_ingest) return fail("lmi_buckets_add_owned_rows: this build already uses lmi_buckets_add_rows");
-    if (nrows < 0 || (nrows > 0 && (!rows || !index))) return fail("lmi_buckets_add_owned_rows: bad arguments");
+static int add_owned_rows_checked(lmi_index* h, const void* rows, int src16, const int64_t* index, int64_t nrows, int on_device, const char* who) {
+    if (!h || !h->building) return fail("%s: call lmi_buckets_begin first", who);
+    if (h->rows_added > 0 && !h->indexed_ingest) return fail("%s: this build already uses lmi_buckets_add_rows", who);
+    if (nrows < 0 || (nrows > 0 && (!rows || !index))) return fail("%s: bad arguments", who);
     if (!on_device)
         for (int64_t i = 0; i < nrows; ++i)
-            if (index[i] < 0 || index[i] >= h->N) return fail("lmi_buckets_add_owned_rows: index[%lld] = %lld outside [0,%lld)", (long long)i, (long long)index[i], (long long)h->N);
+            if (index[i] < 0 || index[i] >= h->N) return fail("%s: index[%lld] = %lld outside [0,%lld)", who, (long long)i, (long long)index[i], (long long)h->N);
     h->indexed_ingest = true;
     if (nrows == 0) return 0;
-    CHK(add_rows_impl(h, rows, 0, index, nrows, on_device, h->pos.as<int>(), h->N));
+    CHK(add_rows_impl(h, rows, src16, 0, index, nrows, on_device, h->pos.as<int>(), h->N));
     h->rows_added += nrows;
     return 0;
+}
+extern "C" LMI_API int lmi_buckets_add_owned_rows(lmi_index* h, const float* rows, const int64_t* index, int64_t nrows,
+                                          int on_device) {
+    return add_owned_rows_checked(h, rows, 0, index, nrows, on_device, "lmi_buckets_add_owned_rows");
+}
+extern "C" LMI_API int lmi_buckets_add_owned_rows_f16(lmi_index* h, const uint16_t* rows, const int64_t* index, int64_t nrows,
+                                              int on_device) {
+    return add_owned_rows_checked(h, rows, 1, index, nrows, on_device, "lmi_buckets_add_owned_rows_f16");
 }
 
 // The prefilter's images of the whole slab: one power-of-two scale from the absmax of every stored value (holes and spare
@@ -330,6 +363,44 @@ extern "C" LMI_API int lmi_bucket_read(lmi_index* h, int bucket, float* rows, ui
         unpack_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab.as<float4>(), h->KGs, p0, n, du, h->stage.as<float>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(rows, h->stage.p, (size_t)n * du * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (ids) HIPCHK(hipMemcpyAsync(ids, h->ids_slab.as<uint32_t>() + p0, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// lmi_bucket_read with the rows as halves.  LMI_STORAGE_F16: the stored halves, unscaled.  LMI_STORAGE_F32 (either layout): narrowed on
+// the device; the flag is read after the synchronisation and a bucket with a value that is not binary16-exact is refused before any row
+// reaches the caller.  Reads only: the index is as it was either way.
+extern "C" LMI_API int lmi_bucket_read_f16(lmi_index* h, int bucket, uint16_t* rows, uint32_t* ids) {
+    if (!h || !h->built) return fail("lmi_bucket_read_f16: the bucket index is not built");
+    if (bucket < 0 || bucket >= h->L) return fail("lmi_bucket_read_f16: bucket %d outside [0,%d)", bucket, h->L);
+    const int64_t n = h->h_nb_rows[bucket];
+    if (n == 0) return 0;
+    CHK(set_dev(h));
+    const int64_t p0 = (int64_t)h->h_rb_start[bucket] * 32;
+    const int du = h->d_user;  // the caller's columns (the L2 norm column is not returned)
+    if (rows) {
+        unsigned short* out = nullptr;
+        CHK(h->stage.reserve((size_t)n * du * 2));
+        out = h->stage.as<unsigned short>();
+        if (h->storage == LMI_STORAGE_F16) {
+            long long total = n * cdiv(du, 8);
+            unpack16_half_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->KG16, frag16x16(h), p0, n, du, h->xscale.as<float>(), out);
+            HIPCHK(hipGetLastError());
+        } else {
+            CHK(h->rd_flag.reserve(16));
+            HIPCHK(hipMemsetAsync(h->rd_flag.p, 0, 4, h->stream));
+            long long total = n * du;
+            if (h->prefilter) narrow16_kernel<false><<<cdiv(total, 256), 256, 0, h->stream>>>(h->rowmajor.as<float>(), h->dp, p0, n, du, out, h->rd_flag.as<unsigned>());
+            else narrow16_kernel<true><<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab.as<float>(), h->KGs, p0, n, du, out, h->rd_flag.as<unsigned>());
+            HIPCHK(hipGetLastError());
+            unsigned bad = 0;
+            HIPCHK(hipMemcpyAsync(&bad, h->rd_flag.p, 4, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            if (bad) return fail("lmi_bucket_read_f16: a value of bucket %d is not exactly representable in binary16 (or not finite); nothing was returned -- read it with lmi_bucket_read", bucket);
+        }
+        HIPCHK(hipMemcpyAsync(rows, out, (size_t)n * du * 2, hipMemcpyDeviceToHost, h->stream));
     }
     if (ids) HIPCHK(hipMemcpyAsync(ids, h->ids_slab.as<uint32_t>() + p0, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

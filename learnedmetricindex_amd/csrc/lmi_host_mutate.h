@@ -115,18 +115,19 @@ static int repack(lmi_index* h, const std::vector<int>& from, const std::vector<
     return 0;
 }
 
-extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const int64_t* labels, const uint32_t* ids, int64_t nrows,
-                                          int on_device, int64_t* n_stored) {
-    CHK(mut_check(h, "lmi_buckets_insert"));
+// lmi_buckets_insert / lmi_buckets_insert_f16 (src16: the rows are halves; `who`: the entry point, for the refusals of mut_check)
+static int insert_impl(lmi_index* h, const void* rows, int src16, const int64_t* labels, const uint32_t* ids, int64_t nrows,
+                       int on_device, int64_t* n_stored, const char* who) {
+    CHK(mut_check(h, who));
     if (nrows < 0 || (nrows > 0 && (!rows || !labels || !ids)))
-        return fail("lmi_buckets_insert: bad arguments (rows, labels and ids are required; the ids are the caller's)");
-    if (nrows >= (1ll << 31)) return fail("lmi_buckets_insert: %lld rows in one call (fewer than 2^31)", (long long)nrows);
+        return fail("%s: bad arguments (rows, labels and ids are required; the ids are the caller's)", who);
+    if (nrows >= (1ll << 31)) return fail("%s: %lld rows in one call (fewer than 2^31)", who, (long long)nrows);
     const int L = h->L;
     std::vector<int64_t> add(L, 0);
     int64_t stored = 0;
     for (int64_t i = 0; i < nrows; ++i) {
         const int64_t b = labels[i];
-        if (b < 0 || b >= L) return fail("lmi_buckets_insert: labels[%lld] = %lld outside [0,%d); nothing was inserted", (long long)i, (long long)b, L);
+        if (b < 0 || b >= L) return fail("%s: labels[%lld] = %lld outside [0,%d); nothing was inserted", who, (long long)i, (long long)b, L);
         if (owns(h, (int)b)) { add[b]++; stored++; }
     }
     if (n_stored) *n_stored = 0;
@@ -141,7 +142,7 @@ extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const
         if (need > cap[b]) {
             // + a quarter (not x2: the images of a 10M x 768 index are 46 GB) and at least a chunk
             const int64_t c = need + std::max<int64_t>(need / 4, chunk_rb);
-            if (c > max_slab_rb(h)) return fail("lmi_buckets_insert: bucket %d would exceed the 32-bit positions of the slab", b);
+            if (c > max_slab_rb(h)) return fail("%s: bucket %d would exceed the 32-bit positions of the slab", who, b);
             cap[b] = (int)c;
             start[b] = (int)std::min<int64_t>(tail, INT32_MAX);
             moved[b] = 1;
@@ -166,12 +167,13 @@ extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const
         for (int b = 0; b < L; ++b) paths[moved[b] ? 1 : 0] += add[b] > 0;
     }
     if (total > max_slab_rb(h))
-        return fail("lmi_buckets_insert: %lld row-blocks of rows, spare row-blocks and holes exceed the 32-bit positions of the slab", (long long)total);
+        return fail("%s: %lld row-blocks of rows, spare row-blocks and holes exceed the 32-bit positions of the slab", who, (long long)total);
     CHK(set_dev(h));
     // every allocation the call needs before the first change (a failure leaves the index as it was)
     const int64_t piece = std::max<int64_t>(1, (256ll << 20) / ((int64_t)h->d * 4));   // add_rows_impl's pieces
     const int64_t np = std::min(piece, nrows);
-    if (!on_device) CHK(h->stage.reserve((size_t)np * h->d_user * 4));
+    if (!on_device) CHK(h->stage.reserve((size_t)np * h->d_user * (src16 ? 2 : 4)));
+    if (src16) CHK(h->wide.reserve((size_t)np * h->d_user * 4));
     if (h->metric == LMI_METRIC_L2) CHK(h->aug_rows.reserve((size_t)np * h->d * 4));
     CHK(h->mut_pos.reserve((size_t)nrows * 4));
     CHK(h->mut_ids.reserve((size_t)nrows * 4));
@@ -214,7 +216,7 @@ extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const
     HIPCHK(hipMemcpyAsync(h->mut_ids.p, ids, (size_t)nrows * 4, hipMemcpyHostToDevice, h->stream));
     scatter_ids_kernel<<<cdiv(nrows, 256), 256, 0, h->stream>>>(h->mut_ids.as<uint32_t>(), h->mut_pos.as<int>(), nrows, h->ids_slab.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    CHK(add_rows_impl(h, rows, 0, nullptr, nrows, on_device, h->mut_pos.as<int>(), nrows));
+    CHK(add_rows_impl(h, rows, src16, 0, nullptr, nrows, on_device, h->mut_pos.as<int>(), nrows));
     // the touched rows: [n_old, n_new) of every bucket that received some (range lists of lmi_mutate.h)
     std::vector<int> list((size_t)L * 5);
     int* l_b = list.data();
@@ -268,6 +270,15 @@ extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const
     for (int i = 0; i < 4; ++i) h->mut_paths[i] += paths[i];
     if (n_stored) *n_stored = stored;
     return 0;
+}
+
+extern "C" LMI_API int lmi_buckets_insert(lmi_index* h, const float* rows, const int64_t* labels, const uint32_t* ids, int64_t nrows,
+                                          int on_device, int64_t* n_stored) {
+    return insert_impl(h, rows, 0, labels, ids, nrows, on_device, n_stored, "lmi_buckets_insert");
+}
+extern "C" LMI_API int lmi_buckets_insert_f16(lmi_index* h, const uint16_t* rows, const int64_t* labels, const uint32_t* ids, int64_t nrows,
+                                              int on_device, int64_t* n_stored) {
+    return insert_impl(h, rows, 1, labels, ids, nrows, on_device, n_stored, "lmi_buckets_insert_f16");
 }
 
 extern "C" LMI_API int lmi_buckets_delete(lmi_index* h, const uint32_t* ids, int64_t n, int64_t* n_removed) {

@@ -4,14 +4,14 @@
 #include "lmi_host_model.h"
 #include "lmi_host_scan.h"
 
-static int check_scan_args(lmi_index* h, int nq, int nb, int k, int* kout) {
-    if (!h->built) return fail("lmi_scan_topk: the bucket index is not built (lmi_buckets_begin/add_rows/end)");
-    if (nq < 0 || nb < 1) return fail("lmi_scan_topk: bad nq/n_buckets");
-    if (nb > 1024) return fail("lmi_scan_topk: n_buckets %d exceeds 1024 (the rank merge keeps 16 four-bit cursors per lane)", nb);
-    if (k < 1 || k > LMI_MAX_K) return fail("lmi_scan_topk: k %d outside [1,%d]", k, LMI_MAX_K);
+static int check_scan_args(lmi_index* h, int nq, int nb, int k, int* kout, const char* who = "lmi_scan_topk") {
+    if (!h->built) return fail("%s: the bucket index is not built (lmi_buckets_begin/add_rows/end)", who);
+    if (nq < 0 || nb < 1) return fail("%s: bad nq/n_buckets", who);
+    if (nb > 1024) return fail("%s: n_buckets %d exceeds 1024 (the rank merge keeps 16 four-bit cursors per lane)", who, nb);
+    if (k < 1 || k > LMI_MAX_K) return fail("%s: k %d outside [1,%d]", who, k, LMI_MAX_K);
     *kout = nb == 1 ? KPB : k;  // LearnedIndex.py:122-124: a single rank is returned unmerged
-    if ((long long)nb * KPB < *kout) return fail("lmi_scan_topk: k %d exceeds n_buckets*10 candidates", k);
-    if ((long long)nq * nb >= (1ll << 31)) return fail("lmi_scan_topk: nq*n_buckets too large");
+    if ((long long)nb * KPB < *kout) return fail("%s: k %d exceeds n_buckets*10 candidates", who, k);
+    if ((long long)nq * nb >= (1ll << 31)) return fail("%s: nq*n_buckets too large", who);
     return 0;
 }
 
@@ -35,16 +35,20 @@ static int out_stage(lmi_index* h, int nq, int kout, float* dists, uint32_t* ids
     return 0;
 }
 
-extern "C" LMI_API int lmi_scan_topk(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order,
-                             int nb, int k, float* dists, uint32_t* ids, uint32_t* keys, int on_device) {
-    if (!h) return fail("lmi_scan_topk: NULL handle");
+// The three search calls take their queries as binary32 or (q16; the *_f16 entry points) as halves: a half array is uploaded as it is
+// -- half the bytes -- and widened on the device into the handle's q_nav / q_srch (input_ptr16; with on_device from the caller's
+// memory, which is only read); from there on the call is the binary32 call on the widened values.
+static int scan_topk_impl(lmi_index* h, const void* queries_search, int q16, int nq, const int32_t* bucket_order,
+                          int nb, int k, float* dists, uint32_t* ids, uint32_t* keys, int on_device) {
+    if (!h) return fail("%s: NULL handle", q16 ? "lmi_scan_topk_f16" : "lmi_scan_topk");
     int kout = 0;
-    CHK(check_scan_args(h, nq, nb, k, &kout));
+    CHK(check_scan_args(h, nq, nb, k, &kout, q16 ? "lmi_scan_topk_f16" : "lmi_scan_topk"));
     if (nq == 0) return 0;
     CHK(set_dev(h));
     const void* d_qs = nullptr;
     const void* d_order = nullptr;
-    CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
+    if (q16) CHK(input_ptr16(h, queries_search, nq, h->d_user, on_device, h->q16_srch, h->q_srch, &d_qs));
+    else CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
     CHK(input_ptr(h, bucket_order, (size_t)nq * nb * 4, on_device, h->order, &d_order));
     OutStage o;
     CHK(out_stage(h, nq, kout, dists, ids, keys, on_device, o));
@@ -55,19 +59,31 @@ extern "C" LMI_API int lmi_scan_topk(lmi_index* h, const float* queries_search, 
     return 0;
 }
 
-extern "C" LMI_API int lmi_search(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb,
-                          int k, float* dists, uint32_t* ids, uint32_t* keys, int32_t* bucket_order, int on_device) {
-    if (!h) return fail("lmi_search: NULL handle");
+extern "C" LMI_API int lmi_scan_topk(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order,
+                             int nb, int k, float* dists, uint32_t* ids, uint32_t* keys, int on_device) {
+    return scan_topk_impl(h, queries_search, 0, nq, bucket_order, nb, k, dists, ids, keys, on_device);
+}
+extern "C" LMI_API int lmi_scan_topk_f16(lmi_index* h, const uint16_t* queries_search, int nq, const int32_t* bucket_order,
+                                 int nb, int k, float* dists, uint32_t* ids, uint32_t* keys, int on_device) {
+    return scan_topk_impl(h, queries_search, 1, nq, bucket_order, nb, k, dists, ids, keys, on_device);
+}
+
+static int search_impl(lmi_index* h, const void* queries_nav, const void* queries_search, int q16, int nq, int nb,
+                       int k, float* dists, uint32_t* ids, uint32_t* keys, int32_t* bucket_order, int on_device) {
+    const char* who = q16 ? "lmi_search_f16" : "lmi_search";
+    if (!h) return fail("%s: NULL handle", who);
     int kout = 0;
-    CHK(check_scan_args(h, nq, nb, k, &kout));
-    if (h->n_layers == 0) return fail("lmi_search: no MLP set (lmi_set_mlp)");
-    if (h->dims[h->n_layers] != h->L) return fail("lmi_search: MLP has %d classes, index has %d buckets", h->dims[h->n_layers], h->L);
+    CHK(check_scan_args(h, nq, nb, k, &kout, q16 ? "lmi_scan_topk_f16" : "lmi_scan_topk"));
+    if (h->n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
+    if (h->dims[h->n_layers] != h->L) return fail("%s: MLP has %d classes, index has %d buckets", who, h->dims[h->n_layers], h->L);
     if (nq == 0) return 0;
     CHK(set_dev(h));
     const void* d_qn = nullptr;
     const void* d_qs = nullptr;
-    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_qn));
+    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->dims[0], on_device, h->q16_nav, h->q_nav, &d_qn));
+    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_qn));
     if (queries_search == queries_nav && h->dims[0] == h->d_user) d_qs = d_qn;
+    else if (q16) CHK(input_ptr16(h, queries_search, nq, h->d_user, on_device, h->q16_srch, h->q_srch, &d_qs));
     else CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
     int* d_order = bucket_order;
     if (!on_device || !bucket_order) { CHK(h->order.reserve((size_t)nq * nb * 4)); d_order = h->order.as<int>(); }
@@ -82,19 +98,31 @@ extern "C" LMI_API int lmi_search(lmi_index* h, const float* queries_nav, const 
     return 0;
 }
 
+extern "C" LMI_API int lmi_search(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb,
+                          int k, float* dists, uint32_t* ids, uint32_t* keys, int32_t* bucket_order, int on_device) {
+    return search_impl(h, queries_nav, queries_search, 0, nq, nb, k, dists, ids, keys, bucket_order, on_device);
+}
+extern "C" LMI_API int lmi_search_f16(lmi_index* h, const uint16_t* queries_nav, const uint16_t* queries_search, int nq, int nb,
+                              int k, float* dists, uint32_t* ids, uint32_t* keys, int32_t* bucket_order, int on_device) {
+    return search_impl(h, queries_nav, queries_search, 1, nq, nb, k, dists, ids, keys, bucket_order, on_device);
+}
+
 // LearnedIndex.search for a multi-level index in ONE call (LearnedIndex.py:216-325 the walk, :328-373 the bucket scans): lmi_nav_order +
 // lmi_scan_topk without the host in between.  Host buffers: the scan vectors' upload (30 MB at 10 000 x 768: 1.2 ms from pageable memory)
 // goes over the library's side stream WHILE the walk runs (0.4-1 ms); the walk's bucket order never leaves the device unless asked for.
-extern "C" LMI_API int lmi_search_tree(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
-                               float* dists, uint32_t* ids, uint32_t* keys, int32_t* slab_ids, int32_t* entries, int on_device) {
-    if (!h) return fail("lmi_search_tree: NULL handle");
+// q16: the halves of the scan vectors take the same side-stream upload (15 MB there) and are widened into q_srch behind the join.
+static int search_tree_impl(lmi_index* h, const void* queries_nav, const void* queries_search, int q16, int nq, int nb, int k,
+                            float* dists, uint32_t* ids, uint32_t* keys, int32_t* slab_ids, int32_t* entries, int on_device) {
+    const char* who = q16 ? "lmi_search_tree_f16" : "lmi_search_tree";
+    if (!h) return fail("%s: NULL handle", who);
     int kout = 0;
-    CHK(check_scan_args(h, nq, nb, k, &kout));
+    CHK(check_scan_args(h, nq, nb, k, &kout, q16 ? "lmi_scan_topk_f16" : "lmi_scan_topk"));
     if (nq == 0) return 0;
-    CHK(nav_check(h, nq, nb, "lmi_search_tree"));
+    CHK(nav_check(h, nq, nb, who));
     const void* d_qn = nullptr;
     const void* d_qs = queries_search;
-    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_qn));
+    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->dims[0], on_device, h->q16_nav, h->q_nav, &d_qn));
+    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_qn));
     const bool same = queries_search == queries_nav && h->dims[0] == h->d_user;
     if (same) d_qs = d_qn;
     CHK(h->nav_slab.reserve((size_t)nq * nb * 4));
@@ -103,7 +131,15 @@ extern "C" LMI_API int lmi_search_tree(lmi_index* h, const float* queries_nav, c
     int* d_ent = (on_device && entries) ? entries : h->nav_ent.as<int>();
     OutStage o;
     CHK(out_stage(h, nq, kout, dists, ids, keys, on_device, o));
-    if (!on_device && !same) CHK(h->q_srch.reserve((size_t)nq * h->d_user * 4));
+    // q_srch is written from the side stream below.  Its last reader is the previous call's scan: a host-pointer call ended
+    // synchronised, but an on_device *_f16 call widened into q_srch and its scan may still be reading it -- then the side stream
+    // first waits for everything enqueued so far (here, before the walk is enqueued, so the upload still runs beside the walk)
+    if (!on_device && !same && !q16 && h->q_srch_async) {
+        CHK(side_fork(h));
+        h->q_srch_async = false;
+    }
+    if ((!on_device || q16) && !same) CHK(h->q_srch.reserve((size_t)nq * h->d_user * 4));
+    if (q16 && !on_device && !same) CHK(h->q16_srch.reserve((size_t)nq * h->d_user * 2));
     begin_call(h);
     CHK(record(h, 0));
     CHK(nav_enqueue(h, static_cast<const float*>(d_qn), nq, nb, d_slab, d_ent));
@@ -111,16 +147,31 @@ extern "C" LMI_API int lmi_search_tree(lmi_index* h, const float* queries_nav, c
     CHK(stamp_end(h, ST_MLP1));
     if (!on_device && !same) {
         // the scan vectors: uploaded beside the walk (the copy's host side returns when the bytes are staged; the stream waits for its event)
-        CHK(side_ensure(h));   // (no fork: the buffer's last reader was the previous call's scan, and a host-buffer call ends synchronised)
-        HIPCHK(hipMemcpyAsync(h->q_srch.p, queries_search, (size_t)nq * h->d_user * 4, hipMemcpyHostToDevice, h->side));
+        CHK(side_ensure(h));   // (no fork here: see q_srch_async above; q16_srch's last reader was a host-pointer call's widening, which ended synchronised)
+        if (q16) HIPCHK(hipMemcpyAsync(h->q16_srch.p, queries_search, (size_t)nq * h->d_user * 2, hipMemcpyHostToDevice, h->side));
+        else HIPCHK(hipMemcpyAsync(h->q_srch.p, queries_search, (size_t)nq * h->d_user * 4, hipMemcpyHostToDevice, h->side));
         HIPCHK(hipEventRecord(h->side_join, h->side));
         HIPCHK(hipStreamWaitEvent(h->stream, h->side_join, 0));
+        if (q16) CHK(widen16_enqueue(h->q16_srch.p, nq, h->d_user, h->q_srch.as<float>(), h->stream));
+        d_qs = h->q_srch.p;
+    } else if (q16 && !same) {   // device halves: widened into the handle's buffer
+        h->q_srch_async = true;
+        CHK(widen16_enqueue(queries_search, nq, h->d_user, h->q_srch.as<float>(), h->stream));
         d_qs = h->q_srch.p;
     }
     CHK(scan_enqueue(h, static_cast<const float*>(d_qs), nq, d_slab, nb, kout, 0, o.d, o.id, o.key));
     if (!on_device) CHK(copy_back(h, {{dists, o.d, o.bytes}, {ids, o.id, o.bytes}, {keys, o.key, o.bytes},
                                       {slab_ids, d_slab, (size_t)nq * nb * 4}, {entries, d_ent, (size_t)nq * nb * 4}}));
     return 0;
+}
+
+extern "C" LMI_API int lmi_search_tree(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                               float* dists, uint32_t* ids, uint32_t* keys, int32_t* slab_ids, int32_t* entries, int on_device) {
+    return search_tree_impl(h, queries_nav, queries_search, 0, nq, nb, k, dists, ids, keys, slab_ids, entries, on_device);
+}
+extern "C" LMI_API int lmi_search_tree_f16(lmi_index* h, const uint16_t* queries_nav, const uint16_t* queries_search, int nq, int nb, int k,
+                                   float* dists, uint32_t* ids, uint32_t* keys, int32_t* slab_ids, int32_t* entries, int on_device) {
+    return search_tree_impl(h, queries_nav, queries_search, 1, nq, nb, k, dists, ids, keys, slab_ids, entries, on_device);
 }
 
 extern "C" LMI_API int lmi_knn_ip(int device, const float* xq, int64_t nq, const float* xb, int64_t nb, int d, int k,

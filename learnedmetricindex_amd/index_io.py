@@ -3,11 +3,13 @@ DataFrames -- replaces the reference's whole-object pickle (search.py:234-241, u
 which stores the models only and drops `data_prediction` and the vectors.
 
     <dir>/meta.json      format/version, N, d, metric ("ip" | "l2"), storage ("f32" | "f16"; optional, absent = "f32"),
+                         vectors ("f16"; optional, absent = "f32": which vectors file the directory holds),
                          n_categories, bucket paths, model descriptions
     <dir>/weights.npz    Linear weights/biases of the root and internal models (float32)
     <dir>/sizes.npy      int64 [B]    objects per bucket, in bucket-id order
     <dir>/ids.npy        uint32 [N]   object labels, bucket-contiguous
-    <dir>/vectors.f32    float32 [N, d] scan vectors, bucket-contiguous row-major (memory-mappable)
+    <dir>/vectors.f32.npy   float32 [N, d] scan vectors, bucket-contiguous row-major (memory-mappable) -- or, written from an
+    <dir>/vectors.f16.npy   f16-resident index, the same as float16 [N, d]: the halves the index holds, half the bytes
 
 `save_index` reads the vectors back from HBM bucket by bucket (lmi_bucket_read); `load_index` streams
 them into a fresh device slab in pieces, so neither needs N x d floats of host memory at once."""
@@ -35,6 +37,14 @@ def _get(store, prefix, n):
     return [(store[f"{prefix}W{i}"], store[f"{prefix}b{i}"]) for i in range(n)]
 
 
+def vectors_file(meta: dict):
+    """(file name, dtype) of the scan vectors of a directory with this meta.json: the optional key "vectors" names the
+    element type ("f16": vectors.f16.npy); a directory without it holds vectors.f32.npy."""
+    kind = meta.get("vectors", "f32")
+    assert kind in ("f32", "f16"), f"unknown vectors type {kind!r} in meta.json"
+    return f"vectors.{kind}.npy", np.dtype(np.float16 if kind == "f16" else np.float32)
+
+
 def save_index(path: str, li: LearnedIndex, n_categories: List[int]) -> None:
     """Writes the resident index of `li` (after prepare()/search()) to directory `path`."""
     eng = li._engine
@@ -46,8 +56,11 @@ def save_index(path: str, li: LearnedIndex, n_categories: List[int]) -> None:
     meta = {"format": FORMAT, "version": VERSION, "N": N, "d": d, "metric": eng.metric, "n_categories": [int(v) for v in n_categories],
             "bucket_paths": [[int(v) for v in p] for p in li.bucket_paths],
             "root_layers": _put(weights, "root_", li.root_model), "internal": []}
-    if getattr(eng, "storage", "f32") != "f32":   # how the index was resident (the vectors on disk are f32 either way); a reader
-        meta["storage"] = eng.storage             # that does not know the key loads an f32-resident index: same results
+    if getattr(eng, "storage", "f32") != "f32":   # how the index was resident; a reader that does not know the key loads an
+        meta["storage"] = eng.storage             # f32-resident index: same results
+    if getattr(eng, "storage", "f32") == "f16":   # ... and its vectors go to disk as the halves it holds (every other engine:
+        meta["vectors"] = "f16"                   # vectors.f32.npy and no key, as ever)
+    vname, vdtype = vectors_file(meta)
     for i, (p, net) in enumerate(li.internal_models.items()):
         meta["internal"].append({"path": [int(v) for v in p], "layers": _put(weights, f"int{i}_", net)})
     if li._path_ids is not None:  # multi-level: bucket id -> path
@@ -55,11 +68,11 @@ def save_index(path: str, li: LearnedIndex, n_categories: List[int]) -> None:
     np.savez(os.path.join(path, "weights.npz"), **weights)
     np.save(os.path.join(path, "sizes.npy"), sizes)
     ids = np.empty(N, dtype=np.uint32)
-    vec = np.lib.format.open_memmap(os.path.join(path, "vectors.f32.npy"), mode="w+", dtype=np.float32, shape=(N, d))
+    vec = np.lib.format.open_memmap(os.path.join(path, vname), mode="w+", dtype=vdtype, shape=(N, d))
     o = 0
     for b, n in enumerate(sizes):
         if n:
-            rows, bid = eng.read_bucket(b)
+            rows, bid = eng.read_bucket(b) if vdtype == np.float32 else eng.read_bucket(b, dtype=vdtype)
             vec[o:o + n], ids[o:o + n] = rows, bid
             o += int(n)
     vec.flush()
@@ -83,7 +96,7 @@ def load_index(path: str, device: int = 0, storage=None) -> Tuple[LearnedIndex, 
     li = LearnedIndex(root, internal, [tuple(p) for p in meta["bucket_paths"]])
     sizes = np.load(os.path.join(path, "sizes.npy"))
     ids = np.load(os.path.join(path, "ids.npy"))
-    vec = np.load(os.path.join(path, "vectors.f32.npy"), mmap_mode="r")
+    vec = np.load(os.path.join(path, vectors_file(meta)[0]), mmap_mode="r")   # halves are streamed in as halves, into either storage
     if storage is None:
         storage = meta.get("storage", "f32")
     assert storage in _capi.Index.STORAGES, f"unknown storage {storage!r}"

@@ -78,6 +78,17 @@ def _array_fingerprint(a) -> int:
     return h.digest()
 
 
+def _scan_dtype(df: pd.DataFrame, cols: list):
+    """np.float16 when every feature column of the scan frame is float16 -- data distributed as halves, which the library
+    takes as it is (`lmi_buckets_add_rows_f16`: no host widening, half the upload) -- else np.float32."""
+    return np.float16 if len(cols) and all(df[c].dtype == np.float16 for c in cols) else np.float32
+
+
+def _query_array(a):
+    """C-contiguous float16 (kept: uploaded as halves) or float32 (everything else) view of a query array."""
+    return np.ascontiguousarray(a, dtype=np.float16 if getattr(a, "dtype", None) == np.float16 else np.float32)
+
+
 def _frame_bytes(df: pd.DataFrame) -> int:
     return int(df.shape[0]) * int(df.shape[1]) * 4
 
@@ -252,9 +263,10 @@ class LearnedIndex(Logger):
             frame = data_search.loc[data_navigation.index]
         eng.buckets_begin(bucket_of, len(cols), n_bucket_ids, ids=labels.astype(np.uint32))
         piece = max(1, (256 << 20) // (4 * max(1, len(cols))))
+        dtype = _scan_dtype(frame, cols)   # a float16 frame is passed on as halves, block by block
         for r0 in range(0, frame.shape[0], piece):
             block = frame.iloc[r0: r0 + piece]
-            eng.add_rows(np.ascontiguousarray(block[cols].to_numpy(dtype=np.float32)), r0)
+            eng.add_rows(np.ascontiguousarray(block[cols].to_numpy(dtype=dtype)), r0)
         eng.buckets_end()
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
@@ -322,7 +334,7 @@ class LearnedIndex(Logger):
                                  "is not supported (rebuild the index): nothing was inserted")
         cols = _feature_columns(srch)
         frame = srch if srch.index.equals(nav.index) else srch.loc[nav.index]
-        rows = np.ascontiguousarray(frame[cols].to_numpy(dtype=np.float32))
+        rows = np.ascontiguousarray(frame[cols].to_numpy(dtype=_scan_dtype(frame, cols)))
         eng.insert(rows, bucket_of, labels.astype(np.uint32))
         self._engine_key = self._mutated_key()
         return dp
@@ -400,8 +412,8 @@ class LearnedIndex(Logger):
 
     def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
         measured_time = defaultdict(float)
-        qn = np.ascontiguousarray(queries_navigation, dtype=np.float32)
-        qs = qn if queries_search is queries_navigation else np.ascontiguousarray(queries_search, dtype=np.float32)
+        qn = _query_array(queries_navigation)   # float16 arrays stay halves: the engine uploads them as they are
+        qs = qn if queries_search is queries_navigation else _query_array(queries_search)
         assert qn.shape[0] == qs.shape[0]
         nq = qs.shape[0]
         if n_buckets >= 2:

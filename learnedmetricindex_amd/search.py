@@ -147,17 +147,19 @@ class VectorSource:
     def _path(self, kind: str, what: str, ext: str) -> str:
         return os.path.join(self.root, kind, self.size, f"{what}.{ext}")
 
-    def load(self, kind: str, key: str) -> Tuple[np.ndarray, np.ndarray]:
-        """(objects f32[N,d], queries f32[nq,d]) of embedding `kind`."""
+    def load(self, kind: str, key: str, keep_f16: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(objects f32[N,d], queries f32[nq,d]) of embedding `kind`.  `keep_f16`: arrays the files hold as float16 are returned as
+        float16 -- for `--storage f16`, which takes halves as they are (no host copy of twice the size)."""
         out = []
         for what in ("dataset", "query"):
             if os.path.exists(self._path(kind, what, "h5")):
                 import h5py
 
                 with h5py.File(self._path(kind, what, "h5"), "r") as fh:
-                    out.append(np.asarray(fh[key], dtype=np.float32))
+                    out.append(np.asarray(fh[key], dtype=np.float16 if keep_f16 and fh[key].dtype == np.float16 else np.float32))
             elif os.path.exists(self._path(kind, what, "npy")):
-                out.append(np.load(self._path(kind, what, "npy")).astype(np.float32, copy=False))
+                a = np.load(self._path(kind, what, "npy"))
+                out.append(a if keep_f16 and a.dtype == np.float16 else a.astype(np.float32, copy=False))
             elif self.synthetic:
                 self.generated.add(kind)
                 out.append(self._generate(kind, what))
@@ -234,7 +236,7 @@ def recall_against_bruteforce(queries: np.ndarray, objects: pd.DataFrame, knns: 
     """recall@k of the first `sample` queries (notebook cell 31: |found & true| / (k * nq)); ground truth from the
     GPU brute-force Baseline over the scan vectors."""
     m, kk = min(sample, knns.shape[0]), min(k, 10)
-    _, truth, _ = Baseline().search(queries[:m], objects.to_numpy(dtype=np.float32), k=kk)
+    _, truth, _ = Baseline().search(queries[:m].astype(np.float32, copy=False), objects.to_numpy(dtype=np.float32), k=kk)
     labels = objects.index.to_numpy()
     truth = labels[truth - 1]  # Baseline ids are 1-based positions
     return float(np.mean([len(set(t) & set(f)) / kk for t, f in zip(truth.tolist(), knns[:m, :k].tolist())]))
@@ -249,10 +251,15 @@ def run(exp: Experiment) -> Dict:
     LOG.info("navigation vectors %s, queries %s", nav_x.shape, nav_q.shape)
     nav = pd.DataFrame(nav_x)
     nav.index += 1  # object ids are 1-based
+    # --storage f16: scan vectors that the files hold as float16 go to the library as halves, unwidened.  Only where the scan
+    # vectors are a dataset of their own: when one dataset serves navigation and scan, the builder needs it as float32 anyway and a
+    # second, float16 copy would cost host memory instead of saving it.  The scan queries stay halves too, but beside float32
+    # navigation queries they are widened on the host (`_capi._queries`): the driver saves on the ingest, not on the query upload.
+    keep_f16 = exp.storage == "f16"
     if exp.dataset == SCAN_KIND:
         scan, scan_q = nav, nav_q
     else:  # navigate in the narrow embedding, scan in clip768v2 (not normalised by the driver, as upstream)
-        sx, scan_q = src.load(SCAN_KIND, SCAN_KEY)
+        sx, scan_q = src.load(SCAN_KIND, SCAN_KEY, keep_f16=keep_f16)
         scan = pd.DataFrame(sx)
         scan.index += 1
         LOG.info("scan vectors %s, queries %s", scan.shape, scan_q.shape)

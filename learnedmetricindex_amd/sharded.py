@@ -57,6 +57,23 @@ def estimate_bucket_work(index, sample_nav_t, nb: int, sizes) -> np.ndarray:
     return sizes * (routed[: sizes.shape[0]] + 1.0)
 
 
+def ingest_owned(index, data, labels, L: int, owner, rank: int, ids=None, piece: int = 1 << 18) -> int:
+    """Builds rank `rank`'s shard of a bucket-sharded index (`Index.add_owned_rows`): of the rows of `data` (a host array or
+    memory map [N, d]) only those of the buckets with owner[b] == rank are read, `piece` rows at a time, and handed over with their
+    original row numbers.  `data` is passed on in the type it has: float16 rows go in as halves (`lmi_buckets_add_owned_rows_f16`),
+    anything else as float32.  Returns the number of rows this rank holds."""
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    owned = (np.asarray(owner).reshape(-1)[:L] == rank).astype(np.uint8)
+    mine = np.flatnonzero(owned[labels] == 1).astype(np.int64)
+    dtype = np.float16 if data.dtype == np.float16 else np.float32
+    index.buckets_begin(labels, data.shape[1], L, ids, owned)
+    for lo in range(0, mine.shape[0], piece):
+        sel = mine[lo:lo + piece]
+        index.add_owned_rows(np.ascontiguousarray(data[sel], dtype=dtype), sel)
+    index.buckets_end()
+    return int(mine.shape[0])
+
+
 def pack_block(xp, dists, ids, keys):
     """[3, nq, kout] int32 block: float32 distance bits | uint32 ids | uint32 keys (xp: numpy or torch)."""
     if xp is np:
