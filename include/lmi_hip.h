@@ -218,6 +218,31 @@ LMI_API int lmi_buckets_insert(lmi_index *h, const float *rows, const int64_t *l
  * handle is one), when a label is outside [0, L) or when rows, spare row-blocks and holes would pass the 32-bit positions
  * of the slab; a slab that must grow is copied into new allocations, so a failed allocation leaves the old index. */
 LMI_API int lmi_buckets_delete(lmi_index *h, const uint32_t *ids, int64_t n, int64_t *n_removed);
+/* A filtered copy of a built index, derived on the device (no reference counterpart: the reference filters its DataFrames and
+ * rebuilds).  ids[n] (host) lists the objects the new index holds (LMI_SUBSET_KEEP) or leaves out (LMI_SUBSET_DROP); ids that are
+ * not present and duplicates are ignored; *n_kept (nullable) <- the objects the new index holds.  LMI_SUBSET_DROP with n == 0 is the
+ * full copy, LMI_SUBSET_KEEP with n == 0 the index of zero objects.
+ * *out is a NEW, INDEPENDENT handle on h's device: it owns copies of the root model, the node models, the tree tables and its own
+ * index images -- nothing is borrowed (it is no clone view and does not count as one), h may be destroyed before it, and either may
+ * be rebuilt or mutated without the other noticing.  It carries h's settings: metric, storage, prefilter on or off,
+ * lmi_set_fused_mlp, lmi_set_stop_mass, lmi_set_path_mass, the timing level and the `owned` mask of a sharded rank; a chunk length
+ * fixed by lmi_set_chunk_rows stays fixed, otherwise it is chosen as lmi_buckets_begin chooses it, for the subset's own size.  Its
+ * stream is the NULL stream until lmi_set_stream.
+ * The new handle holds exactly what lmi_create + those settings + lmi_buckets_begin / add_rows / end would hold for the object list
+ * "every bucket's kept objects, in the order h holds them": every search returns the same dists, ids and keys bit for bit,
+ * lmi_bucket_sizes / lmi_bucket_read / lmi_bucket_read_f16 / lmi_index_bytes return the same, and lmi_debug_layout shows a fresh
+ * build's layout with all four counters zero -- the slack, relocated buckets and holes of a mutated h do not survive, so the full copy
+ * is also h's compaction.  An LMI_STORAGE_F16 index, which lmi_buckets_delete refuses, loses objects this way without any binary32
+ * image: the kept halves are moved as stored and brought to the subset's own scale by an exact power of two.  An owned bucket that is
+ * left empty no longer counts as holding rows on some rank (lmi_buckets_delete's rule); buckets of other ranks keep h's word.
+ * The call synchronises h's stream first, only READS h -- so it is allowed while clone views of h live, and on a clone view -- and
+ * returns when the new index is complete.  Peak device memory: h's images + the subset's + 8 bytes per slab row of h (the keep and
+ * source maps, freed before the call returns).
+ * Refused, with *out left NULL and h untouched: h is not built or is being built, an unknown mode, n < 0, n > 0 with NULL ids, NULL
+ * out.  A failed allocation frees whatever the call allocated; the message says how many bytes it wanted. */
+#define LMI_SUBSET_KEEP 0   /* ids lists the objects the new index holds      */
+#define LMI_SUBSET_DROP 1   /* ids lists the objects the new index leaves out */
+LMI_API int lmi_subset(lmi_index *h, const uint32_t *ids, int64_t n, int mode, lmi_index **out, int64_t *n_kept /* nullable */);
 /* sizes[L] <- number of objects per bucket (0 for buckets not owned). */
 LMI_API int lmi_bucket_sizes(lmi_index *h, int64_t *sizes);
 /* Reads one bucket back to the host in bucket order (what `data_search.loc[g.index].to_numpy()`

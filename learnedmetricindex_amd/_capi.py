@@ -52,6 +52,7 @@ SIGNATURES = {
     "lmi_buckets_end": (ctypes.c_int, [_vp]),
     "lmi_buckets_insert": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _i64p]),
     "lmi_buckets_delete": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _i64p]),
+    "lmi_subset": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp), _i64p]),
     "lmi_bucket_sizes": (ctypes.c_int, [_vp, _vp]),
     "lmi_mlp_topk": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_mlp_proba": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -492,6 +493,29 @@ class Index:
         _check(lib().lmi_buckets_delete(self._h, _ptr(ids_a), int(ids_a.shape[0]), ctypes.byref(out)))
         self.N = getattr(self, "N", 0) - out.value
         return out.value
+
+    def subset(self, ids, drop: bool = False) -> "Index":
+        """A new, independent `Index` that holds only some of this one's objects, derived on the device (`lmi_subset`): those
+        whose id is in `ids` (default) or, with `drop=True`, all but those; ids not present and duplicates are ignored
+        (`drop=True` with no ids is the full copy).  It owns its models and images -- it is no clone view, this index may be
+        closed, mutated or rebuilt without it noticing -- carries this one's settings, and holds exactly what a fresh build of
+        the kept objects (every bucket's, in the order held here) would: same search results bit for bit, same layout.  Works on
+        a `storage="f16"` index, which `delete` refuses, while clone views live, and on a clone view.  `N` is the kept count.
+        Ids that are not integers or lie outside uint32 raise ValueError before the library is called."""
+        a = np.asarray(ids).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":   # (an empty list is float64 and has nothing to truncate)
+            raise ValueError(f"subset: ids must be integers, not {a.dtype}")
+        if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+            raise ValueError("subset: ids must fit uint32")
+        ids_a = _np(a, np.uint32)
+        v = Index.__new__(Index)
+        v._h, v._views = _vp(), []
+        kept = ctypes.c_int64(0)
+        _check(lib().lmi_subset(self._h, _ptr(ids_a), int(ids_a.shape[0]), 1 if drop else 0, ctypes.byref(v._h), ctypes.byref(kept)))
+        for name in ("device", "n_classes", "d_nav", "d", "L", "metric", "storage", "stop_mass", "path_mass"):
+            setattr(v, name, getattr(self, name, None))
+        v.N, v.bytes_in = kept.value, 0
+        return v
 
     def bucket_sizes(self) -> np.ndarray:
         out = np.zeros(self.L, dtype=np.int64)

@@ -1,11 +1,12 @@
 // lmi_hip.hip -- host side of liblmi_hip.so: the C ABI declared in include/lmi_hip.h, one translation unit.
 // Owns the device-resident index (fragment-major slab, ids, CSR of buckets), the packed MLP weights and the per-call
-// workspaces; enqueues the kernels of lmi_kernels.h .. lmi_mutate.h on one HIP stream.  This file: handle creation,
+// workspaces; enqueues the kernels of lmi_kernels.h .. lmi_subset.h on one HIP stream.  This file: handle creation,
 // destruction, clone views and the setters; everything else in the lmi_host*.h headers.
 #include "lmi_host.h"         // the kernel headers, error macros, DevBuf, the handle, per-call helpers
 #include "lmi_host_model.h"   // model packing, MLP forward, tree navigation
 #include "lmi_host_build.h"   // lmi_buckets_begin / add_rows / end, bucket read
 #include "lmi_host_mutate.h"  // lmi_buckets_insert / lmi_buckets_delete
+#include "lmi_host_subset.h"  // lmi_subset
 #include "lmi_host_scan.h"    // scan_plan, the scan's stages, scan_enqueue, lmi_workspace_bytes
 #include "lmi_host_search.h"  // lmi_scan_topk / lmi_search / lmi_search_tree / lmi_knn_ip, lmi_pipeline_submit
 #include "lmi_host_comm.h"    // lmi_merge_gathered, RCCL
@@ -173,6 +174,7 @@ extern "C" LMI_API int lmi_set_chunk_rows(lmi_index* h, int rows) {
     if (rows < P2_TILE_ROWS || rows % P2_TILE_ROWS) return fail("lmi_set_chunk_rows: rows must be a positive multiple of %d", P2_TILE_ROWS);
     if (h->building || h->built) return fail("lmi_set_chunk_rows: must be called before lmi_buckets_begin");
     h->chunk_rows = rows;
+    h->chunk_rows_set = rows;
     h->chunk_rows_auto = false;
     return 0;
 }

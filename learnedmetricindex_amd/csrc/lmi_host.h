@@ -67,7 +67,11 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
         size_t want = bytes + bytes / 8 + 256;
-        HIPCHK(hipMalloc(&p, want));
+        if (hipError_t e = hipMalloc(&p, want); e != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return fail("a device allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
+        }
         cap = want;
         return 0;
     }
@@ -131,6 +135,7 @@ struct lmi_index {
     DevBuf aug_rows, q_aug, qn2;   // L2: augmented ingest pieces / queries, |q|^2
     int chunk_rows = 2048;
     bool chunk_rows_auto = true;  // until lmi_set_chunk_rows: lmi_buckets_begin picks 256..2048 by the index size
+    int chunk_rows_set = 0;       // lmi_set_chunk_rows' value (a very large bucket raises chunk_rows above it; lmi_subset starts from it again)
     int64_t n_rb_total = 0;
     std::vector<int> h_nb_rows, h_rb_start, h_nch;
     DevBuf slab, ids_slab, pos, d_nb_rows, d_rb_start, d_nch;

@@ -12,14 +12,20 @@ static int kg16_for(const lmi_index* h, int d) {
 // before it learns that the item is over; the data is never used, the addresses must be the allocation's)
 static size_t slab16_bytes(const lmi_index* h) { return (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KG16 * 1024 + 8192; }
 
-extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, const int64_t* labels,
-                                 const uint32_t* ids, const uint8_t* owned) {
-    if (!h) return fail("lmi_buckets_begin: NULL handle");
-    if (N < 0 || d < 1 || L < 1 || (N > 0 && !labels)) return fail("lmi_buckets_begin: bad arguments");
+// The part of lmi_buckets_begin that follows from the per-bucket counts alone (lmi_subset starts here: it knows how many objects every
+// bucket keeps, not a label array): the handle's shape, the chunk length, the layout, the zero-filled images and the device copies of the
+// bucket tables.  counts[L]: the rows this handle stores per bucket (0 for a bucket it does not own); any[L]: the bucket holds rows on some
+// rank; owned: lmi_buckets_begin's (nullable).  The ids' image is reserved, not filled; the caller marks the handle `building`.
+static int begin_checks(lmi_index* h, int64_t N, int L, const char* who) {
     if (h->storage_req == LMI_STORAGE_F16)
-        if (const char* why = storage16_conflict(h)) return fail("lmi_buckets_begin: LMI_STORAGE_F16: %s", why);
-    if (N >= (1ll << 31) - 64ll * L) return fail("lmi_buckets_begin: N too large for 32-bit positions");
-    if (L >= (1 << ROUTE_ID_BITS)) return fail("lmi_buckets_begin: %d buckets, the routing kernels take fewer than %d", L, 1 << ROUTE_ID_BITS);
+        if (const char* why = storage16_conflict(h)) return fail("%s: LMI_STORAGE_F16: %s", who, why);
+    if (N >= (1ll << 31) - 64ll * L) return fail("%s: N too large for 32-bit positions", who);
+    if (L >= (1 << ROUTE_ID_BITS)) return fail("%s: %d buckets, the routing kernels take fewer than %d", who, L, 1 << ROUTE_ID_BITS);
+    return 0;
+}
+static int begin_layout(lmi_index* h, int64_t N, int d, int L, const int* counts, const unsigned char* any, const uint8_t* owned,
+                        const char* who) {
+    CHK(begin_checks(h, N, L, who));
     CHK(set_dev(h));
     if (h->storage_req == LMI_STORAGE_F16) CHK(storage16_kernel_attrs(h));
     h->N = N;
@@ -33,14 +39,7 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
     h->L = L;
     h->KGs = (int)rup(cdiv(d, 8), STAGE_G);
     h->built = false;
-    h->h_nb_rows.assign(L, 0);
-    std::vector<unsigned char> seen(owned ? L : 0, 0);   // (a sharded rank: which buckets hold rows on ANY rank)
-    for (int64_t i = 0; i < N; ++i) {
-        int64_t b = labels[i];
-        if (b < 0 || b >= L) return fail("lmi_buckets_begin: labels[%lld] = %lld outside [0,%d)", (long long)i, (long long)b, L);
-        if (!owned || owned[b]) h->h_nb_rows[b]++;
-        if (owned) seen[b] = 1;
-    }
+    h->h_nb_rows.assign(counts, counts + L);
     h->h_rb_start.assign(L + 1, 0);
     h->h_nch.assign(L, 0);
     // Chunk rows not set by the caller: small indexes (or small shards) get smaller chunks so that a scan has
@@ -53,7 +52,7 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
         long long owned_rows = 0;
         // buckets with rows on any rank: the queries of a batch spread over all of them, whoever owns them
         int nonempty = 0;
-        for (int b = 0; b < L; ++b) { max_rows = std::max(max_rows, h->h_nb_rows[b]); owned_rows += h->h_nb_rows[b]; nonempty += owned ? seen[b] : h->h_nb_rows[b] > 0; }
+        for (int b = 0; b < L; ++b) { max_rows = std::max(max_rows, h->h_nb_rows[b]); owned_rows += h->h_nb_rows[b]; nonempty += any[b] != 0; }
         h->n_nonempty = std::max(1, nonempty);
         if (h->chunk_rows_auto) {
             h->chunk_rows = (int)std::min<long long>(2048, std::max<long long>(P2_TILE_ROWS, rup(owned_rows / 4096, P2_TILE_ROWS)));
@@ -79,25 +78,10 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
     }
     h->n_rb_total = h->h_rb_start[L];
     h->h_cap_rb.assign(L, 0);
-    h->h_any.assign(L, 0);
-    for (int b = 0; b < L; ++b) {
-        h->h_cap_rb[b] = h->h_rb_start[b + 1] - h->h_rb_start[b];
-        h->h_any[b] = owned ? seen[b] : h->h_nb_rows[b] > 0;
-    }
+    h->h_any.assign(any, any + L);
+    for (int b = 0; b < L; ++b) h->h_cap_rb[b] = h->h_rb_start[b + 1] - h->h_rb_start[b];
     if (owned) h->h_owned.assign(owned, owned + L);
     else h->h_owned.clear();
-    // bucket-contiguous position of every object (stable: ascending original row inside a bucket,
-    // the order pandas groupby yields) and the id of every slab row
-    std::vector<int> pos((size_t)N);
-    std::vector<uint32_t> ids_slab((size_t)std::max<int64_t>(h->n_rb_total, 1) * 32, 0u);
-    std::vector<int> fill(L, 0);
-    for (int64_t i = 0; i < N; ++i) {
-        int b = (int)labels[i];
-        if (owned && !owned[b]) { pos[i] = -1; continue; }
-        int p = h->h_rb_start[b] * 32 + fill[b]++;
-        pos[i] = p;
-        ids_slab[p] = ids ? ids[i] : (uint32_t)(i + 1);  // search.py:190-191: 1-based labels
-    }
     const size_t slab_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KGs * 1024;
     if (h->prefilter) h->KG16 = kg16_for(h, d);
     if (h->storage == LMI_STORAGE_F16) {   // fp16 fragments only (lmi_store16.h): filled piece by piece, unscaled until buckets_end
@@ -121,10 +105,7 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
         CHK(h->slab.reserve(slab_bytes));
         HIPCHK(hipMemsetAsync(h->slab.p, 0, slab_bytes, h->stream));
     }
-    CHK(h->ids_slab.reserve(ids_slab.size() * 4));
-    HIPCHK(hipMemcpy(h->ids_slab.p, ids_slab.data(), ids_slab.size() * 4, hipMemcpyHostToDevice));
-    CHK(h->pos.reserve(std::max<size_t>(pos.size(), 1) * 4));
-    if (N) HIPCHK(hipMemcpy(h->pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    CHK(h->ids_slab.reserve((size_t)std::max<int64_t>(h->n_rb_total, 1) * 32 * 4));
     CHK(h->d_nb_rows.reserve(L * 4));
     CHK(h->d_rb_start.reserve((L + 1) * 4));
     CHK(h->d_nch.reserve(L * 4));
@@ -135,6 +116,39 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
     h->indexed_ingest = false;
     h->owned_total = 0;
     for (int b = 0; b < L; ++b) h->owned_total += h->h_nb_rows[b];
+    return 0;
+}
+
+extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, const int64_t* labels,
+                                 const uint32_t* ids, const uint8_t* owned) {
+    if (!h) return fail("lmi_buckets_begin: NULL handle");
+    if (N < 0 || d < 1 || L < 1 || (N > 0 && !labels)) return fail("lmi_buckets_begin: bad arguments");
+    CHK(begin_checks(h, N, L, "lmi_buckets_begin"));   // (first, as ever: a build that cannot be is refused before its labels are read)
+    h->built = false;                                   // (from here on the handle holds no index, also when a label is refused below)
+    std::vector<int> counts(L, 0);
+    std::vector<unsigned char> any(L, 0);   // (a sharded rank: which buckets hold rows on ANY rank)
+    for (int64_t i = 0; i < N; ++i) {
+        int64_t b = labels[i];
+        if (b < 0 || b >= L) return fail("lmi_buckets_begin: labels[%lld] = %lld outside [0,%d)", (long long)i, (long long)b, L);
+        if (!owned || owned[b]) counts[b]++;
+        any[b] = 1;
+    }
+    CHK(begin_layout(h, N, d, L, counts.data(), any.data(), owned, "lmi_buckets_begin"));
+    // bucket-contiguous position of every object (stable: ascending original row inside a bucket,
+    // the order pandas groupby yields) and the id of every slab row
+    std::vector<int> pos((size_t)N);
+    std::vector<uint32_t> ids_slab((size_t)std::max<int64_t>(h->n_rb_total, 1) * 32, 0u);
+    std::vector<int> fill(L, 0);
+    for (int64_t i = 0; i < N; ++i) {
+        int b = (int)labels[i];
+        if (owned && !owned[b]) { pos[i] = -1; continue; }
+        int p = h->h_rb_start[b] * 32 + fill[b]++;
+        pos[i] = p;
+        ids_slab[p] = ids ? ids[i] : (uint32_t)(i + 1);  // search.py:190-191: 1-based labels
+    }
+    HIPCHK(hipMemcpy(h->ids_slab.p, ids_slab.data(), ids_slab.size() * 4, hipMemcpyHostToDevice));
+    CHK(h->pos.reserve(std::max<size_t>(pos.size(), 1) * 4));
+    if (N) HIPCHK(hipMemcpy(h->pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
     h->building = true;
     return 0;
 }

@@ -1,0 +1,201 @@
+// lmi_host_subset.h -- lmi_subset: a second, independent index that holds some of a built index's objects (kernels: lmi_subset.h).
+#pragma once
+#include "lmi_host_mutate.h"
+#include "lmi_subset.h"
+
+// ------------------------------------------------------------------------------------------------
+// No reference counterpart (the reference filters its DataFrames and rebuilds).  The new handle is what lmi_create + the source's
+// settings + lmi_buckets_begin / add_rows / end over "every bucket's kept objects, in the order the source holds them" would be, made on
+// the device: the rows are marked against the id list and counted per bucket, the host lays the new index out from the counts
+// (begin_layout, lmi_host_build.h), the kept rows are gathered from the source's slabs straight into the new ones, and what a build
+// derives from the rows is derived from the new handle's own rows.  The source is only read.
+namespace {
+// a copy of one packed Linear stack: allocations of pack_model's sizes, the weights device to device
+int copy_model(hipStream_t st, int n_layers, const std::vector<int>& n_rb, const std::vector<int>& KG, const std::vector<DevBuf>& Wf,
+               const std::vector<DevBuf>& bias, std::vector<DevBuf>& o_W, std::vector<DevBuf>& o_b) {
+    o_W.assign(n_layers, DevBuf());
+    o_b.assign(n_layers, DevBuf());
+    for (int i = 0; i < n_layers; ++i) {
+        const size_t wb = (size_t)n_rb[i] * KG[i] * 1024, bb = (size_t)n_rb[i] * 32 * sizeof(float);
+        CHK(o_W[i].reserve(wb));
+        CHK(o_b[i].reserve(bb));
+        HIPCHK(hipMemcpyAsync(o_W[i].p, Wf[i].p, wb, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(o_b[i].p, bias[i].p, bb, hipMemcpyDeviceToDevice, st));
+    }
+    return 0;
+}
+int copy_table(hipStream_t st, const DevBuf& src, size_t bytes, DevBuf& dst) {
+    CHK(dst.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+// blocks of a grid-stride gather over `pieces` 16-byte pieces: enough waves to keep every CU's memory pipe busy, no more than the work
+int gather_blocks(const lmi_index* h, long long pieces) { return (int)std::max<long long>(1, std::min<long long>((pieces + 255) / 256, (long long)h->num_cus * 32)); }
+}  // namespace
+
+// everything of lmi_subset behind the argument checks: fills the fresh handle c from h (h->stream is idle; c runs on the NULL stream)
+static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t n, int mode, int64_t* n_kept) {
+    const int L = h->L;
+    hipStream_t st = c->stream;
+    // ---- h's settings (lmi_create read the environment's again) ----
+    c->metric = h->metric;
+    c->storage_req = h->storage;
+    c->prefilter = h->prefilter;
+    c->fused_mlp = h->fused_mlp;
+    c->stop_mass = h->stop_mass;
+    c->path_mass = h->path_mass;
+    c->timing_level = h->timing_level;
+    c->chunk_rows_auto = h->chunk_rows_auto;
+    c->chunk_rows_set = h->chunk_rows_set;
+    if (!h->chunk_rows_auto) c->chunk_rows = h->chunk_rows_set;
+    // ---- the models and the tree: copies of its own (the device descriptors point at the weights: rebuilt at the first use) ----
+    c->dims = h->dims; c->n_rb = h->n_rb; c->KG = h->KG;
+    CHK(copy_model(st, h->n_layers, h->n_rb, h->KG, h->Wf, h->bias, c->Wf, c->bias));
+    c->n_layers = h->n_layers;
+    c->node_models.resize(h->node_models.size());
+    for (size_t m = 0; m < h->node_models.size(); ++m) {
+        const auto& s = h->node_models[m];
+        auto& t = c->node_models[m];
+        t.dims = s.dims; t.n_rb = s.n_rb; t.KG = s.KG;
+        CHK(copy_model(st, s.n_layers, s.n_rb, s.KG, s.Wf, s.bias, t.Wf, t.bias));
+        t.n_layers = s.n_layers;
+    }
+    if (h->tree_set) {
+        c->h_child_offset = h->h_child_offset; c->h_child_model = h->h_child_model; c->h_child_bucket = h->h_child_bucket;
+        const size_t total = h->h_child_model.size();
+        CHK(copy_table(st, h->d_child_offset, h->h_child_offset.size() * 4, c->d_child_offset));
+        CHK(copy_table(st, h->d_child_model, std::max<size_t>(total, 1) * 4, c->d_child_model));
+        CHK(copy_table(st, h->d_child_bucket, std::max<size_t>(total, 1) * 4, c->d_child_bucket));
+        c->tree_set = true;
+    }
+    c->desc_dirty = true;
+    // ---- 1: mark the rows that stay and count them per bucket; the counts come back to the host ----
+    std::vector<uint32_t> list(ids, ids + n);
+    if (!std::is_sorted(list.begin(), list.end())) std::sort(list.begin(), list.end());   // (a list that arrives sorted is only checked)
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    const int64_t slab_rows = h->n_rb_total * 32;
+    std::vector<int> cnt(L, 0), iota(L);   // (iota: compact_map_kernel's bucket list; alive until the stream has taken it)
+    const bool some = h->owned_total > 0 && (mode == LMI_SUBSET_DROP || !list.empty());
+    if (some) {
+        CHK(c->mut_ids.reserve(std::max<size_t>(list.size(), 1) * 4));
+        CHK(c->mut_keep.reserve((size_t)slab_rows * 4));   // the keep flags, later the new rows' source positions
+        CHK(c->mut_src.reserve((size_t)slab_rows * 4));    // the stable compaction map
+        CHK(c->mut_word.reserve((size_t)L * 4 + 16));
+        CHK(c->mut_list.reserve((size_t)L * 4));
+        if (!list.empty()) HIPCHK(hipMemcpyAsync(c->mut_ids.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(c->mut_word.p, 0, (size_t)L * 4 + 16, st));
+        int max_n = 0;
+        for (int b = 0; b < L; ++b) max_n = std::max(max_n, h->h_nb_rows[b]);
+        mark_subset_kernel<<<dim3(std::max(1, std::min(64, cdiv(max_n, 256))), L), 256, 0, st>>>(
+            h->ids_slab.as<uint32_t>(), h->d_rb_start.as<int>(), h->d_nb_rows.as<int>(), c->mut_ids.as<uint32_t>(), (int)list.size(), mode,
+            c->mut_keep.as<int>(), c->mut_word.as<int>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(cnt.data(), c->mut_word.p, (size_t)L * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    int64_t kept = 0;
+    for (int b = 0; b < L; ++b) kept += cnt[b];
+    // ---- 2: the layout of a fresh build of the kept objects.  An owned bucket that is left empty holds rows on no rank any more
+    //         (lmi_buckets_delete's rule); the buckets of other ranks keep h's word ----
+    std::vector<unsigned char> any(L, 0);
+    for (int b = 0; b < L; ++b) any[b] = owns(h, b) ? cnt[b] > 0 : h->h_any[b];
+    CHK(begin_layout(c, h->N - (h->owned_total - kept), h->d_user, L, cnt.data(), any.data(), h->h_owned.empty() ? nullptr : h->h_owned.data(),
+                     "lmi_subset"));
+    if (c->d != h->d || c->dp != h->dp || c->KGs != h->KGs || (c->prefilter && c->storage == LMI_STORAGE_F16 && (c->KG16 != h->KG16 || frag16x16(c) != frag16x16(h))))
+        return fail("internal: the new handle's images are shaped differently from the source's (%s:%d)", __FILE__, __LINE__);
+    const int64_t new_rows = c->n_rb_total * 32;
+    HIPCHK(hipMemsetAsync(c->ids_slab.p, 0, (size_t)std::max<int64_t>(c->n_rb_total, 1) * 32 * 4, st));
+    if (kept > 0) {
+        // ---- 3: the stable source map: every bucket's kept rows in order (compact_map_kernel over all buckets, in h's layout), then
+        //         per row of the NEW slab the slab row of h it comes from (-1 behind a bucket's last row) ----
+        for (int b = 0; b < L; ++b) iota[b] = b;
+        HIPCHK(hipMemcpyAsync(c->mut_list.p, iota.data(), (size_t)L * 4, hipMemcpyHostToDevice, st));
+        compact_map_kernel<<<L, CM_THREADS, 0, st>>>(c->mut_list.as<int>(), h->d_nb_rows.as<int>(), h->d_rb_start.as<int>(), h->d_nb_rows.as<int>(),
+                                                    c->mut_keep.as<int>(), c->mut_src.as<int>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(c->mut_keep.p, 0xFF, (size_t)new_rows * 4, st));   // (new_rows <= slab_rows: no bucket grows)
+        int max_n = 0;
+        for (int b = 0; b < L; ++b) max_n = std::max(max_n, cnt[b]);
+        subset_srcpos_kernel<<<dim3(std::max(1, std::min(64, cdiv(max_n, 256))), L), 256, 0, st>>>(
+            h->d_rb_start.as<int>(), c->mut_src.as<int>(), c->d_rb_start.as<int>(), c->d_nb_rows.as<int>(), c->mut_keep.as<int>());
+        HIPCHK(hipGetLastError());
+        const int* srcpos = c->mut_keep.as<int>();
+        // ---- 4: the gather of the stored image, the ids alongside ----
+        if (c->storage == LMI_STORAGE_F16) {
+            const long long pieces = c->n_rb_total * c->KG16 * 64;
+            unsigned* maxbits = c->mut_word.as<unsigned>() + L;   // (zeroed above)
+            subset_gather_frag16_kernel<<<gather_blocks(c, pieces), 256, 0, st>>>(h->slab16.as<uint4>(), h->ids_slab.as<uint32_t>(), srcpos, c->n_rb_total,
+                                                                                   c->KG16, frag16x16(c), c->slab16.as<uint4>(), c->ids_slab.as<uint32_t>(),
+                                                                                   maxbits);
+        } else if (c->prefilter) {
+            const long long pieces = new_rows * (c->dp / 4);
+            subset_gather_rows_kernel<<<gather_blocks(c, pieces), 256, 0, st>>>(h->rowmajor.as<float4>(), h->ids_slab.as<uint32_t>(), srcpos, new_rows,
+                                                                                 c->dp / 4, c->rowmajor.as<float4>(), c->ids_slab.as<uint32_t>());
+        } else {
+            const long long pieces = c->n_rb_total * c->KGs * 64;
+            subset_gather_frag32_kernel<<<gather_blocks(c, pieces), 256, 0, st>>>(h->slab.as<float4>(), h->ids_slab.as<uint32_t>(), srcpos, c->n_rb_total,
+                                                                                   c->KGs, c->slab.as<float4>(), c->ids_slab.as<uint32_t>());
+        }
+        HIPCHK(hipGetLastError());
+    }
+    // ---- 5: what lmi_buckets_end derives from the rows, from the new handle's own ----
+    c->rows_added = c->N;
+    c->have16 = false;
+    if (c->storage == LMI_STORAGE_F16 && c->n_rb_total > 0) {
+        // the stored halves are x * s_old; the kept rows' own scale s_new >= s_old, and the pieces times the power of two s_new / s_old
+        // are the halves x * s_new a fresh build stores (exact: the product is below 1 and only moves the exponent up)
+        CHK(c->xscale.reserve(16));
+        CHK(c->bnorm.reserve((size_t)L * 4));
+        CHK(c->bdelta.reserve((size_t)L * 4));
+        CHK(c->mut_stage.reserve(16));
+        HIPCHK(hipMemsetAsync(c->bnorm.p, 0, (size_t)L * 4, st));
+        HIPCHK(hipMemsetAsync(c->bdelta.p, 0, (size_t)L * 4, st));   // ||x^ - x'|| = 0: the stored value IS x'
+        subset_scale16_kernel<<<1, 1, 0, st>>>(c->mut_word.as<unsigned>() + L, h->xscale.as<float>(), c->xmaxbits.as<unsigned>(), c->xscale.as<float>(),
+                                              c->mut_stage.as<float>());
+        HIPCHK(hipGetLastError());
+        rescale16_kernel<<<c->num_cus * 8, 256, 0, st>>>(c->slab16.as<uint4>(), (long long)c->n_rb_total * c->KG16 * 64, c->mut_stage.as<float>(),
+                                                        c->xmaxbits.as<unsigned>());
+        HIPCHK(hipGetLastError());
+        dim3 g(64, L);
+        bucket_norm16_kernel<<<g, 256, 0, st>>>(c->slab16.as<uint4>(), c->d, c->KG16, frag16x16(c), c->d_rb_start.as<int>(), c->d_nb_rows.as<int>(),
+                                               c->bnorm.as<unsigned>());
+        HIPCHK(hipGetLastError());
+        c->have16 = true;
+    } else if (c->prefilter && c->n_rb_total > 0) {
+        CHK(prefilter_images(c));   // its own absmax, scale, fp16 fragments and norms
+    }
+    unsigned st16[2] = {0u, 0u};   // LMI_STORAGE_F16: [1] = the S16_* flags the rescale raised (none, by the argument above)
+    if (c->have16 && c->storage == LMI_STORAGE_F16) HIPCHK(hipMemcpyAsync(st16, c->xmaxbits.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (st16[1]) return fail("internal: bringing the kept halves to the subset's scale was not exact (flags %u)", st16[1]);
+    for (DevBuf* b : {&c->mut_ids, &c->mut_keep, &c->mut_src, &c->mut_word, &c->mut_list, &c->mut_stage}) b->release();   // the call's maps
+    c->building = false;
+    c->built = true;
+    if (n_kept) *n_kept = kept;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_subset(lmi_index* h, const uint32_t* ids, int64_t n, int mode, lmi_index** out, int64_t* n_kept) {
+    if (!out) return fail("lmi_subset: out is NULL");
+    *out = nullptr;
+    if (n_kept) *n_kept = 0;
+    if (!h) return fail("lmi_subset: NULL handle");
+    if (h->building) return fail("lmi_subset: the index is being built (lmi_buckets_end has not run)");
+    if (!h->built) return fail("lmi_subset: the bucket index is not built (lmi_buckets_end has not run)");
+    if (mode != LMI_SUBSET_KEEP && mode != LMI_SUBSET_DROP)
+        return fail("lmi_subset: unknown mode %d (LMI_SUBSET_KEEP = 0, LMI_SUBSET_DROP = 1)", mode);
+    if (n < 0 || (n > 0 && !ids)) return fail("lmi_subset: bad arguments (n >= 0; ids is required when n > 0)");
+    CHK(set_dev(h));
+    HIPCHK(hipStreamSynchronize(h->stream));   // what was enqueued on h before the call (a build's tail, a mutation) is in the slabs
+    lmi_index* c = nullptr;
+    if (lmi_create(h->device, &c) != 0) return fail("lmi_subset: %s", std::string(g_err).c_str());
+    if (subset_fill(h, c, ids, n, mode, n_kept) != 0) {   // the new handle and everything the call allocated go; h was only read
+        const std::string why = g_err;
+        (void)hipStreamSynchronize(c->stream);
+        (void)lmi_destroy(c);
+        if (n_kept) *n_kept = 0;
+        return fail("lmi_subset: %s; no index was made and the source is unchanged", why.c_str());
+    }
+    *out = c;
+    return 0;
+}

@@ -349,6 +349,19 @@ class LearnedIndex(Logger):
         self._engine_key = self._mutated_key()
         return n
 
+    def subset(self, ids, drop: bool = False) -> "LearnedIndex":
+        """A new `LearnedIndex` over the same models and bucket paths whose HBM-resident index holds only the objects whose id
+        (DataFrame index label) is in `ids` -- or, with `drop=True`, all but those (an extension; `lmi_subset`).  The copy is
+        derived on the device, is independent of this object's resident index (either may be closed or mutated), and is laid
+        out like a fresh build of the kept objects; it is answered by `search_resident`.  Unlike `delete` it works on a
+        `storage="f16"` index.  Ids not present are ignored; this object is unchanged."""
+        eng = self._resident("subset")
+        other = LearnedIndex(self.root_model, self.internal_models, self.bucket_paths)
+        other._engine = eng.subset(np.asarray(ids).reshape(-1), drop=drop)
+        other._engine_key = self._mutated_key()
+        other._path_ids, other._entry_paths, other._nav_cap = self._path_ids, self._entry_paths, self._nav_cap
+        return other
+
     def _resident(self, what: str):
         assert self._engine is not None, f"{what}: no resident index: call prepare()/search() or index_io.load_index()"
         return self._engine

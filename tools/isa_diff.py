@@ -33,7 +33,8 @@ def device_code(so_path):
         elif cur and line.strip():
             bodies[cur].append(re.sub(r"//.*$", "", re.sub(r"^\s*[0-9a-f]+:\s*", "", line)).strip())
     for body in bodies.values():
-        while body and (body[-1].startswith("s_nop") or body[-1].startswith("s_code_end")):
+        # (the code object's last kernel also carries the section's trailing padding, which objdump elides as a line of "...")
+        while body and (body[-1].startswith("s_nop") or body[-1].startswith("s_code_end") or body[-1] == "..."):
             body.pop()
     return notes, {k: v for k, v in bodies.items() if k in notes}
 
