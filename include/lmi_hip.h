@@ -357,6 +357,37 @@ LMI_API int lmi_allgather_merge(lmi_index *h, void *comm, int rank, int world, c
 LMI_API int lmi_knn_ip(int device, const float *xq, int64_t nq, const float *xb, int64_t nb, int d, int k,
                float *D, int64_t *I);
 
+/* Lloyd's k-means on the device, deterministic (replaces the label provider of the index build:
+ * faiss.Kmeans(d, k, niter=20, seed=2023).train(x); index.search(x, 1)     li/clustering/faiss_kmeans.py:8-24; seeding is the
+ * caller's: `centroids` carries the initial centroids in).  The same input gives the same centroids and labels bit for bit on any
+ * launch geometry; tests/kmeans_ref.py restates the call in numpy on top of oracle.knn_l2.
+ * No handle (like lmi_knn_ip): the work runs on the NULL stream of `device` and the call returns when the outputs have landed.
+ * on_device covers x [n][d], centroids [k][d] and labels [n]: device pointers, x is only read; otherwise host pointers -- x is
+ * uploaded once, in pieces, and stays resident for all passes.  counts [k] and changed [niter+1] are host pointers, nullable.
+ * Arithmetic contract
+ *   assignment   cn_j = the chain acc = fmaf(c[t], c[t], acc) from 0, t = 0..d-1; s_ij = the chain acc = fmaf(x[t], c[t], acc)
+ *                from 0; key_ij = fmaf(1.0f, -0.5f * cn_j, s_ij) -- the key of LMI_METRIC_L2 (oracle.knn_l2).  label_i starts at 0
+ *                with best = key_i0 and becomes j only when key_ij > best, j ascending: ties go to the lower centroid, a NaN never wins.
+ *   update       e = the smallest integer with max|x| < 2^e (0 for all-zero data); q(v) = rint(v * 2^(36-e)): the product is exact
+ *                in binary64, the rounding is to nearest even, the result an int64.  S = the sum of q(x) over a cluster's rows per
+ *                dimension, in int64: |q| <= 2^36 and n <= 2^26, so |S| <= 2^62, and integer addition is associative -- any
+ *                reduction tree, grid or atomic order gives the same S.  A cluster with cnt > 0 gets
+ *                c = (float)((double)S / (double)cnt * 2^(e-36)): one int64 -> binary64 conversion, one IEEE binary64 division, an
+ *                exact scaling, one rounding to binary32.  A cluster with cnt == 0 keeps its centroid.
+ *   schedule     pass it = 0..niter assigns; changed[it] = rows whose label differs from the previous pass (labels start at -1:
+ *                changed[0] = n); after every pass but the last the centroids are updated.  The labels returned are the assignment
+ *                to the centroids returned, counts is their histogram.  A pass it >= 1 with changed[it] == 0 is a fixed point: the
+ *                call stops there and the remaining changed entries are 0 -- the result is the same as if it had gone on.
+ * Refused, with nothing written: n < 1, d < 1, d > 4096, k < 1, k > n, k > 16384, niter < 0, niter > 1000, n > 2^26 (the bound of
+ * the integer sums), NULL x / centroids / labels; and, found on the device in the pass that takes max|x|, any value of x or of the
+ * initial centroids that is not finite.  A failed allocation names the bytes it wanted; the call frees all it allocated.
+ * Peak device memory: 8n bytes (sorted rows and their labels) + k' * (8d + 4 * roundup(d+1, 32) + 12) with k' = roundup(k, 32) (sums, fragments, counts)
+ * + 8 * (niter + 2); with host pointers 4nd + 4kd + 4n more for x, the centroids and the labels. */
+LMI_API int lmi_kmeans(int device, const float *x, int64_t n, int d, int k, int niter,
+                       float *centroids /* [k][d], in: initial, out: final */, int32_t *labels /* [n] out */,
+                       int64_t *counts /* [k] host, nullable */, int64_t *changed /* [niter+1] host, nullable */,
+                       int on_device);
+
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);
 /* Mean of the timing slots over the calls made since lmi_timings_reset (the newest 128 at most), read

@@ -73,6 +73,8 @@ SIGNATURES = {
     "lmi_pipeline_submit": (ctypes.c_int, [_vp] * 7 + [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_knn_ip": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int,
                                   ctypes.c_int, _vp, _vp]),
+    "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                  ctypes.c_int]),
     "lmi_timings": (ctypes.c_int, [_vp, _vp]),
     "lmi_timings_reset": (ctypes.c_int, [_vp]),
     "lmi_set_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -696,3 +698,51 @@ def knn_ip(xq, xb, k: int = 10, device: int = 0):
     _check(lib().lmi_knn_ip(int(device), _ptr(xq), xq.shape[0], _ptr(xb), xb.shape[0], xq.shape[1], int(k),
                             _ptr(D), _ptr(I)))
     return D, I
+
+
+def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int = 0):
+    """Lloyd's k-means on the device (`lmi_kmeans`): (centroids f32[k,d], labels i32[n], counts i64[k], changed i64[niter+1]).
+    The same input gives the same result bit for bit (include/lmi_hip.h states the arithmetic; tests/kmeans_ref.py restates it).
+    `x`: a float32 numpy array [n,d], or a contiguous float32 torch tensor on the device -- then `centroids` and `labels` come back
+    as tensors on that device and `x` is only read.  `init`: f32 [k,d] initial centroids; None: the rows
+    `np.random.RandomState(seed).choice(n, k, replace=False)` of `x`.  `changed[it]`: rows whose label moved in pass `it`
+    (zeros behind a fixed point).  Argument errors raise ValueError before the library is loaded."""
+    is_np = isinstance(x, np.ndarray)
+    if not is_np and not (hasattr(x, "data_ptr") and hasattr(x, "is_cuda")):
+        raise ValueError("kmeans: x must be a numpy array or a torch tensor on the device")
+    if str(x.dtype).replace("torch.", "") != "float32":
+        raise ValueError(f"kmeans: x must be float32, not {x.dtype}")
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"kmeans: x must be [n,d] with n, d >= 1, not {tuple(x.shape)}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    k, niter = int(k), int(niter)
+    if k < 1 or k > n:
+        raise ValueError(f"kmeans: k {k} outside [1, n = {n}]")
+    if niter < 0:
+        raise ValueError(f"kmeans: niter {niter} < 0")
+    if init is not None:
+        init = np.asarray(init.detach().cpu().numpy() if hasattr(init, "detach") else init)
+        if init.dtype != np.float32 or init.shape != (k, d):
+            raise ValueError(f"kmeans: init must be float32 [{k},{d}], not {init.dtype} {tuple(init.shape)}")
+    counts = np.zeros(k, dtype=np.int64)
+    changed = np.zeros(niter + 1, dtype=np.int64)
+    if is_np:
+        x = np.ascontiguousarray(x)
+        cent = np.array(x[np.random.RandomState(seed).choice(n, k, replace=False)] if init is None else init, dtype=np.float32, order="C")
+        labels = np.empty(n, dtype=np.int32)
+        _check(lib().lmi_kmeans(int(device), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 0))
+        return cent, labels, counts, changed
+    if not x.is_cuda or not x.is_contiguous():
+        raise ValueError("kmeans: a torch x must be a contiguous tensor on the device")
+    import torch
+
+    if init is None:
+        rows = torch.from_numpy(np.random.RandomState(seed).choice(n, k, replace=False)).to(x.device)
+        cent = x[rows].clone()
+    else:
+        cent = torch.from_numpy(np.array(init, dtype=np.float32, order="C")).to(x.device)
+    labels = torch.empty(n, dtype=torch.int32, device=x.device)
+    torch.cuda.synchronize(x.device)   # the call runs on the NULL stream; whatever produced x may not have
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    _check(lib().lmi_kmeans(int(dev), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
+    return cent, labels, counts, changed

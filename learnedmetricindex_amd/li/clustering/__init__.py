@@ -2,7 +2,8 @@
 
 `ClusteringAlgorithm`: (data f32[n,d], n_clusters, params|None) -> (fitted object, labels int32[n]).
 `faiss_kmeans` needs the faiss wheel (absent in the MI355X image); it is imported lazily so that the
-registry itself always imports."""
+registry itself always imports.  `hip_kmeans` is Lloyd's algorithm in HIP (`lmi_kmeans`), deterministic; it loads the
+library when it is called, so it is imported lazily too."""
 from typing import Any, Callable, Dict, Optional, Tuple
 
 import numpy as np
@@ -22,7 +23,14 @@ def faiss_kmeans(data, n_clusters, parameters):
     return cluster(data, n_clusters, parameters)
 
 
+def hip_kmeans(data, n_clusters, parameters):
+    from .hip_kmeans import cluster
+
+    return cluster(data, n_clusters, parameters)
+
+
 algorithms: Dict[str, ClusteringAlgorithm] = {
     "faiss_kmeans": faiss_kmeans,
+    "hip_kmeans": hip_kmeans,
     "scikit_kmeans": scikit_kmeans,
 }

@@ -1,0 +1,69 @@
+"""Host side of `lmi_kmeans` (no GPU): the numpy reference of tests/kmeans_ref.py reproduces what the four parity cases were chosen
+for, the registry and search.py know `hip_kmeans`, and `_capi.kmeans` refuses bad arguments before it loads the library."""
+import numpy as np
+import pytest
+
+import kmeans_ref
+
+
+@pytest.mark.parametrize("key", sorted(kmeans_ref.CASES))
+def test_reference_cases_cover_what_they_claim(oracle, key):
+    empty, fixed = kmeans_ref.CASES[key]
+    x, c0, c, labels, counts, changed = kmeans_ref.case(*key)
+    assert np.array_equal(c0[0], c0[1])                       # two equal initial centroids
+    assert counts.sum() == key[0] and changed[0] == key[0]
+    assert int((counts == 0).sum()) == empty
+    if fixed is not None:
+        assert changed[fixed] == 0 and (changed[1:fixed] > 0).all() and not changed[fixed:].any()
+    # the labels are the assignment to the centroids returned
+    assert np.array_equal(labels, kmeans_ref.assign(oracle, x, c))
+
+
+def test_labels_still_move_in_the_last_pass_of_case_1():
+    assert kmeans_ref.case(3001, 45, 7, 1)[5][kmeans_ref.NITER] > 0
+
+
+def test_case_4_has_exact_ties(oracle):
+    """5 rows of (600, 768, 257, 4) whose two best distances to the final centroids are exactly equal: the lower centroid wins."""
+    x, _, c, labels, _, _ = kmeans_ref.case(600, 768, 257, 4)
+    D, I = oracle.knn_l2(x, c, k=2)
+    tie = D[:, 0] == D[:, 1]
+    assert int(tie.sum()) == 5
+    assert (I[tie, 0] < I[tie, 1]).all() and np.array_equal(I[:, 0], labels)
+
+
+def test_registry_and_driver_know_hip_kmeans():
+    from learnedmetricindex_amd.li.clustering import algorithms
+
+    assert "hip_kmeans" in algorithms and callable(algorithms["hip_kmeans"])
+    from learnedmetricindex_amd import search
+
+    e = search.Experiment.from_argv(["--clustering-algorithm", "hip_kmeans", "--n-categories", "8"])
+    assert e.clustering_algorithm == ["hip_kmeans"]
+    assert e.build_configuration() is not None
+
+
+def test_wrapper_refuses_bad_arguments_without_loading_the_library(monkeypatch):
+    from learnedmetricindex_amd import _capi
+
+    def no_lib():
+        raise AssertionError("the library was loaded")
+
+    monkeypatch.setattr(_capi, "lib", no_lib)
+    x = np.zeros((10, 4), dtype=np.float32)
+    with pytest.raises(ValueError, match="k 11"):
+        _capi.kmeans(x, 11)
+    with pytest.raises(ValueError, match="k 0"):
+        _capi.kmeans(x, 0)
+    with pytest.raises(ValueError, match="niter -1"):
+        _capi.kmeans(x, 2, niter=-1)
+    with pytest.raises(ValueError, match="init"):
+        _capi.kmeans(x, 2, init=np.zeros((2, 5), dtype=np.float32))
+    with pytest.raises(ValueError, match="init"):
+        _capi.kmeans(x, 2, init=np.zeros((2, 4), dtype=np.float64))
+    with pytest.raises(ValueError, match="float32"):
+        _capi.kmeans(x.astype(np.float64), 2)
+    with pytest.raises(ValueError, match="float32"):
+        _capi.kmeans(np.zeros((10, 4), dtype=np.int32), 2)
+    with pytest.raises(ValueError, match=r"\[n,d\]"):
+        _capi.kmeans(np.zeros(10, dtype=np.float32), 2)
