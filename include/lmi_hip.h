@@ -388,6 +388,50 @@ LMI_API int lmi_kmeans(int device, const float *x, int64_t n, int d, int k, int 
                        int64_t *counts /* [k] host, nullable */, int64_t *changed /* [niter+1] host, nullable */,
                        int on_device);
 
+/* Adam steps on a Linear/ReLU stack with the cross-entropy loss, on the device, deterministic (replaces the training stage of the
+ * index build: NeuralNetwork.train_batch, li/model.py:185-211, whose epoch is ONE optimizer step on its last mini-batch).  The same
+ * input gives the same parameters and moments bit for bit on any launch geometry; tests/train_ref.py restates the call in numpy on
+ * top of oracle.forward_logits and oracle.softmax.  Initialisation and the choice of rows are the caller's.
+ * No handle (like lmi_kmeans): the work runs on the NULL stream of `device` and the call returns when the outputs have landed.
+ * on_device covers x [n][dims[0]] and labels [n]: device pointers, only read, the named rows are gathered by a kernel; otherwise host
+ * pointers -- only the rows that batch_rows names are gathered on the host and uploaded, in pieces; x itself is never uploaded.
+ * Everything else is a host pointer.  W[i] [dims[i+1]][dims[i]] and b[i] [dims[i+1]] in lmi_set_mlp's layout: in the initial, out
+ * the trained parameters.  adam [4 * n_layers]: adam[4i .. 4i+3] = m(W_i), v(W_i), m(b_i), v(b_i), in and out; NULL: zeros in, discarded.
+ * *t: in the Adam steps taken so far, out += n_steps; NULL: 0.  batch_rows [n_steps][bsz]: the rows of x step s trains on (a row may
+ * repeat).  losses [n_steps], nullable.
+ * Arithmetic contract -- step s uses the parameters as they stand at its start; B = bsz, rows in batch_rows[s] order
+ *   forward      lmi_set_mlp's chain: z_l[r][o] = the chain acc = fmaf(a_l[r][k], W_l[o][k], acc) from b_l[o], k ascending; a_0 = the
+ *                rows of x, a_{l+1} = z_l > 0 ? z_l : +0 for every layer but the last.
+ *   loss grad.   p = lmi_mlp_proba's softmax of the last z: the maximum by `v > m ? v : m` from class 0, the library's own expf, the
+ *                row sum as one chain of adds in class order, one division.  g[r][c] = (p[r][c] - [c == y_r]) * (1.0f / (float)B):
+ *                one binary32 subtract, one divide, one multiply.
+ *   weight grad. dW_l[o][i] = the chain acc = fmaf(g[r][o], a_l[r][i], acc) from +0, r = 0..B-1.
+ *   bias grad.   db_l[o] = the chain acc = acc + g[r][o] from +0, r ascending.
+ *   back-prop.   da[r][i] = the chain acc = fmaf(g[r][o], W_l[o][i], acc) from +0, o ascending; then g <- z_{l-1}[r][i] > 0 ? da : +0
+ *                (false on NaN).  da_l is taken before W_l is updated.
+ *   chains       no chain is split over r, o or k and nothing is added atomically: the result does not depend on the grid.  (The
+ *                chains run in v_mfma_f32_32x32x2_f32 and are padded to a multiple of 32 links by fmaf(+0, +0, acc): acc unchanged, -0 -> +0.)
+ *   Adam         torch's defaults (betas 0.9 / 0.999, eps 1e-8, no weight decay).  Host, binary64: P1 = 0.9^t', P2 = 0.999^t' as the
+ *                t'-fold products of the double literals from 1.0 (no pow), t' = the step's 1-based count; step = (float)(lr / (1 - P1)),
+ *                r2 = (float)sqrt(1 - P2).  Per parameter in binary32, every operation rounded on its own:
+ *                m = 0.9f*m + 0.1f*grad;  v = 0.999f*v + (0.001f*grad)*grad;  den = sqrtf(v)/r2 + 1e-8f;  param = param - step*(m/den),
+ *                sqrtf and / correctly rounded (hipcc's default for binary32; __fsqrt_rn would be the native, unrounded form here).
+ *   losses       losses[s] = (float)((1/B) * sum_r -(double)logf(p[r][y_r])), summed in binary64: a diagnostic, not part of the bit
+ *                contract (the device's logf is not the host's).
+ * Refused, with nothing written: n < 1; n_layers outside 1..LMI_MAX_LAYERS; dims[0] or a hidden width outside 1..4096; classes
+ * (dims[n_layers]) outside 1..16384; bsz outside 1..256; n_steps outside 0..100 000; lr not finite or <= 0; *t < 0; a needed pointer
+ * NULL; a batch_rows entry outside [0, n); a label of a named row outside [0, classes); and, found on the device before the first
+ * step, a named row of x or an initial weight or bias that is not finite.  Parameters that become non-finite during training are
+ * not an error.  n_steps == 0 changes nothing.  A failed allocation names the bytes it wanted; the call frees all it allocated.
+ * Peak device memory: n_steps * bsz * (4 * dims[0] + 4) for the named rows and their labels (+ 8 * n_steps * bsz with on_device)
+ * + the sum over the layers of 12 * out * (in + 1) (parameters and both moments) + 8 * bsz * out (z and g) + 4 * (n_steps + bsz) + 12. */
+LMI_API int lmi_train(int device, const float *x, int64_t n, const int32_t *labels /* [n][dims[0]], [n] */,
+                      int n_layers, const int *dims, float *const *W, float *const *b /* host; in: initial, out: trained */,
+                      float *const *adam /* host, [4*n_layers], in/out; NULL: zeros in, discarded */,
+                      int64_t *t /* host; in: steps taken so far, out: += n_steps; NULL: 0 */,
+                      const int64_t *batch_rows /* host, [n_steps][bsz] */, int n_steps, int bsz,
+                      double lr, float *losses /* host [n_steps], nullable */, int on_device /* covers x and labels */);
+
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);
 /* Mean of the timing slots over the calls made since lmi_timings_reset (the newest 128 at most), read

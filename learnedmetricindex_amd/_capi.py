@@ -75,6 +75,8 @@ SIGNATURES = {
                                   ctypes.c_int, _vp, _vp]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
+    "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                 ctypes.POINTER(_vp), _i64p, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, ctypes.c_int]),
     "lmi_timings": (ctypes.c_int, [_vp, _vp]),
     "lmi_timings_reset": (ctypes.c_int, [_vp]),
     "lmi_set_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -746,3 +748,70 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
     dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _check(lib().lmi_kmeans(int(dev), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
     return cent, labels, counts, changed
+
+
+def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0):
+    """Adam steps on a Linear/ReLU stack on the device (`lmi_train`): returns `(layers, state, losses)`.
+    `x` f32 [n,d] and `labels` int32 [n]: numpy arrays, or contiguous torch tensors on the device (both; they are only read).
+    `layers` = [(W [out,in], b [out]), ...] the initial parameters (copied, not changed); `batch_rows` int64 [n_steps, bsz]: the rows
+    step s trains on; `state` = (adam, t) as returned by an earlier call -- adam = [m(W_0), v(W_0), m(b_0), v(b_0), m(W_1), ...], t the
+    Adam steps taken so far -- or None: zeros.  `losses` f32 [n_steps].  The same input gives the same parameters and moments bit for bit
+    (include/lmi_hip.h states the arithmetic; tests/train_ref.py restates it).  Argument errors raise ValueError before the library is
+    loaded."""
+    is_np = isinstance(x, np.ndarray)
+    if not is_np and not (hasattr(x, "data_ptr") and hasattr(x, "is_cuda")):
+        raise ValueError("train: x must be a numpy array or a torch tensor on the device")
+    if isinstance(labels, np.ndarray) != is_np:
+        raise ValueError("train: x and labels must both be numpy arrays or both be tensors on the device")
+    if str(x.dtype).replace("torch.", "") != "float32":
+        raise ValueError(f"train: x must be float32, not {x.dtype}")
+    if str(labels.dtype).replace("torch.", "") != "int32":
+        raise ValueError(f"train: labels must be int32, not {labels.dtype}")
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"train: x must be [n,d] with n, d >= 1, not {tuple(x.shape)}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if tuple(labels.shape) != (n,):
+        raise ValueError(f"train: labels must be [{n}], not {tuple(labels.shape)}")
+    Ws = [np.array(W, dtype=np.float32, order="C") for W, _ in layers]
+    bs = [np.array(b, dtype=np.float32, order="C") for _, b in layers]
+    nl = len(Ws)
+    if nl < 1:
+        raise ValueError("train: no layers")
+    dims = [d] + [int(W.shape[0]) for W in Ws]
+    for i, (W, b) in enumerate(zip(Ws, bs)):
+        if W.shape != (dims[i + 1], dims[i]) or b.shape != (dims[i + 1],):
+            raise ValueError(f"train: layer {i} must be W [{dims[i + 1]},{dims[i]}] and b [{dims[i + 1]}], not {W.shape} and {b.shape}")
+    rows = np.ascontiguousarray(batch_rows, dtype=np.int64)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError(f"train: batch_rows must be [n_steps,bsz] with bsz >= 1, not {rows.shape}")
+    n_steps, bsz = int(rows.shape[0]), int(rows.shape[1])
+    if not (np.isfinite(lr) and lr > 0):
+        raise ValueError(f"train: lr {lr} is not a finite positive number")
+    shapes = [s for W, b in zip(Ws, bs) for s in (W.shape, W.shape, b.shape, b.shape)]
+    if state is None:
+        adam, t0 = [np.zeros(s, dtype=np.float32) for s in shapes], 0
+    else:
+        adam, t0 = [np.array(a, dtype=np.float32, order="C") for a in state[0]], int(state[1])
+        if [a.shape for a in adam] != shapes:
+            raise ValueError("train: state[0] must hold m(W), v(W), m(b), v(b) of every layer, in the layers' shapes")
+        if t0 < 0:
+            raise ValueError(f"train: state t {t0} < 0")
+    if is_np:
+        x, labels, on_device = np.ascontiguousarray(x), np.ascontiguousarray(labels), 0
+    else:
+        if not (x.is_cuda and x.is_contiguous() and labels.is_cuda and labels.is_contiguous()):
+            raise ValueError("train: torch x and labels must be contiguous tensors on the device")
+        import torch
+
+        torch.cuda.synchronize(x.device)   # the call runs on the NULL stream; whatever produced x may not have
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        on_device = 1
+    losses = np.zeros(n_steps, dtype=np.float32)
+    t = ctypes.c_int64(t0)
+    dims_c = (ctypes.c_int32 * (nl + 1))(*dims)
+    Wp = (_vp * nl)(*[W.ctypes.data for W in Ws])
+    bp = (_vp * nl)(*[b.ctypes.data for b in bs])
+    ap = (_vp * (4 * nl))(*[a.ctypes.data for a in adam])
+    _check(lib().lmi_train(int(device), _ptr(x), n, _ptr(labels), nl, dims_c, Wp, bp, ap, ctypes.byref(t), _ptr(rows), n_steps, bsz,
+                           float(lr), _ptr(losses), on_device))
+    return list(zip(Ws, bs)), (adam, int(t.value)), losses

@@ -1,6 +1,6 @@
 // lmi_hip.hip -- host side of liblmi_hip.so: the C ABI declared in include/lmi_hip.h, one translation unit.
 // Owns the device-resident index (fragment-major slab, ids, CSR of buckets), the packed MLP weights and the per-call
-// workspaces; enqueues the kernels of lmi_kernels.h .. lmi_kmeans.h on one HIP stream.  This file: handle creation,
+// workspaces; enqueues the kernels of lmi_kernels.h .. lmi_train.h on one HIP stream.  This file: handle creation,
 // destruction, clone views and the setters; everything else in the lmi_host*.h headers.
 #include "lmi_host.h"         // the kernel headers, error macros, DevBuf, the handle, per-call helpers
 #include "lmi_host_model.h"   // model packing, MLP forward, tree navigation
@@ -13,6 +13,8 @@
 #include "lmi_host_debug.h"   // timings, statistics, test hooks
 #include "lmi_kmeans.h"       // the kernels of lmi_kmeans
 #include "lmi_host_kmeans.h"  // lmi_kmeans
+#include "lmi_train.h"        // the kernels of lmi_train
+#include "lmi_host_train.h"   // lmi_train
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

@@ -7,7 +7,8 @@ prefix plus the positions of the objects placed under it; fitting a node = clust
 rounds until every category is predicted for at least one object (the reference's stopping rule, :176-194), then
 place the node's objects by argmax MLP(x) -- NOT by their k-means label (:76, :270-274).  Placement of level l
 produces the work-list of level l + 1.  Training is torch autograd on the GPU (mini-batches drawn without DataFrame
-label games: positions, not labels, index the tensors); placement runs through the HIP MLP kernel
+label games: positions, not labels, index the tensors) or, with `trainer="hip"`, the same effective schedule in the HIP
+trainer (`NeuralNetwork.train_batch_hip`, lmi_train: repeatable bit for bit); placement runs through the HIP MLP kernel
 (`NeuralNetwork.predict`).  What callers of the reference see is unchanged: `root_model`, `internal_models`
 (path padded with EMPTY_VALUE -> model, in breadth-first lexicographic order), `bucket_paths`."""
 import time
@@ -55,9 +56,13 @@ class _PositionBatches(torch.utils.data.Dataset):
 
 
 class LearnedIndexBuilder(Logger):
-    def __init__(self, data: pd.DataFrame, config: BuildConfiguration):
+    def __init__(self, data: pd.DataFrame, config: BuildConfiguration, trainer: str = "torch", trainer_seed: int = 2023):
+        if trainer not in ("torch", "hip"):
+            raise ValueError(f"trainer {trainer!r}: expected 'torch' or 'hip'")
         self.data = data
         self.config = config
+        self.trainer = trainer   # "hip": NeuralNetwork.train_batch_hip (lmi_train) in place of train_batch
+        self.trainer_seed = trainer_seed   # "hip": seeds every node's generator of training rows
         self.root_model: Optional[NeuralNetwork] = None
         self.internal_models: Dict[Tuple, NeuralNetwork] = {}
         self.bucket_paths: List[Tuple] = []
@@ -109,14 +114,27 @@ class LearnedIndexBuilder(Logger):
             want = fan_out if x.shape[0] >= fan_out else max(x.shape[0] // 5, 2)
             _, labels = cluster(x, want, None)
         secs = time.time() - t
-        n_classes = len(np.unique(labels))
+        # the classes are the clusters that received rows, renumbered in ascending order (a no-op unless the clustering left one empty)
+        used, labels = np.unique(labels, return_inverse=True)
+        n_classes = len(used)
         if n_classes != fan_out:
             self.logger.debug("clustering produced %d of %d categories; training on %d", n_classes, fan_out, n_classes)
-        batches = torch.utils.data.DataLoader(_PositionBatches(x, labels), batch_size=MINI_BATCH, shuffle=True)
         net = NeuralNetwork(input_dim=x.shape[1], output_dim=n_classes, lr=lr, model_type=model_type)
+        if self.trainer == "hip":
+            # the node's vectors go up once: the trainer gathers its rows from that tensor and the placement check of every round
+            # reads it; a node over a quarter of the free device memory stays on the host (only the named rows are uploaded)
+            tx, ty = x, np.ascontiguousarray(labels, dtype=np.int32)
+            if x.nbytes <= torch.cuda.mem_get_info()[0] // 4:
+                tx, ty = torch.from_numpy(x).cuda(), torch.from_numpy(ty).cuda()
+        else:
+            batches = torch.utils.data.DataLoader(_PositionBatches(x, labels), batch_size=MINI_BATCH, shuffle=True)
         for round_no in range(1, TRAINING_ROUND_LIMIT + 1):
-            net.train_batch(batches, epochs=epochs, logger=self.logger)
-            chosen = net.predict(x)
+            if self.trainer == "hip":
+                net.train_batch_hip(tx, ty, epochs=epochs, seed=self.trainer_seed, logger=self.logger)
+                chosen = net.predict(tx)
+            else:
+                net.train_batch(batches, epochs=epochs, logger=self.logger)
+                chosen = net.predict(x)
             if len(np.unique(chosen)) == n_classes:
                 if round_no > 1:
                     self.logger.debug("needed %d epochs (%d rounds of %d)", round_no * epochs, round_no, epochs)

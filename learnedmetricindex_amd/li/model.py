@@ -188,6 +188,48 @@ class NeuralNetwork(Logger):
             self.optimizer.step()
         return losses
 
+    # ---- training: HIP (lmi_train) -------------------------------------------------------------
+    @staticmethod
+    def hip_batch_size(n: int) -> int:
+        """Rows of the ONE mini-batch train_batch steps on per epoch: the last of a shuffled pass in batches of 256."""
+        return n - 256 * ((n - 1) // 256)
+
+    @staticmethod
+    def hip_batch_rows(rng: np.random.Generator, n: int, epochs: int) -> np.ndarray:
+        """int64 [epochs, r]: per epoch r = hip_batch_size(n) distinct rows, drawn in O(r) (no permutation of n)."""
+        r = NeuralNetwork.hip_batch_size(n)
+        if epochs < 1:
+            return np.zeros((0, r), dtype=np.int64)
+        return np.stack([rng.choice(n, r, replace=False) for _ in range(epochs)]).astype(np.int64).reshape(epochs, r)
+
+    def train_batch_hip(self, x, y, epochs=5, seed=2023, logger=None):
+        """train_batch's effective schedule on the device (`lmi_train`): per epoch ONE Adam step on r = n - 256*floor((n-1)/256)
+        distinct random rows -- without the forward passes train_batch runs over the other mini-batches and throws away.
+        `x` f32 [n,d] and `y` [n]: numpy arrays, or contiguous tensors on the device (then only the named rows are read there).
+        The rows come from one `np.random.default_rng(seed)` per network, kept across calls like the Adam state; the weights start
+        from the torch modules' and are written back to them.  The same calls give the same weights bit for bit."""
+        self._engine = None
+        n = int(x.shape[0])
+        if getattr(self, "_hip_rng", None) is None:
+            self._hip_rng, self._hip_state = np.random.default_rng(seed), None
+        rows = self.hip_batch_rows(self._hip_rng, n, epochs)
+        if isinstance(x, np.ndarray):
+            x, y = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(y, dtype=np.int32)
+        else:
+            y = y.to(device=x.device, dtype=torch.int32).contiguous()
+        lr = self.optimizer.param_groups[0]["lr"]
+        layers, self._hip_state, losses = _capi.train(x, y, linear_layers(self.model), rows, lr, state=self._hip_state)
+        lin = [m for m in self.model.layers if isinstance(m, nn.Linear)]
+        with torch.no_grad():
+            for m, (W, b) in zip(lin, layers):
+                m.weight.copy_(torch.from_numpy(W))
+                m.bias.copy_(torch.from_numpy(b))
+        step = max(epochs // 10, 1)
+        if logger:
+            for ep in range(step, epochs, step):
+                logger.debug(f"Epoch {ep} | Loss {losses[ep]:.5f}")
+        return losses.tolist()
+
     # ---- inference: HIP ---------------------------------------------------------------------
     def engine(self):
         """The device-side MLP (weights packed fragment-major in HBM)."""
@@ -205,9 +247,17 @@ class NeuralNetwork(Logger):
         return np.ascontiguousarray(data_X, dtype=np.float32)
 
     def predict(self, data_X):
-        """argmax class per row, int64 (model.py:213-224) -- used for object placement."""
-        x = self._as_numpy(data_X)
+        """argmax class per row, int64 (model.py:213-224) -- used for object placement.  A contiguous float32 tensor on the
+        device is read where it is (`lmi_mlp_topk`, on_device)."""
         eng = self.engine()
+        if isinstance(data_X, torch.Tensor) and data_X.is_cuda and data_X.dtype == torch.float32 and data_X.is_contiguous():
+            order = torch.empty((data_X.shape[0], 1), dtype=torch.int32, device=data_X.device)
+            torch.cuda.synchronize(data_X.device)   # the engine's stream is not torch's
+            for r0 in range(0, data_X.shape[0], self._CHUNK):
+                eng.mlp_topk_device(data_X[r0: r0 + self._CHUNK], 1, order[r0: r0 + self._CHUNK])
+            torch.cuda.synchronize(data_X.device)
+            return order[:, 0].cpu().numpy().astype(np.int64)
+        x = self._as_numpy(data_X)
         out = np.empty(x.shape[0], dtype=np.int64)
         for r0 in range(0, x.shape[0], self._CHUNK):
             out[r0: r0 + self._CHUNK] = eng.mlp_topk(x[r0: r0 + self._CHUNK], 1)[:, 0]

@@ -76,6 +76,7 @@ class Experiment:
     stop_mass: Optional[float] = None
     path_mass: Optional[float] = None
     storage: str = "f32"
+    trainer: str = "torch"
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -105,6 +106,9 @@ class Experiment:
         p.add_argument("--storage", choices=("f32", "f16"), default="f32",
                        help="how the resident index keeps the scan vectors: f16 = the fp16 fragments only, a third of the device memory, "
                             "for vectors that are binary16-exact (refused otherwise); same results")
+        p.add_argument("--trainer", choices=("torch", "hip"), default="torch",
+                       help="how the nodes' models are trained: torch = the reference's loop (autograd, a DataLoader pass per epoch); "
+                            "hip = its effective schedule on the device (lmi_train), repeatable bit for bit")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -265,7 +269,7 @@ def run(exp: Experiment) -> Dict:
         LOG.info("scan vectors %s, queries %s", scan.shape, scan_q.shape)
 
     t0 = time.time()
-    index, placement, n_buckets_in_index, build_s, cluster_s = LearnedIndexBuilder(nav, exp.build_configuration()).build()
+    index, placement, n_buckets_in_index, build_s, cluster_s = LearnedIndexBuilder(nav, exp.build_configuration(), trainer=exp.trainer).build()
     LOG.info("index with %d buckets: clustering %.2fs, build %.2fs, total %.2fs", n_buckets_in_index, cluster_s, build_s,
              time.time() - t0)
     if exp.save:
