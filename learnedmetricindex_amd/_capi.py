@@ -275,14 +275,19 @@ class Index:
     def clone_view(self) -> "Index":
         """A second handle on the same index (`lmi_clone_view`): shares the weights and the bucket slabs, has its own
         workspaces, stream and timings.  Closed with (before) this one."""
-        v = Index.__new__(Index)
-        v._h = _vp()
+        v = self._derived()
         _check(lib().lmi_clone_view(self._h, ctypes.byref(v._h)))
-        for a in ("device", "n_classes", "d_nav", "d", "L", "N", "metric", "storage", "stop_mass", "path_mass"):
-            setattr(v, a, getattr(self, a, None))
-        v._views = []
+        v.N = getattr(self, "N", None)
         v._parent = self
         self.__dict__.setdefault("_views", []).append(v)
+        return v
+
+    def _derived(self) -> "Index":
+        """An `Index` without a handle yet that describes this one's models and index (`clone_view`, `subset`)."""
+        v = Index.__new__(Index)
+        v._h, v._views = _vp(), []
+        for a in ("device", "n_classes", "d_nav", "d", "L", "metric", "storage", "stop_mass", "path_mass"):
+            setattr(v, a, getattr(self, a, None))
         return v
 
     def __del__(self):
@@ -341,17 +346,9 @@ class Index:
     # ---- MLP -------------------------------------------------------------------------------
     def set_mlp(self, layers: Sequence) -> None:
         """layers = [(W [out,in], b [out]), ...] in torch.nn.Linear layout."""
-        Ws = [_np(W, np.float32) for W, _ in layers]
-        bs = [_np(b, np.float32) for _, b in layers]
-        dims = [Ws[0].shape[1]] + [W.shape[0] for W in Ws]
-        for i, (W, b) in enumerate(zip(Ws, bs)):
-            assert W.shape == (dims[i + 1], dims[i]) and b.shape == (dims[i + 1],)
-        n = len(Ws)
-        dims_c = (ctypes.c_int32 * (n + 1))(*dims)
-        Wp = (_vp * n)(*[W.ctypes.data for W in Ws])
-        bp = (_vp * n)(*[b.ctypes.data for b in bs])
+        Ws, bs, n, dims_c, Wp, bp = self._pack_layers(layers)
         _check(lib().lmi_set_mlp(self._h, n, dims_c, Wp, bp))
-        self.d_nav, self.n_classes = dims[0], dims[-1]
+        self.d_nav, self.n_classes = dims_c[0], dims_c[n]
 
     def set_fused_mlp(self, mode: int) -> None:
         """2: always the one-launch MLP kernel, 0: always the per-layer kernels, 1 (default): by batch size; identical outputs."""
@@ -375,9 +372,9 @@ class Index:
         _check(lib().lmi_set_path_mass(self._h, ctypes.c_float(mass)))
         self.path_mass = float(np.float32(mass))
 
-    # ---- multi-level navigation ---------------------------------------------------------------
     @staticmethod
     def _pack_layers(layers):
+        """(W arrays, b arrays -- kept alive by the caller --, n, dims, W pointers, b pointers) as lmi_set_mlp / lmi_nav_set_model take them."""
         Ws = [_np(W, np.float32) for W, _ in layers]
         bs = [_np(b, np.float32) for _, b in layers]
         dims = [Ws[0].shape[1]] + [W.shape[0] for W in Ws]
@@ -386,6 +383,7 @@ class Index:
         n = len(Ws)
         return Ws, bs, n, (ctypes.c_int32 * (n + 1))(*dims), (_vp * n)(*[W.ctypes.data for W in Ws]), (_vp * n)(*[b.ctypes.data for b in bs])
 
+    # ---- multi-level navigation ---------------------------------------------------------------
     def nav_set_model(self, model_id: int, layers: Sequence) -> None:
         """Model of an internal node (model_id >= 1; the root is set_mlp)."""
         Ws, bs, n, dims_c, Wp, bp = self._pack_layers(layers)
@@ -512,12 +510,9 @@ class Index:
         if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
             raise ValueError("subset: ids must fit uint32")
         ids_a = _np(a, np.uint32)
-        v = Index.__new__(Index)
-        v._h, v._views = _vp(), []
+        v = self._derived()
         kept = ctypes.c_int64(0)
         _check(lib().lmi_subset(self._h, _ptr(ids_a), int(ids_a.shape[0]), 1 if drop else 0, ctypes.byref(v._h), ctypes.byref(kept)))
-        for name in ("device", "n_classes", "d_nav", "d", "L", "metric", "storage", "stop_mass", "path_mass"):
-            setattr(v, name, getattr(self, name, None))
         v.N, v.bytes_in = kept.value, 0
         return v
 

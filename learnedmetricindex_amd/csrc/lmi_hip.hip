@@ -2,7 +2,7 @@
 // Owns the device-resident index (fragment-major slab, ids, CSR of buckets), the packed MLP weights and the per-call
 // workspaces; enqueues the kernels of lmi_kernels.h .. lmi_train.h on one HIP stream.  This file: handle creation,
 // destruction, clone views and the setters; everything else in the lmi_host*.h headers.
-#include "lmi_host.h"         // the kernel headers, error macros, DevBuf, the handle, per-call helpers
+#include "lmi_host.h"         // the kernel headers, the handle (lmi_handle.h: error macros, DevBuf), per-call helpers
 #include "lmi_host_model.h"   // model packing, MLP forward, tree navigation
 #include "lmi_host_build.h"   // lmi_buckets_begin / add_rows / end, bucket read
 #include "lmi_host_mutate.h"  // lmi_buckets_insert / lmi_buckets_delete
@@ -118,16 +118,11 @@ extern "C" LMI_API int lmi_destroy(lmi_index* h) {
         (void)hipEventDestroy(h->side_fork);
         (void)hipEventDestroy(h->side_join);
     }
-    for (auto& b : h->Wf) b.release();
-    for (auto& b : h->bias) b.release();
     if (h->h_oflag) (void)hipHostFree(h->h_oflag);
-    for (auto& m : h->node_models) { for (auto& b : m.Wf) b.release(); for (auto& b : m.bias) b.release(); }
-    each_index_buf(h, [](DevBuf& b) { b.release(); });
-    each_call_buf(h, [](DevBuf& b) { b.release(); });
     for (int r = 0; r < lmi_index::EV_RING; ++r)
         for (int i = 0; i < 10; ++i)
             if (h->ev_ring[r][i]) (void)hipEventDestroy(h->ev_ring[r][i]);
-    delete h;
+    delete h;   // every DevBuf frees what it owns
     return 0;
 }
 
@@ -142,28 +137,7 @@ extern "C" LMI_API int lmi_clone_view(lmi_index* h, lmi_index** out) {
     CHK(set_dev(h));
     CHK(build_descs(h));                       // the device copy of the model descriptors is shared as it stands
     HIPCHK(hipStreamSynchronize(h->stream));
-    lmi_index* c = new lmi_index(*h);          // vectors are copied, DevBufs are pointer copies: sorted out below
-    c->stream = nullptr; c->side = nullptr; c->side_fork = nullptr; c->side_join = nullptr;
-    for (auto& b : c->Wf) b.borrow();
-    for (auto& b : c->bias) b.borrow();
-    for (auto& m : c->node_models) { for (auto& b : m.Wf) b.borrow(); for (auto& b : m.bias) b.borrow(); }
-    each_index_buf(c, [](DevBuf& b) { b.borrow(); });
-    each_call_buf(c, [](DevBuf& b) { b.forget(); });
-    c->ts_set = nullptr;
-    memset(c->ts_mask, 0, sizeof(c->ts_mask));
-    c->h_oflag = nullptr;
-    c->overflow_armed = 0;
-    c->x_cap = 0;
-    memset(c->ev_ring, 0, sizeof(c->ev_ring));
-    memset(c->valid_ring, 0, sizeof(c->valid_ring));
-    c->ev_cur = 0; c->ev_calls = 0;
-    c->ev = c->ev_ring[0]; c->ev_valid = c->valid_ring[0];
-    c->stats_pending = false;
-    c->last_nslots = 0; c->last_fast = false;
-    c->parent = h;             // lmi_buckets_insert / _delete refuse to run on h while c lives (c copied h's bucket tables)
-    c->live_clones = 0;
-    h->live_clones++;
-    *out = c;
+    *out = clone_handle(h);
     return 0;
 }
 
@@ -206,12 +180,7 @@ extern "C" LMI_API int lmi_set_storage(lmi_index* h, int storage) {
 extern "C" LMI_API int lmi_index_bytes(lmi_index* h, int64_t* bytes) {
     if (!h || !bytes) return fail("lmi_index_bytes: NULL argument");
     if (!h->building && !h->built) return fail("lmi_index_bytes: no index (valid from lmi_buckets_begin on)");
-    // what the handle holds for the index right now: the vector images, the ids, the per-bucket tables (a clone view: its parent's)
-    const DevBuf* b[] = {&h->slab, &h->slab16, &h->rowmajor, &h->ids_slab, &h->d_nb_rows, &h->d_rb_start, &h->d_nch,
-                         &h->xscale, &h->xmaxbits, &h->bnorm, &h->bdelta};
-    int64_t t = 0;
-    for (const DevBuf* x : b) t += x->p ? (int64_t)x->cap : 0;
-    *bytes = t;
+    *bytes = h->index_bytes();
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// lmi_host.h -- what every host-side header shares: error reporting, the growing device buffer, the handle (lmi_index) and the
+// lmi_host.h -- what every host-side header shares: the kernel headers, the handle (lmi_handle.h) and the
 // per-call helpers (timing events and device stamps, input staging, the library's side stream).
 #pragma once
 #include "lmi_kernels.h"
@@ -12,235 +12,23 @@
 #include "lmi_mutate.h"
 #include "lmi_store16.h"
 
+#include "lmi_handle.h"   // error reporting, DevBuf, the handle and its parts, clone_handle
+
 #include <algorithm>
 #include <cfloat>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <initializer_list>
-#include <string>
-#include <vector>
 
 #include "lmi_hip.h"
 
 using namespace lmi;
 
+static_assert(LMI_STORAGE_F32 == 0 && LMI_METRIC_IP == 0, "lmi_handle.h spells the defaults of storage / storage_req / metric as 0");
+
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return -1;
-}
-
-#define HIPCHK(expr)                                                                                \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess)                                                                       \
-            return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-#define CHK(expr)              \
-    do {                       \
-        int r_ = (expr);       \
-        if (r_ != 0) return r_; \
-    } while (0)
-
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline long long rup(long long a, long long b) { return (a + b - 1) / b * b; }
-
-// device buffer that only grows
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool borrowed = false;  // lmi_clone_view: the memory belongs to the handle this one was cloned from
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (borrowed) return fail("internal: a buffer shared with the parent handle would have to grow");
-        if (p) HIPCHK(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        if (hipError_t e = hipMalloc(&p, want); e != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail("a device allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
-        }
-        cap = want;
-        return 0;
-    }
-    void release() {
-        if (p && !borrowed) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        borrowed = false;
-    }
-    void borrow() { borrowed = p != nullptr; }   // keep the pointer, never free it
-    void forget() { p = nullptr; cap = 0; borrowed = false; }  // a copied struct's workspace: start empty
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 }  // namespace
-
-struct lmi_index {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;           // library-owned: the per-layer MLP of a batch's tail beside the fused kernel (mlp_enqueue)
-    hipEvent_t side_fork = nullptr, side_join = nullptr;
-    int num_cus = 256;
-    int scan_blocks_per_cu = 2;
-
-    // ---- MLP ----
-    int n_layers = 0;
-    std::vector<int> dims;    // dims[0..n_layers]
-    std::vector<int> n_rb;    // per layer: output row-blocks
-    std::vector<int> KG;      // per layer: k-groups of the layer's input
-    std::vector<DevBuf> Wf;   // packed weights
-    std::vector<DevBuf> bias; // padded bias
-
-    // ---- fused MLP / multi-level navigation (lmi_mlp_fused.h) ----
-    struct NodeModel {            // an internal node's model (model id >= 1; the root is the fields above)
-        int n_layers = 0;
-        std::vector<int> dims, n_rb, KG;
-        std::vector<DevBuf> Wf, bias;
-    };
-    std::vector<NodeModel> node_models;   // index = model id - 1
-    int fused_mlp = 1;                    // lmi_set_fused_mlp: 0 never, 1 when the batch fills the chip, 2 always
-    float stop_mass = 0.0f;               // lmi_set_stop_mass: 0 off; (0, 1]: a query's bucket order ends once this much probability is covered
-    float path_mass = 0.0f;               // lmi_set_path_mass: 0 off; (0, 1]: a query's walk ends once its recorded buckets cover this much path probability
-    bool desc_dirty = true;
-    DevBuf d_models;                      // ModelDesc[1 + node_models.size()]
-    int fm_s0 = 0, fm_s1 = 0, fm_act0 = 0, fm_lds = 0, fm_logits_lds = 0;  // LDS plan of the current model set
-    bool fm_ok = false;                   // every model fits the fused kernel
-    // the tree: flat child index = child_offset[model] + class
-    std::vector<int> h_child_offset, h_child_model, h_child_bucket;
-    DevBuf d_child_offset, d_child_model, d_child_bucket;
-    bool tree_set = false;
-    DevBuf gather_send, gather_recv;      // lmi_allgather_merge
-    DevBuf pq_prob, pq_ent, pq_len, nav_len, nav_slab, nav_ent, nav_count, nav_colq, nav_active;
-    DevBuf pq_mass, nav_parent_mass, nav_cum;   // the path-mass stop: reserved only while it is on
-
-    // ---- buckets ----
-    bool building = false, built = false;
-    int64_t N = 0;
-    int d = 0, L = 0, KGs = 0;     // d: dims of the STORED vectors (L2 metric: user dims + the norm column, padded to 4)
-    int metric = 0, d_user = 0;    // lmi_set_metric; dims of the caller's vectors
-    DevBuf aug_rows, q_aug, qn2;   // L2: augmented ingest pieces / queries, |q|^2
-    int chunk_rows = 2048;
-    bool chunk_rows_auto = true;  // until lmi_set_chunk_rows: lmi_buckets_begin picks 256..2048 by the index size
-    int chunk_rows_set = 0;       // lmi_set_chunk_rows' value (a very large bucket raises chunk_rows above it; lmi_subset starts from it again)
-    int64_t n_rb_total = 0;
-    std::vector<int> h_nb_rows, h_rb_start, h_nch;
-    DevBuf slab, ids_slab, pos, d_nb_rows, d_rb_start, d_nch;
-    int64_t rows_added = 0, owned_total = 0;
-    bool indexed_ingest = false;  // lmi_buckets_add_owned_rows: only the owned objects are passed in
-    DevBuf stage;  // H2D staging for add_rows / host query uploads
-    DevBuf wide;   // a piece of half rows widened to binary32 for an LMI_STORAGE_F32 build (the *_f16 ingest calls; widen16_kernel)
-    DevBuf q16_nav, q16_srch;   // the uploaded halves of a host-pointer *_f16 search call, widened into q_nav / q_srch
-    bool q_srch_async = false;  // an on_device *_f16 call widened into q_srch and did not synchronise: a later side-stream upload into
-                                // q_srch (lmi_search_tree, host pointers) must wait for that call's scan first
-    DevBuf rd_flag;             // lmi_bucket_read_f16 on an LMI_STORAGE_F32 index: [0] != 0 -> a value was not binary16-exact
-    // ---- fp16 prefilter (lmi_prefilter.h) ----
-    bool prefilter = true;   // lmi_set_prefilter
-    bool pf_hw_ok = false;   // fp16 subnormal self-test passed on this device
-    bool have16 = false;     // slab16 built by lmi_buckets_end
-    int KG16 = 0;
-    int dp = 0;   // row pitch (floats) of `rowmajor` (LMI_STORAGE_F16: no such image; d rounded up to 8, the floats of a query the re-rank stages)
-    int storage = LMI_STORAGE_F32;       // of the index being built / built: LMI_STORAGE_F16 keeps slab16 only (lmi_store16.h)
-    int storage_req = LMI_STORAGE_F32;   // lmi_set_storage: what the next lmi_buckets_begin builds
-    bool attrs16_done = false;           // storage16_kernel_attrs ran for this handle's device
-    DevBuf slab16, rowmajor, xscale, xmaxbits, bnorm, bdelta, qdelta;
-    DevBuf qnorm, qscale, qfrag16, eps2, cand_cnt, cand_row, cand_s, fallback, pf_bound, nkeep, surv_row, rs_flag, rs_active;
-    DevBuf grp_scratch;      // route_group_kernel<true>: the bucket sort of fan-outs past ROUTE_MAX_BUCKETS
-    int ps_force_wide = -1;  // LMI_PS_WIDE=0/1 pins it (developer aid)
-    int n_nonempty = 1;      // buckets with rows, on any rank (lmi_buckets_begin)
-    DevBuf x_log, x_ext, x_off, fb_list;  // the candidates' overflow log, its by-column sorted form and offsets (lmi_prefilter.h, OverflowLog);
-                                          // the fallback list: [count, fail0, fail1, log head, sorted total, pad x 3 | nslots slots]
-    unsigned x_cap = 0;                   // entries of the log (0: not allocated yet)
-    DevBuf redo;   // [1] count | [L] bucket flags | [columns] column flags (bytes): overflow_rebound_kernel
-    size_t stamps_off = 0;         // developer builds: byte offset of the phase stamps inside pf_bound
-    bool pf_small = true;          // d <= 128: pass2_small_kernel (LMI_PF_SMALL=0 in the environment: pass2_kernel for every d)
-    bool pf_redo = true;           // overflow_rebound_kernel + pass 2's redo launch (LMI_PF_NO_REDO=1 in the environment: off)
-    bool rescore_streamed = true;  // lmi_rescore.h (LMI_RESCORE_SIMPLE=1 in the environment: select_rescore_kernel)
-    int last_nslots = 0, last_nb = 0;
-    long long last_ncols = 0;
-    bool last_fast = false;
-    bool pf_qbound = true;        // LMI_PF_QBOUND=0: per-bucket bounds only (query_bound_kernel off)
-    bool pf_primary = true;       // LMI_PF_PRIMARY=0: pass 1 samples every column although one bound per query is used
-    bool debug_emit_all = false;  // lmi_debug_emit_all
-
-    // ---- per-call workspaces ----
-    DevBuf act[2], xfrag, logits, order, q_nav, q_srch;
-    DevBuf m, cb_start, item_base, part_base, stats, head, slot_local, slot_col, colmap, qfrag, grp, col_thr;
-    DevBuf part_score, part_row, rank_d, rank_id, out_d, out_id, out_key;
-    // hipEvents of the last EV_RING calls: lmi_timings reads the newest set, lmi_timings_mean averages all
-    // sets since lmi_timings_reset with ONE stream synchronisation (no per-call sync in a timed loop)
-    static constexpr int EV_RING = 128;
-    hipEvent_t ev_ring[EV_RING][10] = {};
-    bool valid_ring[EV_RING][10] = {};
-    int ev_cur = 0;
-    int timing_level = 2;  // lmi_set_timing
-    long long ev_calls = 0;  // calls since lmi_timings_reset
-    hipEvent_t* ev = ev_ring[0];
-    bool* ev_valid = valid_ring[0];
-    long long h_stats[4] = {0, 0, 0, 0};
-    bool stats_pending = false;
-    // device-side phase stamps (timing level 2; lmi_kernels.h): a ring of EV_RING sets of ST_COUNT words, the set of the current
-    // call, which of its stamps a kernel of the call was given (host-side mask), the chip's constant clock in kHz
-    DevBuf ts_ring;
-    unsigned ts_mask[EV_RING] = {};
-    unsigned long long* ts_set = nullptr;
-    double wall_khz = 100000.0;
-    DevBuf fr_dbg;                // LMI_FR_DEBUG=1: route_kernel's / pack_kernel's phase stamps (lmi_debug_peek "fr_dbg")
-    DevBuf cb_alloc, cb_bucket;   // lmi_front.h: the call-tagged granules of route_kernel (zero at allocation) and the col-blocks' buckets
-    unsigned* h_oflag = nullptr;  // a word of pinned host memory (device-visible): "the last batch used the overflow log" (RescoreParams::host_oflag)
-    int overflow_armed = 0;       // calls for which overflow_rebound_kernel + pass 2's redo launch stay in the sequence (re-armed by h_oflag)
-    bool fr_bump_pending = false; // route_kernel was launched and the launch that bumps the granules' tag (bound_merge2_kernel) not yet: a call that
-                                  // failed in between is repaired by a bump launch of its own at the next call
-    int use_tail = 1;             // tail_kernel (lmi_tail.h): selection + re-rank + rank merge in one wave per query (LMI_TAIL=0: the five launches of round 4;
-                                  // 2: also group-wise for n_buckets > 4)
-    bool graded_chunks = true;    // pass 2's items: chunk length per bucket and call (LMI_P2_GRADED=0: the index's static chunk everywhere)
-    int chunk_lvl_rows[3] = {0, 0, 0};   // LMI_P2_CHUNKS=a,b,c (rows; 0 = 1, 1/2, 1/4 of the static chunk)
-    float chunk_frac[2] = {0.16f, 0.05f};   // LMI_P2_CHUNK_FRAC=f0,f1: the last f0 of the work in chunks of b rows, the last f1 in chunks of c
-    bool use_front = true;        // route_kernel + pack_kernel (lmi_front.h) instead of the eight preparation launches (LMI_FRONT=0 in the environment: off)
-
-    // ---- mutation of a built index (lmi_buckets_insert / lmi_buckets_delete, lmi_mutate.h) ----
-    std::vector<int> h_cap_rb;           // per bucket: row-blocks reserved at h_rb_start[b] (cdiv(n_b, 32) after a build)
-    std::vector<unsigned char> h_owned;  // lmi_buckets_begin's `owned` (empty: every bucket)
-    std::vector<unsigned char> h_any;    // per bucket: holds rows on some rank (n_nonempty)
-    lmi_index* parent = nullptr;         // a clone view: the handle whose memory it borrows
-    int live_clones = 0;                 // clone views of this handle that are alive (a mutation is refused while any is)
-    int64_t mut_paths[4] = {0, 0, 0, 0}; // lmi_debug_layout: buckets filled in their slack, buckets relocated, growth re-packs, hole re-packs
-    DevBuf mut_pos, mut_ids, mut_list, mut_keep, mut_src, mut_stage, mut_word;
-};
-
-// The handle's device buffers, each listed once.  each_index_buf: the index and the models' tables -- what a clone view borrows from
-// its parent; each_call_buf: workspaces, staging and timing buffers -- every handle's own.  (The models' weights: vectors of their own.)
-template <class F>
-static void each_index_buf(lmi_index* h, F f) {
-    DevBuf* b[] = {&h->d_models, &h->d_child_offset, &h->d_child_model, &h->d_child_bucket, &h->slab, &h->ids_slab, &h->pos, &h->d_nb_rows,
-                   &h->d_rb_start, &h->d_nch, &h->slab16, &h->rowmajor, &h->xscale, &h->xmaxbits, &h->bnorm, &h->bdelta};
-    for (DevBuf* x : b) f(*x);
-}
-template <class F>
-static void each_call_buf(lmi_index* h, F f) {
-    DevBuf* b[] = {&h->gather_send, &h->gather_recv, &h->pq_prob, &h->pq_ent, &h->pq_len, &h->nav_len, &h->nav_slab, &h->nav_ent, &h->nav_count,
-                   &h->nav_colq, &h->nav_active, &h->pq_mass, &h->nav_parent_mass, &h->nav_cum, &h->aug_rows, &h->q_aug, &h->qn2, &h->stage, &h->wide, &h->q16_nav, &h->q16_srch, &h->rd_flag, &h->qdelta, &h->qnorm, &h->qscale, &h->qfrag16,
-                   &h->eps2, &h->cand_cnt, &h->cand_row, &h->cand_s, &h->fallback, &h->pf_bound, &h->nkeep, &h->redo, &h->surv_row, &h->rs_flag,
-                   &h->rs_active, &h->act[0], &h->act[1], &h->xfrag, &h->logits, &h->order, &h->q_nav, &h->q_srch, &h->m, &h->cb_start,
-                   &h->item_base, &h->part_base, &h->stats, &h->head, &h->slot_local, &h->slot_col, &h->colmap, &h->qfrag, &h->grp, &h->col_thr,
-                   &h->part_score, &h->part_row, &h->rank_d, &h->rank_id, &h->out_d, &h->out_id, &h->out_key, &h->x_log, &h->x_ext, &h->x_off,
-                   &h->fb_list, &h->grp_scratch, &h->ts_ring, &h->fr_dbg, &h->cb_alloc, &h->cb_bucket, &h->mut_pos, &h->mut_ids, &h->mut_list,
-                   &h->mut_keep, &h->mut_src, &h->mut_stage, &h->mut_word};
-    for (DevBuf* x : b) f(*x);
-}
 
 // the low-dimensional form of the prefilter (d <= 128: lmi_pass2_small.h) for an index of kg16 k16-groups; otherwise pass2_kernel
 static bool low_d_form(const lmi_index* h, int kg16) { return h->pf_small && kg16 <= PS_MAXKG; }

@@ -34,9 +34,7 @@ extern "C" LMI_API int lmi_merge_gathered(lmi_index* h, const float* gd, const u
     HIPCHK(hipMemcpyAsync(dists, out.p, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ids, out.as<char>() + nout, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    in.release();
-    out.release();
-    return 0;
+    return 0;   // (in and out free themselves, on the early returns above too)
 }
 
 // ---- RCCL (resolved from the process image -- PyTorch-ROCm has it loaded -- or from librccl.so) ----------------

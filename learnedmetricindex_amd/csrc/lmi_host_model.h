@@ -17,29 +17,29 @@ static int pack_from_host(lmi_index* h, const float* src, int rows, int cols, in
 }
 
 // packs one Linear stack (torch layout W[out][in]) fragment-major: shared by lmi_set_mlp and lmi_nav_set_model
-static int pack_model(lmi_index* h, const char* who, int n_layers, const int* dims, const float* const* W, const float* const* b,
-                      std::vector<int>& o_dims, std::vector<int>& o_nrb, std::vector<int>& o_KG, std::vector<DevBuf>& o_W,
-                      std::vector<DevBuf>& o_b) {
+// (m.n_layers stays 0 -- "no weights" -- until every layer is in place)
+static int pack_model(lmi_index* h, const char* who, int n_layers, const int* dims, const float* const* W, const float* const* b, Model& m) {
+    h->desc_dirty = true;
+    m.n_layers = 0;
     if (n_layers < 1 || n_layers > LMI_MAX_LAYERS) return fail("%s: n_layers %d out of range", who, n_layers);
     for (int i = 0; i <= n_layers; ++i)
         if (dims[i] < 1) return fail("%s: dims[%d] = %d", who, i, dims[i]);
-    for (auto& x : o_W) x.release();
-    for (auto& x : o_b) x.release();
-    o_dims.assign(dims, dims + n_layers + 1);
-    o_nrb.assign(n_layers, 0);
-    o_KG.assign(n_layers, 0);
-    o_W.assign(n_layers, DevBuf());
-    o_b.assign(n_layers, DevBuf());
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.n_rb.assign(n_layers, 0);
+    m.KG.assign(n_layers, 0);
+    m.Wf.assign(n_layers, DevBuf());   // (the earlier weights go with their buffers)
+    m.bias.assign(n_layers, DevBuf());
     for (int i = 0; i < n_layers; ++i) {
-        o_nrb[i] = cdiv(dims[i + 1], 32);
-        o_KG[i] = (i == 0) ? cdiv(dims[0], 8) : o_nrb[i - 1] * 4;  // hidden K = padded features
+        m.n_rb[i] = cdiv(dims[i + 1], 32);
+        m.KG[i] = (i == 0) ? cdiv(dims[0], 8) : m.n_rb[i - 1] * 4;  // hidden K = padded features
         if (!W[i] || !b[i]) return fail("%s: NULL weight/bias for layer %d", who, i);
-        CHK(pack_from_host(h, W[i], dims[i + 1], dims[i], o_nrb[i], o_KG[i], o_W[i]));
-        std::vector<float> bp((size_t)o_nrb[i] * 32, 0.0f);
+        CHK(pack_from_host(h, W[i], dims[i + 1], dims[i], m.n_rb[i], m.KG[i], m.Wf[i]));
+        std::vector<float> bp((size_t)m.n_rb[i] * 32, 0.0f);
         std::copy(b[i], b[i] + dims[i + 1], bp.begin());
-        CHK(o_b[i].reserve(bp.size() * sizeof(float)));
-        HIPCHK(hipMemcpy(o_b[i].p, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
+        CHK(m.bias[i].reserve(bp.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(m.bias[i].p, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    m.n_layers = n_layers;
     return 0;
 }
 
@@ -47,11 +47,7 @@ extern "C" LMI_API int lmi_set_mlp(lmi_index* h, int n_layers, const int* dims, 
                            const float* const* b) {
     if (!h) return fail("lmi_set_mlp: NULL handle");
     CHK(set_dev(h));
-    h->desc_dirty = true;
-    h->n_layers = 0;
-    CHK(pack_model(h, "lmi_set_mlp", n_layers, dims, W, b, h->dims, h->n_rb, h->KG, h->Wf, h->bias));
-    h->n_layers = n_layers;
-    return 0;
+    return pack_model(h, "lmi_set_mlp", n_layers, dims, W, b, h->models[0]);
 }
 
 extern "C" LMI_API int lmi_set_stop_mass(lmi_index* h, float mass) {
@@ -90,25 +86,20 @@ extern "C" LMI_API int lmi_nav_set_model(lmi_index* h, int model_id, int n_layer
     if (!h) return fail("lmi_nav_set_model: NULL handle");
     if (model_id < 1 || model_id > 1 << 20) return fail("lmi_nav_set_model: model_id %d (the root, model 0, is lmi_set_mlp)", model_id);
     CHK(set_dev(h));
-    if ((size_t)model_id > h->node_models.size()) h->node_models.resize(model_id);
-    auto& m = h->node_models[model_id - 1];
-    h->desc_dirty = true;
+    if ((size_t)model_id >= h->models.size()) h->models.resize(model_id + 1);
     h->tree_set = false;
-    m.n_layers = 0;
-    CHK(pack_model(h, "lmi_nav_set_model", n_layers, dims, W, b, m.dims, m.n_rb, m.KG, m.Wf, m.bias));
-    m.n_layers = n_layers;
-    return 0;
+    return pack_model(h, "lmi_nav_set_model", n_layers, dims, W, b, h->models[model_id]);
 }
 
 extern "C" LMI_API int lmi_nav_set_tree(lmi_index* h, int n_models, const int32_t* child_offset, const int32_t* child_model,
                                 const int32_t* child_bucket) {
     if (!h) return fail("lmi_nav_set_tree: NULL handle");
-    if (h->n_layers == 0) return fail("lmi_nav_set_tree: no root model (lmi_set_mlp)");
-    if (n_models != 1 + (int)h->node_models.size()) return fail("lmi_nav_set_tree: %d models, %d set (root + lmi_nav_set_model)", n_models, 1 + (int)h->node_models.size());
+    if (h->root().n_layers == 0) return fail("lmi_nav_set_tree: no root model (lmi_set_mlp)");
+    if (n_models != (int)h->models.size()) return fail("lmi_nav_set_tree: %d models, %d set (root + lmi_nav_set_model)", n_models, (int)h->models.size());
     if (!child_offset || !child_model || !child_bucket || child_offset[0] != 0) return fail("lmi_nav_set_tree: bad arguments");
     for (int m = 0; m < n_models; ++m) {
-        const int classes = m == 0 ? h->dims[h->n_layers] : (h->node_models[m - 1].n_layers ? h->node_models[m - 1].dims.back() : -1);
-        if (classes < 0) return fail("lmi_nav_set_tree: model %d has no weights (lmi_nav_set_model)", m);
+        if (h->models[m].n_layers == 0) return fail("lmi_nav_set_tree: model %d has no weights (lmi_nav_set_model)", m);
+        const int classes = h->models[m].dims.back();
         if (child_offset[m + 1] - child_offset[m] != classes) return fail("lmi_nav_set_tree: model %d has %d classes, %d children listed", m, classes, child_offset[m + 1] - child_offset[m]);
     }
     const int total = child_offset[n_models];
@@ -135,31 +126,27 @@ extern "C" LMI_API int lmi_nav_set_tree(lmi_index* h, int n_models, const int32_
 // device descriptors of every model + the LDS plan of mlp_fused_kernel for the current model set
 static int build_descs(lmi_index* h) {
     if (!h->desc_dirty) return 0;
-    const int nm = 1 + (int)h->node_models.size();
+    const int nm = (int)h->models.size();
     std::vector<ModelDesc> D(nm);
-    bool ok = h->n_layers > 0, logits_lds = true;
+    bool ok = true, logits_lds = true;
     int w0 = 0, w1 = 0;
-    auto add = [&](ModelDesc& d, int n_layers, const std::vector<int>& dims, const std::vector<int>& n_rb, const std::vector<int>& KG,
-                   const std::vector<DevBuf>& Wf, const std::vector<DevBuf>& bias) {
+    for (int m = 0; m < nm; ++m) {
+        const Model& M = h->models[m];
+        ModelDesc& d = D[m];
         memset(&d, 0, sizeof(d));
-        d.n_layers = n_layers;
-        if (n_layers == 0) { ok = false; return; }
-        for (int i = 0; i <= n_layers; ++i) d.dims[i] = dims[i];
-        for (int i = 0; i < n_layers; ++i) {
-            d.KG[i] = KG[i];
-            d.W[i] = Wf[i].as<float4>();
-            d.b[i] = bias[i].as<float>();
-            const int padded = n_rb[i] * 32;
-            const bool last = i + 1 == n_layers;
+        d.n_layers = M.n_layers;
+        if (M.n_layers == 0) { ok = false; continue; }
+        for (int i = 0; i <= M.n_layers; ++i) d.dims[i] = M.dims[i];
+        for (int i = 0; i < M.n_layers; ++i) {
+            d.KG[i] = M.KG[i];
+            d.W[i] = M.Wf[i].as<float4>();
+            d.b[i] = M.bias[i].as<float>();
+            const int padded = M.n_rb[i] * 32;
+            const bool last = i + 1 == M.n_layers;
             if (padded > FM_MAXH) { if (last) logits_lds = false; else ok = false; continue; }
             int& wref = (i & 1) ? w1 : w0;
             wref = std::max(wref, padded);
         }
-    };
-    add(D[0], h->n_layers, h->dims, h->n_rb, h->KG, h->Wf, h->bias);
-    for (int m = 1; m < nm; ++m) {
-        const auto& M = h->node_models[m - 1];
-        add(D[m], M.n_layers, M.dims, M.n_rb, M.KG, M.Wf, M.bias);
     }
     h->fm_s0 = w0 + 1;
     h->fm_s1 = w1 + 1;
@@ -184,9 +171,9 @@ static int build_descs(lmi_index* h) {
 static void fused_base(lmi_index* h, const float* d_q, int nq, FusedParams& P) {
     memset(&P, 0, sizeof(P));
     P.models = h->d_models.as<ModelDesc>();
-    P.n_models = 1 + (int)h->node_models.size();
+    P.n_models = (int)h->models.size();
     P.x = d_q;
-    P.d = h->dims[0];
+    P.d = h->root().dims[0];
     P.nq = nq;
     P.s0 = h->fm_s0;
     P.s1 = h->fm_s1;
@@ -199,18 +186,19 @@ static void fused_base(lmi_index* h, const float* d_q, int nq, FusedParams& P) {
 // mass > 0: the order is cut by the probability-mass stop (never together with d_probs)
 static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs,
                               float mass) {
-    const int L = h->dims[h->n_layers];
+    const Model& R = h->root();
+    const int L = R.dims[R.n_layers];
     const int ncb = cdiv(nq, 32);
     // pack the queries as the B operand of layer 0
-    CHK(h->xfrag.reserve((size_t)ncb * h->KG[0] * 1024));
+    CHK(h->xfrag.reserve((size_t)ncb * R.KG[0] * 1024));
     {
-        long long total = (long long)ncb * 32 * h->KG[0];
-        pack_gather_kernel<<<cdiv(total, 256), 256, 0, st>>>(d_q, h->dims[0], nullptr, nq, (long long)ncb * 32,
-                                                            h->KG[0], h->xfrag.as<float4>(), st == h->stream ? tsp(h, ST_MLP0) : nullptr);
+        long long total = (long long)ncb * 32 * R.KG[0];
+        pack_gather_kernel<<<cdiv(total, 256), 256, 0, st>>>(d_q, R.dims[0], nullptr, nq, (long long)ncb * 32,
+                                                            R.KG[0], h->xfrag.as<float4>(), st == h->stream ? tsp(h, ST_MLP0) : nullptr);
         HIPCHK(hipGetLastError());
     }
     int maxrb = 0;
-    for (int i = 0; i + 1 < h->n_layers; ++i) maxrb = std::max(maxrb, h->n_rb[i]);
+    for (int i = 0; i + 1 < R.n_layers; ++i) maxrb = std::max(maxrb, R.n_rb[i]);
     for (int i = 0; i < 2; ++i) CHK(h->act[i].reserve((size_t)std::max(1, ncb) * std::max(1, maxrb) * 4 * 1024));
     float* d_logits = d_logits_out;
     if (!d_logits) {
@@ -218,19 +206,19 @@ static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, in
         d_logits = h->logits.as<float>();
     }
     const float4* in = h->xfrag.as<float4>();
-    for (int i = 0; i < h->n_layers; ++i) {
-        const bool last = i + 1 == h->n_layers;
+    for (int i = 0; i < R.n_layers; ++i) {
+        const bool last = i + 1 == R.n_layers;
         // col-blocks per wave: 4 when that already gives every CU two blocks, else 2, else 1 (e.g. the
         // 120-class output layer has 4 feature blocks = one block row; 768->512 on 10 000 queries had 316
         // blocks of CBW 4 on 256 CUs)
-        const int rows = cdiv(h->n_rb[i], 4);
+        const int rows = cdiv(R.n_rb[i], 4);
         const int cbw = rows * cdiv(ncb, 4) >= 2 * h->num_cus ? 4 : rows * cdiv(ncb, 2) >= 2 * h->num_cus ? 2 : 1;
         dim3 grid(cdiv(ncb, cbw), rows);
         float* o = last ? d_logits : h->act[i & 1].as<float>();
-        const int KGn = last ? 0 : h->n_rb[i] * 4;
+        const int KGn = last ? 0 : R.n_rb[i] * 4;
 #define LMI_MLP_LAUNCH(LASTV, CBWV)                                                                        \
-        mlp_layer_kernel<LASTV, CBWV><<<grid, 256, 0, st>>>(h->Wf[i].as<float4>(), h->bias[i].as<float>(), in, \
-                                                           h->KG[i], h->n_rb[i], ncb, o, KGn, nq, L)
+        mlp_layer_kernel<LASTV, CBWV><<<grid, 256, 0, st>>>(R.Wf[i].as<float4>(), R.bias[i].as<float>(), in, \
+                                                           R.KG[i], R.n_rb[i], ncb, o, KGn, nq, L)
         if (last) {
             if (cbw == 4) LMI_MLP_LAUNCH(true, 4); else if (cbw == 2) LMI_MLP_LAUNCH(true, 2); else LMI_MLP_LAUNCH(true, 1);
         } else {
@@ -249,8 +237,8 @@ static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, in
 }
 
 static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs = nullptr) {
-    if (h->n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
-    const int L = h->dims[h->n_layers];
+    if (h->root().n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
+    const int L = h->root().dims.back();
     if (nb < 1 || nb > L) return fail("lmi_mlp_topk: n_buckets %d outside [1,%d]", nb, L);
     CHK(build_descs(h));
     // the probability-mass stop (lmi_set_stop_mass) cuts a bucket order; predict_proba's full class order and a single rank are never cut
@@ -293,7 +281,7 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
         else mlp_fused_kernel<FM_TOPK><<<grid, 256, h->fm_lds, h->stream>>>(P);
         HIPCHK(hipGetLastError());
         if (nq_head < nq) {
-            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr, mass));
+            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->root().dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr, mass));
             CHK(side_join(h));
         }
         if (!h->fm_logits_lds) {
@@ -314,10 +302,10 @@ extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int 
     if (nq < 0) return fail("lmi_mlp_topk: nq < 0");
     if (nq == 0) return 0;
     CHK(set_dev(h));
-    if (h->n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
-    const int L = h->dims[h->n_layers];
+    if (h->root().n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
+    const int L = h->root().dims.back();
     const void* d_q = nullptr;
-    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_q));
+    CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_q));
     int* d_order = bucket_order;
     float* d_logits = logits;
     if (!on_device) {
@@ -340,10 +328,10 @@ extern "C" LMI_API int lmi_mlp_proba(lmi_index* h, const float* queries_nav, int
     if (nq < 0) return fail("lmi_mlp_proba: nq < 0");
     if (nq == 0) return 0;
     CHK(set_dev(h));
-    if (h->n_layers == 0) return fail("lmi_mlp_proba: no MLP set (lmi_set_mlp)");
-    const int L = h->dims[h->n_layers];
+    if (h->root().n_layers == 0) return fail("lmi_mlp_proba: no MLP set (lmi_set_mlp)");
+    const int L = h->root().dims.back();
     const void* d_q = nullptr;
-    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_q));
+    CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_q));
     int* d_order = classes;
     float* d_probs = probs;
     if (!on_device) {
@@ -378,14 +366,14 @@ static int nav_check(lmi_index* h, int nq, int nb, const char* who) {
     CHK(build_descs(h));
     if (!h->fm_ok || !h->fm_logits_lds)
         return fail("%s: a model of the tree does not fit the fused kernel (layer outputs <= %d, LDS plan %d bytes)", who, FM_MAXH, h->fm_lds);
-    const int nm = 1 + (int)h->node_models.size();
+    const int nm = (int)h->models.size();
     const int cap = h->h_child_offset[nm];
     if ((long long)nq * cap >= (1ll << 31) || (long long)nq * nb >= (1ll << 31)) return fail("%s: nq too large for this tree", who);
     if (cap == 0) return fail("%s: empty tree", who);
     return 0;
 }
 static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_slab, int* d_ent) {
-    const int nm = 1 + (int)h->node_models.size();
+    const int nm = (int)h->models.size();
     const int cap = h->h_child_offset[nm];
     CHK(h->pq_prob.reserve((size_t)nq * cap * 4));
     CHK(h->pq_ent.reserve((size_t)nq * cap * 4));
@@ -495,7 +483,7 @@ extern "C" LMI_API int lmi_nav_order(lmi_index* h, const float* queries_nav, int
     if (nq == 0) return 0;
     CHK(nav_check(h, nq, nb, "lmi_nav_order"));
     const void* d_q = nullptr;
-    CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_q));
+    CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_q));
     CHK(h->nav_slab.reserve((size_t)nq * nb * 4));
     CHK(h->nav_ent.reserve((size_t)nq * nb * 4));
     int* d_slab = on_device ? slab_ids : h->nav_slab.as<int>();

@@ -83,18 +83,19 @@ static int redo_ranges(lmi_index* h, const int* d_list, int stride, int n, int c
 static int repack(lmi_index* h, const std::vector<int>& from, const std::vector<int>& to, const std::vector<int>& nrb, int64_t alloc_new) {
     SlabImage im[3];
     const int n = slab_images(h, im);
-    void* fresh[3] = {nullptr, nullptr, nullptr};
+    DevBuf fresh[3];   // (an early return frees them)
     size_t bytes[3] = {0, 0, 0};
     for (int i = 0; i < n; ++i) {
         bytes[i] = (size_t)std::max<int64_t>(alloc_new, 1) * im[i].rb_bytes + im[i].extra;
-        hipError_t e = hipMalloc(&fresh[i], bytes[i]);
+        hipError_t e = hipMalloc(&fresh[i].p, bytes[i]);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            for (int j = 0; j < i; ++j) (void)hipFree(fresh[j]);
+            fresh[i].p = nullptr;
             return fail("lmi_buckets_insert: growing the slab to %lld row-blocks failed (%s); the index is unchanged", (long long)alloc_new, hipGetErrorString(e));
         }
+        fresh[i].cap = bytes[i];
     }
-    for (int i = 0; i < n; ++i) HIPCHK(hipMemsetAsync(fresh[i], 0, bytes[i], h->stream));
+    for (int i = 0; i < n; ++i) HIPCHK(hipMemsetAsync(fresh[i].p, 0, bytes[i], h->stream));
     const int L = h->L;
     for (int b = 0; b < L;) {   // runs of buckets that are consecutive at both ends: one copy each (all of them after a build)
         int e = b + 1;
@@ -102,16 +103,12 @@ static int repack(lmi_index* h, const std::vector<int>& from, const std::vector<
         while (e < L && from[e] == from[b] + len && to[e] == to[b] + len) len += nrb[e++];
         if (len > 0)
             for (int i = 0; i < n; ++i)
-                HIPCHK(hipMemcpyAsync((char*)fresh[i] + (size_t)to[b] * im[i].rb_bytes, im[i].buf->as<char>() + (size_t)from[b] * im[i].rb_bytes,
+                HIPCHK(hipMemcpyAsync(fresh[i].as<char>() + (size_t)to[b] * im[i].rb_bytes, im[i].buf->as<char>() + (size_t)from[b] * im[i].rb_bytes,
                                       (size_t)len * im[i].rb_bytes, hipMemcpyDeviceToDevice, h->stream));
         b = e;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; ++i) {
-        im[i].buf->release();
-        im[i].buf->p = fresh[i];
-        im[i].buf->cap = bytes[i];
-    }
+    for (int i = 0; i < n; ++i) *im[i].buf = std::move(fresh[i]);
     return 0;
 }
 

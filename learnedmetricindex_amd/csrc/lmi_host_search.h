@@ -74,15 +74,15 @@ static int search_impl(lmi_index* h, const void* queries_nav, const void* querie
     if (!h) return fail("%s: NULL handle", who);
     int kout = 0;
     CHK(check_scan_args(h, nq, nb, k, &kout, q16 ? "lmi_scan_topk_f16" : "lmi_scan_topk"));
-    if (h->n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
-    if (h->dims[h->n_layers] != h->L) return fail("%s: MLP has %d classes, index has %d buckets", who, h->dims[h->n_layers], h->L);
+    if (h->root().n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
+    if (h->root().dims.back() != h->L) return fail("%s: MLP has %d classes, index has %d buckets", who, h->root().dims.back(), h->L);
     if (nq == 0) return 0;
     CHK(set_dev(h));
     const void* d_qn = nullptr;
     const void* d_qs = nullptr;
-    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->dims[0], on_device, h->q16_nav, h->q_nav, &d_qn));
-    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_qn));
-    if (queries_search == queries_nav && h->dims[0] == h->d_user) d_qs = d_qn;
+    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->root().dims[0], on_device, h->q16_nav, h->q_nav, &d_qn));
+    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_qn));
+    if (queries_search == queries_nav && h->root().dims[0] == h->d_user) d_qs = d_qn;
     else if (q16) CHK(input_ptr16(h, queries_search, nq, h->d_user, on_device, h->q16_srch, h->q_srch, &d_qs));
     else CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
     int* d_order = bucket_order;
@@ -121,9 +121,9 @@ static int search_tree_impl(lmi_index* h, const void* queries_nav, const void* q
     CHK(nav_check(h, nq, nb, who));
     const void* d_qn = nullptr;
     const void* d_qs = queries_search;
-    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->dims[0], on_device, h->q16_nav, h->q_nav, &d_qn));
-    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->dims[0] * 4, on_device, h->q_nav, &d_qn));
-    const bool same = queries_search == queries_nav && h->dims[0] == h->d_user;
+    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->root().dims[0], on_device, h->q16_nav, h->q_nav, &d_qn));
+    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_qn));
+    const bool same = queries_search == queries_nav && h->root().dims[0] == h->d_user;
     if (same) d_qs = d_qn;
     CHK(h->nav_slab.reserve((size_t)nq * nb * 4));
     CHK(h->nav_ent.reserve((size_t)nq * nb * 4));
@@ -260,11 +260,11 @@ extern "C" LMI_API int lmi_pipeline_submit(lmi_index* h, void* s_in_, void* s_na
     if (!s_in_ || !s_run_ || !ev_in_ || !ev_out_ || !qn_host || !qn_dev || !dists_out || !ids_out || !bo_dev) return fail("lmi_pipeline_submit: NULL argument");
     if (overlap_nav && (!s_nav_ || !ev_nav_)) return fail("lmi_pipeline_submit: overlap_nav needs a navigation stream and event");
     if ((qs_host == nullptr) != (qs_dev == nullptr)) return fail("lmi_pipeline_submit: qs_host and qs_dev go together");
-    if (nq < 1 || h->n_layers == 0 || !h->built) return fail("lmi_pipeline_submit: empty batch, no MLP or no bucket index");
+    if (nq < 1 || h->root().n_layers == 0 || !h->built) return fail("lmi_pipeline_submit: empty batch, no MLP or no bucket index");
     CHK(set_dev(h));
     hipStream_t s_in = static_cast<hipStream_t>(s_in_), s_nav = static_cast<hipStream_t>(s_nav_), s_run = static_cast<hipStream_t>(s_run_);
     hipEvent_t ev_in = static_cast<hipEvent_t>(ev_in_), ev_nav = static_cast<hipEvent_t>(ev_nav_), ev_out = static_cast<hipEvent_t>(ev_out_);
-    HIPCHK(hipMemcpyAsync(qn_dev, qn_host, (size_t)nq * h->dims[0] * 4, hipMemcpyHostToDevice, s_in));
+    HIPCHK(hipMemcpyAsync(qn_dev, qn_host, (size_t)nq * h->root().dims[0] * 4, hipMemcpyHostToDevice, s_in));
     if (qs_host) HIPCHK(hipMemcpyAsync(qs_dev, qs_host, (size_t)nq * h->d_user * 4, hipMemcpyHostToDevice, s_in));
     HIPCHK(hipEventRecord(ev_in, s_in));
     const float* q_scan = qs_dev ? qs_dev : qn_dev;

@@ -11,17 +11,18 @@
 // derives from the rows is derived from the new handle's own rows.  The source is only read.
 namespace {
 // a copy of one packed Linear stack: allocations of pack_model's sizes, the weights device to device
-int copy_model(hipStream_t st, int n_layers, const std::vector<int>& n_rb, const std::vector<int>& KG, const std::vector<DevBuf>& Wf,
-               const std::vector<DevBuf>& bias, std::vector<DevBuf>& o_W, std::vector<DevBuf>& o_b) {
-    o_W.assign(n_layers, DevBuf());
-    o_b.assign(n_layers, DevBuf());
-    for (int i = 0; i < n_layers; ++i) {
-        const size_t wb = (size_t)n_rb[i] * KG[i] * 1024, bb = (size_t)n_rb[i] * 32 * sizeof(float);
-        CHK(o_W[i].reserve(wb));
-        CHK(o_b[i].reserve(bb));
-        HIPCHK(hipMemcpyAsync(o_W[i].p, Wf[i].p, wb, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(o_b[i].p, bias[i].p, bb, hipMemcpyDeviceToDevice, st));
+int copy_model(hipStream_t st, const Model& s, Model& t) {
+    t.dims = s.dims; t.n_rb = s.n_rb; t.KG = s.KG;
+    t.Wf.assign(s.n_layers, DevBuf());
+    t.bias.assign(s.n_layers, DevBuf());
+    for (int i = 0; i < s.n_layers; ++i) {
+        const size_t wb = (size_t)s.n_rb[i] * s.KG[i] * 1024, bb = (size_t)s.n_rb[i] * 32 * sizeof(float);
+        CHK(t.Wf[i].reserve(wb));
+        CHK(t.bias[i].reserve(bb));
+        HIPCHK(hipMemcpyAsync(t.Wf[i].p, s.Wf[i].p, wb, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(t.bias[i].p, s.bias[i].p, bb, hipMemcpyDeviceToDevice, st));
     }
+    t.n_layers = s.n_layers;
     return 0;
 }
 int copy_table(hipStream_t st, const DevBuf& src, size_t bytes, DevBuf& dst) {
@@ -38,28 +39,12 @@ static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t 
     const int L = h->L;
     hipStream_t st = c->stream;
     // ---- h's settings (lmi_create read the environment's again) ----
-    c->metric = h->metric;
+    static_cast<Settings&>(*c) = *h;
     c->storage_req = h->storage;
-    c->prefilter = h->prefilter;
-    c->fused_mlp = h->fused_mlp;
-    c->stop_mass = h->stop_mass;
-    c->path_mass = h->path_mass;
-    c->timing_level = h->timing_level;
-    c->chunk_rows_auto = h->chunk_rows_auto;
-    c->chunk_rows_set = h->chunk_rows_set;
     if (!h->chunk_rows_auto) c->chunk_rows = h->chunk_rows_set;
     // ---- the models and the tree: copies of its own (the device descriptors point at the weights: rebuilt at the first use) ----
-    c->dims = h->dims; c->n_rb = h->n_rb; c->KG = h->KG;
-    CHK(copy_model(st, h->n_layers, h->n_rb, h->KG, h->Wf, h->bias, c->Wf, c->bias));
-    c->n_layers = h->n_layers;
-    c->node_models.resize(h->node_models.size());
-    for (size_t m = 0; m < h->node_models.size(); ++m) {
-        const auto& s = h->node_models[m];
-        auto& t = c->node_models[m];
-        t.dims = s.dims; t.n_rb = s.n_rb; t.KG = s.KG;
-        CHK(copy_model(st, s.n_layers, s.n_rb, s.KG, s.Wf, s.bias, t.Wf, t.bias));
-        t.n_layers = s.n_layers;
-    }
+    c->models.resize(h->models.size());
+    for (size_t m = 0; m < h->models.size(); ++m) CHK(copy_model(st, h->models[m], c->models[m]));
     if (h->tree_set) {
         c->h_child_offset = h->h_child_offset; c->h_child_model = h->h_child_model; c->h_child_bucket = h->h_child_bucket;
         const size_t total = h->h_child_model.size();
