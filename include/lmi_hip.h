@@ -489,6 +489,40 @@ LMI_API int lmi_debug_read_candidates(lmi_index *h, int64_t slot, int cap, uint3
  * lmi_buckets_insert calls.  Any pointer may be NULL.  Launches nothing and reads no device memory. */
 LMI_API int lmi_debug_layout(lmi_index *h, int32_t *rb_start, int32_t *cap_rb, int64_t *n_rb_total, int64_t *alloc_rb,
                              int64_t *counters);
+/* Test hooks for the scan's dispatch (tests/test_gpu_seams.py; no reference counterpart): which of its kernel forms a scan takes.
+ * The first fourteen words are the call's plan, decided from (handle, nq, n_buckets, k) before the first launch; the rest are the
+ * template instances the launch code picks on top of it (-1: that launch is not part of the call). */
+enum {
+    LMI_PLAN_FAST = 0,            /* fp16 prefilter + exact re-rank; 0: the all-f32 scan                                      */
+    LMI_PLAN_LOW_D,               /* the low-dimensional prefilter kernels (K <= 128)                                          */
+    LMI_PLAN_PS_WIDE,             /* ... in their wide form                                                                    */
+    LMI_PLAN_TILE_CB,             /* col-blocks per query tile                                                                 */
+    LMI_PLAN_SAMPLE_MAX,          /* pass 1's largest sampling stride                                                          */
+    LMI_PLAN_QBOUND,              /* one bound per query                                                                       */
+    LMI_PLAN_PRIMARY_NB,          /* > 0 (= n_buckets): pass 1 samples the primary slots only                                  */
+    LMI_PLAN_USE_FRONT,           /* route_kernel + pack_kernel; 0: the separate preparation kernels                           */
+    LMI_PLAN_STREAMED,            /* the streamed re-rank; 0: select_rescore_kernel                                            */
+    LMI_PLAN_G,                   /* slots of one query per re-rank wave                                                       */
+    LMI_PLAN_USE_TAIL,            /* tail_kernel; 0: select_kernel + rescore_kernel x 2                                        */
+    LMI_PLAN_TAIL_MERGES,         /* ... which also merges the ranks                                                           */
+    LMI_PLAN_KG16,                /* k16-groups of the fp16 fragments                                                          */
+    LMI_PLAN_DP,                  /* row pitch (floats) of the re-rank                                                         */
+    LMI_PLAN_ROUTE_NB_TEMPLATE,   /* route_kernel<NB>: the specialised rank count, 0 = the generic instance                    */
+    LMI_PLAN_PACK_GS,             /* pack_kernel<GS, CP, vec>                                                                  */
+    LMI_PLAN_PACK_CP,
+    LMI_PLAN_PACK_VEC,
+    LMI_PLAN_ROUTE_SORT_GLOBAL,   /* route_group_kernel sorts in a global scratch buffer; 0: in LDS (separate kernels only)    */
+    LMI_PLAN_MERGE_KIND,          /* who writes the caller's rows: 0 the fused tail, 1 merge_ranks_kernel, 2 merge_kernel      */
+    LMI_PLAN_RESCORE_SMALL_WAVES, /* waves per block of rescore_kernel's small form (select_kernel + rescore_kernel only)      */
+    LMI_PLAN_OVERFLOW_SORTED,     /* overflow_rebound_kernel + pass 2's redo launch ran (lmi_debug_last_plan only; else -1)    */
+    LMI_PLAN_COUNT
+};
+/* lmi_debug_last_plan: what the last scan on this handle did, recorded by the scan and its launch sites as they ran (all zero
+ * before the first scan; a clone view starts so).  lmi_debug_plan: what a scan of nq queries x n_buckets with this k would do --
+ * the same plan function and the same argument checks as lmi_scan_topk; launches nothing and changes nothing.  Both write
+ * min(n, LMI_PLAN_COUNT) words. */
+LMI_API int lmi_debug_last_plan(lmi_index *h, int32_t *out, int n);
+LMI_API int lmi_debug_plan(lmi_index *h, int nq, int n_buckets, int k, int32_t *out, int n);
 
 #ifdef __cplusplus
 }

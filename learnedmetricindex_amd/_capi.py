@@ -18,6 +18,11 @@ K_PER_BUCKET = 10
 T_INFERENCE, T_ROUTE, T_SCAN, T_MERGE, T_TOTAL, T_PF_SAMPLE, T_PF_EMIT, T_RESCORE, T_FALLBACK, T_CLOCK_MHZ, T_COUNT = (
     0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12)   # (T_CLOCK_MHZ is not a time: the shader clock held under pass 2, from in-kernel counters)
 
+#: the LMI_PLAN_* words of include/lmi_hip.h, in their order (lmi_debug_last_plan / lmi_debug_plan)
+PLAN_FIELDS = ("fast", "low_d", "ps_wide", "tile_cb", "sample_max", "qbound", "primary_nb", "use_front", "streamed", "G", "use_tail",
+               "tail_merges", "KG16", "dp", "route_nb_template", "pack_gs", "pack_cp", "pack_vec", "route_sort_global", "merge_kind",
+               "rescore_small_waves", "overflow_sorted")
+
 _lib = None
 
 _f32p = ctypes.POINTER(ctypes.c_float)
@@ -92,6 +97,8 @@ SIGNATURES = {
     "lmi_debug_read_candidates": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp,
                                                  ctypes.POINTER(ctypes.c_int), _f32p, _f32p, _f32p]),
     "lmi_debug_layout": (ctypes.c_int, [_vp, _vp, _vp, _i64p, _i64p, _vp]),
+    "lmi_debug_last_plan": (ctypes.c_int, [_vp, _i32p, ctypes.c_int]),
+    "lmi_debug_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int]),
     # binary16 rows and queries as they are distributed (uint16 bit patterns; arguments as the namesakes')
     "lmi_buckets_add_rows_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "lmi_buckets_add_owned_rows_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
@@ -339,6 +346,20 @@ class Index:
         _check(lib().lmi_debug_layout(self._h, _ptr(rb_start), _ptr(cap_rb), ctypes.byref(n_rb), ctypes.byref(alloc),
                                       _ptr(counters)))
         return dict(rb_start=rb_start, cap_rb=cap_rb, n_rb_total=n_rb.value, alloc_rb=alloc.value, counters=counters)
+
+    def debug_last_plan(self) -> dict:
+        """Test hook (`lmi_debug_last_plan`): the kernel forms the last scan on this handle took, as recorded while it ran --
+        `PLAN_FIELDS` -> int.  The plan's fields, then the launch sites' template choices (-1: that launch was not part of the call)."""
+        w = (ctypes.c_int32 * len(PLAN_FIELDS))()
+        _check(lib().lmi_debug_last_plan(self._h, w, len(PLAN_FIELDS)))
+        return dict(zip(PLAN_FIELDS, (int(v) for v in w)))
+
+    def debug_plan(self, nq: int, nb: int, k: int = 10) -> dict:
+        """Test hook (`lmi_debug_plan`): the forms a scan of nq queries x nb buckets with this k would take on this handle; the
+        argument checks of `scan_topk`, nothing is launched.  `overflow_sorted` depends on the handle's history: -1 here."""
+        w = (ctypes.c_int32 * len(PLAN_FIELDS))()
+        _check(lib().lmi_debug_plan(self._h, int(nq), int(nb), int(k), w, len(PLAN_FIELDS)))
+        return dict(zip(PLAN_FIELDS, (int(v) for v in w)))
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(lib().lmi_set_stream(self._h, _vp(stream_ptr)))

@@ -1,6 +1,7 @@
 // lmi_host_debug.h -- reading a call's phase timings (events or device stamps), scan / prefilter statistics and the test hooks.
 #pragma once
 #include "lmi_host_mutate.h"
+#include "lmi_host_search.h"
 
 static int read_event_set(const hipEvent_t* ev, const bool* ev_valid, float* ms) {
     for (int i = 0; i < LMI_T_COUNT; ++i) ms[i] = 0.0f;
@@ -136,6 +137,25 @@ extern "C" LMI_API int lmi_debug_layout(lmi_index* h, int32_t* rb_start, int32_t
     if (n_rb_total) *n_rb_total = h->n_rb_total;
     if (alloc) *alloc = alloc_rb(h);
     if (counters) std::copy(h->mut_paths, h->mut_paths + 4, counters);
+    return 0;
+}
+
+// ---- test hooks (tests/test_gpu_seams.py): which kernel forms a scan takes ----
+extern "C" LMI_API int lmi_debug_last_plan(lmi_index* h, int32_t* out, int n) {
+    if (!h || !out) return fail("lmi_debug_last_plan: NULL argument");
+    if (n < 1) return fail("lmi_debug_last_plan: n %d < 1", n);
+    std::copy(h->last_plan, h->last_plan + std::min<int>(n, LMI_PLAN_COUNT), out);
+    return 0;
+}
+
+extern "C" LMI_API int lmi_debug_plan(lmi_index* h, int nq, int nb, int k, int32_t* out, int n) {
+    if (!h || !out) return fail("lmi_debug_plan: NULL argument");
+    if (n < 1) return fail("lmi_debug_plan: n %d < 1", n);
+    int kout = 0;
+    CHK(check_scan_args(h, nq, nb, k, &kout, "lmi_debug_plan"));
+    int32_t w[LMI_PLAN_COUNT];
+    plan_report(h, scan_plan(h, nq, nb, kout), w);
+    std::copy(w, w + std::min<int>(n, LMI_PLAN_COUNT), out);
     return 0;
 }
 

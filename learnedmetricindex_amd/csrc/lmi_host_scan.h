@@ -76,6 +76,57 @@ static ScanPlan scan_plan(const lmi_index* h, int nq, int nb, int kout) {
     return P;
 }
 
+// ---- the instances the launch sites pick on top of the plan: each condition is ONE function, called by the launch and by the
+// plan report (plan_report, lmi_debug_plan), so that the report cannot drift from the launch ----
+// route_kernel<NB>: the rank counts it is specialised for; 0: the generic instance
+static int route_nb_template(int nb) {
+    switch (nb) {
+        case 1: case 2: case 3: case 4: case 5: case 6: case 8: case 10: case 16: return nb;
+        default: return 0;
+    }
+}
+// pack_kernel<GS, CP, vec>: lanes per row and chunks per lane by the row's 8-float chunks; vec: whole chunks only
+struct PackForm { int gs, cp; bool vec; };
+static PackForm pack_form(int d) {
+    const int nchunk = (d + 7) / 8;
+    PackForm f;
+    f.gs = nchunk <= 8 ? 8 : nchunk <= 16 ? 16 : nchunk <= 32 ? 32 : 64;
+    f.cp = nchunk <= 64 ? 1 : nchunk <= 128 ? 2 : 4;
+    f.vec = d % 8 == 0;
+    return f;
+}
+// route_group_kernel: the bucket sort in LDS, or (huge fan-outs) the same sort in a global scratch buffer
+static bool route_sort_global(int L) { return L > ROUTE_MAX_BUCKETS; }
+// rescore_kernel's small form keeps four waves as long as a block stays under its LDS cap
+static int rescore_small_waves(int dp, int G) { return RC_WAVES * rc_wave_lds(dp, G, true) <= RC_SMALL_LDS_CAP ? RC_WAVES : 1; }
+// who writes the caller's rows: 0 the fused tail (tail_kernel / fallback_kernel), 1 merge_ranks_kernel (rank lists exist: a thread
+// per query), 2 merge_kernel
+static int merge_kind(const ScanPlan& P) { return P.tail_merges ? 0 : (P.fast && P.nb <= 16) ? 1 : 2; }
+
+static_assert(LMI_PLAN_COUNT <= CallState::PLAN_WORDS, "lmi_handle.h holds the plan words");
+// The LMI_PLAN_* words of a call (include/lmi_hip.h): the plan's fields, and the launch sites' choices as the functions above give
+// them for the sites this plan reaches (-1: not launched).  lmi_debug_plan returns this; scan_enqueue starts the handle's record
+// with the plan's fields only (plan_record) and every launch site writes its own word as it launches.
+static void plan_record(const lmi_index* h, const ScanPlan& P, int32_t* w) {
+    for (int i = 0; i < LMI_PLAN_COUNT; ++i) w[i] = -1;
+    w[LMI_PLAN_FAST] = P.fast; w[LMI_PLAN_LOW_D] = P.low_d; w[LMI_PLAN_PS_WIDE] = P.ps_wide; w[LMI_PLAN_TILE_CB] = P.tile_cb;
+    w[LMI_PLAN_SAMPLE_MAX] = P.sample_max; w[LMI_PLAN_QBOUND] = P.qbound; w[LMI_PLAN_PRIMARY_NB] = P.primary_nb;
+    w[LMI_PLAN_USE_FRONT] = P.use_front; w[LMI_PLAN_STREAMED] = P.streamed; w[LMI_PLAN_G] = P.G; w[LMI_PLAN_USE_TAIL] = P.use_tail;
+    w[LMI_PLAN_TAIL_MERGES] = P.tail_merges; w[LMI_PLAN_KG16] = h->KG16; w[LMI_PLAN_DP] = h->dp;
+}
+static void plan_report(const lmi_index* h, const ScanPlan& P, int32_t* w) {
+    plan_record(h, P, w);
+    if (P.use_front) {
+        const PackForm pf = pack_form(h->d);
+        w[LMI_PLAN_ROUTE_NB_TEMPLATE] = route_nb_template(P.nb);
+        w[LMI_PLAN_PACK_GS] = pf.gs; w[LMI_PLAN_PACK_CP] = pf.cp; w[LMI_PLAN_PACK_VEC] = pf.vec;
+    } else {
+        w[LMI_PLAN_ROUTE_SORT_GLOBAL] = route_sort_global(P.L);
+    }
+    if (P.fast && P.streamed && !P.use_tail) w[LMI_PLAN_RESCORE_SMALL_WAVES] = rescore_small_waves(h->dp, P.G);
+    w[LMI_PLAN_MERGE_KIND] = merge_kind(P);
+}
+
 // one call's arguments and what its stages hand on
 struct ScanCall {
     ScanPlan P;
@@ -257,7 +308,9 @@ static int front_separate(lmi_index* h, ScanCall& C) {
     // the work queues (one 1 024-thread block, ~20 us) are only read by the scan kernels: built on the side stream while
     // this one packs the queries
     CHK(side_fork(h));
-    if (L <= ROUTE_MAX_BUCKETS) {
+    const bool sort_global = route_sort_global(L);
+    h->last_plan[LMI_PLAN_ROUTE_SORT_GLOBAL] = sort_global;
+    if (!sort_global) {
         route_group_kernel<false><<<1, 1024, route_group_lds(L), h->side>>>(L, R, nullptr);
     } else {   // huge fan-outs: the same sort in a global scratch buffer
         CHK(h->grp_scratch.reserve(route_group_lds(L) + (size_t)L * 4));
@@ -326,28 +379,32 @@ static int front_fused(lmi_index* h, ScanCall& C) {
     A.ts = tsp(h, ST_FRONT);
     A.dbg = h->fr_dbg.as<unsigned long long>();
     const size_t rlds = fr_route_lds(L);
-    switch (P.nb) {   // the rank count as a compile-time constant: a wave's bucket ids of several steps are loaded at once (lmi_front.h, FrChunk)
+    const int nbt = route_nb_template(P.nb);
+    switch (nbt) {   // the rank count as a compile-time constant: a wave's bucket ids of several steps are loaded at once (lmi_front.h, FrChunk)
 #define LMI_FR_CASE(NBV) case NBV: route_kernel<NBV><<<L, FR_THREADS, rlds, h->stream>>>(A); break;
-        LMI_FR_CASE(1) LMI_FR_CASE(2) LMI_FR_CASE(3) LMI_FR_CASE(4) LMI_FR_CASE(5) LMI_FR_CASE(6) LMI_FR_CASE(8) LMI_FR_CASE(10) LMI_FR_CASE(16)
+        LMI_FR_CASE(0) LMI_FR_CASE(1) LMI_FR_CASE(2) LMI_FR_CASE(3) LMI_FR_CASE(4) LMI_FR_CASE(5) LMI_FR_CASE(6) LMI_FR_CASE(8) LMI_FR_CASE(10) LMI_FR_CASE(16)
 #undef LMI_FR_CASE
-        default: route_kernel<0><<<L, FR_THREADS, rlds, h->stream>>>(A); break;
+        default: return fail("internal: no route_kernel instance for the rank count %d (%s:%d)", nbt, __FILE__, __LINE__);
     }
     HIPCHK(hipGetLastError());
+    h->last_plan[LMI_PLAN_ROUTE_NB_TEMPLATE] = nbt;
     A.ts = nullptr;
     const int pgrid = 1 + (int)P.ncb_bound;
     const size_t plds = fr_pack_lds(L, h->KG16);
-    const int nchunk = (h->d + 7) / 8;
-    const bool vec = h->d % 8 == 0;
-#define LMI_FP_LAUNCH(GSV, CPV) { if (vec) pack_kernel<GSV, CPV, true><<<pgrid, FP_THREADS, plds, h->stream>>>(A); \
-                                  else pack_kernel<GSV, CPV, false><<<pgrid, FP_THREADS, plds, h->stream>>>(A); }
-    if (nchunk <= 8) LMI_FP_LAUNCH(8, 1)
-    else if (nchunk <= 16) LMI_FP_LAUNCH(16, 1)
-    else if (nchunk <= 32) LMI_FP_LAUNCH(32, 1)
-    else if (nchunk <= 64) LMI_FP_LAUNCH(64, 1)
-    else if (nchunk <= 128) LMI_FP_LAUNCH(64, 2)
+    const PackForm pf = pack_form(h->d);
+#define LMI_FP_LAUNCH(GSV, CPV) if (pf.gs == GSV && pf.cp == CPV) { \
+                                    if (pf.vec) pack_kernel<GSV, CPV, true><<<pgrid, FP_THREADS, plds, h->stream>>>(A); \
+                                    else pack_kernel<GSV, CPV, false><<<pgrid, FP_THREADS, plds, h->stream>>>(A); }
+    LMI_FP_LAUNCH(8, 1)
+    else LMI_FP_LAUNCH(16, 1)
+    else LMI_FP_LAUNCH(32, 1)
+    else LMI_FP_LAUNCH(64, 1)
+    else LMI_FP_LAUNCH(64, 2)
     else LMI_FP_LAUNCH(64, 4)
+    else return fail("internal: no pack_kernel instance <%d, %d> (%s:%d)", pf.gs, pf.cp, __FILE__, __LINE__);
 #undef LMI_FP_LAUNCH
     HIPCHK(hipGetLastError());
+    h->last_plan[LMI_PLAN_PACK_GS] = pf.gs; h->last_plan[LMI_PLAN_PACK_CP] = pf.cp; h->last_plan[LMI_PLAN_PACK_VEC] = pf.vec;
     return 0;
 }
 
@@ -594,7 +651,8 @@ static int rerank(lmi_index* h, const ScanCall& C, const RescoreParams& Q) {
     HIPCHK(hipGetLastError());
     // (wide rows: fewer waves per block in the big form, whose per-wave buffers hold the query and 256 survivors per slot; the small
     // form keeps four waves as long as a block stays under 64 KiB)
-    const int wb = rc_waves_for(h->dp, G), ws = RC_WAVES * rc_wave_lds(h->dp, G, true) <= RC_SMALL_LDS_CAP ? RC_WAVES : 1;
+    const int wb = rc_waves_for(h->dp, G), ws = rescore_small_waves(h->dp, G);
+    h->last_plan[LMI_PLAN_RESCORE_SMALL_WAVES] = ws;
     const int blocks = cdiv(groups, ws);
     const int lds = wb * rc_wave_lds(h->dp, G), lds_s = ws * rc_wave_lds(h->dp, G, true);
     // first every group in the small-LDS form (three blocks per CU), then the groups it passed on (more survivors than it holds)
@@ -646,10 +704,12 @@ static int final_merge(lmi_index* h, const ScanCall& C) {
     M.out_d = C.out_d;
     M.out_id = C.out_id;
     M.out_key = C.out_key;
-    if (P.tail_merges) { /* merged by tail_kernel / fallback_kernel */ }
-    else if (M.skip_a && P.nb <= 16) merge_ranks_kernel<<<cdiv(P.nq, 64), 64, 0, h->stream>>>(M);  // rank lists exist: a thread per query
+    const int kind = merge_kind(P);
+    if (kind == 0) { /* merged by tail_kernel / fallback_kernel */ }
+    else if (kind == 1) merge_ranks_kernel<<<cdiv(P.nq, 64), 64, 0, h->stream>>>(M);  // rank lists exist: a thread per query
     else merge_kernel<<<P.nq, 64, 0, h->stream>>>(M);
     HIPCHK(hipGetLastError());
+    h->last_plan[LMI_PLAN_MERGE_KIND] = kind;
     return 0;
 }
 
@@ -660,6 +720,7 @@ static int scan_enqueue(lmi_index* h, const float* d_qs, int nq, const int* d_or
     const ScanPlan& P = C.P;
     C.order = d_order; C.raw = raw;
     C.out_d = d_dists; C.out_id = d_ids; C.out_key = d_keys;
+    plan_record(h, P, h->last_plan);   // (the launch sites add their words)
     CHK(scan_augment_l2(h, C, d_qs));
     CHK(scan_reserve(h, C));
     scan_route_arrays(h, P, C.R);
@@ -674,6 +735,7 @@ static int scan_enqueue(lmi_index* h, const float* d_qs, int nq, const int* d_or
         bool overflow_sorted = false;
         CHK(overflow_arm(h, P, &overflow_sorted));
         if (overflow_sorted) CHK(overflow_redo(h, C, F));
+        h->last_plan[LMI_PLAN_OVERFLOW_SORTED] = overflow_sorted;
         RescoreParams Q;
         rescore_params(h, C, F, overflow_sorted, Q);
 #ifndef LMI_ABL_NOEMIT  // timing-only ablation builds emit nothing: no re-rank, no fallback

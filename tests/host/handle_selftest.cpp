@@ -130,6 +130,7 @@ static lmi_index* make_parent() {
     // a call state that has been used: none of it may show in a clone
     h->q_srch_async = true; h->fr_bump_pending = true; h->stats_pending = true; h->x_cap = 99; h->overflow_armed = 5; h->stamps_off = 64;
     h->last_nslots = 256; h->last_nb = 4; h->last_ncols = 64; h->last_fast = true; h->ev_cur = 5; h->ev_calls = 6;
+    for (int i = 0; i < CallState::PLAN_WORDS; ++i) h->last_plan[i] = 1 + i;
     h->ev = h->ev_ring[5]; h->ev_valid = h->valid_ring[5]; h->valid_ring[5][0] = true; h->ts_mask[5] = 7u;
     h->ts_set = h->ts_ring.as<unsigned long long>();
     for (int i = 0; i < 4; ++i) h->h_stats[i] = 1000 + i;
@@ -187,6 +188,7 @@ static void check_fresh_call_state(const lmi_index* c) {
     for (int i = 0; i < 4; ++i) REQUIRE(c->h_stats[i] == 0);
     REQUIRE(!c->q_srch_async && !c->fr_bump_pending && !c->stats_pending && c->x_cap == 0 && c->overflow_armed == 0 && c->stamps_off == 0);
     REQUIRE(c->last_nslots == 0 && c->last_nb == 0 && c->last_ncols == 0 && !c->last_fast && c->ev_cur == 0 && c->ev_calls == 0);
+    for (int i = 0; i < CallState::PLAN_WORDS; ++i) REQUIRE(c->last_plan[i] == 0);
     REQUIRE(c->ev == c->ev_ring[0] && c->ev_valid == c->valid_ring[0] && !c->valid_ring[5][0] && c->ts_mask[5] == 0u && !c->ts_set && !c->h_oflag);
     REQUIRE(!c->stream && !c->side && !c->side_fork && !c->side_join);
 }

@@ -102,8 +102,15 @@ def test_equals_f32_storage_bit_for_bit(capi, oracle, d, nb, k):
     np.testing.assert_array_equal(b[0][:64].view(np.float32), do.astype(np.float32))
 
 
-@pytest.mark.parametrize("env", [{}, {"LMI_TAIL": "0"}, {"LMI_RESCORE_SIMPLE": "1"}], ids=["default", "LMI_TAIL=0", "LMI_RESCORE_SIMPLE=1"])
-def test_every_row_reading_path(capi, env):
+ROW_READERS = [   # env -> the plan words (debug_last_plan) of the re-rank form the case is about
+    ({}, dict(streamed=1, use_tail=1, tail_merges=1, rescore_small_waves=-1)),                        # tail_kernel
+    ({"LMI_TAIL": "0"}, dict(streamed=1, use_tail=0, tail_merges=0, rescore_small_waves=4)),          # select_kernel + rescore_kernel x 2
+    ({"LMI_RESCORE_SIMPLE": "1"}, dict(streamed=0, use_tail=0, tail_merges=0, rescore_small_waves=-1)),   # select_rescore_kernel
+]
+
+
+@pytest.mark.parametrize("env,form", ROW_READERS, ids=["default", "LMI_TAIL=0", "LMI_RESCORE_SIMPLE=1"])
+def test_every_row_reading_path(capi, env, form):
     """2. tail_kernel | select_kernel + rescore_kernel (small and big form) | select_rescore_kernel, at d = 96."""
     X, lab, Q, order = make(7, 20_000, 96, 16, 256, 4, invalid_frac=0.04, repeat_frac=0.1)
     X, Q = q16(X), q16(Q)
@@ -111,6 +118,8 @@ def test_every_row_reading_path(capi, env):
     for storage in ("f32", "f16"):
         idx = index(capi, X, lab, 16, storage, env=env)
         out.append(scan(idx, Q, order, 10))
+        plan = idx.debug_last_plan()
+        assert plan["fast"] == 1 and {f: plan[f] for f in form} == form, (storage, plan)
         idx.close()
     assert_same(*out)
     assert out[1][3][1] > 0, "no survivor was re-scored"

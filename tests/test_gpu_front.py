@@ -33,6 +33,8 @@ def run(capi, X, labels, L, Q, order, k, front, prefilter=True, metric=None, chu
     d2, i2 = idx.scan_topk(Q, order, k)   # a second call on the same handle: nothing of the first one may linger
     np.testing.assert_array_equal(i, i2)
     np.testing.assert_array_equal(d, d2)
+    plan = idx.debug_last_plan()   # the front that was asked for is the one that ran
+    assert plan["fast"] == int(prefilter) and plan["use_front"] == int(bool(front) and prefilter), plan
     tm = idx.timings()
     idx.close()
     return d, i, tm

@@ -36,6 +36,12 @@ def run(capi, X, labels, L, Q, order, k, tail, prefilter=True, metric="ip", chun
     out2 = idx.scan_topk(Q, order, k, want_keys=want_keys)
     for a, b in zip(out, out2):
         np.testing.assert_array_equal(a, b)
+    # the form that was asked for is the one that ran: tail_kernel or the five launches; it merges the ranks itself up to 4 buckets
+    plan = idx.debug_last_plan()
+    nb = np.asarray(order).reshape(len(Q), -1).shape[1]
+    assert plan["fast"] == int(prefilter), plan
+    assert plan["use_tail"] == int(bool(tail) and prefilter), plan
+    assert plan["tail_merges"] == int(bool(tail) and prefilter and nb <= 4), plan
     st = idx.prefilter_stats() if prefilter else None
     idx.close()
     return out, st
@@ -70,6 +76,26 @@ def dup_data(seed, d, n_dup, n_clusters, spread):
     Q = np.concatenate([np.stack(Qs), X[rs.randint(0, N, 200)] + 0.01 * rs.randn(200, d).astype(np.float32)]).astype(np.float32)
     order = np.stack([np.roll(np.arange(L), -(i % L))[:4] for i in range(Q.shape[0])]).astype(np.int32)
     return X, lab, L, Q, order
+
+
+def ordinary_batch(seed, X, lab, L, n_dup, n_clusters, nq, nb=4):
+    """Queries of dup_data's rows that stay clear of its clusters: noisy copies of rows outside them whose inner product with every
+    cluster's vector is negative -- the copies then rank in the lower half of their bucket for such a query, far below any bound pass 1
+    can sample, so none of them is a candidate and no column's buffer overflows.  (A noisy copy of a row at random does not do: it may
+    be a cluster's row, or score a cluster among its bucket's best.)"""
+    rs = np.random.RandomState(seed)
+    in_cluster = np.zeros(X.shape[0], dtype=bool)
+    bases = []
+    for c in range(n_clusters):
+        rows = np.flatnonzero(lab == (c % L))[100 + c * n_dup: 100 + (c + 1) * n_dup]
+        in_cluster[rows] = True
+        bases.append(X[rows[0]])
+    free = np.flatnonzero(~in_cluster)
+    Q = X[free[rs.randint(0, free.size, 40 * nq)]] + 0.01 * rs.randn(40 * nq, X.shape[1]).astype(np.float32)
+    Q = Q[(Q @ np.stack(bases).T < 0).all(axis=1)][:nq].astype(np.float32)
+    assert Q.shape[0] == nq
+    order = np.stack([np.roll(np.arange(L), -(i % L))[:nb] for i in range(nq)]).astype(np.int32)
+    return np.ascontiguousarray(Q), order
 
 
 @pytest.mark.parametrize("n_dup,spread,what", [(40, 1e-6, "big"), (300, 1e-6, "fallback: survivors"), (1500, 0.0, "fallback: overflow")])
@@ -128,9 +154,10 @@ def test_tail_l2_and_raw_knn(capi, oracle):
 def test_overflow_machinery_arms_itself_after_a_batch_that_needed_it(capi):
     """The sort-by-column machinery of the overflow log (overflow_rebound_kernel + pass 2's redo launch) is NOT in the fused tail's launch
     sequence until a batch has put candidates into the log: that batch's flagged slots pick their entries out of the unsorted log, a flag in
-    pinned host memory arms the machinery, and the next calls on the handle run with it.  Every call must return the all-f32 answer."""
+    pinned host memory arms the machinery, and the next calls on the handle run with it.  Every call must return the all-f32 answer --
+    an ordinary batch on the armed handle too (its two extra launches find nothing to do)."""
     X, lab, L, Q, order = dup_data(9, 64, 1500, 3, 0.0)          # 1 500 exact copies near three queries: far past a column's 1 024 buffer entries
-    Xn, labn, Qn, ordern = make(41, 20_000, 64, L, 300, 4)         # an ordinary batch on the same handle afterwards
+    Qn, ordern = ordinary_batch(41, X, lab, L, 1500, 3, 300)       # an ordinary batch on the same handle afterwards
     idx = capi.Index(0, chunk_rows=2048)
     idx.set_buckets(X, lab, L)
     ref = capi.Index(0, chunk_rows=2048, prefilter=False)
@@ -145,5 +172,14 @@ def test_overflow_machinery_arms_itself_after_a_batch_that_needed_it(capi):
         assert st[1] == 0 and st[5] == 0 and st[3] > 0, st         # log not full, nobody scanned a whole bucket, entries were logged
         seen.append(int(st[4]))                                     # entries sorted by column: 0 on the unarmed call
     assert seen[0] == 0 and seen[1] > 0 and seen[2] > 0, seen
+    assert idx.debug_last_plan()["overflow_sorted"] == 1
+    d, i, keys = idx.scan_topk(Qn, ordern, 10, want_keys=True)      # armed, and nothing in the log
+    plan, st = idx.debug_last_plan(), idx.debug_peek("pf_fallback", 32).view(np.uint32)
+    dn, i_n, keysn = ref.scan_topk(Qn, ordern, 10, want_keys=True)
+    np.testing.assert_array_equal(i, i_n)
+    np.testing.assert_array_equal(d.view(np.uint32), dn.view(np.uint32))
+    np.testing.assert_array_equal(keys, keysn)
+    assert plan["overflow_sorted"] == 1 and plan["use_tail"] == 1, plan
+    assert st[3] == 0 and st[4] == 0, st                            # an ordinary batch: nothing logged, nothing sorted
     ref.close()
     idx.close()
