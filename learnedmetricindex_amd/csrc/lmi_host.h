@@ -13,6 +13,7 @@
 #include "lmi_store16.h"
 
 #include "lmi_handle.h"   // error reporting, DevBuf, the handle and its parts, clone_handle
+#include "lmi_layout.h"   // the bucket layout's arithmetic (host only, pure)
 
 #include <algorithm>
 #include <cfloat>
@@ -24,6 +25,7 @@
 using namespace lmi;
 
 static_assert(LMI_STORAGE_F32 == 0 && LMI_METRIC_IP == 0, "lmi_handle.h spells the defaults of storage / storage_req / metric as 0");
+static_assert(lmi_layout::TILE_ROWS == P2_TILE_ROWS, "lmi_layout.h spells pass 2's tile rows as a number");
 
 namespace {
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
@@ -34,6 +36,50 @@ inline long long rup(long long a, long long b) { return (a + b - 1) / b * b; }
 static bool low_d_form(const lmi_index* h, int kg16) { return h->pf_small && kg16 <= PS_MAXKG; }
 // which fp16 fragment shape the index and the queries are packed in: 16 x 32 for pass2_kernel, 32 x 16 for the low-dimensional kernels
 static int frag16x16(const lmi_index* h) { return low_d_form(h, h->KG16) ? 0 : 1; }
+
+// ---- the stored images: which form of the vectors a handle keeps, and every per-row image of that form ----
+enum StoredForm {
+    FORM_FRAG32,    // f32 fragments (`slab`): lmi_set_prefilter(0), the all-f32 scan
+    FORM_ROWMAJOR,  // row-major f32 (`rowmajor`: exact re-rank / fallback / read-back) + the fp16 fragments (`slab16`) lmi_buckets_end derives
+    FORM_FRAG16,    // fp16 fragments only (`slab16`): LMI_STORAGE_F16 (lmi_store16.h)
+};
+static StoredForm stored_form(const lmi_index* h) {
+    return h->storage == LMI_STORAGE_F16 ? FORM_FRAG16 : h->prefilter ? FORM_ROWMAJOR : FORM_FRAG32;
+}
+// behind the fp16 fragments: pass2_kernel's look-ahead requests up to two stages = 4 KiB past the last row-block's fragments before it
+// learns that the item is over; the data is never used, the addresses must be the allocation's
+constexpr size_t P2_LOOKAHEAD_BYTES = 8192;
+// One image: rb_bytes per row-block of the layout (+ extra behind the last); zeroed: lmi_buckets_begin zero-fills it (rows arrive
+// piece by piece; the others are written whole before they are read).  An image of n row-blocks is allocated for at least one.
+struct SlabImage {
+    DevBuf* buf;
+    size_t rb_bytes, extra;
+    bool zeroed;
+    size_t bytes(int64_t n_rb) const { return (size_t)std::max<int64_t>(n_rb, 1) * rb_bytes + extra; }
+};
+constexpr int MAX_SLAB_IMAGES = 3;
+// every per-row image the handle keeps, row-block-major, the ids last.  planned: also the fp16 fragments that lmi_buckets_end has yet
+// to derive (lmi_buckets_begin reserves them with the build's other images)
+static int slab_images(lmi_index* h, SlabImage* im, bool planned = false) {
+    int n = 0;
+    switch (stored_form(h)) {
+    case FORM_FRAG32: im[n++] = {&h->slab, (size_t)h->KGs * 1024, 0, true}; break;
+    case FORM_ROWMAJOR:
+        im[n++] = {&h->rowmajor, (size_t)32 * h->dp * 4, 0, true};
+        if (h->have16 || planned) im[n++] = {&h->slab16, (size_t)h->KG16 * 1024, P2_LOOKAHEAD_BYTES, false};
+        break;
+    case FORM_FRAG16: im[n++] = {&h->slab16, (size_t)h->KG16 * 1024, P2_LOOKAHEAD_BYTES, true}; break;
+    }
+    im[n++] = {&h->ids_slab, 128, 0, false};
+    return n;
+}
+static int64_t alloc_rb(lmi_index* h) {   // row-blocks every image's allocation holds
+    SlabImage im[MAX_SLAB_IMAGES];
+    const int n = slab_images(h, im);
+    int64_t a = INT64_MAX;
+    for (int i = 0; i < n; ++i) a = std::min<int64_t>(a, im[i].buf->cap < im[i].extra ? 0 : (int64_t)((im[i].buf->cap - im[i].extra) / im[i].rb_bytes));
+    return a;
+}
 
 // why an LMI_STORAGE_F16 build cannot go with the handle's other settings (nullptr: it can)
 static const char* storage16_conflict(const lmi_index* h) {

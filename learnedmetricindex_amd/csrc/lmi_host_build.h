@@ -8,9 +8,16 @@
 static int kg16_for(const lmi_index* h, int d) {
     return low_d_form(h, cdiv(d, 16)) ? (int)cdiv(d, 16) : (int)rup(cdiv(d, 16), PF_STAGE_G);
 }
-// bytes of the fp16 fragments (+ 8 KiB: pass2_kernel's look-ahead requests up to two stages = 4 KiB past the last row-block's fragments
-// before it learns that the item is over; the data is never used, the addresses must be the allocation's)
-static size_t slab16_bytes(const lmi_index* h) { return (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KG16 * 1024 + 8192; }
+// bytes of the fp16 fragments (with pass 2's look-ahead behind them, lmi_host.h)
+static size_t slab16_bytes(const lmi_index* h) { return (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KG16 * 1024 + P2_LOOKAHEAD_BYTES; }
+
+// owned_total / n_nonempty / chunk_rows / h_nch from h_nb_rows and h_any (lmi_layout.h); pick: a build's automatic chunk length
+static void derive_tables(lmi_index* h, const lmi_layout::AutoChunk* pick) {
+    const lmi_layout::Tables t = lmi_layout::derive_tables(h->h_nb_rows, h->h_any, h->chunk_rows, pick, h->h_nch);
+    h->owned_total = t.owned_total;
+    h->n_nonempty = t.n_nonempty;
+    h->chunk_rows = t.chunk_rows;
+}
 
 // The part of lmi_buckets_begin that follows from the per-bucket counts alone (lmi_subset starts here: it knows how many objects every
 // bucket keeps, not a label array): the handle's shape, the chunk length, the layout, the zero-filled images and the device copies of the
@@ -40,72 +47,29 @@ static int begin_layout(lmi_index* h, int64_t N, int d, int L, const int* counts
     h->KGs = (int)rup(cdiv(d, 8), STAGE_G);
     h->built = false;
     h->h_nb_rows.assign(counts, counts + L);
-    h->h_rb_start.assign(L + 1, 0);
-    h->h_nch.assign(L, 0);
-    // Chunk rows not set by the caller: small indexes (or small shards) get smaller chunks so that a scan has
-    // many more work items than the 256 blocks that share them (100 000 rows x 1 000 queries: pass 2 0.169 ms
-    // with 2048-row chunks, 0.089 ms with 256; the 1.25M-row shard of an 8-way split that holds the largest
-    // bucket: 0.90 ms with 2048, 0.69 ms with 512); 10M rows keep 2048.
-    // A bucket is scanned in at most 1024 chunks: very large buckets get larger chunks than that.
-    {
-        int max_rows = 0;
-        long long owned_rows = 0;
-        // buckets with rows on any rank: the queries of a batch spread over all of them, whoever owns them
-        int nonempty = 0;
-        for (int b = 0; b < L; ++b) { max_rows = std::max(max_rows, h->h_nb_rows[b]); owned_rows += h->h_nb_rows[b]; nonempty += any[b] != 0; }
-        h->n_nonempty = std::max(1, nonempty);
-        if (h->chunk_rows_auto) {
-            h->chunk_rows = (int)std::min<long long>(2048, std::max<long long>(P2_TILE_ROWS, rup(owned_rows / 4096, P2_TILE_ROWS)));
-            // d <= 128 (lmi_pass2_small.h): a 2048-row item is ~5 us of work there, about what taking it from the queue and
-            // staging its query fragments costs, while 8192-row items are too few to share out evenly (10M x 45, pass 2 at
-            // 1024 / 2048 / 4096 / 8192 rows per item: 0.590 / 0.441 / 0.385 / 0.412 ms): up to 4096
-            if (low_d_form(h, cdiv(d, 16)))
-                h->chunk_rows = (int)std::min<long long>(4096, std::max<long long>(P2_TILE_ROWS, rup(owned_rows / 1024, P2_TILE_ROWS)));
-            // all-f32 scan (scan_kernel: 128-query tiles, so a bucket's chunk is read by several items): the chunk's 4 d-byte rows should
-            // stay in an XCD's 4-MiB L2 until the bucket's last query tile has come by -- 10M x 768: 2 048-row chunks (6 MB) 35.28 ms,
-            // 1 024-row chunks 34.76 (profiles/r05_exact_chunks.txt)
-            if (!h->prefilter)
-                h->chunk_rows = (int)std::max<long long>(P2_TILE_ROWS, std::min<long long>(h->chunk_rows, (3ll << 20) / (4ll * d) / P2_TILE_ROWS * P2_TILE_ROWS));
-        }
-        const int need = (int)rup(cdiv(max_rows, 1024), 256);
-        if (need > h->chunk_rows) h->chunk_rows = need;
-    }
-    const int chunk_rb = h->chunk_rows / 32;
-    for (int b = 0; b < L; ++b) {
-        int nrb = cdiv(h->h_nb_rows[b], 32);
-        h->h_rb_start[b + 1] = h->h_rb_start[b] + nrb;
-        h->h_nch[b] = cdiv(nrb, chunk_rb);
-    }
-    h->n_rb_total = h->h_rb_start[L];
-    h->h_cap_rb.assign(L, 0);
     h->h_any.assign(any, any + L);
-    for (int b = 0; b < L; ++b) h->h_cap_rb[b] = h->h_rb_start[b + 1] - h->h_rb_start[b];
     if (owned) h->h_owned.assign(owned, owned + L);
     else h->h_owned.clear();
-    const size_t slab_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * h->KGs * 1024;
+    // chunk rows not set by the caller: picked by the index size (lmi_layout.h); the layout of a build has no slack
+    const lmi_layout::AutoChunk pick = {d, low_d_form(h, cdiv(d, 16)), h->prefilter};
+    derive_tables(h, h->chunk_rows_auto ? &pick : nullptr);
+    h->n_rb_total = lmi_layout::fresh_layout(h->h_nb_rows, h->h_rb_start, h->h_cap_rb);
+    // the form's images, the others released.  Zero-filled where the rows arrive piece by piece (LMI_STORAGE_F16: unscaled until
+    // lmi_buckets_end).  The fp16 fragments of the row-major form are reserved with the build's other images, so that a build that cannot
+    // fit fails before the rows are uploaded and lmi_index_bytes reports the index's size from here on; lmi_buckets_end fills them.
     if (h->prefilter) h->KG16 = kg16_for(h, d);
-    if (h->storage == LMI_STORAGE_F16) {   // fp16 fragments only (lmi_store16.h): filled piece by piece, unscaled until buckets_end
-        h->slab.release();
-        h->rowmajor.release();
-        CHK(h->slab16.reserve(slab16_bytes(h)));
-        HIPCHK(hipMemsetAsync(h->slab16.p, 0, slab16_bytes(h), h->stream));
+    SlabImage im[MAX_SLAB_IMAGES];
+    const int nim = slab_images(h, im, true);
+    for (DevBuf* unused : {&h->slab, &h->rowmajor, &h->slab16})
+        if (std::none_of(im, im + nim, [&](const SlabImage& i) { return i.buf == unused; })) unused->release();
+    for (int i = 0; i < nim; ++i) {
+        CHK(im[i].buf->reserve(im[i].bytes(h->n_rb_total)));
+        if (im[i].zeroed) HIPCHK(hipMemsetAsync(im[i].buf->p, 0, im[i].bytes(h->n_rb_total), h->stream));
+    }
+    if (h->storage == LMI_STORAGE_F16) {
         CHK(h->xmaxbits.reserve(16));   // [0] max |x| (bits), [1] S16_* flags
         HIPCHK(hipMemsetAsync(h->xmaxbits.p, 0, 16, h->stream));
-    } else if (h->prefilter) {  // row-major f32 (exact re-rank / fallback / read-back); fp16 fragments at buckets_end
-        const size_t rm_bytes = (size_t)std::max<int64_t>(h->n_rb_total, 1) * 32 * h->dp * 4;
-        h->slab.release();
-        CHK(h->rowmajor.reserve(rm_bytes));
-        HIPCHK(hipMemsetAsync(h->rowmajor.p, 0, rm_bytes, h->stream));
-        // (reserved with the build's other images, so that a build that cannot fit fails before the rows are uploaded and
-        // lmi_index_bytes reports the index's size from here on; lmi_buckets_end fills them)
-        CHK(h->slab16.reserve(slab16_bytes(h)));
-    } else {             // f32 fragments for the all-f32 scan
-        h->rowmajor.release();
-        h->slab16.release();
-        CHK(h->slab.reserve(slab_bytes));
-        HIPCHK(hipMemsetAsync(h->slab.p, 0, slab_bytes, h->stream));
     }
-    CHK(h->ids_slab.reserve((size_t)std::max<int64_t>(h->n_rb_total, 1) * 32 * 4));
     CHK(h->d_nb_rows.reserve(L * 4));
     CHK(h->d_rb_start.reserve((L + 1) * 4));
     CHK(h->d_nch.reserve(L * 4));
@@ -114,8 +78,6 @@ static int begin_layout(lmi_index* h, int64_t N, int d, int L, const int* counts
     HIPCHK(hipMemcpy(h->d_nch.p, h->h_nch.data(), L * 4, hipMemcpyHostToDevice));
     h->rows_added = 0;
     h->indexed_ingest = false;
-    h->owned_total = 0;
-    for (int b = 0; b < L; ++b) h->owned_total += h->h_nb_rows[b];
     return 0;
 }
 
@@ -158,19 +120,33 @@ extern "C" LMI_API int lmi_buckets_begin(lmi_index* h, int64_t N, int d, int L, 
 // src16: the rows are halves (uint16 bit patterns; the *_f16 entry points).  The piece size in ROWS is the same for both types, so a
 // half piece stages half the bytes.  LMI_STORAGE_F16 takes the staged halves as they are (ingest16_half_kernel: no binary32 copy of
 // the piece exists); LMI_STORAGE_F32 widens the piece once (widen16_kernel -> h->wide) and goes on as if it had arrived as floats.
+// An ingest piece: 256 MiB of stored rows.  What a piece of n rows needs reserved: the staging of a host piece (its rows, then its
+// index entries 8-byte aligned), the binary32 form of a half piece for an LMI_STORAGE_F32 index, the piece with its norm column (L2).
+static int64_t ingest_piece_rows(const lmi_index* h) { return std::max<int64_t>(1, (256ll << 20) / ((int64_t)h->d * 4)); }
+static size_t piece_index_offset(const lmi_index* h, int64_t n, int src16) {
+    const size_t row_bytes = (size_t)n * h->d_user * (src16 ? 2 : 4);
+    return src16 ? (size_t)rup((long long)row_bytes, 8) : row_bytes;
+}
+static int ingest_piece_reserve(lmi_index* h, int64_t n, int src16, bool indexed, int on_device) {
+    if (!on_device) CHK(h->stage.reserve(piece_index_offset(h, n, src16) + (indexed ? (size_t)n * 8 : 0)));
+    if (src16 && h->storage != LMI_STORAGE_F16) CHK(h->wide.reserve((size_t)n * h->d_user * 4));
+    if (h->metric == LMI_METRIC_L2) CHK(h->aug_rows.reserve((size_t)n * h->d * 4));
+    return 0;
+}
+
 static int add_rows_impl(lmi_index* h, const void* rows, int src16, int64_t row0, const int64_t* index, int64_t nrows, int on_device,
                          const int* pos, int64_t n_total) {
     CHK(set_dev(h));
     const size_t esz = src16 ? 2 : 4;
-    const int64_t piece = std::max<int64_t>(1, (256ll << 20) / ((int64_t)h->d * 4));
+    const int64_t piece = ingest_piece_rows(h);
+    CHK(ingest_piece_reserve(h, std::min(piece, nrows), src16, index != nullptr, on_device));   // (the first piece is the longest)
     for (int64_t off = 0; off < nrows; off += piece) {
         const int64_t n = std::min(piece, nrows - off);
         const void* raw = static_cast<const char*>(rows) + (size_t)off * h->d_user * esz;
         const long long* idx = index ? reinterpret_cast<const long long*>(index + off) : nullptr;
         if (!on_device) {
             const size_t row_bytes = (size_t)n * h->d_user * esz;
-            const size_t idx_off = src16 ? (size_t)rup((long long)row_bytes, 8) : row_bytes;
-            CHK(h->stage.reserve(idx_off + (index ? (size_t)n * 8 : 0)));
+            const size_t idx_off = piece_index_offset(h, n, src16);
             HIPCHK(hipMemcpyAsync(h->stage.p, raw, row_bytes, hipMemcpyHostToDevice, h->stream));
             raw = h->stage.p;
             if (index) {
@@ -180,39 +156,39 @@ static int add_rows_impl(lmi_index* h, const void* rows, int src16, int64_t row0
         }
         const float* src = static_cast<const float*>(raw);
         if (src16 && h->storage != LMI_STORAGE_F16) {   // halves -> the binary32 piece the kernels below were written for
-            CHK(h->wide.reserve((size_t)n * h->d_user * 4));
             CHK(widen16_enqueue(raw, n, h->d_user, h->wide.as<float>(), h->stream));
             src = h->wide.as<float>();
         }
         if (h->metric == LMI_METRIC_L2) {  // the piece with its norm column, then ingested like any d-column piece
-            CHK(h->aug_rows.reserve((size_t)n * h->d * 4));
             augment_copy_kernel<<<cdiv((long long)n * h->d, 256), 256, 0, h->stream>>>(src, h->d_user, h->d, n, h->aug_rows.as<float>());
             HIPCHK(hipGetLastError());
             augment_norm_kernel<<<cdiv(n, 256), 256, 0, h->stream>>>(src, h->d_user, h->d, n, h->aug_rows.as<float>(), nullptr);
             HIPCHK(hipGetLastError());
             src = h->aug_rows.as<float>();
         }
-        if (h->storage == LMI_STORAGE_F16) {   // the piece -> halves -> its rows' fragments; the exactness flags and the absmax
-            long long total = (long long)n * 2 * h->KG16;
+        switch (stored_form(h)) {
+        case FORM_FRAG16: {   // the piece -> halves -> its rows' fragments; the exactness flags and the absmax
+            const long long total = (long long)n * 2 * h->KG16;
+            const unsigned short* raw16 = static_cast<const unsigned short*>(raw);
             if (!src16)
                 ingest16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n, h->KG16,
                                                                         frag16x16(h), h->slab16.as<uint4>(), h->xmaxbits.as<unsigned>());
             else if (half_src_vec(raw, h->d))
-                ingest16_half_kernel<true><<<cdiv(total, 256), 256, 0, h->stream>>>(static_cast<const unsigned short*>(raw), h->d, pos, row0 + off, idx,
-                                                                                   (long long)n_total, n, h->KG16, frag16x16(h), h->slab16.as<uint4>(),
-                                                                                   h->xmaxbits.as<unsigned>());
+                ingest16_half_kernel<true><<<cdiv(total, 256), 256, 0, h->stream>>>(raw16, h->d, pos, row0 + off, idx, (long long)n_total, n, h->KG16,
+                                                                                   frag16x16(h), h->slab16.as<uint4>(), h->xmaxbits.as<unsigned>());
             else
-                ingest16_half_kernel<false><<<cdiv(total, 256), 256, 0, h->stream>>>(static_cast<const unsigned short*>(raw), h->d, pos, row0 + off, idx,
-                                                                                    (long long)n_total, n, h->KG16, frag16x16(h), h->slab16.as<uint4>(),
-                                                                                    h->xmaxbits.as<unsigned>());
-        } else if (h->prefilter) {
-            long long total = (long long)n * h->d;
-            scatter_rows_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
-                                                                        h->rowmajor.as<float>(), h->dp);
-        } else {
-            long long total = (long long)n * h->KGs;
-            pack_scatter_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
-                                                                        h->KGs, h->slab.as<float4>());
+                ingest16_half_kernel<false><<<cdiv(total, 256), 256, 0, h->stream>>>(raw16, h->d, pos, row0 + off, idx, (long long)n_total, n, h->KG16,
+                                                                                    frag16x16(h), h->slab16.as<uint4>(), h->xmaxbits.as<unsigned>());
+            break;
+        }
+        case FORM_ROWMAJOR:
+            scatter_rows_kernel<<<cdiv((long long)n * h->d, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
+                                                                                      h->rowmajor.as<float>(), h->dp);
+            break;
+        case FORM_FRAG32:
+            pack_scatter_kernel<<<cdiv((long long)n * h->KGs, 256), 256, 0, h->stream>>>(src, h->d, pos, row0 + off, idx, (long long)n_total, n,
+                                                                                        h->KGs, h->slab.as<float4>());
+            break;
         }
         HIPCHK(hipGetLastError());
         if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));
@@ -261,19 +237,25 @@ extern "C" LMI_API int lmi_buckets_add_owned_rows_f16(lmi_index* h, const uint16
 // The prefilter's images of the whole slab: one power-of-two scale from the absmax of every stored value (holes and spare
 // row-blocks hold zeros), the fp16 fragments and every bucket's norm maxima.  lmi_buckets_end, and lmi_buckets_insert when
 // new rows break max|x'| < 1 under the current scale.
+// the scale and every bucket's norm maxima, before they are derived again: reserved, the maxima zero
+static int reset_norm_tables(lmi_index* h) {
+    CHK(h->xscale.reserve(16));
+    CHK(h->bnorm.reserve((size_t)h->L * 4));
+    CHK(h->bdelta.reserve((size_t)h->L * 4));
+    HIPCHK(hipMemsetAsync(h->bnorm.p, 0, (size_t)h->L * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->bdelta.p, 0, (size_t)h->L * 4, h->stream));
+    return 0;
+}
+
 static int prefilter_images(lmi_index* h) {
     // fp16 copy of the slab for the prefilter: one power-of-two scale for the whole index
     // (pass2_kernel's stages hold two k16-groups; the low-dimensional form has no stages: d = 45 is 48 wide, not 64)
     h->KG16 = kg16_for(h, h->d);
     const long long n_rows = (long long)h->n_rb_total * 32;
     CHK(h->xmaxbits.reserve(16));
-    CHK(h->xscale.reserve(16));
-    CHK(h->bnorm.reserve((size_t)h->L * 4));
-    CHK(h->bdelta.reserve((size_t)h->L * 4));
     CHK(h->slab16.reserve(slab16_bytes(h)));
     HIPCHK(hipMemsetAsync(h->xmaxbits.p, 0, 16, h->stream));
-    HIPCHK(hipMemsetAsync(h->bnorm.p, 0, (size_t)h->L * 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->bdelta.p, 0, (size_t)h->L * 4, h->stream));
+    CHK(reset_norm_tables(h));
     absmax_kernel<<<h->num_cus * 8, 256, 0, h->stream>>>(h->rowmajor.as<float>(), n_rows * h->dp, h->xmaxbits.as<unsigned>());
     HIPCHK(hipGetLastError());
     make_scale_kernel<<<1, 1, 0, h->stream>>>(h->xmaxbits.as<unsigned>(), h->xscale.as<float>());
@@ -292,24 +274,31 @@ static int prefilter_images(lmi_index* h) {
     return 0;
 }
 
+// LMI_STORAGE_F16, the images behind the fragments (lmi_buckets_end; lmi_subset on the rows it kept): the norm tables reset, the scale
+// (make_scale: the caller's launch that writes xscale, and `factor` where that is another buffer), the slab times factor[0] in place
+// with the S16_* flags raised in xmaxbits[1], the buckets' norms from the stored halves.  Enqueues only: the caller reads the flags.
+template <class MakeScale>
+static int storage16_images(lmi_index* h, const DevBuf& factor, MakeScale make_scale) {
+    CHK(reset_norm_tables(h));   // (bdelta stays 0: ||x^ - x'|| = 0, the stored value IS x')
+    CHK(make_scale());
+    rescale16_kernel<<<h->num_cus * 8, 256, 0, h->stream>>>(h->slab16.as<uint4>(), (long long)h->n_rb_total * h->KG16 * 64, factor.as<float>(), h->xmaxbits.as<unsigned>());
+    HIPCHK(hipGetLastError());
+    bucket_norm16_kernel<<<dim3(64, h->L), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->d, h->KG16, frag16x16(h), h->d_rb_start.as<int>(),
+                                                               h->d_nb_rows.as<int>(), h->bnorm.as<unsigned>());
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // LMI_STORAGE_F16: the fragments were filled unscaled by lmi_buckets_add_*rows; the scale from their absmax, the slab times the scale
 // in place, the buckets' norms from the stored halves -- and the verdict: the flags are read after the synchronisation, a refused
 // build launches nothing more and leaves the handle without an index.
 static int storage16_finish(lmi_index* h) {
     unsigned* state = h->xmaxbits.as<unsigned>();
-    CHK(h->xscale.reserve(16));
-    CHK(h->bnorm.reserve((size_t)h->L * 4));
-    CHK(h->bdelta.reserve((size_t)h->L * 4));
-    HIPCHK(hipMemsetAsync(h->bnorm.p, 0, (size_t)h->L * 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->bdelta.p, 0, (size_t)h->L * 4, h->stream));   // ||x^ - x'|| = 0: the stored value IS x'
-    make_scale_kernel<<<1, 1, 0, h->stream>>>(state, h->xscale.as<float>());
-    HIPCHK(hipGetLastError());
-    rescale16_kernel<<<h->num_cus * 8, 256, 0, h->stream>>>(h->slab16.as<uint4>(), (long long)h->n_rb_total * h->KG16 * 64, h->xscale.as<float>(), state);
-    HIPCHK(hipGetLastError());
-    dim3 g(64, h->L);
-    bucket_norm16_kernel<<<g, 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->d, h->KG16, frag16x16(h), h->d_rb_start.as<int>(),
-                                                  h->d_nb_rows.as<int>(), h->bnorm.as<unsigned>());
-    HIPCHK(hipGetLastError());
+    CHK(storage16_images(h, h->xscale, [&]() -> int {
+        make_scale_kernel<<<1, 1, 0, h->stream>>>(state, h->xscale.as<float>());
+        HIPCHK(hipGetLastError());
+        return 0;
+    }));
     unsigned st[4] = {0, 0, 0, 0};
     float sc[2] = {1.0f, 1.0f};
     HIPCHK(hipMemcpyAsync(st, state, 16, hipMemcpyDeviceToHost, h->stream));
@@ -353,70 +342,65 @@ extern "C" LMI_API int lmi_bucket_sizes(lmi_index* h, int64_t* sizes) {
     return 0;
 }
 
-extern "C" LMI_API int lmi_bucket_read(lmi_index* h, int bucket, float* rows, uint32_t* ids) {
-    if (!h || !h->built) return fail("lmi_bucket_read: the bucket index is not built");
-    if (bucket < 0 || bucket >= h->L) return fail("lmi_bucket_read: bucket %d outside [0,%d)", bucket, h->L);
+// A bucket's rows [p0, p0 + n) to the caller's `rows`, as floats or (half) as halves, enqueued on the stream.  Floats: the row-major
+// copy as it lies, fragments unpacked through staging (LMI_STORAGE_F16: widened and unscaled, exact: lmi_store16.h).  Halves:
+// LMI_STORAGE_F16 gives the stored halves, unscaled; the f32 forms are narrowed on the device, the flag is read after a synchronisation
+// and a bucket with a value that is not binary16-exact is refused before any row reaches the caller.
+static int read_rows(lmi_index* h, int bucket, int64_t p0, int64_t n, void* rows, bool half, const char* who) {
+    const int du = h->d_user;  // the caller's columns (the L2 norm column is not returned)
+    const StoredForm form = stored_form(h);
+    const size_t out_bytes = (size_t)n * du * (half ? 2 : 4);
+    if (!half && form == FORM_ROWMAJOR) {
+        HIPCHK(hipMemcpy2DAsync(rows, (size_t)du * 4, h->rowmajor.as<float>() + (size_t)p0 * h->dp, (size_t)h->dp * 4, (size_t)du * 4, (size_t)n,
+                                hipMemcpyDeviceToHost, h->stream));
+        return 0;
+    }
+    CHK(h->stage.reserve(out_bytes));
+    const long long pieces = n * cdiv(du, 8);
+    if (!half) {
+        if (form == FORM_FRAG16)
+            unpack16_kernel<<<cdiv(pieces, 256), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->KG16, frag16x16(h), p0, n, du, h->xscale.as<float>(),
+                                                                     h->stage.as<float>());
+        else
+            unpack_kernel<<<cdiv(pieces, 256), 256, 0, h->stream>>>(h->slab.as<float4>(), h->KGs, p0, n, du, h->stage.as<float>());
+        HIPCHK(hipGetLastError());
+    } else if (form == FORM_FRAG16) {
+        unpack16_half_kernel<<<cdiv(pieces, 256), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->KG16, frag16x16(h), p0, n, du, h->xscale.as<float>(),
+                                                                      h->stage.as<unsigned short>());
+        HIPCHK(hipGetLastError());
+    } else {
+        unsigned short* out = h->stage.as<unsigned short>();
+        CHK(h->rd_flag.reserve(16));
+        HIPCHK(hipMemsetAsync(h->rd_flag.p, 0, 4, h->stream));
+        const long long total = n * du;
+        if (form == FORM_ROWMAJOR) narrow16_kernel<false><<<cdiv(total, 256), 256, 0, h->stream>>>(h->rowmajor.as<float>(), h->dp, p0, n, du, out, h->rd_flag.as<unsigned>());
+        else narrow16_kernel<true><<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab.as<float>(), h->KGs, p0, n, du, out, h->rd_flag.as<unsigned>());
+        HIPCHK(hipGetLastError());
+        unsigned bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, h->rd_flag.p, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (bad) return fail("%s: a value of bucket %d is not exactly representable in binary16 (or not finite); nothing was returned -- read it with lmi_bucket_read", who, bucket);
+    }
+    HIPCHK(hipMemcpyAsync(rows, h->stage.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+
+// lmi_bucket_read / lmi_bucket_read_f16 (half: the rows as halves; `who`: the entry point, for the messages).  Reads only.
+static int bucket_read_impl(lmi_index* h, int bucket, void* rows, bool half, uint32_t* ids, const char* who) {
+    if (!h || !h->built) return fail("%s: the bucket index is not built", who);
+    if (bucket < 0 || bucket >= h->L) return fail("%s: bucket %d outside [0,%d)", who, bucket, h->L);
     const int64_t n = h->h_nb_rows[bucket];
     if (n == 0) return 0;
     CHK(set_dev(h));
     const int64_t p0 = (int64_t)h->h_rb_start[bucket] * 32;
-    const int du = h->d_user;  // the caller's columns (the L2 norm column is not returned)
-    if (rows && h->storage == LMI_STORAGE_F16) {   // the rows out of the fp16 fragments, widened and unscaled (exact: lmi_store16.h)
-        CHK(h->stage.reserve((size_t)n * du * 4));
-        long long total = n * cdiv(du, 8);
-        unpack16_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->KG16, frag16x16(h), p0, n, du, h->xscale.as<float>(),
-                                                                h->stage.as<float>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows, h->stage.p, (size_t)n * du * 4, hipMemcpyDeviceToHost, h->stream));
-    } else if (rows && h->prefilter) {
-        HIPCHK(hipMemcpy2DAsync(rows, (size_t)du * 4, h->rowmajor.as<float>() + (size_t)p0 * h->dp, (size_t)h->dp * 4, (size_t)du * 4, (size_t)n,
-                                hipMemcpyDeviceToHost, h->stream));
-    } else if (rows) {
-        CHK(h->stage.reserve((size_t)n * du * 4));
-        long long total = n * cdiv(du, 8);
-        unpack_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab.as<float4>(), h->KGs, p0, n, du, h->stage.as<float>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows, h->stage.p, (size_t)n * du * 4, hipMemcpyDeviceToHost, h->stream));
-    }
+    if (rows) CHK(read_rows(h, bucket, p0, n, rows, half, who));
     if (ids) HIPCHK(hipMemcpyAsync(ids, h->ids_slab.as<uint32_t>() + p0, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
-
-// lmi_bucket_read with the rows as halves.  LMI_STORAGE_F16: the stored halves, unscaled.  LMI_STORAGE_F32 (either layout): narrowed on
-// the device; the flag is read after the synchronisation and a bucket with a value that is not binary16-exact is refused before any row
-// reaches the caller.  Reads only: the index is as it was either way.
+extern "C" LMI_API int lmi_bucket_read(lmi_index* h, int bucket, float* rows, uint32_t* ids) {
+    return bucket_read_impl(h, bucket, rows, false, ids, "lmi_bucket_read");
+}
 extern "C" LMI_API int lmi_bucket_read_f16(lmi_index* h, int bucket, uint16_t* rows, uint32_t* ids) {
-    if (!h || !h->built) return fail("lmi_bucket_read_f16: the bucket index is not built");
-    if (bucket < 0 || bucket >= h->L) return fail("lmi_bucket_read_f16: bucket %d outside [0,%d)", bucket, h->L);
-    const int64_t n = h->h_nb_rows[bucket];
-    if (n == 0) return 0;
-    CHK(set_dev(h));
-    const int64_t p0 = (int64_t)h->h_rb_start[bucket] * 32;
-    const int du = h->d_user;  // the caller's columns (the L2 norm column is not returned)
-    if (rows) {
-        unsigned short* out = nullptr;
-        CHK(h->stage.reserve((size_t)n * du * 2));
-        out = h->stage.as<unsigned short>();
-        if (h->storage == LMI_STORAGE_F16) {
-            long long total = n * cdiv(du, 8);
-            unpack16_half_kernel<<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab16.as<uint4>(), h->KG16, frag16x16(h), p0, n, du, h->xscale.as<float>(), out);
-            HIPCHK(hipGetLastError());
-        } else {
-            CHK(h->rd_flag.reserve(16));
-            HIPCHK(hipMemsetAsync(h->rd_flag.p, 0, 4, h->stream));
-            long long total = n * du;
-            if (h->prefilter) narrow16_kernel<false><<<cdiv(total, 256), 256, 0, h->stream>>>(h->rowmajor.as<float>(), h->dp, p0, n, du, out, h->rd_flag.as<unsigned>());
-            else narrow16_kernel<true><<<cdiv(total, 256), 256, 0, h->stream>>>(h->slab.as<float>(), h->KGs, p0, n, du, out, h->rd_flag.as<unsigned>());
-            HIPCHK(hipGetLastError());
-            unsigned bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, h->rd_flag.p, 4, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (bad) return fail("lmi_bucket_read_f16: a value of bucket %d is not exactly representable in binary16 (or not finite); nothing was returned -- read it with lmi_bucket_read", bucket);
-        }
-        HIPCHK(hipMemcpyAsync(rows, out, (size_t)n * du * 2, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (ids) HIPCHK(hipMemcpyAsync(ids, h->ids_slab.as<uint32_t>() + p0, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return bucket_read_impl(h, bucket, rows, true, ids, "lmi_bucket_read_f16");
 }

@@ -54,30 +54,10 @@ static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t 
         c->tree_set = true;
     }
     c->desc_dirty = true;
-    // ---- 1: mark the rows that stay and count them per bucket; the counts come back to the host ----
-    std::vector<uint32_t> list(ids, ids + n);
-    if (!std::is_sorted(list.begin(), list.end())) std::sort(list.begin(), list.end());   // (a list that arrives sorted is only checked)
-    list.erase(std::unique(list.begin(), list.end()), list.end());
-    const int64_t slab_rows = h->n_rb_total * 32;
-    std::vector<int> cnt(L, 0), iota(L);   // (iota: compact_map_kernel's bucket list; alive until the stream has taken it)
-    const bool some = h->owned_total > 0 && (mode == LMI_SUBSET_DROP || !list.empty());
-    if (some) {
-        CHK(c->mut_ids.reserve(std::max<size_t>(list.size(), 1) * 4));
-        CHK(c->mut_keep.reserve((size_t)slab_rows * 4));   // the keep flags, later the new rows' source positions
-        CHK(c->mut_src.reserve((size_t)slab_rows * 4));    // the stable compaction map
-        CHK(c->mut_word.reserve((size_t)L * 4 + 16));
-        CHK(c->mut_list.reserve((size_t)L * 4));
-        if (!list.empty()) HIPCHK(hipMemcpyAsync(c->mut_ids.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(c->mut_word.p, 0, (size_t)L * 4 + 16, st));
-        int max_n = 0;
-        for (int b = 0; b < L; ++b) max_n = std::max(max_n, h->h_nb_rows[b]);
-        mark_subset_kernel<<<dim3(std::max(1, std::min(64, cdiv(max_n, 256))), L), 256, 0, st>>>(
-            h->ids_slab.as<uint32_t>(), h->d_rb_start.as<int>(), h->d_nb_rows.as<int>(), c->mut_ids.as<uint32_t>(), (int)list.size(), mode,
-            c->mut_keep.as<int>(), c->mut_word.as<int>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(cnt.data(), c->mut_word.p, (size_t)L * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
+    // ---- 1: mark the rows that stay and count them per bucket; the counts come back to the host (16 zeroed bytes behind them: the
+    //         fp16 gather's maximum) ----
+    std::vector<int> cnt, iota(L);   // (iota: compact_map_kernel's bucket list; alive until the stream has taken it)
+    CHK(mark_rows(h, c, ids, n, mode, 16, cnt));
     int64_t kept = 0;
     for (int b = 0; b < L; ++b) kept += cnt[b];
     // ---- 2: the layout of a fresh build of the kept objects.  An owned bucket that is left empty holds rows on no rank any more
@@ -98,7 +78,7 @@ static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t 
         compact_map_kernel<<<L, CM_THREADS, 0, st>>>(c->mut_list.as<int>(), h->d_nb_rows.as<int>(), h->d_rb_start.as<int>(), h->d_nb_rows.as<int>(),
                                                     c->mut_keep.as<int>(), c->mut_src.as<int>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemsetAsync(c->mut_keep.p, 0xFF, (size_t)new_rows * 4, st));   // (new_rows <= slab_rows: no bucket grows)
+        HIPCHK(hipMemsetAsync(c->mut_keep.p, 0xFF, (size_t)new_rows * 4, st));   // (no more rows than h's slab, which mut_keep was sized for: no bucket grows)
         int max_n = 0;
         for (int b = 0; b < L; ++b) max_n = std::max(max_n, cnt[b]);
         subset_srcpos_kernel<<<dim3(std::max(1, std::min(64, cdiv(max_n, 256))), L), 256, 0, st>>>(
@@ -106,45 +86,43 @@ static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t 
         HIPCHK(hipGetLastError());
         const int* srcpos = c->mut_keep.as<int>();
         // ---- 4: the gather of the stored image, the ids alongside ----
-        if (c->storage == LMI_STORAGE_F16) {
+        switch (stored_form(c)) {
+        case FORM_FRAG16: {
             const long long pieces = c->n_rb_total * c->KG16 * 64;
-            unsigned* maxbits = c->mut_word.as<unsigned>() + L;   // (zeroed above)
+            unsigned* maxbits = c->mut_word.as<unsigned>() + L;   // (zeroed by mark_rows)
             subset_gather_frag16_kernel<<<gather_blocks(c, pieces), 256, 0, st>>>(h->slab16.as<uint4>(), h->ids_slab.as<uint32_t>(), srcpos, c->n_rb_total,
                                                                                    c->KG16, frag16x16(c), c->slab16.as<uint4>(), c->ids_slab.as<uint32_t>(),
                                                                                    maxbits);
-        } else if (c->prefilter) {
+            break;
+        }
+        case FORM_ROWMAJOR: {
             const long long pieces = new_rows * (c->dp / 4);
             subset_gather_rows_kernel<<<gather_blocks(c, pieces), 256, 0, st>>>(h->rowmajor.as<float4>(), h->ids_slab.as<uint32_t>(), srcpos, new_rows,
                                                                                  c->dp / 4, c->rowmajor.as<float4>(), c->ids_slab.as<uint32_t>());
-        } else {
+            break;
+        }
+        case FORM_FRAG32: {
             const long long pieces = c->n_rb_total * c->KGs * 64;
             subset_gather_frag32_kernel<<<gather_blocks(c, pieces), 256, 0, st>>>(h->slab.as<float4>(), h->ids_slab.as<uint32_t>(), srcpos, c->n_rb_total,
                                                                                    c->KGs, c->slab.as<float4>(), c->ids_slab.as<uint32_t>());
+            break;
+        }
         }
         HIPCHK(hipGetLastError());
     }
     // ---- 5: what lmi_buckets_end derives from the rows, from the new handle's own ----
     c->rows_added = c->N;
     c->have16 = false;
-    if (c->storage == LMI_STORAGE_F16 && c->n_rb_total > 0) {
+    if (stored_form(c) == FORM_FRAG16 && c->n_rb_total > 0) {
         // the stored halves are x * s_old; the kept rows' own scale s_new >= s_old, and the pieces times the power of two s_new / s_old
         // are the halves x * s_new a fresh build stores (exact: the product is below 1 and only moves the exponent up)
-        CHK(c->xscale.reserve(16));
-        CHK(c->bnorm.reserve((size_t)L * 4));
-        CHK(c->bdelta.reserve((size_t)L * 4));
         CHK(c->mut_stage.reserve(16));
-        HIPCHK(hipMemsetAsync(c->bnorm.p, 0, (size_t)L * 4, st));
-        HIPCHK(hipMemsetAsync(c->bdelta.p, 0, (size_t)L * 4, st));   // ||x^ - x'|| = 0: the stored value IS x'
-        subset_scale16_kernel<<<1, 1, 0, st>>>(c->mut_word.as<unsigned>() + L, h->xscale.as<float>(), c->xmaxbits.as<unsigned>(), c->xscale.as<float>(),
-                                              c->mut_stage.as<float>());
-        HIPCHK(hipGetLastError());
-        rescale16_kernel<<<c->num_cus * 8, 256, 0, st>>>(c->slab16.as<uint4>(), (long long)c->n_rb_total * c->KG16 * 64, c->mut_stage.as<float>(),
-                                                        c->xmaxbits.as<unsigned>());
-        HIPCHK(hipGetLastError());
-        dim3 g(64, L);
-        bucket_norm16_kernel<<<g, 256, 0, st>>>(c->slab16.as<uint4>(), c->d, c->KG16, frag16x16(c), c->d_rb_start.as<int>(), c->d_nb_rows.as<int>(),
-                                               c->bnorm.as<unsigned>());
-        HIPCHK(hipGetLastError());
+        CHK(storage16_images(c, c->mut_stage, [&]() -> int {
+            subset_scale16_kernel<<<1, 1, 0, st>>>(c->mut_word.as<unsigned>() + L, h->xscale.as<float>(), c->xmaxbits.as<unsigned>(), c->xscale.as<float>(),
+                                                  c->mut_stage.as<float>());
+            HIPCHK(hipGetLastError());
+            return 0;
+        }));
         c->have16 = true;
     } else if (c->prefilter && c->n_rb_total > 0) {
         CHK(prefilter_images(c));   // its own absmax, scale, fp16 fragments and norms

@@ -3,7 +3,8 @@
 // The scan kernels find a bucket through rb_start[b] and nb_rows[b] only and mask rows at or past n_b, so a bucket may
 // sit anywhere in the slab with spare row-blocks after its last row.  Insert scatters the new rows behind a bucket's last
 // row (scatter_rows_kernel / pack_scatter_kernel with a positions array of the batch, lmi_prefilter.h / lmi_kernels.h);
-// delete compacts the hit buckets in bucket order through a staging buffer.  What the prefilter derives from the rows
+// delete marks the rows that stay (mark_rows_kernel, which lmi_subset shares) and compacts the hit buckets in bucket order through
+// a staging buffer.  What the prefilter derives from the rows
 // (the fp16 fragments, the per-bucket norm maxima) is redone for the touched row-blocks by the range-list forms below.
 // Every store here is a plain vector store; nothing in this file is read by the query path.
 #pragma once
@@ -75,31 +76,32 @@ __global__ void reset_norms_kernel(const int* __restrict__ bucket, int n, unsign
     bdelta_bits[bucket[i]] = 0u;
 }
 
-// ---- delete ----
-// keep[slab row] <- 0 if the row's id is in del[0..n_del) (sorted ascending, unique), else 1; removed[b] += rows dropped.
-// Live rows of every bucket: grid (x, L), bucket = blockIdx.y.
-__global__ void mark_deleted_kernel(const uint32_t* __restrict__ ids_slab, const int* __restrict__ rb_start,
-                                    const int* __restrict__ nb_rows, const uint32_t* __restrict__ del, int n_del,
-                                    int* __restrict__ keep, int* __restrict__ removed) {
+// ---- delete, lmi_subset ----
+// keep[slab row] <- 1 if the row stays (mode LMI_SUBSET_KEEP = 0: its id is in list[0..n_list), sorted ascending and unique; mode
+// LMI_SUBSET_DROP = 1: it is not), else 0; kept[b] += rows that stay.  Live rows of every bucket: grid (x, L), bucket = blockIdx.y.
+__global__ void mark_rows_kernel(const uint32_t* __restrict__ ids_slab, const int* __restrict__ rb_start,
+                                 const int* __restrict__ nb_rows, const uint32_t* __restrict__ list, int n_list, int mode,
+                                 int* __restrict__ keep, int* __restrict__ kept) {
     const int b = blockIdx.y;
     const int n_b = nb_rows[b];
     const size_t base = (size_t)rb_start[b] * 32;
     int cnt = 0;
     for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n_b; row += gridDim.x * blockDim.x) {
         const uint32_t id = ids_slab[base + row];
-        int lo = 0, hi = n_del;   // first entry >= id
+        int lo = 0, hi = n_list;   // first entry >= id
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (del[mid] < id) lo = mid + 1;
+            if (list[mid] < id) lo = mid + 1;
             else hi = mid;
         }
-        const int hit = lo < n_del && del[lo] == id;
-        keep[base + row] = !hit;
-        cnt += hit;
+        const int hit = lo < n_list && list[lo] == id;
+        const int stays = mode ? !hit : hit;
+        keep[base + row] = stays;
+        cnt += stays;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(removed + b, cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept + b, cnt);
 }
 
 // Stable compaction map of the hit buckets, one 1024-thread block per bucket (blockIdx.x indexes hit[]):

@@ -1,5 +1,6 @@
 // lmi_subset.h -- device side of lmi_subset (lmi_host_subset.h): a second, independent index that holds some of a built index's objects.
 //
+// The rows are marked by lmi_mutate.h's mark_rows_kernel.
 // The rows of the kept objects go STRAIGHT from the source handle's slabs into the new handle's zero-filled slabs, one gather per
 // stored image (row-major f32, f32 fragments, fp16 fragments) with the ids alongside; nothing is staged.  The new layout is a fresh
 // build's (bucket b at row-block rb_start[b], cdiv(n_b, 32) row-blocks, no slack), so the new slab never holds more rows than the old.
@@ -13,34 +14,6 @@
 #include "lmi_mutate.h"
 
 namespace lmi {
-
-// keep[slab row] <- 1 if the row stays (mode 0: its id is in list[0..n_list), sorted ascending and unique; mode 1: it is not), else 0;
-// kept[b] += rows that stay.  Live rows of every bucket: grid (x, L), bucket = blockIdx.y.  (mark_deleted_kernel is the mode-1 form
-// with the count of the rows that go.)
-__global__ void mark_subset_kernel(const uint32_t* __restrict__ ids_slab, const int* __restrict__ rb_start,
-                                   const int* __restrict__ nb_rows, const uint32_t* __restrict__ list, int n_list, int mode,
-                                   int* __restrict__ keep, int* __restrict__ kept) {
-    const int b = blockIdx.y;
-    const int n_b = nb_rows[b];
-    const size_t base = (size_t)rb_start[b] * 32;
-    int cnt = 0;
-    for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n_b; row += gridDim.x * blockDim.x) {
-        const uint32_t id = ids_slab[base + row];
-        int lo = 0, hi = n_list;   // first entry >= id
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (list[mid] < id) lo = mid + 1;
-            else hi = mid;
-        }
-        const int hit = lo < n_list && list[lo] == id;
-        const int stays = mode ? !hit : hit;
-        keep[base + row] = stays;
-        cnt += stays;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept + b, cnt);
-}
 
 // srcpos[new slab row] <- the old slab row it is gathered from.  map: compact_map_kernel's output in the OLD layout (map[old base + j] =
 // in-bucket row of bucket b's j-th kept row); the caller has filled srcpos with -1 (the rows behind a bucket's last in its last row-block).
