@@ -432,6 +432,60 @@ LMI_API int lmi_train(int device, const float *x, int64_t n, const int32_t *labe
                       const int64_t *batch_rows /* host, [n_steps][bsz] */, int n_steps, int bsz,
                       double lr, float *losses /* host [n_steps], nullable */, int on_device /* covers x and labels */);
 
+/* Exact brute-force k-NN on the device for k up to LMI_KNN_MAX_K, deterministic (faiss.knn(xq, xb, k, metric) with any k: the
+ * ground truth of the reference's Baseline, li/Baseline.py:7-21, and of recall@k).  Its k has nothing to do with the bucket scan's
+ * (lmi_knn_ip, k <= 10, stays as it is).  The same input gives the same D and I bit for bit on any launch geometry; oracle.knn_ip
+ * and oracle.knn_l2 restate the call.
+ * No handle (like lmi_kmeans): the work runs on the NULL stream of `device` and the call returns when D and I have landed.
+ * on_device covers xq [nq][d], xb [nb][d], D [nq][k] and I [nq][k]: device pointers, xq and xb are only read and need 4-byte
+ * alignment only (xb is read with 16-byte loads where d % 4 == 0 and its base is 16-byte aligned, element by element otherwise;
+ * xq always element by element); otherwise host pointers -- xb is uploaded in pieces and each piece is scanned against a group of
+ * queries, so the base is never resident as a whole and the device memory of the call does not depend on nb.
+ * Arithmetic contract
+ *   LMI_METRIC_IP  s = the chain acc = fmaf(q[t], x[t], acc) from +0, t = 0..d-1.  D holds the similarities s, descending.
+ *   LMI_METRIC_L2  xn, qn = the same chain on <x,x> and <q,q>; key = the chain s continued by one link fmaf(1.0f, -0.5f * xn, s);
+ *                  rows are ranked by key (score = key); D = fmaf(-2.0f, key, qn), ascending.  This is lmi_set_metric's arithmetic.
+ *   chains         no chain is split over t.  (The chains run in v_mfma_f32_32x32x2_f32, which keeps subnormals, and are padded to a
+ *                  multiple of 32 links by fmaf(+0, +0, acc): acc unchanged, except that a score of -0 -- every link underflowed --
+ *                  becomes +0 where d, or d + 1 for L2, is no multiple of 32.)
+ *   selection      the first k rows in the total order (score descending, row number ascending; -0 == +0) among the rows whose
+ *                  score is > -FLT_MAX: a score that is NaN, -inf or -FLT_MAX is never returned (the oracle's topk_insert from its
+ *                  sentinel).  Non-finite inputs are not refused; they do what the chain does with them.
+ *   geometry       the order is total and every score is one unsplit chain, so the result does not depend on the tiles, the pieces,
+ *                  the splits of a piece, the query groups, the grid or the order in which lists are merged; nothing is added atomically.
+ *   padding        fewer than k admissible rows pad with I = -1 and D = -FLT_MAX (L2: FLT_MAX); nb == 0 is all padding; nq == 0
+ *                  writes nothing and succeeds.
+ * Refused, with nothing written: d outside 1..4096; k outside 1..LMI_KNN_MAX_K; nq or nb < 0 or >= 2^31; an unknown metric; a NULL
+ * pointer that is needed (xq, D, I when nq > 0; xb when nq > 0 and nb > 0).  A failed allocation names the bytes it wanted; the call
+ * frees all it allocated.
+ * Peak device memory, with Q = queries per group (at most 8192 unless forced), Q' = roundup(Q, 32), P = rows per piece (at most
+ * 65536 unless forced; with device pointers at most nb), LR = max(256, k rounded up to a power of two), d' = roundup(d, 32) (L2:
+ * roundup(d + 1, 32)):  4 Q' roundup(P, 64) (scores) + 8 Q splits LR (lists) + 4 Q' d' (query fragments) + 4 Q + 4 P (norms); with
+ * host pointers 4 Q d + 4 P d + 12 Q k more for the queries, the piece and the results.  Q and P shrink when that exceeds 80 % of the
+ * free memory.  lmi_debug_knn_plan reports the sum. */
+#define LMI_KNN_MAX_K 1024
+LMI_API int lmi_knn(int device, const float *xq, int64_t nq, const float *xb, int64_t nb, int d, int k, int metric,
+                    float *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
+/* Tuning / test hook: rows of xb per uploaded or scanned piece (< 2^31), base splits per piece (<= 1024; their partial lists are
+ * merged afterwards), queries per group (<= 2^20).  0 = chosen by the library.  Thread-local, like lmi_last_error; never changes a
+ * result. */
+LMI_API int lmi_knn_set_geometry(int64_t piece_rows, int splits, int64_t query_rows);
+enum {
+    LMI_KNN_PLAN_PIECES = 0,       /* pieces the base was scanned in (0: nb == 0)                                             */
+    LMI_KNN_PLAN_PIECE_ROWS,       /* rows per piece (the last may be shorter)                                               */
+    LMI_KNN_PLAN_SPLITS,           /* splits per piece = lists per query                                                     */
+    LMI_KNN_PLAN_QUERY_GROUPS,     /* groups the queries were taken in                                                       */
+    LMI_KNN_PLAN_QUERY_ROWS,       /* queries per group (the last may be smaller)                                            */
+    LMI_KNN_PLAN_VEC_XQ,           /* 16-byte loads of xq: always 0, the queries are packed element by element               */
+    LMI_KNN_PLAN_VEC_XB,           /* 16-byte loads of xb                                                                    */
+    LMI_KNN_PLAN_WORKSPACE_BYTES,  /* device bytes the call allocated                                                        */
+    LMI_KNN_PLAN_LIST_ROWS,        /* entries of a query's sorted list (LR above)                                            */
+    LMI_KNN_PLAN_COUNT
+};
+/* What the last lmi_knn on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
+ * min(n, LMI_KNN_PLAN_COUNT) words. */
+LMI_API int lmi_debug_knn_plan(int64_t *out, int n);
+
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);
 /* Mean of the timing slots over the calls made since lmi_timings_reset (the newest 128 at most), read

@@ -15,6 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LMI_LIB") or os.path.join(_HERE, "liblmi_hip.so")  # LMI_LIB: A/B builds (tools/)
 K_PER_BUCKET = 10
+KNN_MAX_K = 1024   # LMI_KNN_MAX_K: the largest k of `knn` (lmi_knn); `knn_ip` (lmi_knn_ip) stays at K_PER_BUCKET
 T_INFERENCE, T_ROUTE, T_SCAN, T_MERGE, T_TOTAL, T_PF_SAMPLE, T_PF_EMIT, T_RESCORE, T_FALLBACK, T_CLOCK_MHZ, T_COUNT = (
     0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12)   # (T_CLOCK_MHZ is not a time: the shader clock held under pass 2, from in-kernel counters)
 
@@ -22,6 +23,9 @@ T_INFERENCE, T_ROUTE, T_SCAN, T_MERGE, T_TOTAL, T_PF_SAMPLE, T_PF_EMIT, T_RESCOR
 PLAN_FIELDS = ("fast", "low_d", "ps_wide", "tile_cb", "sample_max", "qbound", "primary_nb", "use_front", "streamed", "G", "use_tail",
                "tail_merges", "KG16", "dp", "route_nb_template", "pack_gs", "pack_cp", "pack_vec", "route_sort_global", "merge_kind",
                "rescore_small_waves", "overflow_sorted")
+#: the LMI_KNN_PLAN_* words, in their order (lmi_debug_knn_plan)
+KNN_PLAN_FIELDS = ("PIECES", "PIECE_ROWS", "SPLITS", "QUERY_GROUPS", "QUERY_ROWS", "VEC_XQ", "VEC_XB", "WORKSPACE_BYTES", "LIST_ROWS")
+KNN_METRICS = {"ip": 0, "l2": 1}   # LMI_METRIC_IP, LMI_METRIC_L2
 
 _lib = None
 
@@ -78,6 +82,10 @@ SIGNATURES = {
     "lmi_pipeline_submit": (ctypes.c_int, [_vp] * 7 + [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_knn_ip": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int,
                                   ctypes.c_int, _vp, _vp]),
+    "lmi_knn": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                               _vp, _vp, ctypes.c_int]),
+    "lmi_knn_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
+    "lmi_debug_knn_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -716,6 +724,64 @@ def knn_ip(xq, xb, k: int = 10, device: int = 0):
     _check(lib().lmi_knn_ip(int(device), _ptr(xq), xq.shape[0], _ptr(xb), xb.shape[0], xq.shape[1], int(k),
                             _ptr(D), _ptr(I)))
     return D, I
+
+
+def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
+    """Exact brute-force k-NN on the device for k up to KNN_MAX_K (`lmi_knn`): (D f32[nq,k], I i64[nq,k]).  metric "ip": the k
+    largest inner products, descending; "l2": the k smallest squared Euclidean distances, ascending; ties go to the lower row; fewer
+    than k rows pad with I = -1 and D = -FLT_MAX (l2: FLT_MAX).  The same input gives the same result bit for bit
+    (include/lmi_hip.h states the arithmetic; oracle.knn_ip / oracle.knn_l2 restate it).  `xq`, `xb`: float32 numpy arrays -- `xb`
+    is uploaded in pieces and never resident as a whole -- or contiguous float32 torch tensors on the device, both of one kind; D and
+    I then come back as tensors on that device and the inputs are only read.  Argument errors raise ValueError before the library is
+    loaded."""
+    is_np = isinstance(xq, np.ndarray), isinstance(xb, np.ndarray)
+    for name, a, np_ in (("xq", xq, is_np[0]), ("xb", xb, is_np[1])):
+        if not np_ and not (hasattr(a, "data_ptr") and hasattr(a, "is_cuda")):
+            raise ValueError(f"knn: {name} must be a numpy array or a torch tensor on the device")
+        if str(a.dtype).replace("torch.", "") != "float32":
+            raise ValueError(f"knn: {name} must be float32, not {a.dtype}")
+        if a.ndim != 2:
+            raise ValueError(f"knn: {name} must be two-dimensional, not {tuple(a.shape)}")
+    if is_np[0] != is_np[1]:
+        raise ValueError("knn: xq and xb must both be numpy arrays or both be torch tensors on the device")
+    if metric not in KNN_METRICS:
+        raise ValueError(f"knn: metric {metric!r} unknown ('ip' or 'l2')")
+    nq, d, nb, k = int(xq.shape[0]), int(xq.shape[1]), int(xb.shape[0]), int(k)
+    if int(xb.shape[1]) != d:
+        raise ValueError(f"knn: xq has {d} columns, xb {int(xb.shape[1])}")
+    if d < 1 or d > 4096:
+        raise ValueError(f"knn: d {d} outside [1, 4096]")
+    if k < 1 or k > KNN_MAX_K:
+        raise ValueError(f"knn: k {k} outside [1, {KNN_MAX_K}]")
+    if is_np[0]:
+        xq, xb = np.ascontiguousarray(xq), np.ascontiguousarray(xb)
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _check(lib().lmi_knn(int(device), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 0))
+        return D, I
+    if not (xq.is_cuda and xb.is_cuda and xq.is_contiguous() and xb.is_contiguous()) or xq.device != xb.device:
+        raise ValueError("knn: torch xq and xb must be contiguous tensors on one device")
+    import torch
+
+    D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
+    I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+    torch.cuda.synchronize(xq.device)   # the call runs on the NULL stream; whatever produced the inputs may not have
+    dev = xq.device.index if xq.device.index is not None else torch.cuda.current_device()
+    _check(lib().lmi_knn(int(dev), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
+    return D, I
+
+
+def knn_set_geometry(piece_rows: int = 0, splits: int = 0, query_rows: int = 0) -> None:
+    """Tuning / test hook (`lmi_knn_set_geometry`): rows of `xb` per piece, splits per piece, queries per group of the `knn` calls
+    of this thread; 0 = chosen by the library.  Never changes a result."""
+    _check(lib().lmi_knn_set_geometry(int(piece_rows), int(splits), int(query_rows)))
+
+
+def knn_last_plan() -> dict:
+    """What the last `knn` on this thread did (`lmi_debug_knn_plan`): `KNN_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(KNN_PLAN_FIELDS))()
+    _check(lib().lmi_debug_knn_plan(w, len(KNN_PLAN_FIELDS)))
+    return dict(zip(KNN_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int = 0):

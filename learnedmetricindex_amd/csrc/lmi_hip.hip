@@ -15,6 +15,8 @@
 #include "lmi_host_kmeans.h"  // lmi_kmeans
 #include "lmi_train.h"        // the kernels of lmi_train
 #include "lmi_host_train.h"   // lmi_train
+#include "lmi_knn.h"          // the kernels of lmi_knn
+#include "lmi_host_knn.h"     // lmi_knn, lmi_knn_set_geometry, lmi_debug_knn_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

@@ -1,0 +1,165 @@
+// lmi_host_knn.h -- lmi_knn: argument checks, the geometry (lmi_knn_plan.h), the call's device buffers, and the schedule on the NULL
+// stream of the device: per query group pack the queries, then per piece of the base (upload,) norms, scores, selection; one merge of
+// the split lists per group writes the group's rows.  lmi_knn_set_geometry, lmi_debug_knn_plan.
+#pragma once
+#include "lmi_host.h"
+#include "lmi_knn.h"
+#include "lmi_knn_plan.h"
+
+static_assert(LMI_KNN_MAX_K == lmi_knn_plan::MAX_K, "lmi_knn_plan.h restates LMI_KNN_MAX_K");
+
+namespace {
+
+thread_local lmi_knn_plan::Forced g_knn_forced;
+thread_local int64_t g_knn_last[LMI_KNN_PLAN_COUNT] = {};
+
+// the device allocations of one lmi_knn call: freed when the call returns, whichever way
+struct KnnScratch {
+    std::vector<void*> owned;
+    int64_t total = 0;
+    ~KnnScratch() { for (void* p : owned) (void)hipFree(p); }
+    template <class T>
+    int alloc(T** out, int64_t bytes, const char* what) {
+        void* p = nullptr;
+        if (hipError_t e = hipMalloc(&p, bytes ? (size_t)bytes : 4); e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("lmi_knn: a device allocation of %lld bytes (%s) failed: %s", (long long)bytes, what, hipGetErrorString(e));
+        }
+        owned.push_back(p);
+        total += bytes;
+        *out = static_cast<T*>(p);
+        return 0;
+    }
+};
+
+template <bool VEC>
+int knn_score_launch(int ct, dim3 grid, const float* x, long long n, int d, const float* xnh, const float4* Qf, int KG, int nct, int nq,
+                     float* S, long long pitch) {
+    if (ct == 1) knn_score_kernel<1, VEC><<<grid, 256>>>(x, n, d, xnh, Qf, KG, nct, nq, S, pitch);
+    else if (ct == 2) knn_score_kernel<2, VEC><<<grid, 256>>>(x, n, d, xnh, Qf, KG, nct, nq, S, pitch);
+    else knn_score_kernel<4, VEC><<<grid, 256>>>(x, n, d, xnh, Qf, KG, nct, nq, S, pitch);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" LMI_API int lmi_knn_set_geometry(int64_t piece_rows, int splits, int64_t query_rows) {
+    if (piece_rows < 0 || piece_rows >= (1ll << 31)) return fail("lmi_knn_set_geometry: piece_rows %lld outside [0, 2^31)", (long long)piece_rows);
+    if (splits < 0 || splits > lmi_knn_plan::MAX_SPLITS) return fail("lmi_knn_set_geometry: splits %d outside [0, %d]", splits, lmi_knn_plan::MAX_SPLITS);
+    if (query_rows < 0 || query_rows > (1ll << 20)) return fail("lmi_knn_set_geometry: query_rows %lld outside [0, 2^20]", (long long)query_rows);
+    g_knn_forced.piece_rows = piece_rows;
+    g_knn_forced.splits = splits;
+    g_knn_forced.query_rows = query_rows;
+    return 0;
+}
+
+extern "C" LMI_API int lmi_debug_knn_plan(int64_t* out, int n) {
+    if (!out || n < 0) return fail("lmi_debug_knn_plan: NULL argument");
+    for (int i = 0; i < std::min(n, (int)LMI_KNN_PLAN_COUNT); ++i) out[i] = g_knn_last[i];
+    return 0;
+}
+
+extern "C" LMI_API int lmi_knn(int device, const float* xq, int64_t nq, const float* xb, int64_t nb, int d, int k, int metric, float* D,
+                               int64_t* I, int on_device) {
+    for (int64_t& w : g_knn_last) w = 0;
+    if (d < 1 || d > 4096) return fail("lmi_knn: d %d outside [1,4096]", d);
+    if (k < 1 || k > LMI_KNN_MAX_K) return fail("lmi_knn: k %d outside [1,%d]", k, LMI_KNN_MAX_K);
+    if (nq < 0 || nq >= (1ll << 31)) return fail("lmi_knn: nq %lld outside [0, 2^31)", (long long)nq);
+    if (nb < 0 || nb >= (1ll << 31)) return fail("lmi_knn: nb %lld outside [0, 2^31)", (long long)nb);
+    if (metric != LMI_METRIC_IP && metric != LMI_METRIC_L2) return fail("lmi_knn: unknown metric %d", metric);
+    if (nq > 0 && (!xq || !D || !I)) return fail("lmi_knn: xq, D and I must not be NULL");
+    if (nq > 0 && nb > 0 && !xb) return fail("lmi_knn: xb must not be NULL");
+    if (nq == 0) return 0;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("lmi_knn: device %d out of range (%d devices)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return fail("lmi_knn: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+
+    const bool l2 = metric == LMI_METRIC_L2;
+    const lmi_knn_plan::Plan p = lmi_knn_plan::make_plan(nq, nb, d, k, l2, on_device != 0, (int64_t)free_b, prop.multiProcessorCount, g_knn_forced);
+    const int LR = p.list_rows, KG = p.kg;
+    KnnScratch mem;
+    float *d_S = nullptr, *d_qn = nullptr, *d_xnh = nullptr, *d_xq = nullptr, *d_xb = nullptr, *d_D = nullptr;
+    float4* d_qf = nullptr;
+    knn_entry* d_lists = nullptr;
+    long long* d_I = nullptr;
+    CHK(mem.alloc(&d_S, p.slab_bytes, "score slab"));
+    CHK(mem.alloc(&d_lists, p.list_bytes, "lists"));
+    CHK(mem.alloc(&d_qf, p.qfrag_bytes, "query fragments"));
+    CHK(mem.alloc(&d_qn, p.qn_bytes, "query norms"));
+    CHK(mem.alloc(&d_xnh, p.xnh_bytes, "base norms"));
+    if (!on_device) {
+        CHK(mem.alloc(&d_xq, p.xq_bytes, "queries"));
+        CHK(mem.alloc(&d_xb, p.xb_bytes, "base piece"));
+        CHK(mem.alloc(&d_D, p.d_bytes, "D"));
+        CHK(mem.alloc(&d_I, p.i_bytes, "I"));
+    }
+    // 16-byte loads of the base: d % 4 == 0 keeps every row and every piece's first row aligned when the array's base is
+    const bool vec_xb = d % 4 == 0 && (reinterpret_cast<uintptr_t>(on_device ? xb : d_xb) & 15) == 0;
+    g_knn_last[LMI_KNN_PLAN_PIECES] = p.pieces;
+    g_knn_last[LMI_KNN_PLAN_PIECE_ROWS] = p.piece_rows;
+    g_knn_last[LMI_KNN_PLAN_SPLITS] = p.splits;
+    g_knn_last[LMI_KNN_PLAN_QUERY_GROUPS] = p.query_groups;
+    g_knn_last[LMI_KNN_PLAN_QUERY_ROWS] = p.query_rows;
+    g_knn_last[LMI_KNN_PLAN_VEC_XQ] = 0;   // knn_pack_kernel loads the queries element by element
+    g_knn_last[LMI_KNN_PLAN_VEC_XB] = vec_xb;
+    g_knn_last[LMI_KNN_PLAN_WORKSPACE_BYTES] = mem.total;
+    g_knn_last[LMI_KNN_PLAN_LIST_ROWS] = LR;
+
+    const size_t lds = (size_t)2 * LR * sizeof(knn_entry);
+    const size_t up = (size_t)64 << 20;   // host memory goes up in pieces of this many bytes
+    for (int64_t g = 0; g < p.query_groups; ++g) {
+        int64_t q0, q1;
+        lmi_knn_plan::group_range(p, g, &q0, &q1);
+        const int gq = (int)(q1 - q0), nct = cdiv(gq, 32), ct = nct >= 3 ? 4 : nct;
+        const float* gxq = xq + (size_t)q0 * d;
+        if (!on_device) {
+            const size_t bytes = (size_t)gq * d * 4;
+            for (size_t o = 0; o < bytes; o += up)
+                HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(d_xq) + o, reinterpret_cast<const char*>(gxq) + o, std::min(up, bytes - o),
+                                      hipMemcpyHostToDevice, nullptr));
+            gxq = d_xq;
+        }
+        knn_pack_kernel<<<cdiv((long long)nct * 32 * KG, 256), 256>>>(gxq, gq, d, nct, KG, l2 ? 1.0f : 0.0f, d_qf);
+        if (l2) knn_norm_kernel<<<cdiv(gq, 64), 64>>>(gxq, gq, d, 0, d_qn);
+        const long long nlist = (long long)gq * p.splits * LR;
+        knn_fill_kernel<<<(int)std::min<long long>(cdiv(nlist, 256), prop.multiProcessorCount * 8), 256>>>(d_lists, nlist);
+        HIPCHK(hipGetLastError());
+        for (int64_t i = 0; i < p.pieces; ++i) {
+            int64_t r0, r1;
+            lmi_knn_plan::piece_range(p, i, &r0, &r1);
+            const long long len = r1 - r0;
+            const float* px = xb + (size_t)r0 * d;
+            if (!on_device) {
+                const size_t bytes = (size_t)len * d * 4;
+                for (size_t o = 0; o < bytes; o += up)
+                    HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(d_xb) + o, reinterpret_cast<const char*>(px) + o, std::min(up, bytes - o),
+                                          hipMemcpyHostToDevice, nullptr));
+                px = d_xb;
+            }
+            if (l2) knn_norm_kernel<<<cdiv(len, 64), 64>>>(px, len, d, 1, d_xnh);
+            const dim3 grid(cdiv(len, KNN_ROWS), cdiv(nct, ct));
+            if (vec_xb) CHK(knn_score_launch<true>(ct, grid, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));
+            else CHK(knn_score_launch<false>(ct, grid, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));
+            knn_select_kernel<<<dim3(gq, p.splits), 64, lds>>>(d_S, p.pitch, len, (unsigned)r0, k, LR, d_lists);
+            HIPCHK(hipGetLastError());
+        }
+        float* oD = on_device ? D + (size_t)q0 * k : d_D;
+        long long* oI = on_device ? reinterpret_cast<long long*>(I) + (size_t)q0 * k : d_I;
+        knn_merge_kernel<<<gq, 64, lds>>>(d_lists, p.splits, LR, k, l2 ? d_qn : nullptr, oD, oI);
+        HIPCHK(hipGetLastError());
+        if (!on_device) {
+            HIPCHK(hipMemcpy(D + (size_t)q0 * k, d_D, (size_t)gq * k * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(I + (size_t)q0 * k, d_I, (size_t)gq * k * 8, hipMemcpyDeviceToHost));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return 0;
+}

@@ -3,6 +3,7 @@
 Cosine distance by brute force: rows are L2-normalised on the host, then ONE `lmi_knn_ip` call (the C ABI's
 `faiss.knn(..., METRIC_INNER_PRODUCT)` replacement: fp16-MFMA prefilter + exact binary32 re-rank over a
 single-bucket index in HBM) yields the k largest inner products per query; distance = 1 - similarity.
+`k` above 10, up to `MAX_K`, goes through `lmi_knn` instead (exact binary32 brute force, no index).
 Same call surface as the reference class: `search(queries, data, k) -> (dists, ids 1-based, seconds)`,
 `build(data) -> seconds`.  There is no CPU path here; `li.utils.pairwise_cosine` remains for callers that
 want the sklearn form."""
@@ -25,7 +26,7 @@ def _unit(x) -> np.ndarray:
 
 
 class Baseline(Logger):
-    MAX_K = _capi.K_PER_BUCKET  # lmi_knn_ip returns at most 10 neighbours per query (LearnedIndex.py:334)
+    MAX_K = _capi.KNN_MAX_K  # k <= 10: lmi_knn_ip (LearnedIndex.py:334), as before; above it the exact k-NN call lmi_knn
 
     def build(self, data) -> float:
         """Nothing to build: the scan is exhaustive."""
@@ -36,7 +37,10 @@ class Baseline(Logger):
         if not 1 <= k <= self.MAX_K:
             raise ValueError(f"Baseline.search: k must be in [1, {self.MAX_K}]")
         t0 = time.time()
-        sims, rows = _capi.knn_ip(_unit(queries), _unit(data), k=k, device=device)
+        if k <= _capi.K_PER_BUCKET:
+            sims, rows = _capi.knn_ip(_unit(queries), _unit(data), k=k, device=device)
+        else:
+            sims, rows = _capi.knn(_unit(queries), _unit(data), k=k, metric="ip", device=device)
         found = rows >= 0  # fewer than k objects: faiss-style padding (-1)
         dists = np.where(found, np.float32(1) - sims, np.float32(np.inf))
         return dists, np.where(found, rows + 1, 0), time.time() - t0

@@ -239,7 +239,8 @@ def bucket_budgets(percentages: Sequence[int], n_buckets_in_index: int) -> List[
 def recall_against_bruteforce(queries: np.ndarray, objects: pd.DataFrame, knns: np.ndarray, k: int, sample: int = 1000):
     """recall@k of the first `sample` queries (notebook cell 31: |found & true| / (k * nq)); ground truth from the
     GPU brute-force Baseline over the scan vectors."""
-    m, kk = min(sample, knns.shape[0]), min(k, 10)
+    # k <= 10: as before; 10 < k <= Baseline.MAX_K (LMI_KNN_MAX_K): the truth has k neighbours too (Baseline goes through lmi_knn), so this is recall@k
+    m, kk = min(sample, knns.shape[0]), (k if k <= Baseline.MAX_K else 10)
     _, truth, _ = Baseline().search(queries[:m].astype(np.float32, copy=False), objects.to_numpy(dtype=np.float32), k=kk)
     labels = objects.index.to_numpy()
     truth = labels[truth - 1]  # Baseline ids are 1-based positions

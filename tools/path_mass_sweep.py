@@ -188,6 +188,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--recall-queries", type=int, default=1000)
+    ap.add_argument("--recall-k", type=int, default=10, help="k of the searches and of recall@k, 1..64; other than 10: the truth comes from lmi_knn")
     ap.add_argument("--masses", type=float, nargs="+", default=[0.0, 0.8, 0.9, 0.99, 0.999], help="0 = off")
     ap.add_argument("--seed", type=int, default=2023)
     ap.add_argument("--walk-cost", action="store_true", help="only: LMI_T_INFERENCE of the walk, mass forms against the plain ones (see walk_cost)")
@@ -202,26 +203,29 @@ def main():
     eng, X, Q, root, nodes, child_bucket = build_index(a)
     sizes = eng.bucket_sizes()
     rq = min(a.recall_queries, a.nq)
-    _, truth = _capi.knn_ip(Q[:rq], X, 10)
+    rk = a.recall_k
+    if not 1 <= rk <= 64:
+        sys.exit("--recall-k must be in 1..64 (LMI_MAX_K)")
+    _, truth = _capi.knn_ip(Q[:rq], X, 10) if rk == 10 else _capi.knn(Q[:rq], X, rk, "ip")
     truth = truth + 1   # ids are 1-based row numbers
     P = probabilities(root, nodes, Q)
     print(f"# {a.n} x {a.d}, tree {a.cats}: {sizes.size} buckets with objects (sizes min/median/max {sizes.min()}/{int(np.median(sizes))}/{sizes.max()}), "
-          f"spread {a.spread}, {a.nq} queries, n_buckets {a.nb}, k 10; recall@10 over {rq} queries; {a.steps} timed batches per row; setup {time.time() - t0:.0f} s")
-    print("# mass | recall@10 | visited buckets per query | scan pairs | walk steps with waiting queries (node models per query) | "
+          f"spread {a.spread}, {a.nq} queries, n_buckets {a.nb}, k {rk}; recall@{rk} over {rq} queries; {a.steps} timed batches per row; setup {time.time() - t0:.0f} s")
+    print(f"# mass | recall@{rk} | visited buckets per query | scan pairs | walk steps with waiting queries (node models per query) | "
           "ms per batch: total, inference, pass 2, rescore | held MHz")
     for mass in a.masses:
         eng.set_path_mass(mass)
         for _ in range(3):
-            eng.search_tree(Q, Q, a.nb, 10)
+            eng.search_tree(Q, Q, a.nb, rk)
         eng.timings_reset()
         for _ in range(a.steps):
-            _, ids, slab, ent = eng.search_tree(Q, Q, a.nb, 10, want_order=True)
+            _, ids, slab, ent = eng.search_tree(Q, Q, a.nb, rk, want_order=True)
         ms, calls = eng.timings_mean()
         pairs = eng.scan_stats()[1]
         want, evals = walk_numpy(P, child_bucket, a.nb, mass)
         if not np.array_equal(want, ent):
             sys.exit(f"mass {mass}: the device's order differs from the restatement in {(want != ent).any(axis=1).sum()} of {a.nq} queries")
-        recall = float(np.mean([len(set(t) & set(f)) / 10.0 for t, f in zip(truth.tolist(), ids[:rq].tolist())]))
+        recall = float(np.mean([len(set(t) & set(f)) / float(rk) for t, f in zip(truth.tolist(), ids[:rq].tolist())]))
         print(f"{'off' if mass == 0 else mass:>6} | {recall:.4f} | {(ent >= 0).sum(axis=1).mean():.3f} | {pairs} | {int(evals.max())} ({evals.mean():.2f}) | "
               f"{ms[_capi.T_TOTAL]:.3f}, {ms[_capi.T_INFERENCE]:.3f}, {ms[_capi.T_PF_EMIT]:.3f}, {ms[_capi.T_RESCORE]:.3f} | "
               f"{ms[_capi.T_CLOCK_MHZ]:.0f}   ({calls} calls)", flush=True)

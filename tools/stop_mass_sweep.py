@@ -88,6 +88,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--recall-queries", type=int, default=1000)
+    ap.add_argument("--recall-k", type=int, default=10, help="k of the searches and of recall@k, 1..64; other than 10: the truth comes from lmi_knn")
     ap.add_argument("--masses", type=float, nargs="+", default=[0.0, 0.9, 0.99, 0.999], help="0 = off")
     ap.add_argument("--seed", type=int, default=2023)
     ap.add_argument("--inference-cost", action="store_true", help="only: LMI_T_INFERENCE with the stop on / off (see inference_cost)")
@@ -108,21 +109,24 @@ def main():
     eng.set_buckets(X, labels, a.leaves)
     sizes = eng.bucket_sizes()
     rq = min(a.recall_queries, a.nq)
-    _, truth = _capi.knn_ip(Q[:rq], X, 10)
+    rk = a.recall_k
+    if not 1 <= rk <= 64:
+        sys.exit("--recall-k must be in 1..64 (LMI_MAX_K)")
+    _, truth = _capi.knn_ip(Q[:rq], X, 10) if rk == 10 else _capi.knn(Q[:rq], X, rk, "ip")
     truth = truth + 1   # ids are 1-based row numbers
     print(f"# {a.n} x {a.d}, {a.leaves} buckets (sizes min/median/max {sizes.min()}/{int(np.median(sizes))}/{sizes.max()}), spread {a.spread}, "
-          f"{a.nq} queries, n_buckets {a.nb}, k 10; recall@10 over {rq} queries; {a.steps} timed batches per row; setup {time.time() - t0:.0f} s")
-    print("# mass | recall@10 | visited buckets per query | scan pairs | ms per batch: total, inference, pass 2, rescore | held MHz")
+          f"{a.nq} queries, n_buckets {a.nb}, k {rk}; recall@{rk} over {rq} queries; {a.steps} timed batches per row; setup {time.time() - t0:.0f} s")
+    print(f"# mass | recall@{rk} | visited buckets per query | scan pairs | ms per batch: total, inference, pass 2, rescore | held MHz")
     for mass in a.masses:
         eng.set_stop_mass(mass)
         for _ in range(3):
-            eng.search(Q, Q, a.nb, 10)
+            eng.search(Q, Q, a.nb, rk)
         eng.timings_reset()
         for _ in range(a.steps):
-            _, ids, bo = eng.search(Q, Q, a.nb, 10)
+            _, ids, bo = eng.search(Q, Q, a.nb, rk)
         ms, calls = eng.timings_mean()
         pairs = eng.scan_stats()[1]
-        recall = float(np.mean([len(set(t) & set(f)) / 10.0 for t, f in zip(truth.tolist(), ids[:rq].tolist())]))
+        recall = float(np.mean([len(set(t) & set(f)) / float(rk) for t, f in zip(truth.tolist(), ids[:rq].tolist())]))
         print(f"{'off' if mass == 0 else mass:>6} | {recall:.4f} | {(bo >= 0).sum(axis=1).mean():.3f} | {pairs} | "
               f"{ms[_capi.T_TOTAL]:.3f}, {ms[_capi.T_INFERENCE]:.3f}, {ms[_capi.T_PF_EMIT]:.3f}, {ms[_capi.T_RESCORE]:.3f} | "
               f"{ms[_capi.T_CLOCK_MHZ]:.0f}   ({calls} calls)", flush=True)
