@@ -204,6 +204,28 @@ def _queries(queries_nav, queries_search):
     return qn, (qn if same else _np(queries_search, dt)), f16
 
 
+def _array_arg(who: str, name: str, a, dtype: Optional[str] = None, rank: Optional[str] = None, kind: bool = True) -> bool:
+    """Whether `a` is a numpy array.  Checks, each only if asked for and in this order: `kind`: numpy or a torch tensor on the device;
+    `dtype`; `rank` "2d": two-dimensional, "nd": [n,d] with n, d >= 1."""
+    is_np = isinstance(a, np.ndarray)
+    if kind and not is_np and not (hasattr(a, "data_ptr") and hasattr(a, "is_cuda")):
+        raise ValueError(f"{who}: {name} must be a numpy array or a torch tensor on the device")
+    if dtype is not None and str(a.dtype).replace("torch.", "") != dtype:
+        raise ValueError(f"{who}: {name} must be {dtype}, not {a.dtype}")
+    if rank is not None and (a.ndim != 2 or (rank == "nd" and min(a.shape) < 1)):
+        want = "[n,d] with n, d >= 1" if rank == "nd" else "two-dimensional"
+        raise ValueError(f"{who}: {name} must be {want}, not {tuple(a.shape)}")
+    return is_np
+
+
+def _sync_device(t) -> int:
+    """The tensor's device index, after a synchronise: these calls run on the NULL stream; whatever produced `t` may not have."""
+    import torch
+
+    torch.cuda.synchronize(t.device)
+    return t.device.index if t.device.index is not None else torch.cuda.current_device()
+
+
 def f16_admissible(x):
     """(ok, reason): whether `storage="f16"` (LMI_STORAGE_F16) would accept the scan vectors `x` -- the library's rule
     (include/lmi_hip.h, decided there on the device) in numpy, for callers who want to know before they upload.  Every value
@@ -734,14 +756,7 @@ def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
     is uploaded in pieces and never resident as a whole -- or contiguous float32 torch tensors on the device, both of one kind; D and
     I then come back as tensors on that device and the inputs are only read.  Argument errors raise ValueError before the library is
     loaded."""
-    is_np = isinstance(xq, np.ndarray), isinstance(xb, np.ndarray)
-    for name, a, np_ in (("xq", xq, is_np[0]), ("xb", xb, is_np[1])):
-        if not np_ and not (hasattr(a, "data_ptr") and hasattr(a, "is_cuda")):
-            raise ValueError(f"knn: {name} must be a numpy array or a torch tensor on the device")
-        if str(a.dtype).replace("torch.", "") != "float32":
-            raise ValueError(f"knn: {name} must be float32, not {a.dtype}")
-        if a.ndim != 2:
-            raise ValueError(f"knn: {name} must be two-dimensional, not {tuple(a.shape)}")
+    is_np = _array_arg("knn", "xq", xq, "float32", "2d"), _array_arg("knn", "xb", xb, "float32", "2d")
     if is_np[0] != is_np[1]:
         raise ValueError("knn: xq and xb must both be numpy arrays or both be torch tensors on the device")
     if metric not in KNN_METRICS:
@@ -765,9 +780,7 @@ def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
 
     D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
     I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
-    torch.cuda.synchronize(xq.device)   # the call runs on the NULL stream; whatever produced the inputs may not have
-    dev = xq.device.index if xq.device.index is not None else torch.cuda.current_device()
-    _check(lib().lmi_knn(int(dev), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
+    _check(lib().lmi_knn(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
     return D, I
 
 
@@ -791,13 +804,7 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
     as tensors on that device and `x` is only read.  `init`: f32 [k,d] initial centroids; None: the rows
     `np.random.RandomState(seed).choice(n, k, replace=False)` of `x`.  `changed[it]`: rows whose label moved in pass `it`
     (zeros behind a fixed point).  Argument errors raise ValueError before the library is loaded."""
-    is_np = isinstance(x, np.ndarray)
-    if not is_np and not (hasattr(x, "data_ptr") and hasattr(x, "is_cuda")):
-        raise ValueError("kmeans: x must be a numpy array or a torch tensor on the device")
-    if str(x.dtype).replace("torch.", "") != "float32":
-        raise ValueError(f"kmeans: x must be float32, not {x.dtype}")
-    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"kmeans: x must be [n,d] with n, d >= 1, not {tuple(x.shape)}")
+    is_np = _array_arg("kmeans", "x", x, "float32", "nd")
     n, d = int(x.shape[0]), int(x.shape[1])
     k, niter = int(k), int(niter)
     if k < 1 or k > n:
@@ -826,9 +833,7 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
     else:
         cent = torch.from_numpy(np.array(init, dtype=np.float32, order="C")).to(x.device)
     labels = torch.empty(n, dtype=torch.int32, device=x.device)
-    torch.cuda.synchronize(x.device)   # the call runs on the NULL stream; whatever produced x may not have
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _check(lib().lmi_kmeans(int(dev), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
+    _check(lib().lmi_kmeans(_sync_device(x), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
     return cent, labels, counts, changed
 
 
@@ -840,17 +845,12 @@ def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0)
     Adam steps taken so far -- or None: zeros.  `losses` f32 [n_steps].  The same input gives the same parameters and moments bit for bit
     (include/lmi_hip.h states the arithmetic; tests/train_ref.py restates it).  Argument errors raise ValueError before the library is
     loaded."""
-    is_np = isinstance(x, np.ndarray)
-    if not is_np and not (hasattr(x, "data_ptr") and hasattr(x, "is_cuda")):
-        raise ValueError("train: x must be a numpy array or a torch tensor on the device")
+    is_np = _array_arg("train", "x", x)
     if isinstance(labels, np.ndarray) != is_np:
         raise ValueError("train: x and labels must both be numpy arrays or both be tensors on the device")
-    if str(x.dtype).replace("torch.", "") != "float32":
-        raise ValueError(f"train: x must be float32, not {x.dtype}")
-    if str(labels.dtype).replace("torch.", "") != "int32":
-        raise ValueError(f"train: labels must be int32, not {labels.dtype}")
-    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"train: x must be [n,d] with n, d >= 1, not {tuple(x.shape)}")
+    _array_arg("train", "x", x, "float32")
+    _array_arg("train", "labels", labels, "int32", kind=False)
+    _array_arg("train", "x", x, rank="nd")
     n, d = int(x.shape[0]), int(x.shape[1])
     if tuple(labels.shape) != (n,):
         raise ValueError(f"train: labels must be [{n}], not {tuple(labels.shape)}")
@@ -883,11 +883,7 @@ def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0)
     else:
         if not (x.is_cuda and x.is_contiguous() and labels.is_cuda and labels.is_contiguous()):
             raise ValueError("train: torch x and labels must be contiguous tensors on the device")
-        import torch
-
-        torch.cuda.synchronize(x.device)   # the call runs on the NULL stream; whatever produced x may not have
-        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        on_device = 1
+        device, on_device = _sync_device(x), 1
     losses = np.zeros(n_steps, dtype=np.float32)
     t = ctypes.c_int64(t0)
     dims_c = (ctypes.c_int32 * (nl + 1))(*dims)

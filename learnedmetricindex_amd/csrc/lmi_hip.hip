@@ -3,6 +3,7 @@
 // workspaces; enqueues the kernels of lmi_kernels.h .. lmi_train.h on one HIP stream.  This file: handle creation,
 // destruction, clone views and the setters; everything else in the lmi_host*.h headers.
 #include "lmi_host.h"         // the kernel headers, the handle (lmi_handle.h: error macros, DevBuf), per-call helpers
+#include "lmi_host_call.h"    // open_device; the scratch and the uploads of the calls that take no handle
 #include "lmi_host_model.h"   // model packing, MLP forward, tree navigation
 #include "lmi_host_build.h"   // lmi_buckets_begin / add_rows / end, bucket read
 #include "lmi_host_mutate.h"  // lmi_buckets_insert / lmi_buckets_delete
@@ -32,14 +33,8 @@ extern "C" LMI_API const char* lmi_last_error(void) { return g_err.c_str(); }
 
 extern "C" LMI_API int lmi_create(int device, lmi_index** out) {
     if (!out) return fail("lmi_create: out is NULL");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("lmi_create: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail("lmi_create: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    CHK(open_device("lmi_create", device, &prop));
     lmi_index* h = new lmi_index();
     h->device = device;
     h->num_cus = prop.multiProcessorCount;

@@ -2,27 +2,11 @@
 // (assign, count `changed`, sort rows by label, integer sums, divide) on the NULL stream of the device.
 #pragma once
 #include "lmi_host.h"
+#include "lmi_host_call.h"
 #include "lmi_kmeans.h"
 #include <cmath>
 
 namespace {
-
-// the device allocations of one lmi_kmeans call: freed when the call returns, whichever way
-struct KmScratch {
-    std::vector<void*> owned;
-    ~KmScratch() { for (void* p : owned) (void)hipFree(p); }
-    template <class T>
-    int alloc(T** out, size_t bytes, const char* what) {
-        void* p = nullptr;
-        if (hipError_t e = hipMalloc(&p, bytes ? bytes : 4); e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail("lmi_kmeans: a device allocation of %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
-        }
-        owned.push_back(p);
-        *out = static_cast<T*>(p);
-        return 0;
-    }
-};
 
 template <bool VEC>
 int km_assign_launch(int ct, int grid, const float* x, long long n, int d, const float4* Cf, int KG, int nct, int k, int* labels,
@@ -45,18 +29,12 @@ extern "C" LMI_API int lmi_kmeans(int device, const float* x, int64_t n, int d, 
     if (k < 1 || k > 16384) return fail("lmi_kmeans: k %d outside [1,16384]", k);
     if (k > n) return fail("lmi_kmeans: k %d exceeds n %lld", k, (long long)n);
     if (niter < 0 || niter > 1000) return fail("lmi_kmeans: niter %d outside [0,1000]", niter);
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("lmi_kmeans: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail("lmi_kmeans: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    CHK(open_device("lmi_kmeans", device, &prop));
 
     const int nct = cdiv(k, 32), KG = (int)(rup(d + 1, 32) / 8);
     const size_t xbytes = (size_t)n * d * 4, cbytes = (size_t)k * d * 4;
-    KmScratch mem;
+    CallScratch mem("lmi_kmeans");
     float *d_x = nullptr, *d_c = nullptr, *d_cnh = nullptr;
     float4* d_cf = nullptr;
     int *d_lab = nullptr, *d_cnt = nullptr, *d_cursor = nullptr, *d_perm = nullptr, *d_slab = nullptr;
@@ -70,10 +48,7 @@ extern "C" LMI_API int lmi_kmeans(int device, const float* x, int64_t n, int d, 
         CHK(mem.alloc(&d_x, xbytes, "x"));
         CHK(mem.alloc(&d_c, cbytes, "centroids"));
         CHK(mem.alloc(&d_lab, (size_t)n * 4, "labels"));
-        const size_t piece = (size_t)64 << 20;   // the rows go up once, in pieces, and stay for every pass
-        for (size_t o = 0; o < xbytes; o += piece)
-            HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(d_x) + o, reinterpret_cast<const char*>(x) + o, std::min(piece, xbytes - o),
-                                  hipMemcpyHostToDevice, nullptr));
+        CHK(upload_pieces(d_x, x, xbytes));   // the rows go up once and stay for every pass
         HIPCHK(hipMemcpyAsync(d_c, centroids, cbytes, hipMemcpyHostToDevice, nullptr));
     }
     CHK(mem.alloc(&d_cf, (size_t)nct * KG * 1024, "centroid fragments"));
@@ -92,8 +67,8 @@ extern "C" LMI_API int lmi_kmeans(int device, const float* x, int64_t n, int d, 
     unsigned h_max[2] = {0, 0};
     HIPCHK(hipMemsetAsync(d_max, 0, 8, nullptr));
     const int gs = (int)std::min<long long>(prop.multiProcessorCount * 8, cdiv((long long)n * d, 256));
-    km_absmax_kernel<<<gs, 256>>>(d_x, (long long)n * d, d_max);
-    km_absmax_kernel<<<std::min(gs, cdiv((long long)k * d, 256)), 256>>>(d_c, (long long)k * d, d_max + 1);
+    dense_absmax_kernel<<<gs, 256>>>(d_x, (long long)n * d, d_max);
+    dense_absmax_kernel<<<std::min(gs, cdiv((long long)k * d, 256)), 256>>>(d_c, (long long)k * d, d_max + 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(h_max, d_max, 8, hipMemcpyDeviceToHost));
     if (h_max[0] >= 0x7f800000u) return fail("lmi_kmeans: x holds a value that is not finite (inf or NaN)");
@@ -120,8 +95,8 @@ extern "C" LMI_API int lmi_kmeans(int device, const float* x, int64_t n, int d, 
         return 0;
     };
     for (int it = 0; it <= niter; ++it) {
-        km_norm_kernel<<<cdiv(k, 64), 64>>>(d_c, k, d, d_cnh);
-        km_pack_kernel<<<cdiv((long long)nct * 32 * KG, 256), 256>>>(d_c, d_cnh, k, d, nct, KG, d_cf);
+        dense_norm_kernel<<<cdiv(k, 64), 64>>>(d_c, k, d, 1, d_cnh);
+        dense_pack_kernel<<<cdiv((long long)nct * 32 * KG, 256), 256>>>(d_c, d_cnh, 0.0f, k, d, nct, KG, d_cf);
         HIPCHK(hipGetLastError());
         if (vec) CHK(km_assign_launch<true>(ct, grid, d_x, n, d, d_cf, KG, nct, k, d_lab, d_changed + it));
         else CHK(km_assign_launch<false>(ct, grid, d_x, n, d, d_cf, KG, nct, k, d_lab, d_changed + it));

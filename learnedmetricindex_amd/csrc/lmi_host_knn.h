@@ -3,6 +3,7 @@
 // the split lists per group writes the group's rows.  lmi_knn_set_geometry, lmi_debug_knn_plan.
 #pragma once
 #include "lmi_host.h"
+#include "lmi_host_call.h"
 #include "lmi_knn.h"
 #include "lmi_knn_plan.h"
 
@@ -12,25 +13,6 @@ namespace {
 
 thread_local lmi_knn_plan::Forced g_knn_forced;
 thread_local int64_t g_knn_last[LMI_KNN_PLAN_COUNT] = {};
-
-// the device allocations of one lmi_knn call: freed when the call returns, whichever way
-struct KnnScratch {
-    std::vector<void*> owned;
-    int64_t total = 0;
-    ~KnnScratch() { for (void* p : owned) (void)hipFree(p); }
-    template <class T>
-    int alloc(T** out, int64_t bytes, const char* what) {
-        void* p = nullptr;
-        if (hipError_t e = hipMalloc(&p, bytes ? (size_t)bytes : 4); e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail("lmi_knn: a device allocation of %lld bytes (%s) failed: %s", (long long)bytes, what, hipGetErrorString(e));
-        }
-        owned.push_back(p);
-        total += bytes;
-        *out = static_cast<T*>(p);
-        return 0;
-    }
-};
 
 template <bool VEC>
 int knn_score_launch(int ct, dim3 grid, const float* x, long long n, int d, const float* xnh, const float4* Qf, int KG, int nct, int nq,
@@ -71,21 +53,15 @@ extern "C" LMI_API int lmi_knn(int device, const float* xq, int64_t nq, const fl
     if (nq > 0 && (!xq || !D || !I)) return fail("lmi_knn: xq, D and I must not be NULL");
     if (nq > 0 && nb > 0 && !xb) return fail("lmi_knn: xb must not be NULL");
     if (nq == 0) return 0;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("lmi_knn: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail("lmi_knn: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    CHK(open_device("lmi_knn", device, &prop));
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
 
     const bool l2 = metric == LMI_METRIC_L2;
     const lmi_knn_plan::Plan p = lmi_knn_plan::make_plan(nq, nb, d, k, l2, on_device != 0, (int64_t)free_b, prop.multiProcessorCount, g_knn_forced);
     const int LR = p.list_rows, KG = p.kg;
-    KnnScratch mem;
+    CallScratch mem("lmi_knn");
     float *d_S = nullptr, *d_qn = nullptr, *d_xnh = nullptr, *d_xq = nullptr, *d_xb = nullptr, *d_D = nullptr;
     float4* d_qf = nullptr;
     knn_entry* d_lists = nullptr;
@@ -108,27 +84,23 @@ extern "C" LMI_API int lmi_knn(int device, const float* xq, int64_t nq, const fl
     g_knn_last[LMI_KNN_PLAN_SPLITS] = p.splits;
     g_knn_last[LMI_KNN_PLAN_QUERY_GROUPS] = p.query_groups;
     g_knn_last[LMI_KNN_PLAN_QUERY_ROWS] = p.query_rows;
-    g_knn_last[LMI_KNN_PLAN_VEC_XQ] = 0;   // knn_pack_kernel loads the queries element by element
+    g_knn_last[LMI_KNN_PLAN_VEC_XQ] = 0;   // dense_pack_kernel loads the queries element by element
     g_knn_last[LMI_KNN_PLAN_VEC_XB] = vec_xb;
     g_knn_last[LMI_KNN_PLAN_WORKSPACE_BYTES] = mem.total;
     g_knn_last[LMI_KNN_PLAN_LIST_ROWS] = LR;
 
     const size_t lds = (size_t)2 * LR * sizeof(knn_entry);
-    const size_t up = (size_t)64 << 20;   // host memory goes up in pieces of this many bytes
     for (int64_t g = 0; g < p.query_groups; ++g) {
         int64_t q0, q1;
         lmi_knn_plan::group_range(p, g, &q0, &q1);
         const int gq = (int)(q1 - q0), nct = cdiv(gq, 32), ct = nct >= 3 ? 4 : nct;
         const float* gxq = xq + (size_t)q0 * d;
         if (!on_device) {
-            const size_t bytes = (size_t)gq * d * 4;
-            for (size_t o = 0; o < bytes; o += up)
-                HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(d_xq) + o, reinterpret_cast<const char*>(gxq) + o, std::min(up, bytes - o),
-                                      hipMemcpyHostToDevice, nullptr));
+            CHK(upload_pieces(d_xq, gxq, (size_t)gq * d * 4));
             gxq = d_xq;
         }
-        knn_pack_kernel<<<cdiv((long long)nct * 32 * KG, 256), 256>>>(gxq, gq, d, nct, KG, l2 ? 1.0f : 0.0f, d_qf);
-        if (l2) knn_norm_kernel<<<cdiv(gq, 64), 64>>>(gxq, gq, d, 0, d_qn);
+        dense_pack_kernel<<<cdiv((long long)nct * 32 * KG, 256), 256>>>(gxq, nullptr, l2 ? 1.0f : 0.0f, gq, d, nct, KG, d_qf);
+        if (l2) dense_norm_kernel<<<cdiv(gq, 64), 64>>>(gxq, gq, d, 0, d_qn);
         const long long nlist = (long long)gq * p.splits * LR;
         knn_fill_kernel<<<(int)std::min<long long>(cdiv(nlist, 256), prop.multiProcessorCount * 8), 256>>>(d_lists, nlist);
         HIPCHK(hipGetLastError());
@@ -138,13 +110,10 @@ extern "C" LMI_API int lmi_knn(int device, const float* xq, int64_t nq, const fl
             const long long len = r1 - r0;
             const float* px = xb + (size_t)r0 * d;
             if (!on_device) {
-                const size_t bytes = (size_t)len * d * 4;
-                for (size_t o = 0; o < bytes; o += up)
-                    HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(d_xb) + o, reinterpret_cast<const char*>(px) + o, std::min(up, bytes - o),
-                                          hipMemcpyHostToDevice, nullptr));
+                CHK(upload_pieces(d_xb, px, (size_t)len * d * 4));
                 px = d_xb;
             }
-            if (l2) knn_norm_kernel<<<cdiv(len, 64), 64>>>(px, len, d, 1, d_xnh);
+            if (l2) dense_norm_kernel<<<cdiv(len, 64), 64>>>(px, len, d, 1, d_xnh);
             const dim3 grid(cdiv(len, KNN_ROWS), cdiv(nct, ct));
             if (vec_xb) CHK(knn_score_launch<true>(ct, grid, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));
             else CHK(knn_score_launch<false>(ct, grid, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));

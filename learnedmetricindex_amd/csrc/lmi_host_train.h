@@ -3,28 +3,11 @@
 // the NULL stream of the device.
 #pragma once
 #include "lmi_host.h"
-#include "lmi_kmeans.h"   // km_absmax_kernel
+#include "lmi_host_call.h"
 #include "lmi_train.h"
 #include <cmath>
 
 namespace {
-
-// the device allocations of one lmi_train call: freed when the call returns, whichever way
-struct TrScratch {
-    std::vector<void*> owned;
-    ~TrScratch() { for (void* p : owned) (void)hipFree(p); }
-    template <class T>
-    int alloc(T** out, size_t bytes, const char* what) {
-        void* p = nullptr;
-        if (hipError_t e = hipMalloc(&p, bytes ? bytes : 4); e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail("lmi_train: a device allocation of %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
-        }
-        owned.push_back(p);
-        *out = static_cast<T*>(p);
-        return 0;
-    }
-};
 
 template <int MODE>
 int tr_launch(const TrGemm& P) {
@@ -65,17 +48,11 @@ extern "C" LMI_API int lmi_train(int device, const float* x, int64_t n, const in
             const int lab = labels[batch_rows[j]];
             if (lab < 0 || lab >= classes) return fail("lmi_train: the label %d of row %lld is outside [0,%d)", lab, (long long)batch_rows[j], classes);
         }
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("lmi_train: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail("lmi_train: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    CHK(open_device("lmi_train", device, &prop));
     if (n_steps == 0) return 0;   // nothing to train on: the parameters, the moments and *t stay as they are
 
-    TrScratch mem;
+    CallScratch mem("lmi_train");
     float* d_xb = nullptr;
     int* d_yb = nullptr;
     CHK(mem.alloc(&d_xb, (size_t)nb * d * 4, "the named rows"));
@@ -133,11 +110,11 @@ extern "C" LMI_API int lmi_train(int device, const float* x, int64_t n, const in
 
     // the non-finite check of the named rows and of the initial weights, before the first step
     unsigned h_max[3] = {0, 0, 0};
-    km_absmax_kernel<<<(int)std::min<long long>(gs, cdiv(nb * d, 256)), 256>>>(d_xb, nb * d, d_max);
+    dense_absmax_kernel<<<(int)std::min<long long>(gs, cdiv(nb * d, 256)), 256>>>(d_xb, nb * d, d_max);
     for (int i = 0; i < n_layers; ++i) {
         const long long wn = (long long)dims[i + 1] * dims[i];
-        km_absmax_kernel<<<(int)std::min<long long>(gs, cdiv(wn, 256)), 256>>>(d_W[i], wn, d_max + 1);
-        km_absmax_kernel<<<cdiv(dims[i + 1], 256), 256>>>(d_b[i], dims[i + 1], d_max + 1);
+        dense_absmax_kernel<<<(int)std::min<long long>(gs, cdiv(wn, 256)), 256>>>(d_W[i], wn, d_max + 1);
+        dense_absmax_kernel<<<cdiv(dims[i + 1], 256), 256>>>(d_b[i], dims[i + 1], d_max + 1);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(h_max, d_max, 12, hipMemcpyDeviceToHost));

@@ -2,91 +2,21 @@
 // (include/lmi_hip.h states the arithmetic).
 //
 // Assignment (km_assign_kernel): S^T = C . X^T by v_mfma_f32_32x32x2_f32, A = centroids in fragment order (lmi_kernels.h) with the
-// extra column -|c|^2/2 at k = d, B = rows of x straight from the caller's row-major array with a 1 at k = d and zeros behind it.
+// extra column -|c|^2/2 at k = d (dense_norm_kernel, dense_pack_kernel: lmi_dense.h), B = rows of x straight from the caller's
+// row-major array with a 1 at k = d and zeros behind it (dense_load_b).
 // In the 32x32 accumulator a lane owns ONE row of x (lane & 31) and 16 centroids, so the running (best key, label) of a row is a
 // register pair; the k order inside every accumulator is 0, 1, 2, ..: the key is the canonical chain of oracle.knn_l2.
 // Update: rows are counting-sorted by label (km_hist_kernel, km_scan_kernel, km_scatter_kernel), blocks over (256 sorted rows x 256
 // dimensions) sum q(x) = rint(x * 2^(36-e)) in int64 registers and add a run's sum to S[cluster][dim] with one 64-bit atomicAdd
 // (km_accum_kernel); integer addition is associative, so S is the same for any order.  km_finish_kernel divides.
 #pragma once
-#include "lmi_kernels.h"
+#include "lmi_dense.h"
 
 namespace lmi {
 
 constexpr int KM_XB = 2;          // 32-row blocks of x per wave
 constexpr int KM_ROWS = 4 * KM_XB * 32;   // rows of x per workgroup (4 waves)
 constexpr int KM_ACC_ROWS = 256;  // sorted rows per km_accum_kernel block
-
-// max |v| as the bit pattern of its absolute value (monotone for binary32; >= 0x7f800000: inf or NaN)
-__global__ void km_absmax_kernel(const float* __restrict__ v, long long total, unsigned* __restrict__ out) {
-    unsigned m = 0;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride)
-        m = max(m, __float_as_uint(v[i]) & 0x7fffffffu);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-
-// cnh[j] = -|c_j|^2 / 2, |c|^2 by the chain fmaf(c[t], c[t], acc) from 0, t ascending.  One thread per centroid.
-__global__ void km_norm_kernel(const float* __restrict__ c, int k, int d, float* __restrict__ cnh) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    const float* r = c + (size_t)j * d;
-    float acc = 0.0f;
-    for (int t = 0; t < d; ++t) acc = __builtin_fmaf(r[t], r[t], acc);
-    cnh[j] = -0.5f * acc;
-}
-
-// centroids [k][d] + cnh -> fragment order [nct][KG][64] float4 (rows >= k and columns > d: zeros).  One thread per (row, k-group).
-__global__ void km_pack_kernel(const float* __restrict__ c, const float* __restrict__ cnh, int k, int d, int nct, int KG,
-                               float4* __restrict__ dst) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)nct * 32 * KG) return;
-    const int g = (int)(idx % KG);
-    const int p = (int)(idx / KG);
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int t = g * 8 + j;
-        v[j] = p >= k ? 0.0f : t < d ? c[(size_t)p * d + t] : t == d ? cnh[p] : 0.0f;
-    }
-    float4* f = dst + ((size_t)(p >> 5) * KG + g) * 64 + (p & 31);
-    f[0] = make_float4(v[0], v[2], v[4], v[6]);
-    f[32] = make_float4(v[1], v[3], v[5], v[7]);
-}
-
-// The B operands of one 32-k chunk for the row `xr` points to: b[s] feeds MFMA step s of the chunk, i.e. this lane's
-// k = 32*ch + 2*s + h.  VEC (d % 4 == 0, x 16-byte aligned): the lane pair (c, 0), (c, 1) reads the row's 128 bytes of the chunk
-// with four 16-byte loads each (h = 0: k 0..15, h = 1: k 16..31) and trades the halves it does not feed with v_permlane32_swap;
-// otherwise sixteen 4-byte loads.  k == d is the 1 that meets the centroid's -|c|^2/2, k > d is zero.
-template <bool VEC>
-__device__ __forceinline__ void km_load_b(const float* __restrict__ xr, int d, int ch, int h, float (&b)[16]) {
-    if constexpr (VEC) {
-        float r[16];
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const int k0 = 32 * ch + 16 * h + 4 * f;
-            float4 v = *reinterpret_cast<const float4*>(xr + (k0 < d ? k0 : 0));
-            if (k0 >= d) v = make_float4(k0 == d ? 1.0f : 0.0f, 0.0f, 0.0f, 0.0f);
-            r[4 * f] = v.x; r[4 * f + 1] = v.y; r[4 * f + 2] = v.z; r[4 * f + 3] = v.w;
-        }
-        // lanes 32..63 of r[2i] (k = 16+2i) <-> lanes 0..31 of r[2i+1] (k = 2i+1): then r[2i] = (k 2i | 2i+1), r[2i+1] = (k 16+2i | 16+2i+1)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r[2 * i]), __float_as_uint(r[2 * i + 1]), false, false);
-            b[i] = __uint_as_float(sw[0]);
-            b[8 + i] = __uint_as_float(sw[1]);
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int t = 32 * ch + 2 * s + h;
-            const float v = xr[t < d ? t : 0];
-            b[s] = t < d ? v : t == d ? 1.0f : 0.0f;
-        }
-    }
-}
 
 // grid cdiv(n, KM_ROWS), block 256: wave w -> rows [(blockIdx.x * 4 + w) * 64, +64) as KM_XB column blocks; the centroid tiles
 // (32 centroids) are visited in ascending order, CT at a time; every tile set streams the rows again (k <= 32 * CT: once).
@@ -122,7 +52,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* __restrict_
         for (int t = 0; t < CT; ++t) ap[t] = Cf + (size_t)(ct0 + t < nct ? ct0 + t : nct - 1) * KG * 64 + lane;
         float bv[KM_XB][16];
 #pragma unroll
-        for (int b = 0; b < KM_XB; ++b) km_load_b<VEC>(xr[b], d, 0, h, bv[b]);
+        for (int b = 0; b < KM_XB; ++b) dense_load_b<VEC>(xr[b], d, 0, h, 1.0f, bv[b]);
         float4 a[CT];
 #pragma unroll
         for (int t = 0; t < CT; ++t) a[t] = ap[t][0];
@@ -131,7 +61,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float* __restrict_
             float bn[KM_XB][16];
             const int chn = ch + 1 < nch ? ch + 1 : ch;
 #pragma unroll
-            for (int b = 0; b < KM_XB; ++b) km_load_b<VEC>(xr[b], d, chn, h, bn[b]);
+            for (int b = 0; b < KM_XB; ++b) dense_load_b<VEC>(xr[b], d, chn, h, 1.0f, bn[b]);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int gn = ch * 4 + g + 1 < KG ? ch * 4 + g + 1 : ch * 4 + g;

@@ -1,16 +1,17 @@
 // lmi_knn.h -- device code of lmi_knn: exact brute-force k-NN for k up to 1024 whose result does not depend on the launch geometry
 // (include/lmi_hip.h states the arithmetic and the order).
 //
-// Scores (knn_score_kernel): S = Q . X^T by v_mfma_f32_32x32x2_f32, as km_assign_kernel does it -- A = a group's queries in fragment
-// order (knn_pack_kernel; L2: a 1 at link d), B = rows of the base straight from the row-major piece (L2: -|x|^2/2 at link d, from
-// knn_norm_kernel), the link order inside every accumulator 0, 1, 2, ..: a score is the canonical chain of oracle.knn_ip / knn_l2.
+// Scores (knn_score_kernel): S = Q . X^T by v_mfma_f32_32x32x2_f32, km_assign_kernel's loop (the two are kept equal: lmi_dense.h) --
+// A = a group's queries in fragment order (dense_pack_kernel; L2: a 1 at link d), B = rows of the base straight from the row-major
+// piece (dense_load_b; L2: -|x|^2/2 at link d, from dense_norm_kernel), the link order inside every accumulator 0, 1, 2, ..: a score is
+// the canonical chain of oracle.knn_ip / knn_l2.
 // A block writes its 256 rows x 32 CT queries to the slab S[query][row of the piece].
 // Selection (knn_select_kernel): one wave per (query, split) reads its stretch of the query's slab row, keeps what beats the k-th best
 // so far -- compared as the pair (score, row) -- in an LDS buffer by ballot compaction, and when the buffer is full sorts it and merges
 // it into the sorted list (bitonic, in LDS), which raises the threshold.  The list lives in global memory between launches: the next
 // piece continues it.  knn_merge_kernel merges a query's split lists and writes the caller's rows.
 #pragma once
-#include "lmi_kmeans.h"
+#include "lmi_dense.h"
 #include <cfloat>
 
 namespace lmi {
@@ -29,62 +30,6 @@ __device__ __forceinline__ unsigned knn_row(knn_entry e) { return (unsigned)e; }
 __device__ __forceinline__ bool knn_better(knn_entry a, knn_entry b) {
     const float sa = knn_score(a), sb = knn_score(b);
     return sa > sb || (sa == sb && knn_row(a) < knn_row(b));
-}
-
-// out[i] = the chain acc = fmaf(x[t], x[t], acc) from 0, t ascending (neg_half: times -0.5f).  One thread per row.
-__global__ void knn_norm_kernel(const float* __restrict__ x, long long n, int d, int neg_half, float* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* r = x + (size_t)i * d;
-    float acc = 0.0f;
-    for (int t = 0; t < d; ++t) acc = __builtin_fmaf(r[t], r[t], acc);
-    out[i] = neg_half ? -0.5f * acc : acc;
-}
-
-// queries [nq][d] -> fragment order [nct][KG][64] float4 (rows >= nq and links > d: zeros; link d: `tail`, the 1 of L2 or 0).
-// One thread per (row, group of 8 links); element loads: any 4-byte aligned xq.
-__global__ void knn_pack_kernel(const float* __restrict__ q, int nq, int d, int nct, int KG, float tail, float4* __restrict__ dst) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)nct * 32 * KG) return;
-    const int g = (int)(idx % KG);
-    const int p = (int)(idx / KG);
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int t = g * 8 + j;
-        v[j] = p >= nq ? 0.0f : t < d ? q[(size_t)p * d + t] : t == d ? tail : 0.0f;
-    }
-    float4* f = dst + ((size_t)(p >> 5) * KG + g) * 64 + (p & 31);
-    f[0] = make_float4(v[0], v[2], v[4], v[6]);
-    f[32] = make_float4(v[1], v[3], v[5], v[7]);
-}
-
-// km_load_b with the value at link d given per row (`tail`: -|x|^2/2 for L2, 0 for the inner product) instead of the constant 1.
-template <bool VEC>
-__device__ __forceinline__ void knn_load_b(const float* __restrict__ xr, int d, int ch, int h, float tail, float (&b)[16]) {
-    if constexpr (VEC) {
-        float r[16];
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const int k0 = 32 * ch + 16 * h + 4 * f;
-            float4 v = *reinterpret_cast<const float4*>(xr + (k0 < d ? k0 : 0));
-            if (k0 >= d) v = make_float4(k0 == d ? tail : 0.0f, 0.0f, 0.0f, 0.0f);
-            r[4 * f] = v.x; r[4 * f + 1] = v.y; r[4 * f + 2] = v.z; r[4 * f + 3] = v.w;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r[2 * i]), __float_as_uint(r[2 * i + 1]), false, false);
-            b[i] = __uint_as_float(sw[0]);
-            b[8 + i] = __uint_as_float(sw[1]);
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int t = 32 * ch + 2 * s + h;
-            const float v = xr[t < d ? t : 0];
-            b[s] = t < d ? v : t == d ? tail : 0.0f;
-        }
-    }
 }
 
 // grid (cdiv(n, KNN_ROWS), cdiv(nct, CT)), block 256: wave w -> rows [(blockIdx.x * 4 + w) * 64, +64) of the piece x [n][d] as KNN_XB
@@ -120,7 +65,7 @@ __global__ __launch_bounds__(256) void knn_score_kernel(const float* __restrict_
     for (int t = 0; t < CT; ++t) ap[t] = Qf + (size_t)(ct0 + t < nct ? ct0 + t : nct - 1) * KG * 64 + lane;
     float bv[KNN_XB][16];
 #pragma unroll
-    for (int b = 0; b < KNN_XB; ++b) knn_load_b<VEC>(xr[b], d, 0, h, tl[b], bv[b]);
+    for (int b = 0; b < KNN_XB; ++b) dense_load_b<VEC>(xr[b], d, 0, h, tl[b], bv[b]);
     float4 a[CT];
 #pragma unroll
     for (int t = 0; t < CT; ++t) a[t] = ap[t][0];
@@ -129,7 +74,7 @@ __global__ __launch_bounds__(256) void knn_score_kernel(const float* __restrict_
         float bn[KNN_XB][16];
         const int chn = ch + 1 < nch ? ch + 1 : ch;
 #pragma unroll
-        for (int b = 0; b < KNN_XB; ++b) knn_load_b<VEC>(xr[b], d, chn, h, tl[b], bn[b]);
+        for (int b = 0; b < KNN_XB; ++b) dense_load_b<VEC>(xr[b], d, chn, h, tl[b], bn[b]);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int gn = ch * 4 + g + 1 < KG ? ch * 4 + g + 1 : ch * 4 + g;

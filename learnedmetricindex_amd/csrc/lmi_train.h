@@ -10,7 +10,7 @@
 // gradient as a row-ordered chain of adds and Adam on b).  Activations are not stored: a_l = z_{l-1} > 0 ? z_{l-1} : +0 is applied
 // where z_{l-1} is read as an operand.
 #pragma once
-#include "lmi_kernels.h"
+#include "lmi_dense.h"   // dense_absmax_kernel: the finite check of the named rows and the weights
 
 namespace lmi {
 

@@ -11,7 +11,8 @@ import numpy as np
 
 NITER = 8
 #: (n, d, k, seed) -> (empty clusters at the end, pass of the fixed point or None) for niter = 8
-CASES = {(3001, 45, 7, 1): (0, None), (2500, 770, 130, 2): (13, 3), (4099, 33, 33, 3): (0, None), (600, 768, 257, 4): (1, 3)}
+CASES = {(3001, 45, 7, 1): (0, None), (2500, 770, 130, 2): (13, 3), (4099, 33, 33, 3): (0, None), (600, 768, 257, 4): (1, 3),
+         (1500, 64, 20, 5): (1, None), (1500, 64, 40, 6): (0, 7)}   # the last two: 16-byte row loads against one and two tiles
 
 
 def exponent(x):

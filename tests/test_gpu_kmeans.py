@@ -1,7 +1,8 @@
 """GPU (`-m gpu`): `lmi_kmeans` -- Lloyd's k-means on the device -- against its numpy restatement (tests/kmeans_ref.py, on top of
 the unchanged oracle's `knn_l2`).  Every comparison is exact: centroids as uint32 bit patterns, labels, counts and `changed` with
-array_equal.  The four parity cases cover odd d, d > 768 that is no multiple of 32, k below a tile, one past a tile and over several
-tiles, ragged n, exact ties, duplicate rows, empty clusters and the early stop (test_kmeans_host.py pins that they do)."""
+array_equal.  The six parity cases cover odd d, d > 768 that is no multiple of 32, k below a tile, one past a tile and over several
+tiles -- and with d a multiple of 4 (16-byte row loads) one tile, two and several -- ragged n, exact ties, duplicate rows, empty
+clusters and the early stop (test_kmeans_host.py pins that they do)."""
 import ctypes
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""Host side of `lmi_kmeans` (no GPU): the numpy reference of tests/kmeans_ref.py reproduces what the four parity cases were chosen
+"""Host side of `lmi_kmeans` (no GPU): the numpy reference of tests/kmeans_ref.py reproduces what the six parity cases were chosen
 for, the registry and search.py know `hip_kmeans`, and `_capi.kmeans` refuses bad arguments before it loads the library."""
 import numpy as np
 import pytest
