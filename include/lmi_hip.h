@@ -126,6 +126,37 @@ LMI_API int lmi_set_stop_mass(lmi_index *h, float mass);
  * lmi_search, lmi_pipeline_submit, lmi_mlp_proba) ignore this setting, the walk ignores that one. */
 LMI_API int lmi_set_path_mass(lmi_index *h, float mass);
 
+/* Row-budget stop (no reference counterpart in code; the LMI literature states its search budget this way: "stop after the
+ * visited buckets hold 1 % of the dataset").  A query visits buckets in the model's order until the buckets it has visited
+ * hold `rows` objects or more.  n(b) is the number of objects the handle's index holds in slab bucket b at the time of the
+ * CALL -- what lmi_bucket_sizes returns; the kernels read it from the index's device table, so it is live, not a snapshot
+ * taken when the setter ran: after lmi_buckets_insert / lmi_buckets_delete the next call cuts by the new counts.
+ * rows == 0 (default): off, every call launches exactly the kernels it launches without the setting.  rows < 0: an error
+ * that leaves the setting as it was.
+ * 1-level calls (lmi_mlp_topk, lmi_search, lmi_search_f16, lmi_pipeline_submit): in the bucket order r_0 = n(class_0) and
+ * r_t = r_{t-1} + n(class_t), summed in int64; a rank whose class is -1 (the NaN case of the ranking) adds 0.  Rank 0 is
+ * always visited, rank t >= 1 is visited iff r_{t-1} < rows.  A rank that is not visited gets bucket_order[q][t] = -1,
+ * which the scan and the merge treat as an unvisited slot.  The bucket that crosses the budget is scanned whole: there are
+ * no partial buckets.  n >= 0, so the sum never decreases and the first cut rank ends the order.
+ * Walk calls (lmi_nav_order, lmi_search_tree, lmi_search_tree_f16): order, priorities and tie rule are untouched.  When
+ * the walk records a bucket, r_j = r_{j-1} + n(child_bucket); a listed bucket without objects (child_bucket -1) adds 0, a
+ * dropped path (-2) is not recorded and adds nothing.  The first bucket is always recorded; after j recorded buckets the
+ * query goes on popping only while r_{j-1} < rows.  A stopped query pops nothing more and never queues for a model again;
+ * its remaining slab_ids / entries slots stay -1.
+ * Together with the other stops: with lmi_set_stop_mass on a 1-level call, or lmi_set_path_mass on a walk call, the query
+ * goes on only while BOTH conditions hold; both are prefix cuts of the same order, so a query visits the smaller of the two
+ * counts.  (lmi_set_stop_mass stays without effect on the walk and lmi_set_path_mass on the 1-level calls.)
+ * Not affected: n_buckets == 1 is never cut, lmi_mlp_proba is never cut, lmi_scan_topk on a caller's own bucket order is
+ * unchanged, kout and all output shapes are unchanged.
+ * Refused before any launch when rows > 0 and n_buckets > 1: a handle without a built index (lmi_mlp_topk on a handle
+ * that only has an MLP keeps working with the stop off); an index built with an `owned` mask that leaves a bucket out (a
+ * sharded rank does not know the other ranks' counts, and ranks that cut differently would merge wrong results); a 1-level
+ * call whose model has more classes than the index has bucket ids (for the walk: a child_bucket that is no bucket id of
+ * the index).  Each message names the condition.
+ * Per handle; a lmi_clone_view copies its parent's value when it is made; lmi_subset hands it on, and the subset cuts by
+ * its OWN counts; may be changed between any two calls, the index is not rebuilt. */
+LMI_API int lmi_set_stop_rows(lmi_index *h, int64_t rows);
+
 /* Multi-level index (len(n_categories) > 1; LearnedIndex.py:216-325, PriorityQueue.py:18-94): the models of
  * the internal nodes and the tree.  Model 0 is the root (lmi_set_mlp); lmi_nav_set_model sets model_id >= 1
  * (arguments as lmi_set_mlp).  lmi_nav_set_tree: child e = child_offset[m] + c is class c of model m:
@@ -225,7 +256,7 @@ LMI_API int lmi_buckets_delete(lmi_index *h, const uint32_t *ids, int64_t n, int
  * *out is a NEW, INDEPENDENT handle on h's device: it owns copies of the root model, the node models, the tree tables and its own
  * index images -- nothing is borrowed (it is no clone view and does not count as one), h may be destroyed before it, and either may
  * be rebuilt or mutated without the other noticing.  It carries h's settings: metric, storage, prefilter on or off,
- * lmi_set_fused_mlp, lmi_set_stop_mass, lmi_set_path_mass, the timing level and the `owned` mask of a sharded rank; a chunk length
+ * lmi_set_fused_mlp, lmi_set_stop_mass, lmi_set_path_mass, lmi_set_stop_rows, the timing level and the `owned` mask of a sharded rank; a chunk length
  * fixed by lmi_set_chunk_rows stays fixed, otherwise it is chosen as lmi_buckets_begin chooses it, for the subset's own size.  Its
  * stream is the NULL stream until lmi_set_stream.
  * The new handle holds exactly what lmi_create + those settings + lmi_buckets_begin / add_rows / end would hold for the object list

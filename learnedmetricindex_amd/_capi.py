@@ -48,6 +48,7 @@ SIGNATURES = {
     "lmi_set_fused_mlp": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_set_stop_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
     "lmi_set_path_mass": (ctypes.c_int, [_vp, ctypes.c_float]),
+    "lmi_set_stop_rows": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "lmi_set_metric": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_set_storage": (ctypes.c_int, [_vp, ctypes.c_int]),
     "lmi_index_bytes": (ctypes.c_int, [_vp, _i64p]),
@@ -271,6 +272,7 @@ class Index:
         self.L = None
         self.stop_mass = 0.0
         self.path_mass = 0.0
+        self.stop_rows = 0
         self.bytes_in = 0   # bytes handed to add_rows / add_owned_rows / insert since the last buckets_begin (counted here, not in the library)
         if chunk_rows is not None:
             _check(lib().lmi_set_chunk_rows(self._h, int(chunk_rows)))
@@ -323,7 +325,7 @@ class Index:
         """An `Index` without a handle yet that describes this one's models and index (`clone_view`, `subset`)."""
         v = Index.__new__(Index)
         v._h, v._views = _vp(), []
-        for a in ("device", "n_classes", "d_nav", "d", "L", "metric", "storage", "stop_mass", "path_mass"):
+        for a in ("device", "n_classes", "d_nav", "d", "L", "metric", "storage", "stop_mass", "path_mass", "stop_rows"):
             setattr(v, a, getattr(self, a, None))
         return v
 
@@ -422,6 +424,16 @@ class Index:
         ignore it, as the walk ignores `stop_mass`."""
         _check(lib().lmi_set_path_mass(self._h, ctypes.c_float(mass)))
         self.path_mass = float(np.float32(mass))
+
+    def set_stop_rows(self, rows: int) -> None:
+        """Row-budget stop (`lmi_set_stop_rows`): 0 = off (default); rows > 0: a query visits buckets in the model's order --
+        the 1-level bucket order (`mlp_topk`, `search`) and the multi-level walk (`nav_order`, `search_tree`) alike -- until
+        the buckets it has visited hold `rows` objects or more, counted by the index's sizes at the time of the call
+        (`bucket_sizes`); the bucket that crosses the budget is scanned whole, the ranks behind it are -1 = unvisited.  With
+        `stop_mass` (1-level) or `path_mass` (walk) set as well a query goes on only while both allow it.  A negative value
+        raises and changes nothing.  `self.stop_rows` holds the value in force (a clone view and a subset start with it)."""
+        _check(lib().lmi_set_stop_rows(self._h, ctypes.c_int64(int(rows))))
+        self.stop_rows = int(rows)
 
     @staticmethod
     def _pack_layers(layers):

@@ -108,6 +108,7 @@ struct Settings {
     int fused_mlp = 1;            // lmi_set_fused_mlp: 0 never, 1 when the batch fills the chip, 2 always
     float stop_mass = 0.0f;       // lmi_set_stop_mass: 0 off; (0, 1]: a query's bucket order ends once this much probability is covered
     float path_mass = 0.0f;       // lmi_set_path_mass: 0 off; (0, 1]: a query's walk ends once its recorded buckets cover this much path probability
+    int64_t stop_rows = 0;        // lmi_set_stop_rows: 0 off; > 0: a query's bucket order / walk ends once the buckets it has visited hold this many objects
     int timing_level = 2;         // lmi_set_timing
     bool chunk_rows_auto = true;  // until lmi_set_chunk_rows: lmi_buckets_begin picks 256..2048 by the index size
     int chunk_rows_set = 0;       // lmi_set_chunk_rows' value (a very large bucket raises chunk_rows above it; lmi_subset starts from it again)
@@ -190,6 +191,7 @@ struct CallState {
     DevBuf gather_send, gather_recv;      // lmi_allgather_merge
     DevBuf pq_prob, pq_ent, pq_len, nav_len, nav_slab, nav_ent, nav_count, nav_colq, nav_active;
     DevBuf pq_mass, nav_parent_mass, nav_cum;   // the path-mass stop: reserved only while it is on
+    DevBuf nav_rows;                            // the row-budget stop of the walk ([nq] int64): reserved only while it is on
     DevBuf aug_rows, q_aug, qn2;   // L2: augmented ingest pieces / queries, |q|^2
     DevBuf stage;  // H2D staging for add_rows / host query uploads
     DevBuf wide;   // a piece of half rows widened to binary32 for an LMI_STORAGE_F32 build (the *_f16 ingest calls; widen16_kernel)

@@ -57,10 +57,50 @@ extern "C" LMI_API int lmi_set_stop_mass(lmi_index* h, float mass) {
     return 0;
 }
 
-// the class ranking behind the per-layer kernels and behind a fused launch whose logits went through global memory: with the stop
-// on (mass > 0) rank_classes_stop_kernel takes rank_classes_kernel's place
-static int rank_enqueue(hipStream_t st, const float* d_logits, int nq, int L, int nb, float mass, int* d_order) {
-    if (mass > 0.0f) rank_classes_stop_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, d_order);
+extern "C" LMI_API int lmi_set_stop_rows(lmi_index* h, int64_t rows) {
+    if (!h) return fail("lmi_set_stop_rows: NULL handle");
+    if (rows < 0) return fail("lmi_set_stop_rows: rows %lld is negative (0: off)", (long long)rows);
+    h->stop_rows = rows;
+    return 0;
+}
+
+// What a call that the row-budget stop would cut (rows > 0, n_buckets > 1) needs, checked before anything is launched: the kernels
+// read n(b) from d_nb_rows for every class / child bucket they meet, and the counts must be the whole index's.
+static int stop_rows_check(lmi_index* h, bool walk, const char* who) {
+    if (!h->built)
+        return fail("%s: lmi_set_stop_rows is on (%lld) and the handle has no built index: the budget counts the objects of the buckets (lmi_buckets_begin/add_rows/end)",
+                    who, (long long)h->stop_rows);
+    for (size_t b = 0; b < h->h_owned.size(); ++b)
+        if (!h->h_owned[b])
+            return fail("%s: lmi_set_stop_rows is on (%lld) and the index was built with an `owned` mask that leaves bucket %zu out: a sharded rank does not know the other ranks' counts",
+                        who, (long long)h->stop_rows, b);
+    if (!walk) {
+        if (h->root().dims.back() > h->L)
+            return fail("%s: lmi_set_stop_rows is on (%lld) and the model has %d classes, the index only %d bucket ids", who, (long long)h->stop_rows,
+                        h->root().dims.back(), h->L);
+    } else {
+        for (size_t e = 0; e < h->h_child_bucket.size(); ++e)
+            if (h->h_child_bucket[e] >= h->L)
+                return fail("%s: lmi_set_stop_rows is on (%lld) and child_bucket[%zu] = %d is no bucket id of the index (%d)", who, (long long)h->stop_rows, e,
+                            h->h_child_bucket[e], h->L);
+    }
+    return 0;
+}
+
+// the stops of a 1-level bucket order as the ranking launches take them: mass 0 / rows 0 = that stop is off
+struct RankStop {
+    float mass = 0.0f;
+    long long rows = 0;
+    const int* nb_rows = nullptr;   // the index's live counts (rows > 0)
+};
+
+// the class ranking behind the per-layer kernels and behind a fused launch whose logits went through global memory: with the row
+// budget on rank_classes_rows_kernel (which applies a mass as well), with the mass stop alone rank_classes_stop_kernel takes
+// rank_classes_kernel's place
+static int rank_enqueue(hipStream_t st, const float* d_logits, int nq, int L, int nb, const RankStop& S, int* d_order) {
+    const float mass = S.mass;
+    if (S.rows > 0) rank_classes_rows_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, S.nb_rows, S.rows, d_order);
+    else if (mass > 0.0f) rank_classes_stop_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, d_order);
     else rank_classes_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, d_order);
     HIPCHK(hipGetLastError());
     return 0;
@@ -163,6 +203,7 @@ static int build_descs(lmi_index* h) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_NAV>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_TOPK_STOP>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_NAV_MASS>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<FM_TOPK_ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, h->fm_lds));
     }
     h->desc_dirty = false;
     return 0;
@@ -183,9 +224,9 @@ static void fused_base(lmi_index* h, const float* d_q, int nq, FusedParams& P) {
 
 // MLP forward + class ranking (+ softmax when d_probs: then nb == L and d_order receives the full class order)
 // the per-layer form: one mlp_layer_kernel launch per Linear, then the ranking (and softmax) kernels, on stream `st`
-// mass > 0: the order is cut by the probability-mass stop (never together with d_probs)
+// stop: the order is cut by the probability-mass stop and / or the row budget (never together with d_probs)
 static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs,
-                              float mass) {
+                              const RankStop& stop) {
     const Model& R = h->root();
     const int L = R.dims[R.n_layers];
     const int ncb = cdiv(nq, 32);
@@ -228,7 +269,7 @@ static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, in
 #undef LMI_MLP_LAUNCH
         HIPCHK(hipGetLastError());
     }
-    CHK(rank_enqueue(st, d_logits, nq, L, nb, mass, d_order));
+    CHK(rank_enqueue(st, d_logits, nq, L, nb, stop, d_order));
     if (d_probs) {
         softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, st>>>(d_logits, d_order, nq, L, d_probs);
         HIPCHK(hipGetLastError());
@@ -243,6 +284,14 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
     CHK(build_descs(h));
     // the probability-mass stop (lmi_set_stop_mass) cuts a bucket order; predict_proba's full class order and a single rank are never cut
     const float mass = (!d_probs && nb > 1) ? h->stop_mass : 0.0f;
+    // the row budget (lmi_set_stop_rows) likewise; both halves of a split batch and every ranking path take the same `stop`
+    RankStop stop;
+    stop.mass = mass;
+    stop.rows = (!d_probs && nb > 1) ? (long long)h->stop_rows : 0;
+    if (stop.rows > 0) {
+        CHK(stop_rows_check(h, false, "lmi_mlp_topk"));
+        stop.nb_rows = h->d_nb_rows.as<int>();
+    }
     // One launch for every layer + ranking when the batch fills the chip (a block = 32 queries, one per CU for the wide
     // models: 8 192 queries 100 us against 138 us for the per-layer kernels); small batches (a rank's slice of a
     // sharded batch, single queries) have too few 32-query blocks for that and take the per-layer kernels, whose grids
@@ -275,17 +324,20 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
         P.classes = d_order;
         P.ts = tsp(h, ST_MLP0);
         P.stop_mass = mass;
+        P.nb_rows = stop.nb_rows;
+        P.stop_rows = stop.rows;
         if (nq_head < nq) CHK(side_fork(h));
         if (d_probs) mlp_fused_kernel<FM_PROBA><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        else if (stop.rows > 0) mlp_fused_kernel<FM_TOPK_ROWS><<<grid, 256, h->fm_lds, h->stream>>>(P);
         else if (mass > 0.0f) mlp_fused_kernel<FM_TOPK_STOP><<<grid, 256, h->fm_lds, h->stream>>>(P);
         else mlp_fused_kernel<FM_TOPK><<<grid, 256, h->fm_lds, h->stream>>>(P);
         HIPCHK(hipGetLastError());
         if (nq_head < nq) {
-            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->root().dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr, mass));
+            CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->root().dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr, stop));
             CHK(side_join(h));
         }
         if (!h->fm_logits_lds) {
-            CHK(rank_enqueue(h->stream, d_logits, nq, L, nb, mass, d_order));
+            CHK(rank_enqueue(h->stream, d_logits, nq, L, nb, stop, d_order));
             if (d_probs) {
                 softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, h->stream>>>(d_logits, d_order, nq, L, d_probs);
                 HIPCHK(hipGetLastError());
@@ -293,7 +345,7 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
         }
         return 0;
     }
-    return mlp_layers_enqueue(h, h->stream, d_q, nq, nb, d_order, d_logits_out, d_probs, mass);
+    return mlp_layers_enqueue(h, h->stream, d_q, nq, nb, d_order, d_logits_out, d_probs, stop);
 }
 
 extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int nq, int nb, int32_t* bucket_order,
@@ -359,6 +411,8 @@ extern "C" LMI_API int lmi_mlp_proba(lmi_index* h, const float* queries_nav, int
 // enqueue.  Larger trees: steps in batches of 4 with the count read back after each (one small synchronisation).
 // The path-mass stop (lmi_set_path_mass > 0): the same launches in their mass forms (mlp_fused_kernel<FM_NAV_MASS>, nav_pop_mass_kernel /
 // nav_pop_lds_mass_kernel) with three more buffers; a single bucket per query (nb == 1) is never cut, so it takes the plain forms.
+// The row-budget stop (lmi_set_stop_rows > 0): the pop kernels in their rows forms (nav_pop_rows_kernel / nav_pop_lds_rows_kernel; with
+// a path mass as well nav_pop_mass_rows_kernel / nav_pop_lds_mass_rows_kernel) with one more buffer; the MLP launches are untouched.
 constexpr int NAV_ENQUEUE_ALL = 16;
 static int nav_check(lmi_index* h, int nq, int nb, const char* who) {
     if (!h->tree_set) return fail("%s: no tree (lmi_nav_set_model / lmi_nav_set_tree)", who);
@@ -375,6 +429,8 @@ static int nav_check(lmi_index* h, int nq, int nb, const char* who) {
 static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_slab, int* d_ent) {
     const int nm = (int)h->models.size();
     const int cap = h->h_child_offset[nm];
+    const bool with_rows = h->stop_rows > 0 && nb > 1;
+    if (with_rows) CHK(stop_rows_check(h, true, "lmi_nav_order"));
     CHK(h->pq_prob.reserve((size_t)nq * cap * 4));
     CHK(h->pq_ent.reserve((size_t)nq * cap * 4));
     CHK(h->pq_len.reserve((size_t)nq * 4));
@@ -387,6 +443,7 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
         CHK(h->nav_parent_mass.reserve((size_t)nq * 4));
         CHK(h->nav_cum.reserve((size_t)nq * 4));
     }
+    if (with_rows) CHK(h->nav_rows.reserve((size_t)nq * 8));
     FillRanges Z;
     Z.count = 0;
     bool fill_ok = true;
@@ -400,6 +457,7 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
         fill(h->nav_cum.p, nq, 0u);
         fill(h->nav_parent_mass.p, nq, 0x3F800000u);  // 1.0f: the root's children get their own probability as their mass
     }
+    if (with_rows) fill(h->nav_rows.p, 2ll * nq, 0u);   // int64 sums: two words each (8 ranges at the most, FillRanges::MAXR is 12)
     if (!fill_ok) return fail("internal: more than %d fill ranges queued (%s:%d)", FillRanges::MAXR, __FILE__, __LINE__);
     Z.ts = tsp(h, ST_MLP0);
     fill_ranges_kernel<<<h->num_cus * 2, 256, 0, h->stream>>>(Z);
@@ -439,6 +497,13 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
         S.parent_mass = h->nav_parent_mass.as<float>();
         S.mass = h->path_mass;
     }
+    NavRows W;
+    memset(&W, 0, sizeof(W));
+    if (with_rows) {
+        W.nb_rows = h->d_nb_rows.as<int>();
+        W.acc = h->nav_rows.as<long long>();
+        W.rows = h->stop_rows;
+    }
     int* counts = h->nav_count.as<int>();
     // A step pops entries until the query hits an internal node; a query expands each node at most once, so there are
     // at most (models) steps.
@@ -453,7 +518,13 @@ static int nav_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_sl
             N.node_count = counts + par * (nm + 1);
             N.active = counts + par * (nm + 1) + nm;
             N.prev_active = (all && it > 0) ? counts + (1 - par) * (nm + 1) + nm : nullptr;
-            if (with_mass) {
+            if (with_mass && with_rows) {
+                if (pop_lds) nav_pop_lds_mass_rows_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N, S, W);
+                else nav_pop_mass_rows_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N, S, W);
+            } else if (with_rows) {
+                if (pop_lds) nav_pop_lds_rows_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N, W);
+                else nav_pop_rows_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N, W);
+            } else if (with_mass) {
                 if (pop_lds) nav_pop_lds_mass_kernel<<<cdiv(nq, 64), 64, (size_t)cap * 64 * 8, h->stream>>>(N, S);
                 else nav_pop_mass_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(N, S);
             } else {

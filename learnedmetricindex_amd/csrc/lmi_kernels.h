@@ -400,6 +400,78 @@ __global__ __launch_bounds__(64) void rank_classes_stop_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------
+// Class ranking with the row-budget stop (lmi_set_stop_rows; no reference counterpart), alone (mass == 0: no softmax at
+// all) or together with the probability-mass stop (mass > 0: rank_classes_stop_kernel's arithmetic, word for word).
+// r_t = r_{t-1} + n(class_t) in int64, n = nb_rows[class] read by ONE lane (the winning class is wave-uniform after the
+// butterfly) and handed to the wave by readfirstlane; a class of -1 (NaN) adds 0.  Rank 0 is always visited, rank t >= 1
+// iff r_{t-1} < rows and, with a mass, c_{t-1} < mass.  Neither sum decreases, so the first rank that is cut ends the
+// selection passes.  One wave per query, launched IN PLACE of rank_classes_kernel / rank_classes_stop_kernel.  The host
+// has checked that every class is a bucket id of the table (L <= its length).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void rank_classes_rows_kernel(const float* __restrict__ logits, int nq, int L, int nb, float mass,
+                                                              const int* __restrict__ nb_rows, long long rows,
+                                                              int* __restrict__ order) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    if (q >= nq) return;
+    const float* l = logits + (size_t)q * L;
+    const bool with_mass = mass > 0.0f;   // a kernel argument: uniform
+    float m = 0.0f, s = 1.0f;
+    if (with_mass) {
+        m = l[0];
+        for (int j = lane; j < L; j += 64) {
+            const float v = l[j];
+            m = v > m ? v : m;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(m, o);
+            m = ov > m ? ov : m;
+        }
+        s = 0.0f;
+        for (int j0 = 0; j0 < L; j0 += 64) {
+            const int j = j0 + lane;
+            const float e = j < L ? lmi_expf(l[j] - m) : 0.0f;   // past L: +0, which leaves the non-negative sum as it is
+#pragma unroll
+            for (int k = 0; k < 64; ++k) s += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), k));
+        }
+    }
+    float pv = INFINITY, c = 0.0f;
+    long long r = 0;
+    int pi = -1;
+    int t = 0;
+    for (; t < nb; ++t) {
+        if (t > 0 && (!(r < rows) || (with_mass && !(c < mass)))) break;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int j = lane; j < L; j += 64) {
+            float v = l[j];
+            bool after = (v < pv) || (v == pv && j > pi);
+            if (after && (v > bv || (v == bv && j < bi))) { bv = v; bi = j; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            float ov = __shfl_xor(bv, o);
+            int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        const bool none = bi == 0x7fffffff;   // ran out of comparable logits (NaN): class -1, probability NaN, no rows
+        int n = 0;
+        if (lane == 0) {
+            order[(size_t)q * nb + t] = none ? -1 : bi;
+            if (!none) n = nb_rows[bi];
+        }
+        r += __builtin_amdgcn_readfirstlane(n);
+        if (with_mass) {
+            const float p = none ? __builtin_nanf("") : lmi_expf(bv - m) / s;   // bv is l[bi]
+            c = t == 0 ? p : c + p;
+        }
+        pv = bv;
+        pi = bi;
+    }
+    for (int u = t + lane; u < nb; u += 64) order[(size_t)q * nb + u] = -1;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Routing: the GPU twin of the `for bucket: filter_path_idxs(bucket_path, path)` loop
 // (LearnedIndex.py:350-353, utils.py:61-65): queries grouped bucket-major (CSR).
 // ------------------------------------------------------------------------------------------------

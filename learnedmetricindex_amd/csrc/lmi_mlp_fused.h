@@ -20,6 +20,9 @@
 //       FM_NAV    the node's children pushed into the query's priority queue    (LearnedIndex.py:220-227, 289-299)
 //       FM_NAV_MASS  the same, and every pushed child's path mass = its parent's path mass * its local probability, one binary32
 //                 multiply (lmi_set_path_mass; no reference counterpart)
+//       FM_TOPK_ROWS  FM_TOPK cut by the row-budget stop: -1 from the first rank whose predecessors' buckets hold `stop_rows`
+//                 objects or more, and -- when stop_mass > 0 as well -- FM_TOPK_STOP's cut too: a rank is visited while both
+//                 conditions hold (lmi_set_stop_rows; no reference counterpart)
 //     Final layers wider than FM_MAXH keep their logits in global memory and the host runs the separate ranking
 //     kernels afterwards.
 #pragma once
@@ -32,7 +35,7 @@ constexpr int FM_COLS = 32;     // columns per block = one MFMA column block
 constexpr int FM_CHUNK = 96;    // input features staged per step of layer 0 (12 k-groups: a multiple of the 3-deep weight prefetch)
 constexpr int FM_CHUNK_S = FM_CHUNK + 1;
 constexpr int FM_MAXH = 512;    // widest layer whose outputs stay in LDS
-enum { FM_TOPK = 0, FM_PROBA = 1, FM_NAV = 2, FM_TOPK_STOP = 3, FM_NAV_MASS = 4 };
+enum { FM_TOPK = 0, FM_PROBA = 1, FM_NAV = 2, FM_TOPK_STOP = 3, FM_NAV_MASS = 4, FM_TOPK_ROWS = 5 };
 
 struct ModelDesc {  // device copy of one model's shape and weights (root = model 0, internal nodes 1..)
     int n_layers;
@@ -54,8 +57,8 @@ struct FusedParams {
     // step of the walk, model m's queries at col_query[m * nq ..)
     const int* node_count;
     const int* col_query;
-    int nb;                      // FM_TOPK, FM_TOPK_STOP
-    int* order;                  // FM_TOPK, FM_TOPK_STOP [nq][nb]
+    int nb;                      // FM_TOPK, FM_TOPK_STOP, FM_TOPK_ROWS
+    int* order;                  // FM_TOPK, FM_TOPK_STOP, FM_TOPK_ROWS [nq][nb]
     float* logits_out;           // nullable [nq][L] (model 0 only)
     float* probs;                // FM_PROBA [nq][L]
     int* classes;                // FM_PROBA [nq][L]
@@ -69,10 +72,13 @@ struct FusedParams {
     int* zero_counts;            // block 0 clears the NEXT step's counters
     int n_zero;
     unsigned long long* ts;      // nullable: device stamp of the launch's start (lmi_kernels.h)
-    float stop_mass;             // FM_TOPK_STOP: in (0, 1]
+    float stop_mass;             // FM_TOPK_STOP: in (0, 1]; FM_TOPK_ROWS: 0 (no mass stop) or in (0, 1]
     // FM_NAV_MASS: the path masses beside the priorities
     float* pq_mass;              // [cap][nq] like pq_prob
     const float* parent_mass;    // [nq] path mass of the entry whose children this launch pushes (1 before the root launch)
+    // FM_TOPK_ROWS (at the end: the other modes' arguments keep their offsets)
+    const int* nb_rows;          // [>= L] objects per bucket of the index, as they are now (the handle's d_nb_rows)
+    long long stop_rows;         // > 0
 };
 
 template <int MODE>
@@ -286,7 +292,7 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
     // Ranking: 8 lanes per column, all 8 columns of a wave side by side (a wave per column, one column after the
     // other, took 27 us of a 106-us block: 32 sequential passes of 12 dependent shuffles each).  Selection pass t
     // finds the t-th class of the descending order, ties -> lower class index (rank_classes_kernel's rule).
-    const int T = (MODE == FM_TOPK || MODE == FM_TOPK_STOP) ? P.nb : L;
+    const int T = (MODE == FM_TOPK || MODE == FM_TOPK_STOP || MODE == FM_TOPK_ROWS) ? P.nb : L;
     const int col = w * 8 + (lane >> 3), sub = lane & 7;
     const bool live = col < ncols;
     const int q = s_q[live ? col : 0];
@@ -294,7 +300,9 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
     // FM_TOPK_STOP: the column's softmax terms by its 8 lanes (rank_classes_stop_kernel's arithmetic: the row maximum, then the
     // exponentials 8 classes at a time, one per lane, added in class order into one chain that every lane of the group carries)
     float sm = 0.0f, ss = 0.0f, cum = 0.0f;
-    if (MODE == FM_TOPK_STOP) {
+    const bool rows_mass = MODE == FM_TOPK_ROWS && P.stop_mass > 0.0f;   // block-uniform: without a mass the row stop needs no softmax
+    long long racc = 0;
+    if (MODE == FM_TOPK_STOP || rows_mass) {
         sm = l[0];
         for (int j = sub; j < L; j += 8) {
             const float v = l[j];
@@ -343,6 +351,18 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(FusedParams P) {
                 P.order[(size_t)q * P.nb + t] = (t == 0 || cum < P.stop_mass) ? cls : -1;
                 const float pr = cls >= 0 ? lmi_expf(l[cls] - sm) / ss : __builtin_nanf("");
                 cum = t == 0 ? pr : cum + pr;
+            } else if (MODE == FM_TOPK_ROWS) {
+                // rank t >= 1 is visited iff r_{t-1} < rows (and c_{t-1} < mass when a mass is set); r_t = r_{t-1} + n(class_t) in
+                // int64, one scattered 4-byte load per rank by this lane, a class of -1 adds 0.  As in FM_TOPK_STOP a column that
+                // is cut keeps going through the selection passes with its wave (and keeps adding sizes nobody reads): the 8
+                // columns of a wave run the passes in lockstep, so stopping one of them would save nothing.
+                const bool go = racc < P.stop_rows && (!rows_mass || cum < P.stop_mass);
+                P.order[(size_t)q * P.nb + t] = (t == 0 || go) ? cls : -1;
+                if (rows_mass) {
+                    const float pr = cls >= 0 ? lmi_expf(l[cls] - sm) / ss : __builtin_nanf("");
+                    cum = t == 0 ? pr : cum + pr;
+                }
+                if (cls >= 0) racc += P.nb_rows[cls];
             } else {
                 const float pr = cls >= 0 ? lmi_expf(l[cls] - s_max[col]) / s_sum[col] : __builtin_nanf("");
                 if (MODE == FM_PROBA) {
@@ -392,6 +412,12 @@ struct NavParams {
 };
 // the path-mass stop (lmi_set_path_mass): what the *_mass_kernel forms take beside NavParams (a struct of its own: the plain forms keep
 // their kernel arguments, and with them their code, as they are)
+// the row-budget stop (lmi_set_stop_rows): what the *_rows_kernel forms take beside NavParams (and NavMass)
+struct NavRows {
+    const int* nb_rows;       // [L] objects per slab bucket, as they are now (the handle's d_nb_rows)
+    long long* acc;           // [nq] objects in the buckets recorded so far (0 before the walk)
+    long long rows;           // > 0
+};
 struct NavMass {
     const float* pq_mass;     // [cap][nq] path mass of every queue entry (mlp_fused_kernel<FM_NAV_MASS>)
     float* cum;               // [nq] path mass of the buckets recorded so far (0 before the walk)
@@ -422,16 +448,27 @@ __device__ __forceinline__ void nav_push(const NavParams& P, int q, int my_cm) {
     if (lane == first) atomicAdd(P.active, total);
 }
 
-// The two pop kernels (lmi_nav_pop.h), compiled twice: as they were, and in their mass forms for the path-mass stop.  Two compilations
-// of one text rather than a `template <bool MASS>` body behind the named kernels: inlined from such a body (by reference or by value),
+// The two pop kernels (lmi_nav_pop.h), compiled four times: as they were, in their mass forms for the path-mass stop, in their rows
+// forms for the row-budget stop, and with both stops.  Several compilations of one text rather than a `template <bool MASS>` body
+// behind the named kernels: inlined from such a body (by reference or by value),
 // hipcc laid the plain kernels out differently (tools/isa_diff.py), and the walk without the stop is to keep its code instruction for
 // instruction.
 constexpr int NAV_LDS_CAP = 128;   // queues of up to this many entries are popped from LDS (nav_pop_lds_kernel)
+#define LMI_NAV_ROWS 0
 #define LMI_NAV_MASS 0
 #include "lmi_nav_pop.h"
 #undef LMI_NAV_MASS
 #define LMI_NAV_MASS 1
 #include "lmi_nav_pop.h"
 #undef LMI_NAV_MASS
+#undef LMI_NAV_ROWS
+#define LMI_NAV_ROWS 1
+#define LMI_NAV_MASS 0
+#include "lmi_nav_pop.h"
+#undef LMI_NAV_MASS
+#define LMI_NAV_MASS 1
+#include "lmi_nav_pop.h"
+#undef LMI_NAV_MASS
+#undef LMI_NAV_ROWS
 
 }  // namespace lmi

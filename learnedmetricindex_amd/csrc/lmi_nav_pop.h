@@ -1,6 +1,8 @@
 // lmi_nav_pop.h -- one step of the multi-level walk: the two pop kernels (queues in global memory / in LDS).  NOT a header of its own:
-// lmi_mlp_fused.h includes it twice inside namespace lmi, with LMI_NAV_MASS 0 (nav_pop_kernel, nav_pop_lds_kernel: the walk as the
-// reference runs it) and 1 (nav_pop_mass_kernel, nav_pop_lds_mass_kernel: the same walk with the path-mass stop of lmi_set_path_mass).
+// lmi_mlp_fused.h includes it four times inside namespace lmi: with LMI_NAV_MASS 0 (nav_pop_kernel, nav_pop_lds_kernel: the walk as the
+// reference runs it) and 1 (nav_pop_mass_kernel, nav_pop_lds_mass_kernel: the same walk with the path-mass stop of lmi_set_path_mass),
+// each with LMI_NAV_ROWS 0 and 1 (nav_pop_rows_kernel, nav_pop_lds_rows_kernel, nav_pop_mass_rows_kernel, nav_pop_lds_mass_rows_kernel:
+// the row-budget stop of lmi_set_stop_rows, alone and together with the path-mass stop).
 //
 // The mass forms: a recorded bucket's path mass -- read from pq_mass when the bucket is recorded -- goes into the query's running sum c
 // (c_0 = m_0, c_j = c_{j-1} + m_j, binary32, in recording order), and the query goes on only while c < mass (false on NaN).  A stopped
@@ -8,7 +10,19 @@
 // queues for a model again; its remaining slots keep the -1 they were filled with.  (out_len is read by these kernels only.)  An
 // internal pop leaves the entry's mass in parent_mass[q]: this step's mlp_fused_kernel<FM_NAV_MASS> multiplies the children's local
 // probabilities by it.
-#if LMI_NAV_MASS
+//
+// The rows forms: a recorded bucket with objects (cb >= 0) adds n(cb) -- one scattered 4-byte load from the index's live table -- to
+// the query's int64 sum in acc[q]; a listed bucket without objects (-1) adds 0; the query goes on only while the sum is below `rows`,
+// and stops the same way (nb into out_len).  With both stops a query goes on only while both conditions hold.
+#if LMI_NAV_MASS && LMI_NAV_ROWS
+#define LMI_NAV_POP nav_pop_mass_rows_kernel
+#define LMI_NAV_POP_LDS nav_pop_lds_mass_rows_kernel
+#define LMI_NAV_ARGS NavParams P, NavMass S, NavRows R
+#elif LMI_NAV_ROWS
+#define LMI_NAV_POP nav_pop_rows_kernel
+#define LMI_NAV_POP_LDS nav_pop_lds_rows_kernel
+#define LMI_NAV_ARGS NavParams P, NavRows R
+#elif LMI_NAV_MASS
 #define LMI_NAV_POP nav_pop_mass_kernel
 #define LMI_NAV_POP_LDS nav_pop_lds_mass_kernel
 #define LMI_NAV_ARGS NavParams P, NavMass S
@@ -25,6 +39,9 @@ __global__ __launch_bounds__(256) void LMI_NAV_POP(LMI_NAV_ARGS) {
     int have = live ? P.out_len[q] : P.nb;
 #if LMI_NAV_MASS
     float cum = live ? S.cum[q] : 0.0f;
+#endif
+#if LMI_NAV_ROWS
+    long long racc = live ? R.acc[q] : 0;
 #endif
     const float* pp = P.pq_prob + (live ? q : 0);   // entry i at [i * nq]
     int* pe = P.pq_ent + (live ? q : 0);
@@ -60,6 +77,10 @@ __global__ __launch_bounds__(256) void LMI_NAV_POP(LMI_NAV_ARGS) {
             S.cum[q] = cum;
             if (!(cum < S.mass)) { P.out_len[q] = P.nb; break; }   // stopped: every later step takes the query for finished
 #endif
+#if LMI_NAV_ROWS
+            if (cb >= 0) { racc += R.nb_rows[cb]; R.acc[q] = racc; }   // cb < L: checked by the host before the walk (stop_rows_check)
+            if (!(racc < R.rows)) { P.out_len[q] = P.nb; break; }      // stopped, as above
+#endif
         }
     }
     nav_push(P, q, my_cm);
@@ -78,6 +99,9 @@ __global__ __launch_bounds__(64) void LMI_NAV_POP_LDS(LMI_NAV_ARGS) {
     int have = live ? P.out_len[q] : P.nb;
 #if LMI_NAV_MASS
     float cum = live ? S.cum[q] : 0.0f;
+#endif
+#if LMI_NAV_ROWS
+    long long racc = live ? R.acc[q] : 0;
 #endif
     const int len = (live && have < P.nb) ? P.pq_len[q] : 0;
     const float* pp = P.pq_prob + (live ? q : 0);
@@ -126,6 +150,10 @@ __global__ __launch_bounds__(64) void LMI_NAV_POP_LDS(LMI_NAV_ARGS) {
             cum = have == 1 ? m : cum + m;
             S.cum[q] = cum;
             if (!(cum < S.mass)) { P.out_len[q] = P.nb; break; }   // stopped: every later step takes the query for finished
+#endif
+#if LMI_NAV_ROWS
+            if (cb >= 0) { racc += R.nb_rows[cb]; R.acc[q] = racc; }   // cb < L: checked by the host before the walk (stop_rows_check)
+            if (!(racc < R.rows)) { P.out_len[q] = P.nb; break; }      // stopped, as above
 #endif
         }
     }

@@ -270,14 +270,16 @@ class LearnedIndex(Logger):
         eng.buckets_end()
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
-                        k: int = 10, stop_mass: Optional[float] = None, path_mass: Optional[float] = None):
+                        k: int = 10, stop_mass: Optional[float] = None, path_mass: Optional[float] = None,
+                        stop_rows: Optional[int] = None):
         """`search` against the index already resident in HBM (after `prepare`, a previous `search`
-        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass` and `path_mass` as there."""
+        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass`, `path_mass` and `stop_rows`
+        as there."""
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         assert self._engine is not None, "no resident index: call prepare()/search() or index_io.load_index()"
         return self._search_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, k,
-                                 time.time(), stop_mass, path_mass)
+                                 time.time(), stop_mass, path_mass, stop_rows)
 
     @staticmethod
     def _check_stop_mass(stop_mass, n_categories) -> None:
@@ -387,6 +389,7 @@ class LearnedIndex(Logger):
         stop_mass: Optional[float] = None,
         path_mass: Optional[float] = None,
         storage: str = "f32",
+        stop_rows: Optional[int] = None,
     ) -> Tuple[npt.NDArray, npt.NDArray[np.uint32], Dict[str, float]]:
         """Searches for `k` nearest neighbors of every query in its `n_buckets` most probable buckets.
         Parameters and return values as the reference (LearnedIndex.py:41-83).  `metric` (an extension; the
@@ -400,28 +403,36 @@ class LearnedIndex(Logger):
         its order, and a query stops once the path probabilities (the product of the local probabilities along a bucket's path)
         of the buckets it has recorded sum to `path_mass` or more -- the slots behind the stop stay unvisited, the result shapes
         do not change.  It holds for this call only.  ValueError on a 1-level index (use `stop_mass` there).
+        `stop_rows` (an extension, 1-level and multi-level indexes alike; `lmi_set_stop_rows`): None = off; an integer >= 1: a
+        query stops visiting buckets once the buckets it has visited hold `stop_rows` objects or more (the bucket that crosses
+        the budget is scanned whole) -- the slots behind the stop stay unvisited, the result shapes do not change.  With
+        `stop_mass` / `path_mass` as well a query goes on only while both allow it.  It holds for this call only.
         `storage` (an extension): "f32" (default) or "f16", how the HBM-resident copy keeps the scan vectors (see `prepare`)."""
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         s = time.time()
         eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged,
                            storage=storage)
-        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass)
+        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass, stop_rows)
 
-    def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None):
-        if stop_mass is None and path_mass is None:
+    def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None,
+                     stop_rows=None):
+        if stop_mass is None and path_mass is None and stop_rows is None:
             return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         # the engine's own settings come back afterwards: a later call without the arguments is as before
-        before = eng.stop_mass, eng.path_mass
+        before = eng.stop_mass, eng.path_mass, eng.stop_rows
         try:
             if stop_mass is not None:
                 eng.set_stop_mass(stop_mass)
             if path_mass is not None:
                 eng.set_path_mass(path_mass)
+            if stop_rows is not None:
+                eng.set_stop_rows(stop_rows)
             return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         finally:
             eng.set_stop_mass(before[0])
             eng.set_path_mass(before[1])
+            eng.set_stop_rows(before[2])
 
     def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
         measured_time = defaultdict(float)
@@ -513,8 +524,9 @@ class LearnedIndex(Logger):
         """(bucket_order int32[nq, n_buckets, n_levels], inference seconds) -- LearnedIndex.py:163-252.
 
         1 level: lmi_mlp_topk on the root model.  More levels: lmi_nav_order on the resident index (`prepare`
-        uploaded the tree); the visited buckets' flat child indices are mapped back to their paths.  With the path-mass stop on
-        (`Index.set_path_mass` on the resident engine) the slots behind a query's stop are EMPTY_VALUE paths."""
+        uploaded the tree); the visited buckets' flat child indices are mapped back to their paths.  With the path-mass stop or the
+        row-budget stop on (`Index.set_path_mass` / `Index.set_stop_rows` on the resident engine) the slots behind a query's stop are
+        EMPTY_VALUE paths."""
         assert self.root_model is not None, "Model is not trained, call `build` first."
         qn = np.ascontiguousarray(queries_navigation, dtype=np.float32)
         n_queries, n_levels = qn.shape[0], len(n_categories)

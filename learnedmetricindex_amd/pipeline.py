@@ -45,12 +45,14 @@ class HostPipeline:
     def __init__(self, index, nq: int, d_nav: int, d_search: int, nb: int, k: int = 10, depth: int = 2,
                  device: Optional[int] = None, same_queries: bool = False, want_bucket_order: bool = False,
                  search_fn=None, overlap_inference: bool = True, two_handles: bool = False, sharded=None, use_graph: bool = False,
-                 direct_out: bool = False, native_submit: bool = True, share_streams: bool = True, stop_mass: Optional[float] = None):
+                 direct_out: bool = False, native_submit: bool = True, share_streams: bool = True, stop_mass: Optional[float] = None,
+                 stop_rows: Optional[int] = None):
         """`search_fn(qn_dev, qs_dev) -> (dists_t, ids_t, bucket_order_t)`: optional replacement of the single-GPU
         `lmi_search` call, run on the compute stream (the bucket-sharded searcher of sharded.py, whose collectives
         then run on that stream too); its output tensors may be reused by its next call.
         `stop_mass`: the probability-mass stop (`Index.set_stop_mass`) for every batch, set on every handle the pipeline
-        alternates between; `close()` gives the index its earlier value back.  None leaves the handles' own setting."""
+        alternates between; `close()` gives the index its earlier value back.  None leaves the handles' own setting.
+        `stop_rows`: the row-budget stop (`Index.set_stop_rows`), handled the same way."""
         import torch
 
         self.index, self.nq, self.nb, self.k, self.depth = index, int(nq), int(nb), int(k), int(depth)
@@ -94,6 +96,16 @@ class HostPipeline:
             before = index.stop_mass
             index.set_stop_mass(stop_mass)
             self._mass_before = before
+        self._rows_before = None
+        if stop_rows is not None:   # likewise; a refused value takes the stop_mass set just above back
+            try:
+                before = index.stop_rows
+                index.set_stop_rows(stop_rows)
+                self._rows_before = before
+            except BaseException:
+                if self._mass_before is not None:
+                    index.set_stop_mass(self._mass_before)
+                raise
         if self.two:
             twin = index.clone_view()
             twin.set_stream(s2.cuda_stream)
@@ -299,6 +311,9 @@ class HostPipeline:
         if self._mass_before is not None:   # the constructor's stop_mass ends with the pipeline
             self.index.set_stop_mass(self._mass_before)
             self._mass_before = None
+        if self._rows_before is not None:
+            self.index.set_stop_rows(self._rows_before)
+            self._rows_before = None
         for h, _ in self.handles[1:]:
             h.close()
             views = getattr(self.index, "_views", [])

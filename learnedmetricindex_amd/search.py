@@ -75,6 +75,7 @@ class Experiment:
     job: str = "unknown"
     stop_mass: Optional[float] = None
     path_mass: Optional[float] = None
+    stop_rows: Optional[int] = None
     storage: str = "f32"
     trainer: str = "torch"
 
@@ -103,6 +104,10 @@ class Experiment:
         p.add_argument("--path-mass", type=float, default=None,
                        help="multi-level indexes: a query's walk stops once the path probabilities of the buckets it has recorded "
                             "sum to this (0 < mass <= 1); default: every query visits its whole budget")
+        p.add_argument("--stop-rows", type=int, default=None,
+                       help="any index: a query stops visiting buckets once the buckets it has visited hold this many objects "
+                            "(an integer >= 1; the bucket that crosses the budget is scanned whole); default: every query visits its "
+                            "whole budget")
         p.add_argument("--storage", choices=("f32", "f16"), default="f32",
                        help="how the resident index keeps the scan vectors: f16 = the fp16 fragments only, a third of the device memory, "
                             "for vectors that are binary16-exact (refused otherwise); same results")
@@ -120,6 +125,8 @@ class Experiment:
             p.error("--path-mass needs a multi-level index (on a 1-level index use --stop-mass)")
         if a["path_mass"] is not None and not 0.0 < a["path_mass"] <= 1.0:
             p.error("--path-mass must lie in (0, 1]")
+        if a["stop_rows"] is not None and a["stop_rows"] < 1:
+            p.error("--stop-rows must be an integer >= 1")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -281,14 +288,15 @@ def run(exp: Experiment) -> Dict:
     sink, out = ResultSink(), {}
     for budget in bucket_budgets(exp.buckets_perc, n_buckets_in_index):
         dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass,
-                                                     path_mass=exp.path_mass)
+                                                     path_mass=exp.path_mass, stop_rows=exp.stop_rows)
         LOG.info("%d buckets: search %.4fs (inference %.4fs, within buckets %.4fs, scan %.4fs, merge %.4fs)", budget,
                  clock["search"], clock["inference"], clock["search_within_buckets"], clock["seq_search"], clock["sort"])
         if exp.evaluate:
             out[f"recall_{budget}"] = recall_against_bruteforce(scan_q, scan, knns, exp.k)
             LOG.info("%d buckets: recall@%d = %.5f", budget, exp.k, out[f"recall_{budget}"])
         stem = exp.tag(f"learned-index-{exp.dataset}-{exp.size}", buck=budget, **({} if exp.stop_mass is None else {"stop": exp.stop_mass}),
-                       **({} if exp.path_mass is None else {"pathmass": exp.path_mass}))
+                       **({} if exp.path_mass is None else {"pathmass": exp.path_mass}),
+                       **({} if exp.stop_rows is None else {"stoprows": exp.stop_rows}))
         sink.write(exp.dataset, exp.size, stem, dists, knns, algo="Learned-index", data=src.stamp(exp.dataset),
                    buildtime=build_s, querytime=clock["search"], size=exp.size, params=stem)
         out[budget] = (dists, knns, clock)

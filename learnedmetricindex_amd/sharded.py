@@ -147,16 +147,26 @@ class ShardedSearcher:
     averages `Index.timings_mean()` how many C-ABI calls one search makes."""
 
     def __init__(self, index, rank: int, world: int, group=None, shard_inference: bool = True, lib_comm=None,
-                 stop_mass: Optional[float] = None):
+                 stop_mass: Optional[float] = None, stop_rows: Optional[int] = None):
         """`lib_comm`: an ncclComm_t from `Index.comm_init` -- the result exchange then runs inside the library
         (`lmi_allgather_merge`: ncclAllGather + merge kernel on the handle's stream) instead of torch.distributed.
         `stop_mass`: the probability-mass stop (`Index.set_stop_mass`), set on the rank's handle until `close()` gives
         the handle its earlier value back; None leaves the handle's own setting.  Every rank cuts the order of the queries
-        it routes (its slice, or the whole batch), so the gathered order carries the -1s and every rank skips the same slots."""
+        it routes (its slice, or the whole batch), so the gathered order carries the -1s and every rank skips the same slots.
+        `stop_rows`: the row-budget stop (`Index.set_stop_rows`), kept and given back like `stop_mass`.  World of one only: a
+        rank of a bucket-sharded index holds its own buckets' counts, not the other ranks', so ValueError for world > 1 (before
+        anything is set)."""
+        if stop_rows is not None and world > 1:
+            raise ValueError("stop_rows is not supported on a bucket-sharded index of more than one rank (a rank does not know the "
+                             "other ranks' bucket sizes); ReplicaSearcher holds the whole index on every rank")
         self._mass_before = None
+        self._rows_before = None
         if stop_mass is not None:
             self._mass_before = index.stop_mass
             index.set_stop_mass(stop_mass)
+        if stop_rows is not None:
+            self._rows_before = index.stop_rows
+            index.set_stop_rows(stop_rows)
         self.index, self.rank, self.world, self.group = index, rank, world, group
         self.lib_comm = lib_comm
         self.shard_inference = bool(shard_inference) and world > 1
@@ -169,10 +179,13 @@ class ShardedSearcher:
         self._coll = {"bucket_order_allgather": [], "result_allgather_merge": []}
 
     def close(self) -> None:
-        """Ends the constructor's `stop_mass`: the handle gets the value it had before (the index itself stays open)."""
+        """Ends the constructor's `stop_mass` / `stop_rows`: the handle gets the values it had before (the index itself stays open)."""
         if self._mass_before is not None:
             self.index.set_stop_mass(self._mass_before)
             self._mass_before = None
+        if self._rows_before is not None:
+            self.index.set_stop_rows(self._rows_before)
+            self._rows_before = None
 
     def _timed(self, name, fn, on_cuda: bool):
         if not self.time_collectives or self.world == 1:
@@ -279,11 +292,16 @@ class ReplicaSearcher:
     shard_inference = False   # (HostPipeline: nothing to route ahead of the search call)
     lib_comm = None
 
-    def __init__(self, index, rank: int, world: int, group=None, stop_mass: Optional[float] = None):
-        """`stop_mass`: as `ShardedSearcher` (a rank's slice of the batch is cut by its own search call; `close()` ends it)."""
+    def __init__(self, index, rank: int, world: int, group=None, stop_mass: Optional[float] = None, stop_rows: Optional[int] = None):
+        """`stop_mass`: as `ShardedSearcher` (a rank's slice of the batch is cut by its own search call; `close()` ends it).
+        `stop_rows`: the row-budget stop, for any world: every rank holds the whole index and with it every bucket's count."""
         self.index, self.rank, self.world, self.group = index, rank, world, group
         self._buf = None
         self._mass_before = None
+        self._rows_before = None
+        if stop_rows is not None:
+            self._rows_before = index.stop_rows
+            index.set_stop_rows(stop_rows)
         if stop_mass is not None:
             self._mass_before = index.stop_mass
             index.set_stop_mass(stop_mass)
