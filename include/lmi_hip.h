@@ -306,7 +306,14 @@ LMI_API int lmi_buckets_insert_f16(lmi_index *h, const uint16_t *rows, const int
 LMI_API int lmi_bucket_read_f16(lmi_index *h, int bucket, uint16_t *rows, uint32_t *ids);
 
 /* Navigation: bucket_order[nq][nb] <- the nb most probable classes per query, most probable first.
- * logits (nullable) [nq][L] <- raw outputs of the last Linear layer. */
+ * logits (nullable) [nq][L] <- raw outputs of the last Linear layer.
+ * With on_device, queries_nav (here and in every call that takes it) must be 16-byte aligned -- any whole device allocation is:
+ * where the input width is a multiple of 4 the fused kernel reads it 16 bytes at a time.
+ * Non-finite values: a logit of -inf is an ordinary value (it ranks last, lower class first, with probability 0).  A NaN logit
+ * compares with nothing, so it is never selected: a query's ranks run out after its comparable classes and the remaining ranks
+ * are class -1 (in lmi_mlp_proba with probability NaN, and the row sum makes every other probability of that query NaN too; a
+ * query whose logits are all NaN -- a NaN feature, for one -- gets -1 and NaN throughout).  The oracle defines no order there;
+ * the fused and the per-layer forms return the same bits. */
 LMI_API int lmi_mlp_topk(lmi_index *h, const float *queries_nav, int nq, int nb, int32_t *bucket_order,
                  float *logits, int on_device);
 
@@ -608,6 +615,45 @@ enum {
  * min(n, LMI_PLAN_COUNT) words. */
 LMI_API int lmi_debug_last_plan(lmi_index *h, int32_t *out, int n);
 LMI_API int lmi_debug_plan(lmi_index *h, int nq, int n_buckets, int k, int32_t *out, int n);
+
+/* Test hooks for the MLP forward's dispatch (tests/test_gpu_mlp_seams.py; no reference counterpart): which form lmi_mlp_topk /
+ * lmi_mlp_proba (and the MLP step of lmi_search / lmi_pipeline_submit) take for a batch.  The words up to LAYERS_QUERIES are the
+ * call's plan, decided from (handle, nq, n_buckets, probabilities wanted, logits wanted) before the first launch; the rest are
+ * what the launch sites pick on top of it. */
+enum {
+    LMI_MLP_PLAN_NUM_CUS = 0,     /* compute units of the handle's device: most thresholds below are functions of it           */
+    LMI_MLP_PLAN_FM_OK,           /* every model of the handle fits mlp_fused_kernel (hidden widths <= 512)                    */
+    LMI_MLP_PLAN_LOGITS_LDS,      /* the last layer's outputs stay in LDS (<= 512 classes); 0: through global memory           */
+    LMI_MLP_PLAN_LDS_BYTES,       /* dynamic LDS of a fused block for the current model set                                    */
+    LMI_MLP_PLAN_FUSED,           /* a mlp_fused_kernel launch is part of the call                                             */
+    LMI_MLP_PLAN_MODE,            /* its instance: 0 TOPK, 1 PROBA, 3 TOPK_STOP, 5 TOPK_ROWS; -1: no fused launch              */
+    LMI_MLP_PLAN_FUSED_BLOCKS,    /* its grid (0: none)                                                                        */
+    LMI_MLP_PLAN_NQ_HEAD,         /* queries the fused launch takes: nq when the batch is not split, 0 when per-layer only     */
+    LMI_MLP_PLAN_LAYERS_QUERIES,  /* queries that go through the mlp_layer_kernel chain: the split's tail, or all, or 0        */
+    LMI_MLP_PLAN_CBW0,            /* mlp_layer_kernel<LAST, CBW>: col-blocks per wave of layer i of that chain (1, 2 or 4);    */
+    LMI_MLP_PLAN_CBW1,            /* -1: no such launch                                                                        */
+    LMI_MLP_PLAN_CBW2,
+    LMI_MLP_PLAN_CBW3,
+    LMI_MLP_PLAN_CBW4,
+    LMI_MLP_PLAN_CBW5,
+    LMI_MLP_PLAN_CBW6,
+    LMI_MLP_PLAN_CBW7,
+    LMI_MLP_PLAN_RANK_KERNEL,     /* the separate ranking launch (behind the per-layer chain, or behind a fused launch whose    */
+                                  /* logits went through global memory): 0 rank_classes_kernel, 1 rank_classes_stop_kernel,    */
+                                  /* 2 rank_classes_rows_kernel; -1: every query is ranked in the fused kernel's epilogue      */
+    LMI_MLP_PLAN_SOFTMAX_KERNEL,  /* softmax_ranked_kernel is part of the call                                                 */
+    LMI_MLP_PLAN_VEC_IN,          /* the fused kernel's layer 0 fetches float4 (d % 4 == 0; a partial last chunk is fetched    */
+                                  /* element by element all the same); -1: no fused launch                                     */
+    LMI_MLP_PLAN_IN_CHUNKS,       /* 96-feature chunks of the fused kernel's layer 0; -1: no fused launch                      */
+    LMI_MLP_PLAN_COUNT
+};
+/* lmi_debug_last_mlp_plan: what the last MLP forward on this handle did, recorded by mlp_enqueue and its launch sites as they ran
+ * (all zero before the first one; a refused call records nothing).  lmi_debug_mlp_plan: what a forward of nq queries would do --
+ * n_buckets as lmi_mlp_topk takes it (ignored with want_proba), want_proba != 0: lmi_mlp_proba, want_logits != 0: lmi_mlp_topk with
+ * its logits output; the same decision function and the same argument checks as the calls; launches nothing and changes nothing.
+ * Both write min(n, LMI_MLP_PLAN_COUNT) words. */
+LMI_API int lmi_debug_last_mlp_plan(lmi_index *h, int32_t *out, int n);
+LMI_API int lmi_debug_mlp_plan(lmi_index *h, int nq, int n_buckets, int want_proba, int want_logits, int32_t *out, int n);
 
 #ifdef __cplusplus
 }

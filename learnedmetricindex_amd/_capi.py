@@ -23,6 +23,9 @@ T_INFERENCE, T_ROUTE, T_SCAN, T_MERGE, T_TOTAL, T_PF_SAMPLE, T_PF_EMIT, T_RESCOR
 PLAN_FIELDS = ("fast", "low_d", "ps_wide", "tile_cb", "sample_max", "qbound", "primary_nb", "use_front", "streamed", "G", "use_tail",
                "tail_merges", "KG16", "dp", "route_nb_template", "pack_gs", "pack_cp", "pack_vec", "route_sort_global", "merge_kind",
                "rescore_small_waves", "overflow_sorted")
+#: the LMI_MLP_PLAN_* words, in their order (lmi_debug_last_mlp_plan / lmi_debug_mlp_plan)
+MLP_PLAN_FIELDS = ("num_cus", "fm_ok", "logits_lds", "lds_bytes", "fused", "mode", "fused_blocks", "nq_head", "layers_queries",
+                   "cbw0", "cbw1", "cbw2", "cbw3", "cbw4", "cbw5", "cbw6", "cbw7", "rank_kernel", "softmax_kernel", "vec_in", "in_chunks")
 #: the LMI_KNN_PLAN_* words, in their order (lmi_debug_knn_plan)
 KNN_PLAN_FIELDS = ("PIECES", "PIECE_ROWS", "SPLITS", "QUERY_GROUPS", "QUERY_ROWS", "VEC_XQ", "VEC_XB", "WORKSPACE_BYTES", "LIST_ROWS")
 KNN_METRICS = {"ip": 0, "l2": 1}   # LMI_METRIC_IP, LMI_METRIC_L2
@@ -108,6 +111,8 @@ SIGNATURES = {
     "lmi_debug_layout": (ctypes.c_int, [_vp, _vp, _vp, _i64p, _i64p, _vp]),
     "lmi_debug_last_plan": (ctypes.c_int, [_vp, _i32p, ctypes.c_int]),
     "lmi_debug_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int]),
+    "lmi_debug_last_mlp_plan": (ctypes.c_int, [_vp, _i32p, ctypes.c_int]),
+    "lmi_debug_mlp_plan": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int]),
     # binary16 rows and queries as they are distributed (uint16 bit patterns; arguments as the namesakes')
     "lmi_buckets_add_rows_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "lmi_buckets_add_owned_rows_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
@@ -392,6 +397,20 @@ class Index:
         w = (ctypes.c_int32 * len(PLAN_FIELDS))()
         _check(lib().lmi_debug_plan(self._h, int(nq), int(nb), int(k), w, len(PLAN_FIELDS)))
         return dict(zip(PLAN_FIELDS, (int(v) for v in w)))
+
+    def debug_last_mlp_plan(self) -> dict:
+        """Test hook (`lmi_debug_last_mlp_plan`): the form the last MLP forward on this handle took (`mlp_topk`, `mlp_proba`, the
+        MLP step of `search`), as recorded while it ran -- `MLP_PLAN_FIELDS` -> int; all zero before the first one."""
+        w = (ctypes.c_int32 * len(MLP_PLAN_FIELDS))()
+        _check(lib().lmi_debug_last_mlp_plan(self._h, w, len(MLP_PLAN_FIELDS)))
+        return dict(zip(MLP_PLAN_FIELDS, (int(v) for v in w)))
+
+    def debug_mlp_plan(self, nq: int, nb: int = 1, want_proba: bool = False, want_logits: bool = False) -> dict:
+        """Test hook (`lmi_debug_mlp_plan`): the form `mlp_topk(q[nq], nb, want_logits)` -- or, with `want_proba`, `mlp_proba(q[nq])` --
+        would take on this handle; the calls' argument checks, nothing is launched."""
+        w = (ctypes.c_int32 * len(MLP_PLAN_FIELDS))()
+        _check(lib().lmi_debug_mlp_plan(self._h, int(nq), int(nb), int(bool(want_proba)), int(bool(want_logits)), w, len(MLP_PLAN_FIELDS)))
+        return dict(zip(MLP_PLAN_FIELDS, (int(v) for v in w)))
 
     def set_stream(self, stream_ptr: int) -> None:
         _check(lib().lmi_set_stream(self._h, _vp(stream_ptr)))

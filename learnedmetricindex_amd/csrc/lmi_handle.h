@@ -211,6 +211,7 @@ struct CallState {
     bool last_fast = false;
     static constexpr int PLAN_WORDS = 32;
     int32_t last_plan[PLAN_WORDS] = {};   // lmi_debug_last_plan: the LMI_PLAN_* words of the last scan, written by scan_enqueue and its launch sites
+    int32_t last_mlp_plan[PLAN_WORDS] = {};   // lmi_debug_last_mlp_plan: the LMI_MLP_PLAN_* words of the last MLP forward, written by mlp_enqueue and its launch sites
     DevBuf act[2], xfrag, logits, order, q_nav, q_srch;
     DevBuf m, cb_start, item_base, part_base, stats, head, slot_local, slot_col, colmap, qfrag, grp, col_thr;
     DevBuf part_score, part_row, rank_d, rank_id, out_d, out_id, out_key;

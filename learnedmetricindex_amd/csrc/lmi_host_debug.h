@@ -159,6 +159,29 @@ extern "C" LMI_API int lmi_debug_plan(lmi_index* h, int nq, int nb, int k, int32
     return 0;
 }
 
+// ---- test hooks (tests/test_gpu_mlp_seams.py): which form an MLP forward takes ----
+extern "C" LMI_API int lmi_debug_last_mlp_plan(lmi_index* h, int32_t* out, int n) {
+    if (!h || !out) return fail("lmi_debug_last_mlp_plan: NULL argument");
+    if (n < 1) return fail("lmi_debug_last_mlp_plan: n %d < 1", n);
+    std::copy(h->last_mlp_plan, h->last_mlp_plan + std::min<int>(n, LMI_MLP_PLAN_COUNT), out);
+    return 0;
+}
+
+extern "C" LMI_API int lmi_debug_mlp_plan(lmi_index* h, int nq, int nb, int want_proba, int want_logits, int32_t* out, int n) {
+    if (!h || !out) return fail("lmi_debug_mlp_plan: NULL argument");
+    if (n < 1) return fail("lmi_debug_mlp_plan: n %d < 1", n);
+    if (nq < 0) return fail("lmi_debug_mlp_plan: nq < 0");
+    const bool proba = want_proba != 0;
+    if (proba && h->root().n_layers > 0) nb = h->root().dims.back();   // lmi_mlp_proba ranks every class
+    RankStop stop;
+    CHK(mlp_call_check(h, nb, proba, "lmi_debug_mlp_plan", stop));
+    const FusedLds F = fused_lds_plan(h->models);   // what build_descs would find, without touching the device
+    int32_t w[LMI_MLP_PLAN_COUNT];
+    mlp_plan_report(h, F, mlp_plan(h->num_cus, h->fused_mlp, F.ok, F.logits_lds, nq, proba, want_logits != 0 && !proba, stop), stop, proba, w);
+    std::copy(w, w + std::min<int>(n, LMI_MLP_PLAN_COUNT), out);
+    return 0;
+}
+
 extern "C" LMI_API int lmi_debug_read_candidates(lmi_index* h, int64_t slot, int cap, uint32_t* rows, float* shat,
                                          int* count, float* eps2, float* qscale, float* xscale) {
     if (!h) return fail("lmi_debug_read_candidates: NULL handle");

@@ -97,12 +97,16 @@ struct RankStop {
 // the class ranking behind the per-layer kernels and behind a fused launch whose logits went through global memory: with the row
 // budget on rank_classes_rows_kernel (which applies a mass as well), with the mass stop alone rank_classes_stop_kernel takes
 // rank_classes_kernel's place
-static int rank_enqueue(hipStream_t st, const float* d_logits, int nq, int L, int nb, const RankStop& S, int* d_order) {
+// (LMI_MLP_PLAN_RANK_KERNEL: 0 rank_classes_kernel, 1 rank_classes_stop_kernel, 2 rank_classes_rows_kernel)
+static int rank_kernel_of(const RankStop& S) { return S.rows > 0 ? 2 : S.mass > 0.0f ? 1 : 0; }
+static int rank_enqueue(lmi_index* h, hipStream_t st, const float* d_logits, int nq, int L, int nb, const RankStop& S, int* d_order) {
     const float mass = S.mass;
-    if (S.rows > 0) rank_classes_rows_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, S.nb_rows, S.rows, d_order);
-    else if (mass > 0.0f) rank_classes_stop_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, d_order);
+    const int kind = rank_kernel_of(S);
+    if (kind == 2) rank_classes_rows_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, S.nb_rows, S.rows, d_order);
+    else if (kind == 1) rank_classes_stop_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, mass, d_order);
     else rank_classes_kernel<<<nq, 64, 0, st>>>(d_logits, nq, L, nb, d_order);
     HIPCHK(hipGetLastError());
+    h->last_mlp_plan[LMI_MLP_PLAN_RANK_KERNEL] = kind;
     return 0;
 }
 
@@ -131,11 +135,24 @@ extern "C" LMI_API int lmi_nav_set_model(lmi_index* h, int model_id, int n_layer
     return pack_model(h, "lmi_nav_set_model", n_layers, dims, W, b, h->models[model_id]);
 }
 
+// every model of a tree reads the same query rows: the walk hands mlp_fused_kernel ONE input width (the root's, fused_base) while a
+// node's layer 0 is packed for its own dims[0], so a node of another width would be evaluated on the wrong features without a fault.
+// Checked when the tree is set and again before every walk (lmi_set_mlp may replace the root under a tree that was set).
+static int tree_widths_check(const lmi_index* h, const char* who) {
+    const int d = h->root().dims[0];
+    for (size_t m = 1; m < h->models.size(); ++m)
+        if (h->models[m].n_layers > 0 && h->models[m].dims[0] != d)
+            return fail("%s: model %zu takes %d input features, the root model %d: every model of a tree reads the same queries", who, m,
+                        h->models[m].dims[0], d);
+    return 0;
+}
+
 extern "C" LMI_API int lmi_nav_set_tree(lmi_index* h, int n_models, const int32_t* child_offset, const int32_t* child_model,
                                 const int32_t* child_bucket) {
     if (!h) return fail("lmi_nav_set_tree: NULL handle");
     if (h->root().n_layers == 0) return fail("lmi_nav_set_tree: no root model (lmi_set_mlp)");
     if (n_models != (int)h->models.size()) return fail("lmi_nav_set_tree: %d models, %d set (root + lmi_nav_set_model)", n_models, (int)h->models.size());
+    CHK(tree_widths_check(h, "lmi_nav_set_tree"));
     if (!child_offset || !child_model || !child_bucket || child_offset[0] != 0) return fail("lmi_nav_set_tree: bad arguments");
     for (int m = 0; m < n_models; ++m) {
         if (h->models[m].n_layers == 0) return fail("lmi_nav_set_tree: model %d has no weights (lmi_nav_set_model)", m);
@@ -163,38 +180,60 @@ extern "C" LMI_API int lmi_nav_set_tree(lmi_index* h, int n_models, const int32_
     return 0;
 }
 
+// the LDS plan of mlp_fused_kernel for a model set, from the models' shapes alone (build_descs and lmi_debug_mlp_plan)
+struct FusedLds {
+    bool ok = true;           // every model fits the fused kernel
+    bool logits_lds = true;   // every model's last layer keeps its outputs in LDS
+    int s0 = 1, s1 = 1;       // strides of the two activation buffers: the widest padded layer of either parity, + 1
+    int lds = 0;              // bytes
+};
+static FusedLds fused_lds_plan(const std::vector<Model>& models) {
+    FusedLds F;
+    int w0 = 0, w1 = 0;
+    for (const Model& M : models) {
+        if (M.n_layers == 0) { F.ok = false; continue; }
+        for (int i = 0; i < M.n_layers; ++i) {
+            const int padded = M.n_rb[i] * 32;
+            const bool last = i + 1 == M.n_layers;
+            if (padded > FM_MAXH) { if (last) F.logits_lds = false; else F.ok = false; continue; }
+            int& wref = (i & 1) ? w1 : w0;
+            wref = std::max(wref, padded);
+        }
+    }
+    F.s0 = w0 + 1;
+    F.s1 = w1 + 1;
+    F.lds = (2 * FM_COLS * FM_CHUNK_S + FM_COLS * F.s0 + FM_COLS * F.s1) * 4;
+    // (cannot fire while the widths kept in LDS are capped at FM_MAXH = 512: 24 832 + 128 (w0 + w1 + 2) <= 156 160 < 162 816)
+    if (F.lds > 160 * 1024 - 1024) F.ok = false;
+    return F;
+}
+
 // device descriptors of every model + the LDS plan of mlp_fused_kernel for the current model set
 static int build_descs(lmi_index* h) {
     if (!h->desc_dirty) return 0;
     const int nm = (int)h->models.size();
     std::vector<ModelDesc> D(nm);
-    bool ok = true, logits_lds = true;
-    int w0 = 0, w1 = 0;
     for (int m = 0; m < nm; ++m) {
         const Model& M = h->models[m];
         ModelDesc& d = D[m];
         memset(&d, 0, sizeof(d));
         d.n_layers = M.n_layers;
-        if (M.n_layers == 0) { ok = false; continue; }
+        if (M.n_layers == 0) continue;
         for (int i = 0; i <= M.n_layers; ++i) d.dims[i] = M.dims[i];
         for (int i = 0; i < M.n_layers; ++i) {
             d.KG[i] = M.KG[i];
             d.W[i] = M.Wf[i].as<float4>();
             d.b[i] = M.bias[i].as<float>();
-            const int padded = M.n_rb[i] * 32;
-            const bool last = i + 1 == M.n_layers;
-            if (padded > FM_MAXH) { if (last) logits_lds = false; else ok = false; continue; }
-            int& wref = (i & 1) ? w1 : w0;
-            wref = std::max(wref, padded);
         }
     }
-    h->fm_s0 = w0 + 1;
-    h->fm_s1 = w1 + 1;
+    const FusedLds F = fused_lds_plan(h->models);
+    const bool ok = F.ok;
+    h->fm_s0 = F.s0;
+    h->fm_s1 = F.s1;
     h->fm_act0 = FM_COLS * h->fm_s0;
-    h->fm_lds = (2 * FM_COLS * FM_CHUNK_S + FM_COLS * h->fm_s0 + FM_COLS * h->fm_s1) * 4;
-    if (h->fm_lds > 160 * 1024 - 1024) ok = false;
+    h->fm_lds = F.lds;
     h->fm_ok = ok;
-    h->fm_logits_lds = logits_lds ? 1 : 0;
+    h->fm_logits_lds = F.logits_lds ? 1 : 0;
     CHK(h->d_models.reserve(sizeof(ModelDesc) * nm));
     HIPCHK(hipMemcpy(h->d_models.p, D.data(), sizeof(ModelDesc) * nm, hipMemcpyHostToDevice));
     if (ok) {
@@ -221,6 +260,56 @@ static void fused_base(lmi_index* h, const float* d_q, int nq, FusedParams& P) {
     P.act0_floats = h->fm_act0;
     P.logits_in_lds = h->fm_logits_lds;
 }
+
+// ---- the MLP forward's dispatch.  mlp_plan() decides which form a batch takes; the functions below it are the instances the
+// launch sites pick on top.  Each is ONE function, called by the launch and by the plan report (mlp_plan_report,
+// lmi_debug_mlp_plan), so that the report cannot drift from the launch ----
+struct MlpPlan {
+    int fused = 0;            // a mlp_fused_kernel launch
+    int mode = -1;            // its FM_* instance
+    int grid = 0;             // its blocks
+    int nq_head = 0;          // the queries it takes
+    int layers_queries = 0;   // the queries of the mlp_layer_kernel chain (a split batch's tail, or the whole batch)
+};
+// fm_ok / logits_lds: the model set's LDS plan (fused_lds_plan); proba: lmi_mlp_proba; want_logits: the caller takes the logits
+static MlpPlan mlp_plan(int num_cus, int fused_mlp, bool fm_ok, bool logits_lds, int nq, bool proba, bool want_logits, const RankStop& stop) {
+    MlpPlan P;
+    // One launch for every layer + ranking when the batch fills the chip (a block = 32 queries, one per CU for the wide
+    // models: 8 192 queries 100 us against 138 us for the per-layer kernels); small batches (a rank's slice of a
+    // sharded batch, single queries) have too few 32-query blocks for that and take the per-layer kernels, whose grids
+    // also split the features (2 048 queries: 79 us against 88 us).  predict_proba always takes the fused kernel.
+    const bool fill = cdiv(nq, FM_COLS) * 2 >= num_cus || proba || fused_mlp == 2;
+    if (!(fused_mlp && fm_ok && fill)) {
+        P.layers_queries = nq;
+        return P;
+    }
+    // every layer, the ranking and the softmax in ONE launch (lmi_mlp_fused.h)
+    // A batch whose last round of 32-query blocks would fill under 30 % of the CUs (10 000 queries: 313 blocks = 256 + 57)
+    // pays a whole second round for it.  The tail's queries go through the per-layer kernels on a side stream instead,
+    // beside the fused kernel's one full round (the fused blocks leave wave slots and half of the MFMA pipe): 182 ->
+    // ~125 us at 10 000 queries; identical results (both forms are the canonical chain).
+    P.fused = 1;
+    P.mode = proba ? FM_PROBA : stop.rows > 0 ? FM_TOPK_ROWS : stop.mass > 0.0f ? FM_TOPK_STOP : FM_TOPK;
+    P.grid = cdiv(nq, FM_COLS);
+    P.nq_head = nq;
+    const int rem = P.grid % num_cus;
+    if (fused_mlp == 1 && !proba && !want_logits && logits_lds && P.grid > num_cus && rem > 0 && rem * 10 < num_cus * 3) {
+        P.nq_head = (P.grid - rem) * FM_COLS;
+        P.grid -= rem;
+        P.layers_queries = nq - P.nq_head;
+    }
+    return P;
+}
+// mlp_layer_kernel<LAST, CBW>: col-blocks per wave: 4 when that already gives every CU two blocks, else 2, else 1 (e.g. the
+// 120-class output layer has 4 feature blocks = one block row; 768->512 on 10 000 queries had 316 blocks of CBW 4 on 256 CUs)
+static int mlp_layer_cbw(int num_cus, int n_rb, int ncb) {
+    const int rows = cdiv(n_rb, 4);
+    return rows * cdiv(ncb, 4) >= 2 * num_cus ? 4 : rows * cdiv(ncb, 2) >= 2 * num_cus ? 2 : 1;
+}
+// mlp_fused_kernel's layer 0, restated for the report: whole chunks are fetched as float4 when the rows are 16-byte multiples,
+// and the input goes through LDS in chunks of FM_CHUNK features
+static int fused_vec_in(int d) { return (d & 3) == 0; }
+static int fused_in_chunks(int KG0) { return cdiv(KG0 * 8, FM_CHUNK); }
 
 // MLP forward + class ranking (+ softmax when d_probs: then nb == L and d_order receives the full class order)
 // the per-layer form: one mlp_layer_kernel launch per Linear, then the ranking (and softmax) kernels, on stream `st`
@@ -249,11 +338,9 @@ static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, in
     const float4* in = h->xfrag.as<float4>();
     for (int i = 0; i < R.n_layers; ++i) {
         const bool last = i + 1 == R.n_layers;
-        // col-blocks per wave: 4 when that already gives every CU two blocks, else 2, else 1 (e.g. the
-        // 120-class output layer has 4 feature blocks = one block row; 768->512 on 10 000 queries had 316
-        // blocks of CBW 4 on 256 CUs)
         const int rows = cdiv(R.n_rb[i], 4);
-        const int cbw = rows * cdiv(ncb, 4) >= 2 * h->num_cus ? 4 : rows * cdiv(ncb, 2) >= 2 * h->num_cus ? 2 : 1;
+        const int cbw = mlp_layer_cbw(h->num_cus, R.n_rb[i], ncb);
+        h->last_mlp_plan[LMI_MLP_PLAN_CBW0 + i] = cbw;
         dim3 grid(cdiv(ncb, cbw), rows);
         float* o = last ? d_logits : h->act[i & 1].as<float>();
         const int KGn = last ? 0 : R.n_rb[i] * 4;
@@ -269,47 +356,72 @@ static int mlp_layers_enqueue(lmi_index* h, hipStream_t st, const float* d_q, in
 #undef LMI_MLP_LAUNCH
         HIPCHK(hipGetLastError());
     }
-    CHK(rank_enqueue(st, d_logits, nq, L, nb, stop, d_order));
+    CHK(rank_enqueue(h, st, d_logits, nq, L, nb, stop, d_order));
     if (d_probs) {
         softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, st>>>(d_logits, d_order, nq, L, d_probs);
         HIPCHK(hipGetLastError());
+        h->last_mlp_plan[LMI_MLP_PLAN_SOFTMAX_KERNEL] = 1;
     }
     return 0;
 }
 
-static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs = nullptr) {
-    if (h->root().n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
+// what mlp_enqueue and lmi_debug_mlp_plan check alike, behind the caller's name, and the stops a bucket order of nb ranks is cut by
+static int mlp_call_check(lmi_index* h, int nb, bool proba, const char* who, RankStop& stop) {
+    if (h->root().n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
     const int L = h->root().dims.back();
-    if (nb < 1 || nb > L) return fail("lmi_mlp_topk: n_buckets %d outside [1,%d]", nb, L);
-    CHK(build_descs(h));
+    if (nb < 1 || nb > L) return fail("%s: n_buckets %d outside [1,%d]", who, nb, L);
     // the probability-mass stop (lmi_set_stop_mass) cuts a bucket order; predict_proba's full class order and a single rank are never cut
-    const float mass = (!d_probs && nb > 1) ? h->stop_mass : 0.0f;
+    stop.mass = (!proba && nb > 1) ? h->stop_mass : 0.0f;
     // the row budget (lmi_set_stop_rows) likewise; both halves of a split batch and every ranking path take the same `stop`
-    RankStop stop;
-    stop.mass = mass;
-    stop.rows = (!d_probs && nb > 1) ? (long long)h->stop_rows : 0;
+    stop.rows = (!proba && nb > 1) ? (long long)h->stop_rows : 0;
     if (stop.rows > 0) {
-        CHK(stop_rows_check(h, false, "lmi_mlp_topk"));
+        CHK(stop_rows_check(h, false, who));
         stop.nb_rows = h->d_nb_rows.as<int>();
     }
-    // One launch for every layer + ranking when the batch fills the chip (a block = 32 queries, one per CU for the wide
-    // models: 8 192 queries 100 us against 138 us for the per-layer kernels); small batches (a rank's slice of a
-    // sharded batch, single queries) have too few 32-query blocks for that and take the per-layer kernels, whose grids
-    // also split the features (2 048 queries: 79 us against 88 us).  predict_proba always takes the fused kernel.
-    const bool fill = cdiv(nq, FM_COLS) * 2 >= h->num_cus || d_probs != nullptr || h->fused_mlp == 2;
-    if (h->fused_mlp && h->fm_ok && fill) {
-        // every layer, the ranking and the softmax in ONE launch (lmi_mlp_fused.h)
-        // A batch whose last round of 32-query blocks would fill under 30 % of the CUs (10 000 queries: 313 blocks = 256 + 57)
-        // pays a whole second round for it.  The tail's queries go through the per-layer kernels on a side stream instead,
-        // beside the fused kernel's one full round (the fused blocks leave wave slots and half of the MFMA pipe): 182 ->
-        // ~125 us at 10 000 queries; identical results (both forms are the canonical chain).
-        int grid = cdiv(nq, FM_COLS);
-        int nq_head = nq;
-        const int rem = grid % h->num_cus;
-        if (h->fused_mlp == 1 && !d_probs && !d_logits_out && h->fm_logits_lds && grid > h->num_cus && rem > 0 && rem * 10 < h->num_cus * 3) {
-            nq_head = (grid - rem) * FM_COLS;
-            grid -= rem;
-        }
+    return 0;
+}
+
+// The LMI_MLP_PLAN_* words of a forward (include/lmi_hip.h).  mlp_plan_record: the plan's fields, as mlp_enqueue starts the handle's
+// record (every launch site then writes its own words as it launches); mlp_plan_report: the sites' words as well, from the same
+// functions the sites call, for the sites this plan reaches -- what lmi_debug_mlp_plan returns.
+static_assert(LMI_MLP_PLAN_COUNT <= CallState::PLAN_WORDS, "lmi_handle.h holds the plan words");
+static_assert(LMI_MLP_PLAN_CBW7 - LMI_MLP_PLAN_CBW0 + 1 == LMI_MAX_LAYERS, "one CBW word per layer");
+static void mlp_plan_record(const lmi_index* h, const FusedLds& F, const MlpPlan& P, int32_t* w) {
+    for (int i = 0; i < LMI_MLP_PLAN_COUNT; ++i) w[i] = -1;
+    w[LMI_MLP_PLAN_NUM_CUS] = h->num_cus; w[LMI_MLP_PLAN_FM_OK] = F.ok; w[LMI_MLP_PLAN_LOGITS_LDS] = F.logits_lds;
+    w[LMI_MLP_PLAN_LDS_BYTES] = F.lds; w[LMI_MLP_PLAN_FUSED] = P.fused; w[LMI_MLP_PLAN_MODE] = P.mode;
+    w[LMI_MLP_PLAN_FUSED_BLOCKS] = P.grid; w[LMI_MLP_PLAN_NQ_HEAD] = P.nq_head; w[LMI_MLP_PLAN_LAYERS_QUERIES] = P.layers_queries;
+    w[LMI_MLP_PLAN_SOFTMAX_KERNEL] = 0;
+}
+static void mlp_plan_report(const lmi_index* h, const FusedLds& F, const MlpPlan& P, const RankStop& stop, bool proba, int32_t* w) {
+    mlp_plan_record(h, F, P, w);
+    const Model& R = h->root();
+    if (P.fused) {
+        w[LMI_MLP_PLAN_VEC_IN] = fused_vec_in(R.dims[0]);
+        w[LMI_MLP_PLAN_IN_CHUNKS] = fused_in_chunks(R.KG[0]);
+    }
+    if (P.layers_queries > 0)
+        for (int i = 0; i < R.n_layers; ++i) w[LMI_MLP_PLAN_CBW0 + i] = mlp_layer_cbw(h->num_cus, R.n_rb[i], cdiv(P.layers_queries, 32));
+    if (P.layers_queries > 0 || !F.logits_lds) {
+        w[LMI_MLP_PLAN_RANK_KERNEL] = rank_kernel_of(stop);
+        w[LMI_MLP_PLAN_SOFTMAX_KERNEL] = proba;
+    }
+}
+
+static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_order, float* d_logits_out, float* d_probs = nullptr) {
+    RankStop stop;
+    CHK(mlp_call_check(h, nb, d_probs != nullptr, "lmi_mlp_topk", stop));
+    const int L = h->root().dims.back();
+    CHK(build_descs(h));
+    const float mass = stop.mass;
+    const MlpPlan plan = mlp_plan(h->num_cus, h->fused_mlp, h->fm_ok, h->fm_logits_lds != 0, nq, d_probs != nullptr, d_logits_out != nullptr, stop);
+    {
+        FusedLds F;   // (build_descs keeps fused_lds_plan's answer in the handle)
+        F.ok = h->fm_ok; F.logits_lds = h->fm_logits_lds != 0; F.s0 = h->fm_s0; F.s1 = h->fm_s1; F.lds = h->fm_lds;
+        mlp_plan_record(h, F, plan, h->last_mlp_plan);   // (the launch sites add their words)
+    }
+    if (plan.fused) {
+        const int grid = plan.grid, nq_head = plan.nq_head;
         FusedParams P;
         fused_base(h, d_q, nq_head, P);
         float* d_logits = d_logits_out;
@@ -327,20 +439,23 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
         P.nb_rows = stop.nb_rows;
         P.stop_rows = stop.rows;
         if (nq_head < nq) CHK(side_fork(h));
-        if (d_probs) mlp_fused_kernel<FM_PROBA><<<grid, 256, h->fm_lds, h->stream>>>(P);
-        else if (stop.rows > 0) mlp_fused_kernel<FM_TOPK_ROWS><<<grid, 256, h->fm_lds, h->stream>>>(P);
-        else if (mass > 0.0f) mlp_fused_kernel<FM_TOPK_STOP><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        if (plan.mode == FM_PROBA) mlp_fused_kernel<FM_PROBA><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        else if (plan.mode == FM_TOPK_ROWS) mlp_fused_kernel<FM_TOPK_ROWS><<<grid, 256, h->fm_lds, h->stream>>>(P);
+        else if (plan.mode == FM_TOPK_STOP) mlp_fused_kernel<FM_TOPK_STOP><<<grid, 256, h->fm_lds, h->stream>>>(P);
         else mlp_fused_kernel<FM_TOPK><<<grid, 256, h->fm_lds, h->stream>>>(P);
         HIPCHK(hipGetLastError());
+        h->last_mlp_plan[LMI_MLP_PLAN_VEC_IN] = fused_vec_in(P.d);
+        h->last_mlp_plan[LMI_MLP_PLAN_IN_CHUNKS] = fused_in_chunks(h->root().KG[0]);
         if (nq_head < nq) {
             CHK(mlp_layers_enqueue(h, h->side, d_q + (size_t)nq_head * h->root().dims[0], nq - nq_head, nb, d_order + (size_t)nq_head * nb, nullptr, nullptr, stop));
             CHK(side_join(h));
         }
         if (!h->fm_logits_lds) {
-            CHK(rank_enqueue(h->stream, d_logits, nq, L, nb, stop, d_order));
+            CHK(rank_enqueue(h, h->stream, d_logits, nq, L, nb, stop, d_order));
             if (d_probs) {
                 softmax_ranked_kernel<<<cdiv(nq, 64), 64, 0, h->stream>>>(d_logits, d_order, nq, L, d_probs);
                 HIPCHK(hipGetLastError());
+                h->last_mlp_plan[LMI_MLP_PLAN_SOFTMAX_KERNEL] = 1;
             }
         }
         return 0;
@@ -416,6 +531,8 @@ extern "C" LMI_API int lmi_mlp_proba(lmi_index* h, const float* queries_nav, int
 constexpr int NAV_ENQUEUE_ALL = 16;
 static int nav_check(lmi_index* h, int nq, int nb, const char* who) {
     if (!h->tree_set) return fail("%s: no tree (lmi_nav_set_model / lmi_nav_set_tree)", who);
+    if (h->root().n_layers == 0) return fail("%s: no root model (lmi_set_mlp)", who);
+    CHK(tree_widths_check(h, who));
     CHK(set_dev(h));
     CHK(build_descs(h));
     if (!h->fm_ok || !h->fm_logits_lds)

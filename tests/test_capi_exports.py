@@ -37,6 +37,18 @@ def test_plan_fields_follow_the_header_enum():
     assert [n.lower() for n in names[:-1]] == [f.lower() for f in _capi.PLAN_FIELDS]
 
 
+def test_mlp_plan_fields_follow_the_header_enum():
+    """_capi.MLP_PLAN_FIELDS names the LMI_MLP_PLAN_* words of lmi_hip.h, in the enum's order (LMI_MLP_PLAN_COUNT closes it)."""
+    from learnedmetricindex_amd import _capi
+
+    text = open(os.path.join(ROOT, "include", "lmi_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    names = re.findall(r"\bLMI_MLP_PLAN_([A-Z0-9_]+)\b\s*(?:=\s*0\s*)?[,\n]", text)
+    assert names[-1] == "COUNT" and len(names) == len(set(names))
+    assert [n.lower() for n in names[:-1]] == [f.lower() for f in _capi.MLP_PLAN_FIELDS]
+    assert len(names) - 1 <= 32   # CallState::PLAN_WORDS
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from learnedmetricindex_amd import _capi
 

@@ -1,7 +1,10 @@
 """GPU (`-m gpu`): the one-launch MLP (csrc/lmi_mlp_fused.h) against the oracle and against the per-layer kernels:
 logits, bucket order and predict_proba bit-identical, for every model shape of the reference's zoo that the
 fixtures hold (MLP 64->128->12, MLP-4 768->512->120, 3-layer MLP-5 on 32-d, 256 classes on 45-d), ragged batch
-sizes, a wide output layer (1 024 classes: logits through global memory) and wide inputs (d = 2 048, chunked)."""
+sizes, a wide output layer (1 024 classes: logits through global memory) and wide inputs (d = 2 048, chunked).
+
+The dispatch between the two forms (fill rule, thin-last-round split, CBW, the 512 / 513 width and class seams), models of one to
+eight Linears, directed ranking / softmax inputs and heterogeneous trees are in test_gpu_mlp_seams.py, with the plan report."""
 import numpy as np
 import pytest
 
