@@ -524,6 +524,69 @@ enum {
  * min(n, LMI_KNN_PLAN_COUNT) words. */
 LMI_API int lmi_debug_knn_plan(int64_t *out, int n);
 
+/* The union scan: for every query the k best objects of the UNION of its visited buckets, k up to LMI_UNION_MAX_K -- what any
+ * inverted-file index answers to search(k).  (lmi_scan_topk keeps the reference's semantics: at most LMI_K_PER_BUCKET per bucket,
+ * merged by rank, k <= LMI_MAX_K; nothing about it changes.)  oracle.knn_ip / oracle.knn_l2 of a query against the concatenated
+ * rows of its buckets restate the call (IP: D -> 1 - D; I -> the id at that ordinal; -1 -> padding).
+ * Outputs: dists [nq][k], ids [nq][k], counts [nq] (nullable); always k columns, also for nb == 1.  on_device as in lmi_search:
+ * every array a device pointer, or every array a host pointer.  The call synchronises the handle's stream internally -- the bucket
+ * order comes back to the host, which plans the work per bucket -- and returns when the outputs have landed, also with on_device.
+ * Contract
+ *   candidates   of query q: the concatenation, over the ranks t = 0..nb-1 with b = bucket_order[q][t] >= 0, of rows 0..n(b)-1 of
+ *                bucket b in the order lmi_bucket_read returns them.  A candidate's ordinal is its position in that concatenation.
+ *                A rank of -1 (or of no bucket id) contributes nothing; a bucket listed twice contributes twice; a bucket this
+ *                handle does not own has no rows.  n(b) is the live count (after lmi_buckets_insert / _delete).
+ *   score        the index's canonical chain over the stored width, lmi_scan_topk's arithmetic: IP acc = fmaf(q[t], x[t], acc) from
+ *                +0; L2 the same chain on [q, 1] and [x, -|x|^2/2] (the stored column).  No chain is split; nothing is added
+ *                atomically.  (The chains run in v_mfma_f32_32x32x2_f32, padded with fmaf(+0, +0, acc) as in lmi_knn.)
+ *   selection    the first k candidates in the total order (score descending with -0 == +0, then ordinal ascending) among the
+ *                scores > -FLT_MAX: NaN, -inf and -FLT_MAX are never returned (lmi_knn's rule).
+ *   output       dist = what the scan writes for that score: IP 1.0f - s, L2 fmaf(-2, key, |q|^2); id = the stored id;
+ *                counts[q] = the number of real results; the slots behind them hold dist = +inf, id = 0.
+ *   geometry     every (query, rank) is scored against its whole bucket and owns one sorted list; a query's lists are merged in the
+ *                total order.  The result does not depend on query groups, waves, tiles or the grid; lmi_union_set_geometry never
+ *                changes a bit.
+ * The stops (lmi_set_stop_mass, lmi_set_path_mass, lmi_set_stop_rows) act through the bucket order exactly as in lmi_search /
+ * lmi_search_tree; lmi_scan_union takes the caller's order as given.
+ * Refused before any launch: an index that is not built; k outside 1..LMI_UNION_MAX_K; nb < 1, nb > 1024 or nq * nb >= 2^31;
+ * nb * (largest bucket) >= 2^32 - 1 (ordinals are 32-bit); a needed pointer that is NULL; an index whose stored form is not the
+ * row-major one (lmi_set_prefilter(0) or LMI_STORAGE_F16: reading candidates out of fragments is left to a follow-up).  nq == 0
+ * writes nothing and succeeds.  Clone views and lmi_subset copies are allowed: the call only reads the index.  There is no _f16
+ * query form, no lmi_pipeline_submit form and no cross-rank merge: a sharded rank returns its own part.
+ * What lmi_timings, lmi_scan_stats, lmi_prefilter_stats, lmi_debug_last_plan and lmi_debug_last_mlp_plan report after a union call
+ * is not defined; a following ordinary search behaves as if the union call had not happened.
+ * Device memory of a call (allocated and freed by it), with Q = queries per group, LR = max(128, k rounded up to a power of two),
+ * d' = the stored width rounded up to 32:  a wave's score slab, 4 bytes per (slot, row of its bucket, rounded up to 64) pair, at most
+ * 2 GiB unless forced or one tile of 32 slots needs more + 8 Q nb LR (lists) + 4 d' per packed query of a wave (at most 256 MiB) +
+ * about 50 bytes per slot of a group (tables); with host pointers 8 Q k + 4 Q more.  Q is at most what keeps the lists within
+ * 1 GiB (at least 32); the slab, then Q shrink when the sum exceeds 80 % of the free memory. */
+#define LMI_UNION_MAX_K 1024
+LMI_API int lmi_scan_union(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb, int k,
+                           float *dists, uint32_t *ids, int32_t *counts, int on_device);
+/* lmi_mlp_topk followed by lmi_scan_union; bucket_order (nullable) [nq][nb] <- the order that was scanned. */
+LMI_API int lmi_search_union(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb, int k,
+                             float *dists, uint32_t *ids, int32_t *counts, int32_t *bucket_order, int on_device);
+/* lmi_nav_order followed by lmi_scan_union; slab_ids, entries (nullable) [nq][nb] as lmi_search_tree returns them. */
+LMI_API int lmi_search_tree_union(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb, int k,
+                                  float *dists, uint32_t *ids, int32_t *counts, int32_t *slab_ids, int32_t *entries, int on_device);
+/* Tuning / test hook: queries per group (<= 2^20) and the bytes of a wave's score slab (one tile of 32 slots is taken even where it
+ * needs more).  0 = chosen by the library.  Thread-local, like lmi_last_error; never changes a result. */
+LMI_API int lmi_union_set_geometry(int64_t query_rows, int64_t slab_bytes);
+enum {
+    LMI_UNION_PLAN_GROUPS = 0,        /* groups the queries were taken in                                                     */
+    LMI_UNION_PLAN_QUERY_ROWS,        /* queries per group (the last may be smaller)                                          */
+    LMI_UNION_PLAN_WAVES,             /* waves of the last group (0: none of its slots had rows)                              */
+    LMI_UNION_PLAN_SLAB_BYTES,        /* bytes of the score slab (the largest wave's)                                         */
+    LMI_UNION_PLAN_LIST_ROWS,         /* entries of a sorted list (LR above)                                                  */
+    LMI_UNION_PLAN_LISTS_PER_QUERY,   /* lists per query = nb: one per (query, rank)                                          */
+    LMI_UNION_PLAN_WORKSPACE_BYTES,   /* device bytes the call allocated                                                      */
+    LMI_UNION_PLAN_VEC_ROWS,          /* 16-byte loads of the index's rows (stored width % 4 == 0)                            */
+    LMI_UNION_PLAN_COUNT
+};
+/* What the last union call on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
+ * min(n, LMI_UNION_PLAN_COUNT) words. */
+LMI_API int lmi_debug_union_plan(int64_t *out, int n);
+
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);
 /* Mean of the timing slots over the calls made since lmi_timings_reset (the newest 128 at most), read

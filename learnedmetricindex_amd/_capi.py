@@ -29,6 +29,9 @@ MLP_PLAN_FIELDS = ("num_cus", "fm_ok", "logits_lds", "lds_bytes", "fused", "mode
 #: the LMI_KNN_PLAN_* words, in their order (lmi_debug_knn_plan)
 KNN_PLAN_FIELDS = ("PIECES", "PIECE_ROWS", "SPLITS", "QUERY_GROUPS", "QUERY_ROWS", "VEC_XQ", "VEC_XB", "WORKSPACE_BYTES", "LIST_ROWS")
 KNN_METRICS = {"ip": 0, "l2": 1}   # LMI_METRIC_IP, LMI_METRIC_L2
+UNION_MAX_K = 1024   # LMI_UNION_MAX_K: the largest k of the union scan (`Index.scan_union`, `search_union`, `search_tree_union`)
+#: the LMI_UNION_PLAN_* words, in their order (lmi_debug_union_plan)
+UNION_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "LIST_ROWS", "LISTS_PER_QUERY", "WORKSPACE_BYTES", "VEC_ROWS")
 
 _lib = None
 
@@ -90,6 +93,11 @@ SIGNATURES = {
                                _vp, _vp, ctypes.c_int]),
     "lmi_knn_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "lmi_debug_knn_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    "lmi_scan_union": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_search_union": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_search_tree_union": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_union_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
+    "lmi_debug_union_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -648,6 +656,81 @@ class Index:
         _check(fn(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(keys), _ptr(bo), 0))
         return (d, i, bo, keys) if want_keys else (d, i, bo)
 
+    # ---- the union scan: the k best objects of the union of a query's visited buckets, k <= UNION_MAX_K (include/lmi_hip.h) ----
+    @staticmethod
+    def _union_args(who: str, k: int, nb: int, **arrays) -> None:
+        """Argument errors of the union calls, raised before the library loads."""
+        if not isinstance(k, (int, np.integer)) or k < 1 or k > UNION_MAX_K:
+            raise ValueError(f"{who}: k {k!r} outside [1, {UNION_MAX_K}]")
+        if not isinstance(nb, (int, np.integer)) or nb < 1 or nb > 1024:
+            raise ValueError(f"{who}: n_buckets {nb!r} outside [1, 1024]")
+        for name, a in arrays.items():
+            if a is None or not hasattr(a, "shape") or len(a.shape) != 2:
+                raise ValueError(f"{who}: {name} must be a two-dimensional array")
+        rows = {int(a.shape[0]) for a in arrays.values()}
+        if len(rows) > 1:
+            raise ValueError(f"{who}: the arrays disagree about the number of queries ({sorted(rows)})")
+
+    def scan_union(self, queries_search, bucket_order, k: int = 10):
+        """(dists f32[nq,k], ids u32[nq,k], counts i32[nq]) of `lmi_scan_union`: per query the k best objects of the union of the
+        buckets `bucket_order[q]` lists (-1: none); behind `counts[q]` real results dist = +inf, id = 0."""
+        if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
+            raise ValueError("scan_union: bucket_order must be a two-dimensional array")
+        nb = int(bucket_order.shape[1])
+        self._union_args("scan_union", k, nb, queries_search=queries_search, bucket_order=bucket_order)
+        q = _np(queries_search, np.float32)
+        bo = _np(bucket_order, np.int32)
+        nq = q.shape[0]
+        d = np.empty((nq, k), dtype=np.float32)
+        i = np.empty((nq, k), dtype=np.uint32)
+        c = np.empty((nq,), dtype=np.int32)
+        _check(lib().lmi_scan_union(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0))
+        return d, i, c
+
+    def search_union(self, queries_nav, queries_search, nb: int, k: int = 10):
+        """`lmi_search_union`: (dists, ids, counts, bucket order i32[nq,nb])."""
+        self._union_args("search_union", k, nb, queries_nav=queries_nav, queries_search=queries_search)
+        same = queries_search is queries_nav
+        qn = _np(queries_nav, np.float32)
+        qs = qn if same else _np(queries_search, np.float32)
+        nq = qn.shape[0]
+        d = np.empty((nq, k), dtype=np.float32)
+        i = np.empty((nq, k), dtype=np.uint32)
+        c = np.empty((nq,), dtype=np.int32)
+        bo = np.empty((nq, nb), dtype=np.int32)
+        _check(lib().lmi_search_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0))
+        return d, i, c, bo
+
+    def search_tree_union(self, queries_nav, queries_search, nb: int, k: int = 10):
+        """`lmi_search_tree_union`: (dists, ids, counts, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb])."""
+        self._union_args("search_tree_union", k, nb, queries_nav=queries_nav, queries_search=queries_search)
+        same = queries_search is queries_nav
+        qn = _np(queries_nav, np.float32)
+        qs = qn if same else _np(queries_search, np.float32)
+        nq = qn.shape[0]
+        d = np.empty((nq, k), dtype=np.float32)
+        i = np.empty((nq, k), dtype=np.uint32)
+        c = np.empty((nq,), dtype=np.int32)
+        slab = np.empty((nq, nb), dtype=np.int32)
+        ent = np.empty((nq, nb), dtype=np.int32)
+        _check(lib().lmi_search_tree_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab), _ptr(ent), 0))
+        return d, i, c, slab, ent
+
+    def scan_union_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, counts_t=None) -> None:
+        """Device tensors (float32 queries, int32 order, float32 / uint32-sized / int32 outputs); returns when they have landed."""
+        self._union_args("scan_union_device", k, nb, queries_search=qs_t, bucket_order=bo_t)
+        _check(lib().lmi_scan_union(self._h, _ptr(qs_t), int(qs_t.shape[0]), _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1))
+
+    def search_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, bo_t=None) -> None:
+        self._union_args("search_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
+        _check(lib().lmi_search_union(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
+                                      _ptr(counts_t), _ptr(bo_t), 1))
+
+    def search_tree_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, slab_t=None, ent_t=None) -> None:
+        self._union_args("search_tree_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
+        _check(lib().lmi_search_tree_union(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
+                                           _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1))
+
     # ---- query path, device tensors (torch), asynchronous on the handle's stream --------------
     def search_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, keys_t=None, bo_t=None) -> None:
         """Device tensors; both query tensors torch.float16 -> `lmi_search_f16`: they are widened into the handle's buffers."""
@@ -826,6 +909,19 @@ def knn_last_plan() -> dict:
     w = (ctypes.c_int64 * len(KNN_PLAN_FIELDS))()
     _check(lib().lmi_debug_knn_plan(w, len(KNN_PLAN_FIELDS)))
     return dict(zip(KNN_PLAN_FIELDS, (int(v) for v in w)))
+
+
+def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:
+    """Tuning / test hook (`lmi_union_set_geometry`): queries per group and bytes of a wave's score slab of the union calls on this
+    thread; 0 = the library's choice.  Never changes a result."""
+    _check(lib().lmi_union_set_geometry(int(query_rows), int(slab_bytes)))
+
+
+def union_last_plan() -> dict:
+    """What the last union call on this thread did (`lmi_debug_union_plan`): `UNION_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(UNION_PLAN_FIELDS))()
+    _check(lib().lmi_debug_union_plan(w, len(UNION_PLAN_FIELDS)))
+    return dict(zip(UNION_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int = 0):

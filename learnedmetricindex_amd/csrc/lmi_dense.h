@@ -6,8 +6,8 @@
 // carry one link more than d: at link d a row of X holds a value the caller gives and a row of F another, so that their product adds
 // one term to the chain (L2: the 1 meets the -|.|^2/2); links past d are zeros.  The link order inside every accumulator is
 // 0, 1, 2, ..: an element of S is the canonical fmaf chain of oracle.knn_ip / knn_l2.
-// The loop that runs the product is written out in km_assign_kernel and again in knn_score_kernel: the two must stay equal
-// (DESIGN.md 5.11 says why it is not a function here).
+// The loop that runs the product is written out in km_assign_kernel, again in knn_score_kernel and again in union_score_kernel
+// (lmi_union.h): the three must stay equal (DESIGN.md 5.11 says why it is not a function here).
 #pragma once
 #include "lmi_kernels.h"
 

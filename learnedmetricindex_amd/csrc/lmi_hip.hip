@@ -18,6 +18,8 @@
 #include "lmi_host_train.h"   // lmi_train
 #include "lmi_knn.h"          // the kernels of lmi_knn
 #include "lmi_host_knn.h"     // lmi_knn, lmi_knn_set_geometry, lmi_debug_knn_plan
+#include "lmi_union.h"        // the kernels of the union scan
+#include "lmi_host_union.h"   // lmi_scan_union / lmi_search_union / lmi_search_tree_union, lmi_union_set_geometry, lmi_debug_union_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

@@ -147,17 +147,15 @@ __device__ __forceinline__ void knn_bitonic_sort_up(knn_entry* e, int n, int lan
         }
 }
 
-// grid (nq, splits), block 64, dynamic LDS 2 * LR entries.  The wave of (query q, split s) continues lists[(q * splits + s) * LR ..)
-// (best-first, LR a power of two >= max(k, 128)) with the scores S[q * pitch + a .. b), [a, b) = split s of the piece's len rows; a
-// score's row number is row_base + its position.  Only scores > -FLT_MAX are taken (a NaN is not).
-__global__ __launch_bounds__(64) void knn_select_kernel(const float* __restrict__ S, long long pitch, long long len, unsigned row_base,
-                                                        int k, int LR, knn_entry* __restrict__ lists) {
+// One wave (a 64-thread block, dynamic LDS 2 * LR entries): continues the sorted list `mine` (best-first, LR a power of two >=
+// max(k, 128); fresh: starts from an empty list instead of reading it) with the scores row[a .. b); the score at position p enters as
+// the pair (score, row_base + p).  Only scores > -FLT_MAX are taken (a NaN is not).  knn_select_kernel and union_select_kernel
+// (lmi_union.h) are this with their own addressing.
+__device__ __forceinline__ void knn_select_wave(const float* __restrict__ row, long long a, long long b, unsigned row_base, int k, int LR,
+                                                knn_entry* __restrict__ mine, bool fresh) {
     extern __shared__ knn_entry knn_lds[];
-    const int lane = threadIdx.x, q = blockIdx.x, s = blockIdx.y, splits = gridDim.y;
-    const long long a = len * s / splits, b = len * (s + 1) / splits;
-    if (a >= b) return;   // uniform
-    knn_entry* mine = lists + ((size_t)q * splits + s) * LR;
-    for (int i = lane; i < LR; i += 64) knn_lds[i] = mine[i];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < LR; i += 64) knn_lds[i] = fresh ? KNN_EMPTY : mine[i];
     __syncthreads();
     knn_entry thr = knn_lds[k - 1];
     knn_entry* buf = knn_lds + LR;
@@ -171,7 +169,6 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const float* __restrict_
         cnt = 0;
         __syncthreads();
     };
-    const float* row = S + (size_t)q * pitch;
     for (long long p0 = a; p0 < b; p0 += 256) {
         float v[4];
 #pragma unroll
@@ -194,6 +191,16 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const float* __restrict_
     if (cnt) flush();
     else __syncthreads();
     for (int i = lane; i < LR; i += 64) mine[i] = knn_lds[i];
+}
+
+// grid (nq, splits), block 64, dynamic LDS 2 * LR entries.  The wave of (query q, split s) continues lists[(q * splits + s) * LR ..)
+// with the scores S[q * pitch + a .. b), [a, b) = split s of the piece's len rows; a score's row number is row_base + its position.
+__global__ __launch_bounds__(64) void knn_select_kernel(const float* __restrict__ S, long long pitch, long long len, unsigned row_base,
+                                                        int k, int LR, knn_entry* __restrict__ lists) {
+    const int q = blockIdx.x, s = blockIdx.y, splits = gridDim.y;
+    const long long a = len * s / splits, b = len * (s + 1) / splits;
+    if (a >= b) return;   // uniform
+    knn_select_wave(S + (size_t)q * pitch, a, b, row_base, k, LR, lists + ((size_t)q * splits + s) * LR, false);
 }
 
 // grid nq, block 64, dynamic LDS 2 * LR entries: merges the `splits` lists of query q and writes D[q][k], I[q][k] -- the first k

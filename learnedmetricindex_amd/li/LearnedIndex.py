@@ -271,15 +271,24 @@ class LearnedIndex(Logger):
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
                         k: int = 10, stop_mass: Optional[float] = None, path_mass: Optional[float] = None,
-                        stop_rows: Optional[int] = None):
+                        stop_rows: Optional[int] = None, merge: str = "ranks"):
         """`search` against the index already resident in HBM (after `prepare`, a previous `search`
-        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass`, `path_mass` and `stop_rows`
-        as there."""
+        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass`, `path_mass`, `stop_rows`
+        and `merge` as there."""
+        self._check_merge(merge)
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         assert self._engine is not None, "no resident index: call prepare()/search() or index_io.load_index()"
         return self._search_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, k,
-                                 time.time(), stop_mass, path_mass, stop_rows)
+                                 time.time(), stop_mass, path_mass, stop_rows, merge)
+
+    MERGES = ("ranks", "union")
+
+    @classmethod
+    def _check_merge(cls, merge) -> None:
+        if merge not in cls.MERGES:
+            raise ValueError(f"merge {merge!r} unknown: 'ranks' (at most 10 results per visited bucket, merged by rank; the reference) "
+                             "or 'union' (the k best objects of all visited buckets)")
 
     @staticmethod
     def _check_stop_mass(stop_mass, n_categories) -> None:
@@ -390,6 +399,7 @@ class LearnedIndex(Logger):
         path_mass: Optional[float] = None,
         storage: str = "f32",
         stop_rows: Optional[int] = None,
+        merge: str = "ranks",
     ) -> Tuple[npt.NDArray, npt.NDArray[np.uint32], Dict[str, float]]:
         """Searches for `k` nearest neighbors of every query in its `n_buckets` most probable buckets.
         Parameters and return values as the reference (LearnedIndex.py:41-83).  `metric` (an extension; the
@@ -407,18 +417,25 @@ class LearnedIndex(Logger):
         query stops visiting buckets once the buckets it has visited hold `stop_rows` objects or more (the bucket that crosses
         the budget is scanned whole) -- the slots behind the stop stay unvisited, the result shapes do not change.  With
         `stop_mass` / `path_mass` as well a query goes on only while both allow it.  It holds for this call only.
-        `storage` (an extension): "f32" (default) or "f16", how the HBM-resident copy keeps the scan vectors (see `prepare`)."""
+        `storage` (an extension): "f32" (default) or "f16", how the HBM-resident copy keeps the scan vectors (see `prepare`).
+        `merge` (an extension): "ranks" (default) is the reference: at most 10 results per visited bucket, merged rank by rank,
+        k <= 20 for n_buckets >= 2.  "union" returns the `k` best objects of the union of the visited buckets (`lmi_search_union` /
+        `lmi_search_tree_union`): k up to 1024, results [nq, k] for any n_buckets; a query whose buckets hold fewer than k objects
+        is padded with dist = +inf, id = 0.  The stops compose with it.  It needs the default storage ("f32", prefilter on).
+        ValueError for anything else."""
+        self._check_merge(merge)
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         s = time.time()
         eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged,
                            storage=storage)
-        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass, stop_rows)
+        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass, stop_rows, merge)
 
     def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None,
-                     stop_rows=None):
+                     stop_rows=None, merge="ranks"):
+        run = self._search_union if merge == "union" else self._search_chunks
         if stop_mass is None and path_mass is None and stop_rows is None:
-            return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
+            return run(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         # the engine's own settings come back afterwards: a later call without the arguments is as before
         before = eng.stop_mass, eng.path_mass, eng.stop_rows
         try:
@@ -428,11 +445,36 @@ class LearnedIndex(Logger):
                 eng.set_path_mass(path_mass)
             if stop_rows is not None:
                 eng.set_stop_rows(stop_rows)
-            return self._search_chunks(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
+            return run(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         finally:
             eng.set_stop_mass(before[0])
             eng.set_path_mass(before[1])
             eng.set_stop_rows(before[2])
+
+    def _search_union(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
+        """merge="union": the batch goes to the library whole (it groups the queries itself); a multi-level index is walked in
+        pieces of `_nav_chunk()` queries, the walk's queue limit."""
+        measured_time = defaultdict(float)
+        qn = np.ascontiguousarray(_query_array(queries_navigation), dtype=np.float32)   # the union calls take binary32 queries
+        qs = qn if queries_search is queries_navigation else np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
+        assert qn.shape[0] == qs.shape[0]
+        nq = qs.shape[0]
+        if len(n_categories) == 1:
+            assert n_buckets <= eng.n_classes, "n_buckets exceeds the number of classes"
+        if nq == 0:
+            return np.empty((0, k)), np.empty((0, k), dtype=np.uint32), measured_time
+        t0 = time.time()
+        if len(n_categories) == 1:
+            d32, nns = eng.search_union(qn, qs, n_buckets, k)[:2]
+        else:
+            step = self._nav_chunk()
+            parts = [eng.search_tree_union(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets, k)[:2]
+                     for lo in range(0, nq, step)]
+            d32 = parts[0][0] if len(parts) == 1 else np.concatenate([p[0] for p in parts])
+            nns = parts[0][1] if len(parts) == 1 else np.concatenate([p[1] for p in parts])
+        measured_time["search_within_buckets"] = time.time() - t0   # wall time of the calls: the library times no phase of them
+        measured_time["search"] = time.time() - s
+        return d32.astype(np.float64), nns, measured_time
 
     def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
         measured_time = defaultdict(float)

@@ -78,6 +78,7 @@ class Experiment:
     stop_rows: Optional[int] = None
     storage: str = "f32"
     trainer: str = "torch"
+    merge: str = "ranks"
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -114,6 +115,10 @@ class Experiment:
         p.add_argument("--trainer", choices=("torch", "hip"), default="torch",
                        help="how the nodes' models are trained: torch = the reference's loop (autograd, a DataLoader pass per epoch); "
                             "hip = its effective schedule on the device (lmi_train), repeatable bit for bit")
+        p.add_argument("--merge", choices=("ranks", "union"), default="ranks",
+                       help="ranks = at most 10 results per visited bucket, merged by rank (the reference; k <= 20); union = the k best "
+                            "objects of all visited buckets, k up to 1024 -- with --eval, recall@k then measures what the index returned "
+                            "for that k")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -127,6 +132,10 @@ class Experiment:
             p.error("--path-mass must lie in (0, 1]")
         if a["stop_rows"] is not None and a["stop_rows"] < 1:
             p.error("--stop-rows must be an integer >= 1")
+        if a["merge"] == "union" and not 1 <= a["k"] <= 1024:
+            p.error("--merge union takes --k from 1 to 1024")
+        if a["merge"] == "union" and a["storage"] != "f32":
+            p.error("--merge union needs --storage f32 (the union scan reads the row-major f32 image)")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -288,7 +297,7 @@ def run(exp: Experiment) -> Dict:
     sink, out = ResultSink(), {}
     for budget in bucket_budgets(exp.buckets_perc, n_buckets_in_index):
         dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass,
-                                                     path_mass=exp.path_mass, stop_rows=exp.stop_rows)
+                                                     path_mass=exp.path_mass, stop_rows=exp.stop_rows, merge=exp.merge)
         LOG.info("%d buckets: search %.4fs (inference %.4fs, within buckets %.4fs, scan %.4fs, merge %.4fs)", budget,
                  clock["search"], clock["inference"], clock["search_within_buckets"], clock["seq_search"], clock["sort"])
         if exp.evaluate:
@@ -296,7 +305,8 @@ def run(exp: Experiment) -> Dict:
             LOG.info("%d buckets: recall@%d = %.5f", budget, exp.k, out[f"recall_{budget}"])
         stem = exp.tag(f"learned-index-{exp.dataset}-{exp.size}", buck=budget, **({} if exp.stop_mass is None else {"stop": exp.stop_mass}),
                        **({} if exp.path_mass is None else {"pathmass": exp.path_mass}),
-                       **({} if exp.stop_rows is None else {"stoprows": exp.stop_rows}))
+                       **({} if exp.stop_rows is None else {"stoprows": exp.stop_rows}),
+                       **({} if exp.merge == "ranks" else {"merge": exp.merge}))
         sink.write(exp.dataset, exp.size, stem, dists, knns, algo="Learned-index", data=src.stamp(exp.dataset),
                    buildtime=build_s, querytime=clock["search"], size=exp.size, params=stem)
         out[budget] = (dists, knns, clock)
