@@ -552,13 +552,14 @@ LMI_API int lmi_debug_knn_plan(int64_t *out, int n);
  * nb * (largest bucket) >= 2^32 - 1 (ordinals are 32-bit); a needed pointer that is NULL; an index whose stored form is not the
  * row-major one (lmi_set_prefilter(0) or LMI_STORAGE_F16: reading candidates out of fragments is left to a follow-up).  nq == 0
  * writes nothing and succeeds.  Clone views and lmi_subset copies are allowed: the call only reads the index.  There is no _f16
- * query form, no lmi_pipeline_submit form and no cross-rank merge: a sharded rank returns its own part.
+ * query form and no lmi_pipeline_submit form; a sharded rank returns its own part (across ranks: lmi_scan_union_part below).
  * What lmi_timings, lmi_scan_stats, lmi_prefilter_stats, lmi_debug_last_plan and lmi_debug_last_mlp_plan report after a union call
  * is not defined; a following ordinary search behaves as if the union call had not happened.
  * Device memory of a call (allocated and freed by it), with Q = queries per group, LR = max(128, k rounded up to a power of two),
  * d' = the stored width rounded up to 32:  a wave's score slab, 4 bytes per (slot, row of its bucket, rounded up to 64) pair, at most
  * 2 GiB unless forced or one tile of 32 slots needs more + 8 Q nb LR (lists) + 4 d' per packed query of a wave (at most 256 MiB) +
- * about 50 bytes per slot of a group (tables); with host pointers 8 Q k + 4 Q more.  Q is at most what keeps the lists within
+ * about 50 bytes per slot of a group (tables); with host pointers 8 Q k + 4 Q more (lmi_scan_union_part: 20 Q k + 4 Q, the staged
+ * part; the geometry is still chosen with 8 Q k).  Q is at most what keeps the lists within
  * 1 GiB (at least 32); the slab, then Q shrink when the sum exceeds 80 % of the free memory. */
 #define LMI_UNION_MAX_K 1024
 LMI_API int lmi_scan_union(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb, int k,
@@ -586,6 +587,48 @@ enum {
 /* What the last union call on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
  * min(n, LMI_UNION_PLAN_COUNT) words. */
 LMI_API int lmi_debug_union_plan(int64_t *out, int n);
+
+/* The union scan across the ranks of a bucket-sharded index (no reference counterpart): every rank scans the buckets it owns and
+ * hands on a PART; the merge of the parts is what lmi_scan_union returns on one handle that holds the whole index, bit for bit, for
+ * any assignment of the buckets (each owned by exactly one part) and any world size.
+ * A part is int32 words [LMI_UNION_PART_PLANES][nq][k]; per (query, j < k), best first:
+ *   LMI_UPART_SCORE  the bits of the score the selection ordered by (IP: the similarity; L2: the key of the augmented chain)
+ *   LMI_UPART_DIST   the bits lmi_scan_union writes in dists
+ *   LMI_UPART_ID     the stored id
+ *   LMI_UPART_RANK   the position t in bucket_order[q] of the bucket the object came from
+ *   LMI_UPART_ROW    its row in that bucket, in lmi_bucket_read's order
+ * and behind the real results the padding: SCORE = the bits of -FLT_MAX, DIST = +inf, ID = 0, RANK = ROW = 0xffffffff.
+ * Why these planes: the ranks' lists must be merged in the single handle's order, (score, ordinal).  The distance cannot replace the
+ * score -- 1.0f - s and fmaf(-2, key, |q|^2) round, two scores may share a distance's bits, and a merge by distance would then order
+ * them by key instead of by score.  The ordinal cannot be computed by a rank, which holds its own buckets' counts only (why
+ * lmi_set_stop_rows is refused on an `owned` mask); (RANK, ROW) orders exactly as the ordinal does and needs no other rank's counts.
+ *
+ * lmi_scan_union_part is lmi_scan_union in every respect -- candidates, score, selection, refusals, geometry and its hooks, the plan
+ * words, memory (with host pointers the staged part: above) -- except that it writes `part` instead of dists / ids; counts as there.
+ * On a handle that owns every bucket the DIST and ID planes and counts equal lmi_scan_union's outputs bit for bit. */
+#define LMI_UNION_PART_PLANES 5
+enum { LMI_UPART_SCORE = 0, LMI_UPART_DIST, LMI_UPART_ID, LMI_UPART_RANK, LMI_UPART_ROW };
+LMI_API int lmi_scan_union_part(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb, int k,
+                                int32_t *part /* [5][nq][k] */, int32_t *counts /* [nq], nullable */, int on_device);
+/* parts [world][LMI_UNION_PART_PLANES][nq][k], dense: part w as rank w wrote it (an all-gather of the parts is this layout).  Per
+ * query the first k of its world * k entries in the total order: score descending (binary32 compare, -0 == +0), then RANK ascending,
+ * then ROW ascending, then the lower part index; an entry whose ROW is 0xffffffff is padding and is never selected.  dists / ids
+ * [nq][k] <- DIST / ID of the selected entries, +inf / 0 behind them; counts[q] (nullable) <- the number of real entries.  world == 1
+ * reproduces the part.  on_device as in lmi_merge_gathered: device pointers -> asynchronous on the handle's stream; host pointers ->
+ * the parts are uploaded and the result is copied back before the call returns.  The handle needs no built index: it provides the
+ * device and the stream.  One wave per query merges the parts' lists in LDS (32 bytes per entry of LR = max(128, k rounded up to a
+ * power of two): at most 32 KiB); no device memory is allocated with device pointers.
+ * Refused before any launch: a NULL handle; world outside 1..64; k outside 1..LMI_UNION_MAX_K; nq < 0; a block of 2^31 words or
+ * more (world * LMI_UNION_PART_PLANES * nq * k, checked in 64 bits); a needed pointer that is NULL.  nq == 0 writes nothing and
+ * succeeds. */
+LMI_API int lmi_merge_union_parts(lmi_index *h, const int32_t *parts /* [world][5][nq][k], dense */, int world, int nq, int k,
+                                  float *dists, uint32_t *ids, int32_t *counts /* nullable */, int on_device);
+/* The same exchange through RCCL inside the library, as lmi_allgather_merge: every rank passes its part (a DEVICE pointer) -> ONE
+ * ncclAllGather of the 5 * nq * k words (20 nq k bytes per rank) on the handle's stream -> the merge kernel -> dists / ids / counts
+ * (device), identical on every rank.  Refusals as lmi_merge_union_parts, and a NULL communicator or a rank outside 0..world-1; fails
+ * cleanly when RCCL is absent. */
+LMI_API int lmi_allgather_merge_union(lmi_index *h, void *comm, int rank, int world, const int32_t *part /* device */, int nq, int k,
+                                      float *dists, uint32_t *ids, int32_t *counts /* nullable */);
 
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);

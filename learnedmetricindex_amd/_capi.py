@@ -32,6 +32,8 @@ KNN_METRICS = {"ip": 0, "l2": 1}   # LMI_METRIC_IP, LMI_METRIC_L2
 UNION_MAX_K = 1024   # LMI_UNION_MAX_K: the largest k of the union scan (`Index.scan_union`, `search_union`, `search_tree_union`)
 #: the LMI_UNION_PLAN_* words, in their order (lmi_debug_union_plan)
 UNION_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "LIST_ROWS", "LISTS_PER_QUERY", "WORKSPACE_BYTES", "VEC_ROWS")
+UNION_PART_PLANES = 5   # LMI_UNION_PART_PLANES: a part of the union scan is int32 [5, nq, k] -- the LMI_UPART_* planes, in their order:
+UPART_SCORE, UPART_DIST, UPART_ID, UPART_RANK, UPART_ROW = range(5)
 
 _lib = None
 
@@ -98,6 +100,9 @@ SIGNATURES = {
     "lmi_search_tree_union": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_union_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
     "lmi_debug_union_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    "lmi_scan_union_part": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "lmi_merge_union_parts": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_allgather_merge_union": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -730,6 +735,65 @@ class Index:
         self._union_args("search_tree_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
         _check(lib().lmi_search_tree_union(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
                                            _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1))
+
+    # ---- the union scan across ranks: a rank's part and the merge of the parts (include/lmi_hip.h, lmi_scan_union_part) ----
+    @staticmethod
+    def _union_merge_args(who: str, world, nq, k) -> None:
+        """Argument errors of the merges of union parts, raised before the library loads."""
+        if not isinstance(world, (int, np.integer)) or world < 1 or world > 64:
+            raise ValueError(f"{who}: world {world!r} outside [1, 64]")
+        if not isinstance(k, (int, np.integer)) or k < 1 or k > UNION_MAX_K:
+            raise ValueError(f"{who}: k {k!r} outside [1, {UNION_MAX_K}]")
+        if not isinstance(nq, (int, np.integer)) or nq < 0:
+            raise ValueError(f"{who}: nq {nq!r} is negative")
+
+    def scan_union_part(self, queries_search, bucket_order, k: int = 10):
+        """(part i32[5, nq, k], counts i32[nq]) of `lmi_scan_union_part`: this handle's part of the union scan -- score bits, dist bits,
+        ids, ranks and rows per result (the `UPART_*` planes), padding behind `counts[q]` real results."""
+        if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
+            raise ValueError("scan_union_part: bucket_order must be a two-dimensional array")
+        nb = int(bucket_order.shape[1])
+        self._union_args("scan_union_part", k, nb, queries_search=queries_search, bucket_order=bucket_order)
+        q = _np(queries_search, np.float32)
+        bo = _np(bucket_order, np.int32)
+        nq = q.shape[0]
+        part = np.empty((UNION_PART_PLANES, nq, k), dtype=np.int32)
+        c = np.empty((nq,), dtype=np.int32)
+        _check(lib().lmi_scan_union_part(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(part), _ptr(c), 0))
+        return part, c
+
+    def scan_union_part_device(self, qs_t, bo_t, nb: int, k: int, part_t, counts_t=None) -> None:
+        """Device tensors (float32 queries, int32 order, a contiguous int32 [5, nq, k] part); returns when they have landed."""
+        self._union_args("scan_union_part_device", k, nb, queries_search=qs_t, bucket_order=bo_t)
+        if part_t is None or tuple(part_t.shape) != (UNION_PART_PLANES, int(qs_t.shape[0]), int(k)):
+            raise ValueError(f"scan_union_part_device: part must be [{UNION_PART_PLANES}, nq, k]")
+        _check(lib().lmi_scan_union_part(self._h, _ptr(qs_t), int(qs_t.shape[0]), _ptr(bo_t), int(nb), int(k), _ptr(part_t), _ptr(counts_t), 1))
+
+    def merge_union_parts(self, parts, world: int, nq: int, k: int, out_d, out_i, counts=None) -> None:
+        """`lmi_merge_union_parts`: parts [world, 5, nq, k] int32, dense (numpy: host pointers, the call returns with the result;
+        torch: device pointers, asynchronous on the handle's stream) -> out_d f32[nq, k], out_i u32[nq, k], counts i32[nq]."""
+        self._union_merge_args("merge_union_parts", world, nq, k)
+        if parts is None or out_d is None or out_i is None:
+            raise ValueError("merge_union_parts: parts, out_d and out_i must not be None")
+        if int(np.prod(tuple(parts.shape))) != world * UNION_PART_PLANES * nq * k:
+            raise ValueError(f"merge_union_parts: parts must hold [world, {UNION_PART_PLANES}, nq, k] words, not {tuple(parts.shape)}")
+        on_device = 0 if isinstance(parts, np.ndarray) else 1
+        if on_device == 0:
+            parts = _np(parts, np.int32)
+        _check(lib().lmi_merge_union_parts(self._h, _ptr(parts), int(world), int(nq), int(k), _ptr(out_d), _ptr(out_i), _ptr(counts), on_device))
+
+    def allgather_merge_union(self, comm, rank: int, world: int, part_t, out_d_t, out_i_t, counts_t=None) -> None:
+        """This rank's [5, nq, k] device part -> merged (dists, ids, counts) on every rank (`lmi_allgather_merge_union`)."""
+        if part_t is None or len(part_t.shape) != 3 or int(part_t.shape[0]) != UNION_PART_PLANES:
+            raise ValueError(f"allgather_merge_union: part must be [{UNION_PART_PLANES}, nq, k]")
+        nq, k = int(part_t.shape[1]), int(part_t.shape[2])
+        self._union_merge_args("allgather_merge_union", world, nq, k)
+        if not isinstance(rank, (int, np.integer)) or rank < 0 or rank >= world:
+            raise ValueError(f"allgather_merge_union: rank {rank!r} of {world}")
+        if comm is None or out_d_t is None or out_i_t is None:
+            raise ValueError("allgather_merge_union: comm, out_d and out_i must not be None")
+        _check(lib().lmi_allgather_merge_union(self._h, comm, int(rank), int(world), _ptr(part_t), nq, k, _ptr(out_d_t), _ptr(out_i_t),
+                                               _ptr(counts_t)))
 
     # ---- query path, device tensors (torch), asynchronous on the handle's stream --------------
     def search_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, keys_t=None, bo_t=None) -> None:

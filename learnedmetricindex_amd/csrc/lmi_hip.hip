@@ -10,7 +10,7 @@
 #include "lmi_host_subset.h"  // lmi_subset
 #include "lmi_host_scan.h"    // scan_plan, the scan's stages, scan_enqueue, lmi_workspace_bytes
 #include "lmi_host_search.h"  // lmi_scan_topk / lmi_search / lmi_search_tree / lmi_knn_ip, lmi_pipeline_submit
-#include "lmi_host_comm.h"    // lmi_merge_gathered, RCCL
+#include "lmi_host_comm.h"    // lmi_merge_gathered, RCCL; lmi_merge_union_parts, lmi_allgather_merge_union (lmi_union_merge.h)
 #include "lmi_host_debug.h"   // timings, statistics, test hooks
 #include "lmi_kmeans.h"       // the kernels of lmi_kmeans
 #include "lmi_host_kmeans.h"  // lmi_kmeans
@@ -19,7 +19,7 @@
 #include "lmi_knn.h"          // the kernels of lmi_knn
 #include "lmi_host_knn.h"     // lmi_knn, lmi_knn_set_geometry, lmi_debug_knn_plan
 #include "lmi_union.h"        // the kernels of the union scan
-#include "lmi_host_union.h"   // lmi_scan_union / lmi_search_union / lmi_search_tree_union, lmi_union_set_geometry, lmi_debug_union_plan
+#include "lmi_host_union.h"   // lmi_scan_union / lmi_scan_union_part / lmi_search_union / lmi_search_tree_union, geometry and plan hooks
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

@@ -1,6 +1,8 @@
-// lmi_host_comm.h -- the exchange step of the bucket-sharded mode: lmi_merge_gathered and the RCCL calls (lmi_comm_*, lmi_allgather_merge).
+// lmi_host_comm.h -- the exchange step of the bucket-sharded mode: lmi_merge_gathered and the RCCL calls (lmi_comm_*, lmi_allgather_merge);
+// for the union scan lmi_merge_union_parts and lmi_allgather_merge_union (the kernel: lmi_union_merge.h).
 #pragma once
 #include "lmi_host.h"
+#include "lmi_union_merge.h"
 #include <dlfcn.h>
 #include <mutex>
 #include <rccl/rccl.h>  // types only: the functions are resolved at run time (lmi_comm_*), the library does not link RCCL
@@ -33,6 +35,52 @@ extern "C" LMI_API int lmi_merge_gathered(lmi_index* h, const float* gd, const u
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(dists, out.p, nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ids, out.as<char>() + nout, nout, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;   // (in and out free themselves, on the early returns above too)
+}
+
+namespace {
+// what both merges of union parts refuse before any launch; *go <- whether there is anything to do
+int union_merge_check(const char* who, lmi_index* h, int world, int nq, int k, bool* go) {
+    *go = false;
+    if (!h) return fail("%s: NULL handle", who);
+    if (world < 1 || world > 64) return fail("%s: world %d outside [1,64]", who, world);
+    if (k < 1 || k > LMI_UNION_MAX_K) return fail("%s: k %d outside [1,%d]", who, k, LMI_UNION_MAX_K);
+    if (nq < 0) return fail("%s: nq %d is negative", who, nq);
+    if ((long long)world * LMI_UNION_PART_PLANES * nq * k >= (1ll << 31)) return fail("%s: world*5*nq*k too large", who);
+    *go = nq > 0;
+    return 0;
+}
+int union_merge_launch(lmi_index* h, const int* parts, int world, int nq, int k, float* dists, unsigned* ids, int* counts) {
+    int LR = 128;   // lmi_union_plan::list_rows_for(k)
+    while (LR < k) LR <<= 1;
+    union_merge_kernel<<<nq, 64, (size_t)4 * LR * 8, h->stream>>>(parts, world, nq, k, LR, dists, ids, counts);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+extern "C" LMI_API int lmi_merge_union_parts(lmi_index* h, const int32_t* parts, int world, int nq, int k, float* dists, uint32_t* ids,
+                                             int32_t* counts, int on_device) {
+    const char* who = "lmi_merge_union_parts";
+    bool go = false;
+    CHK(union_merge_check(who, h, world, nq, k, &go));
+    if (!go) return 0;
+    if (!parts || !dists || !ids) return fail("%s: parts, dists and ids must not be NULL", who);
+    CHK(set_dev(h));
+    if (on_device) return union_merge_launch(h, parts, world, nq, k, dists, ids, counts);
+    const size_t nin = (size_t)world * LMI_UNION_PART_PLANES * nq * k * 4, nout = (size_t)nq * k * 4;
+    DevBuf in, out;
+    CHK(in.reserve(nin));
+    CHK(out.reserve(2 * nout + (size_t)nq * 4));
+    float* d_D = out.as<float>();
+    unsigned* d_I = reinterpret_cast<unsigned*>(out.as<char>() + nout);
+    int* d_C = reinterpret_cast<int*>(out.as<char>() + 2 * nout);
+    HIPCHK(hipMemcpyAsync(in.p, parts, nin, hipMemcpyHostToDevice, h->stream));
+    CHK(union_merge_launch(h, in.as<int>(), world, nq, k, d_D, d_I, d_C));
+    HIPCHK(hipMemcpyAsync(dists, d_D, nout, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ids, d_I, nout, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HIPCHK(hipMemcpyAsync(counts, d_C, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;   // (in and out free themselves, on the early returns above too)
 }
@@ -130,4 +178,26 @@ extern "C" LMI_API int lmi_allgather_merge(lmi_index* h, void* comm, int rank, i
                                                    nq, kout, dists, ids);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// The union scan's exchange: this rank's part (lmi_scan_union_part, a device pointer) -> ONE ncclAllGather of its 5 * nq * k words over
+// `comm` on the handle's stream -> union_merge_kernel -> dists / ids [nq][k], counts [nq] (device), identical on every rank.
+extern "C" LMI_API int lmi_allgather_merge_union(lmi_index* h, void* comm, int rank, int world, const int32_t* part, int nq, int k,
+                                                 float* dists, uint32_t* ids, int32_t* counts) {
+    const char* who = "lmi_allgather_merge_union";
+    bool go = false;
+    CHK(union_merge_check(who, h, world, nq, k, &go));
+    if (!comm) return fail("%s: NULL communicator", who);
+    if (rank < 0 || rank >= world) return fail("%s: rank %d of %d", who, rank, world);
+    if (!go) return 0;
+    if (!part || !dists || !ids) return fail("%s: part, dists and ids must not be NULL", who);
+    if (!rccl()->ok) return fail("%s: RCCL (librccl.so) is not available in this process", who);
+    CHK(set_dev(h));
+    const size_t words = (size_t)LMI_UNION_PART_PLANES * nq * k;
+    CHK(h->gather_send.reserve(words * 4));
+    CHK(h->gather_recv.reserve((size_t)world * words * 4));
+    HIPCHK(hipMemcpyAsync(h->gather_send.p, part, words * 4, hipMemcpyDeviceToDevice, h->stream));
+    ncclResult_t e = rccl()->AllGather(h->gather_send.p, h->gather_recv.p, words, ncclInt32, static_cast<ncclComm_t>(comm), h->stream);
+    if (e != ncclSuccess) return rccl_fail("ncclAllGather", e);
+    return union_merge_launch(h, h->gather_recv.as<int>(), world, nq, k, dists, ids, counts);
 }

@@ -1,16 +1,20 @@
 // lmi_host_union.h -- the union scan: argument checks, the geometry (lmi_union_plan.h), the call's device buffers and the schedule on
 // the handle's stream.  The bucket order comes back to the host once (that is the call's internal synchronisation): per query group the
 // host sorts the slots by bucket, cuts them into waves and writes the item tables; per wave pack, score, select; per group one finish.
-// lmi_scan_union, lmi_search_union, lmi_search_tree_union, lmi_union_set_geometry, lmi_debug_union_plan.
+// lmi_scan_union, lmi_scan_union_part, lmi_search_union, lmi_search_tree_union, lmi_union_set_geometry, lmi_debug_union_plan.
 #pragma once
 #include "lmi_host.h"
 #include "lmi_host_call.h"
 #include "lmi_host_model.h"
 #include "lmi_host_scan.h"
 #include "lmi_union.h"
+#include "lmi_union_merge.h"
 #include "lmi_union_plan.h"
 
 static_assert(LMI_UNION_MAX_K == lmi_union_plan::MAX_K, "lmi_union_plan.h restates LMI_UNION_MAX_K");
+static_assert(LMI_UNION_PART_PLANES == UNION_PART_PLANES && LMI_UPART_SCORE == UPART_SCORE && LMI_UPART_DIST == UPART_DIST &&
+                  LMI_UPART_ID == UPART_ID && LMI_UPART_RANK == UPART_RANK && LMI_UPART_ROW == UPART_ROW,
+              "lmi_union_merge.h restates the planes of a part");
 
 namespace {
 
@@ -44,9 +48,10 @@ int union_check(lmi_index* h, const char* who, int nq, int nb, int k) {
     return 0;
 }
 
-// d_qs [nq][d_user] and d_order [nq][nb] on the device, already enqueued on h->stream; dists / ids / counts as the caller gave them
+// d_qs [nq][d_user] and d_order [nq][nb] on the device, already enqueued on h->stream; dists / ids / counts as the caller gave them.
+// part != nullptr (lmi_scan_union_part): the caller's [LMI_UNION_PART_PLANES][nq][k] block is written instead of dists / ids.
 int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const int* d_order, int nb, int k, float* dists, uint32_t* ids,
-               int32_t* counts, int on_device) {
+               int32_t* counts, int on_device, int32_t* part = nullptr) {
     namespace up = lmi_union_plan;
     hipStream_t st = h->stream;
     const int L = h->L;
@@ -158,6 +163,7 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     int *d_rowq = nullptr, *d_tile_cnt = nullptr, *d_slot_n = nullptr, *d_C = nullptr;
     long long *d_tile_off = nullptr, *d_slot_pos0 = nullptr;
     unsigned *d_slot_base = nullptr, *d_I = nullptr;
+    int* d_P = nullptr;   // a group's staged part: [LMI_UNION_PART_PLANES][Q * k]
     int64_t max_group_tiles = 0;
     for (const Group& G : groups) max_group_tiles = std::max<int64_t>(max_group_tiles, (int64_t)G.tile_cnt.size());
     CHK(mem.alloc(&d_S, (size_t)max_slab, "score slab"));
@@ -172,8 +178,11 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     CHK(mem.alloc(&d_slot_base, (size_t)Q * nb * 4, "slot bases"));
     CHK(mem.alloc(&d_slot_pos0, (size_t)Q * nb * 8, "slot positions"));
     if (!on_device) {
-        CHK(mem.alloc(&d_D, (size_t)Q * k * 4, "dists"));
-        CHK(mem.alloc(&d_I, (size_t)Q * k * 4, "ids"));
+        if (part) CHK(mem.alloc(&d_P, (size_t)LMI_UNION_PART_PLANES * Q * k * 4, "part"));
+        else {
+            CHK(mem.alloc(&d_D, (size_t)Q * k * 4, "dists"));
+            CHK(mem.alloc(&d_I, (size_t)Q * k * 4, "ids"));
+        }
         CHK(mem.alloc(&d_C, (size_t)Q * 4, "counts"));
     }
     g_union_last[LMI_UNION_PLAN_GROUPS] = p.query_groups;
@@ -211,17 +220,30 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
             union_select_kernel<<<(int)W.slots, 64, lds, st>>>(d_S, d_slots + W.slot0, k, LR, d_lists);
             HIPCHK(hipGetLastError());
         }
-        float* oD = on_device ? dists + (size_t)G.q0 * k : d_D;
-        unsigned* oI = on_device ? ids + (size_t)G.q0 * k : d_I;
         int* oC = on_device ? (counts ? counts + G.q0 : nullptr) : d_C;
-        union_finish_kernel<<<(int)gq, 64, lds, st>>>(d_lists, d_slot_n, d_slot_base, d_slot_pos0, nb, LR, k, C.qn2 ? C.qn2 + G.q0 : nullptr,
-                                                     h->ids_slab.as<unsigned>(), oD, oI, oC);
-        HIPCHK(hipGetLastError());
-        if (!on_device) {
-            HIPCHK(hipMemcpyAsync(dists + (size_t)G.q0 * k, d_D, (size_t)gq * k * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(ids + (size_t)G.q0 * k, d_I, (size_t)gq * k * 4, hipMemcpyDeviceToHost, st));
-            if (counts) HIPCHK(hipMemcpyAsync(counts + G.q0, d_C, (size_t)gq * 4, hipMemcpyDeviceToHost, st));
+        if (part) {
+            // device pointers: the group's rows of every plane of the caller's block; host pointers: the staged planes, Q * k words apart
+            int* oP = on_device ? part + (size_t)G.q0 * k : d_P;
+            const long long plane = on_device ? (long long)nq * k : (long long)Q * k;
+            union_finish_part_kernel<<<(int)gq, 64, lds, st>>>(d_lists, d_slot_n, d_slot_base, d_slot_pos0, nb, LR, k,
+                                                              C.qn2 ? C.qn2 + G.q0 : nullptr, h->ids_slab.as<unsigned>(), oP, plane, oC);
+            HIPCHK(hipGetLastError());
+            if (!on_device)
+                for (int pl = 0; pl < LMI_UNION_PART_PLANES; ++pl)
+                    HIPCHK(hipMemcpyAsync(part + ((size_t)pl * nq + G.q0) * k, d_P + (size_t)pl * plane, (size_t)gq * k * 4,
+                                          hipMemcpyDeviceToHost, st));
+        } else {
+            float* oD = on_device ? dists + (size_t)G.q0 * k : d_D;
+            unsigned* oI = on_device ? ids + (size_t)G.q0 * k : d_I;
+            union_finish_kernel<<<(int)gq, 64, lds, st>>>(d_lists, d_slot_n, d_slot_base, d_slot_pos0, nb, LR, k,
+                                                         C.qn2 ? C.qn2 + G.q0 : nullptr, h->ids_slab.as<unsigned>(), oD, oI, oC);
+            HIPCHK(hipGetLastError());
+            if (!on_device) {
+                HIPCHK(hipMemcpyAsync(dists + (size_t)G.q0 * k, d_D, (size_t)gq * k * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(ids + (size_t)G.q0 * k, d_I, (size_t)gq * k * 4, hipMemcpyDeviceToHost, st));
+            }
         }
+        if (!on_device && counts) HIPCHK(hipMemcpyAsync(counts + G.q0, d_C, (size_t)gq * 4, hipMemcpyDeviceToHost, st));
         // the next group rewrites the tables and the lists; the host tables above live until the call returns
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -259,6 +281,24 @@ extern "C" LMI_API int lmi_scan_union(lmi_index* h, const float* queries_search,
     CHK(input_ptr(h, bucket_order, (size_t)nq * nb * 4, on_device, h->order, &d_order));
     begin_call(h);
     return union_core(h, who, static_cast<const float*>(d_qs), nq, static_cast<const int*>(d_order), nb, k, dists, ids, counts, on_device);
+}
+
+extern "C" LMI_API int lmi_scan_union_part(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, int k,
+                                           int32_t* part, int32_t* counts, int on_device) {
+    const char* who = "lmi_scan_union_part";
+    for (int64_t& w : g_union_last) w = 0;
+    if (!h) return fail("%s: NULL handle", who);
+    CHK(union_check(h, who, nq, nb, k));
+    if (nq == 0) return 0;
+    if (!queries_search || !bucket_order || !part) return fail("%s: queries_search, bucket_order and part must not be NULL", who);
+    CHK(set_dev(h));
+    const void* d_qs = nullptr;
+    const void* d_order = nullptr;
+    CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
+    CHK(input_ptr(h, bucket_order, (size_t)nq * nb * 4, on_device, h->order, &d_order));
+    begin_call(h);
+    return union_core(h, who, static_cast<const float*>(d_qs), nq, static_cast<const int*>(d_order), nb, k, nullptr, nullptr, counts, on_device,
+                      part);
 }
 
 extern "C" LMI_API int lmi_search_union(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,

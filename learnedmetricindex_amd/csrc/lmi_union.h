@@ -11,7 +11,8 @@
 //   union_select_kernel  one wave per slot: knn_select_wave over the slot's slab row into the slot's OWN list, entries
 //                        (score bits, ordinal) -- no two slots share a list, so nothing is written concurrently.
 // Per group, union_finish_kernel merges a query's nb lists (knn_merge_kernel's scheme), maps each ordinal to (rank, row), the row to
-// its slab position and id, the score to the scan's dist, and writes padding and counts.
+// its slab position and id, the score to the scan's dist, and writes padding and counts.  union_finish_part_kernel is the same body
+// writing a part (lmi_scan_union_part: score, dist, id, rank, row per result) for the merge across ranks (lmi_union_merge.h).
 #pragma once
 #include "lmi_knn.h"
 
@@ -145,15 +146,18 @@ __global__ __launch_bounds__(64) void union_select_kernel(const float* __restric
     knn_select_wave(S + sl.s_off, 0, sl.n, sl.base, k, LR, lists + sl.list, true);
 }
 
-// grid = the group's queries, block 64, dynamic LDS 2 * LR entries.  Query q (of the group): merges the lists of its ranks with rows
-// (slot_n[q][t] > 0; the others were never written) and writes D[q][k], I[q][k], counts[q] (nullable).  An entry's ordinal o belongs to
-// the last rank t with slot_base[q][t] <= o (the bases are the exclusive sums of slot_n: a rank without rows shares its successor's base
-// and is never the last); its object is row o - base of that bucket, at slab position slot_pos0[q][t] + row.  dist: sim_to_dist.
-__global__ __launch_bounds__(64) void union_finish_kernel(const knn_entry* __restrict__ lists, const int* __restrict__ slot_n,
-                                                          const unsigned* __restrict__ slot_base, const long long* __restrict__ slot_pos0,
-                                                          int nb, int LR, int k, const float* __restrict__ qn2,
-                                                          const unsigned* __restrict__ ids_slab, float* __restrict__ D,
-                                                          unsigned* __restrict__ I, int* __restrict__ counts) {
+// One wave, dynamic LDS 2 * LR entries.  Query q (of the group): merges the lists of its ranks with rows (slot_n[q][t] > 0; the others
+// were never written) and writes D[q][k], I[q][k], counts[q] (nullable).  An entry's ordinal o belongs to the last rank t with
+// slot_base[q][t] <= o (the bases are the exclusive sums of slot_n: a rank without rows shares its successor's base and is never the
+// last); its object is row o - base of that bucket, at slab position slot_pos0[q][t] + row.  dist: sim_to_dist.
+// PART: D and I are not used; part [LMI_UNION_PART_PLANES][plane] int32 words, plane = the words between two planes, gets at
+// q * k + j the score's bits, the dist's bits, the id, the rank t and the row (behind the real results: -FLT_MAX, +inf, 0, ~0, ~0).
+template <bool PART>
+__device__ __forceinline__ void union_finish_body(const knn_entry* __restrict__ lists, const int* __restrict__ slot_n,
+                                                  const unsigned* __restrict__ slot_base, const long long* __restrict__ slot_pos0, int nb,
+                                                  int LR, int k, const float* __restrict__ qn2, const unsigned* __restrict__ ids_slab,
+                                                  float* __restrict__ D, unsigned* __restrict__ I, int* __restrict__ counts,
+                                                  int* __restrict__ part, long long plane) {
     extern __shared__ knn_entry knn_lds[];
     const int lane = threadIdx.x, q = blockIdx.x;
     const int* sn = slot_n + (size_t)q * nb;
@@ -177,6 +181,7 @@ __global__ __launch_bounds__(64) void union_finish_kernel(const knn_entry* __res
         if (j >= k) continue;
         float dv = __builtin_inff();
         unsigned iv = 0u;
+        [[maybe_unused]] unsigned rank = 0xffffffffu, row = 0xffffffffu;
         if (have) {
             const unsigned o = knn_row(e);
             int lo = 0, hi = nb - 1;   // the last t with sb[t] <= o
@@ -187,11 +192,37 @@ __global__ __launch_bounds__(64) void union_finish_kernel(const knn_entry* __res
             }
             iv = ids_slab[sp[lo] + (long long)(o - sb[lo])];
             dv = sim_to_dist(knn_score(e), qn2, q);
+            if constexpr (PART) { rank = (unsigned)lo; row = o - sb[lo]; }
         }
-        D[(size_t)q * k + j] = dv;
-        I[(size_t)q * k + j] = iv;
+        if constexpr (PART) {
+            int* out = part + (size_t)q * k + j;
+            out[0 * plane] = (int)(have ? (unsigned)(e >> 32) : (unsigned)(KNN_EMPTY >> 32));
+            out[1 * plane] = (int)__float_as_uint(dv);
+            out[2 * plane] = (int)iv;
+            out[3 * plane] = (int)rank;
+            out[4 * plane] = (int)row;
+        } else {
+            D[(size_t)q * k + j] = dv;
+            I[(size_t)q * k + j] = iv;
+        }
     }
     if (counts && lane == 0) counts[q] = real;
+}
+
+// grid = the group's queries, block 64, dynamic LDS 2 * LR entries
+__global__ __launch_bounds__(64) void union_finish_kernel(const knn_entry* __restrict__ lists, const int* __restrict__ slot_n,
+                                                          const unsigned* __restrict__ slot_base, const long long* __restrict__ slot_pos0,
+                                                          int nb, int LR, int k, const float* __restrict__ qn2,
+                                                          const unsigned* __restrict__ ids_slab, float* __restrict__ D,
+                                                          unsigned* __restrict__ I, int* __restrict__ counts) {
+    union_finish_body<false>(lists, slot_n, slot_base, slot_pos0, nb, LR, k, qn2, ids_slab, D, I, counts, nullptr, 0);
+}
+__global__ __launch_bounds__(64) void union_finish_part_kernel(const knn_entry* __restrict__ lists, const int* __restrict__ slot_n,
+                                                               const unsigned* __restrict__ slot_base,
+                                                               const long long* __restrict__ slot_pos0, int nb, int LR, int k,
+                                                               const float* __restrict__ qn2, const unsigned* __restrict__ ids_slab,
+                                                               int* __restrict__ part, long long plane, int* __restrict__ counts) {
+    union_finish_body<true>(lists, slot_n, slot_base, slot_pos0, nb, LR, k, qn2, ids_slab, nullptr, nullptr, counts, part, plane);
 }
 
 }  // namespace lmi

@@ -9,6 +9,10 @@ Two layouts of the routing step (`ShardedSearcher(shard_inference=...)`):
   * False: every rank runs the MLP on the whole batch -- ONE collective per search (the all-gather above);
   * True (default for world > 1): every rank routes its 1/world slice of the batch and the bucket order
     (nq*nb*4 bytes) is all-gathered first -- TWO small collectives, 1/world of the MLP work per rank.
+`merge="union"` (both searchers) answers with the union scan instead: the k <= 1024 best objects of all visited
+buckets.  A rank's scan writes a PART (`Index.scan_union_part_device`: score bits | dist bits | ids | ranks | rows, int32 [5, nq, k]); the
+one result collective moves 20*nq*k bytes per rank and the merge orders by (score, bucket rank, row) -- by score, not by distance, whose
+rounding can make two scores one; by (rank, row), which orders as the single handle's ordinal does and needs no other rank's bucket sizes.
 `ReplicaSearcher` is the other mode SURVEY section 8e names: QUERY-sharded replicas -- every rank holds the whole
 index and answers its 1/world slice of the batch; one all-gather of [dists | ids | bucket order] rows.  A query's
 answer does not depend on the rest of its batch, so the result is again byte-identical for every world size.  It
@@ -138,6 +142,30 @@ def merge_blocks_numpy(gathered: np.ndarray, kout: int):
     return np.take_along_axis(d, order, 1).astype(np.float32), np.take_along_axis(i, order, 1)
 
 
+def merge_union_parts_numpy(gathered: np.ndarray):
+    """Host restatement of union_merge_kernel (lmi_merge_union_parts), used by the CPU tests only: gathered int32 [world, 5, nq, k] ->
+    (dists f32[nq, k], ids u32[nq, k], counts i32[nq])."""
+    world, five, nq, k = gathered.shape
+    assert five == 5
+    flat = lambda p: np.ascontiguousarray(gathered[:, p].transpose(1, 0, 2)).reshape(nq, world * k)
+    score = flat(0).view(np.float32).astype(np.float64)
+    dist, ids = flat(1).view(np.float32), flat(2).view(np.uint32)
+    rank, row = flat(3).view(np.uint32).astype(np.int64), flat(4).view(np.uint32).astype(np.int64)
+    real = row != 0xFFFFFFFF
+    src = np.broadcast_to(np.repeat(np.arange(world), k)[None, :], row.shape)
+    # padding behind everything real; -score: -0.0 and +0.0 compare equal
+    order = np.lexsort((src, row, rank, np.where(real, -score, np.inf)), axis=1)[:, :k]
+    sel = np.take_along_axis(real, order, 1)
+    d = np.where(sel, np.take_along_axis(dist, order, 1), np.float32(np.inf)).astype(np.float32)
+    i = np.where(sel, np.take_along_axis(ids, order, 1), 0).astype(np.uint32)
+    return d, i, sel.sum(axis=1).astype(np.int32)
+
+
+def _check_merge(merge) -> None:
+    if merge not in ("ranks", "union"):
+        raise ValueError(f"merge must be 'ranks' or 'union', not {merge!r}")
+
+
 class ShardedSearcher:
     """Device-side driver of the sharded search for one rank (torch tensors in, torch tensors out).
 
@@ -172,6 +200,7 @@ class ShardedSearcher:
         self.shard_inference = bool(shard_inference) and world > 1
         self.calls_per_search = 2 if self.shard_inference else 1
         self._buf = None
+        self._ubuf = None
         self._bo_loc = None
         # time_collectives: every collective of a search is bracketed by two events on the current stream (device tensors) -- what a
         # rank really WAITS for each exchange, the other ranks' lateness included; read with collective_ms() after a synchronize
@@ -241,9 +270,48 @@ class ShardedSearcher:
         if hi > lo:
             self.index.mlp_topk_device(qn_t[lo:hi], nb, bo_loc[: hi - lo])
 
-    def search_routed(self, qs_t, bo_loc, nb: int, k: int):
-        """The rest of a sharded search: all-gather of the bucket order, scan of the owned buckets, all-gather + merge."""
+    def _union_buffers(self, nq: int, nb: int, k: int, dev):
+        import torch
+
+        if self._ubuf is None or self._ubuf[0].shape != (5, nq, k) or self._ubuf[4].shape != (nq, nb):
+            self._ubuf = (torch.empty((5, nq, k), dtype=torch.int32, device=dev),
+                          torch.empty((nq, k), dtype=torch.float32, device=dev),
+                          torch.empty((nq, k), dtype=torch.int32, device=dev),
+                          torch.empty((nq,), dtype=torch.int32, device=dev),
+                          torch.empty((nq, nb), dtype=torch.int32, device=dev))
+        return self._ubuf
+
+    def _scan_exchange_union(self, qs_t, bo, nb: int, k: int):
+        """merge="union" behind the routing: this rank's part of the union scan over `bo`, then the exchange -- none for a world of one
+        without a communicator, `lmi_allgather_merge_union` with a `lib_comm`, else one all-gather of the [5, nq, k] block and
+        `lmi_merge_union_parts`.  -> (dists [nq, k], ids, bucket order, counts)."""
+        import torch
+
         nq = qs_t.shape[0]
+        part, out_d, out_i, cnt, _ = self._union_buffers(nq, nb, k, qs_t.device)
+        self.index.scan_union_part_device(qs_t, bo, nb, k, part, cnt)
+        if self.world == 1 and self.lib_comm is None:
+            return part[1].view(torch.float32), part[2], bo, cnt
+        if self.lib_comm is not None:
+            self._timed("result_allgather_merge",
+                        lambda: self.index.allgather_merge_union(self.lib_comm, self.rank, self.world, part, out_d, out_i, cnt), part.is_cuda)
+            return out_d, out_i, bo, cnt
+
+        def exchange():
+            g = all_gather_blocks(part, self.world, self.group)  # [world, 5, nq, k]
+            self.index.merge_union_parts(g, self.world, nq, k, out_d, out_i, cnt)
+
+        self._timed("result_allgather_merge", exchange, part.is_cuda)
+        return out_d, out_i, bo, cnt
+
+    def search_routed(self, qs_t, bo_loc, nb: int, k: int, merge: str = "ranks"):
+        """The rest of a sharded search: all-gather of the bucket order, scan of the owned buckets, all-gather + merge.
+        merge="union": the union scan, k <= 1024 -> (dists [nq, k], ids, bucket order, counts)."""
+        _check_merge(merge)
+        nq = qs_t.shape[0]
+        if merge == "union":
+            bo = self._timed("bucket_order_allgather", lambda: all_gather_rows(bo_loc, nq, self.world, self.group), bo_loc.is_cuda)
+            return self._scan_exchange_union(qs_t, bo, nb, k)
         kout = self.index.kout(nb, k)
         blk, out_d, out_i, _ = self._buffers(nq, nb, kout, qs_t.device)
         bo = self._timed("bucket_order_allgather", lambda: all_gather_rows(bo_loc, nq, self.world, self.group), bo_loc.is_cuda)
@@ -268,16 +336,22 @@ class ShardedSearcher:
         self._timed("result_allgather_merge", exchange, blk.is_cuda)
         return out_d, out_i, bo
 
-    def search(self, qn_t, qs_t, nb: int, k: int):
+    def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks"):
+        """(dists, ids, bucket order); merge="union": the union scan, k <= 1024 -> (dists [nq, k], ids, bucket order, counts)."""
+        _check_merge(merge)
         nq = qn_t.shape[0]
-        kout = self.index.kout(nb, k)
-        blk, out_d, out_i, bo = self._buffers(nq, nb, kout, qn_t.device)
-        # the three planes of `blk` are written in place by lmi_search / lmi_scan_topk
         if self.shard_inference:
             if self._bo_loc is None or self._bo_loc.shape[1] != nb or self._bo_loc.shape[0] != row_slice(nq, self.rank, self.world)[0]:
                 self._bo_loc = self.new_route_buffer(nq, nb, qn_t.device)
             self.route_local(qn_t, nb, self._bo_loc)
-            return self.search_routed(qs_t, self._bo_loc, nb, k)
+            return self.search_routed(qs_t, self._bo_loc, nb, k, merge)
+        if merge == "union":
+            bo = self._union_buffers(nq, nb, k, qn_t.device)[4]
+            self.index.mlp_topk_device(qn_t, nb, bo)
+            return self._scan_exchange_union(qs_t, bo, nb, k)
+        kout = self.index.kout(nb, k)
+        blk, out_d, out_i, bo = self._buffers(nq, nb, kout, qn_t.device)
+        # the three planes of `blk` are written in place by lmi_search / lmi_scan_topk
         self.index.search_device(qn_t, qs_t, nb, k, blk[0], blk[1], blk[2], bo)
         return self._exchange(blk, out_d, out_i, bo, nq, kout)
 
@@ -319,9 +393,32 @@ class ReplicaSearcher:
                          torch.empty((per, nb), dtype=torch.int32, device=dev))
         return self._buf
 
-    def search(self, qn_t, qs_t, nb: int, k: int):
+    def _search_union(self, qn_t, qs_t, nb: int, k: int):
+        """merge="union": `search_union_device` on the rank's slice, then one all-gather of [k dists | k ids | count | nb buckets] rows."""
         import torch
 
+        nq, dev = qn_t.shape[0], qn_t.device
+        per, lo, hi = row_slice(nq, self.rank, self.world)
+        d = torch.full((per, k), float("inf"), dtype=torch.float32, device=dev)
+        i = torch.zeros((per, k), dtype=torch.int32, device=dev)
+        c = torch.zeros((per,), dtype=torch.int32, device=dev)
+        bo = torch.full((per, nb), -1, dtype=torch.int32, device=dev)
+        if hi > lo:
+            n = hi - lo
+            self.index.search_union_device(qn_t[lo:hi], qs_t[lo:hi], nb, k, d[:n], i[:n], c[:n], bo[:n])
+        if self.world == 1:
+            return d[:nq], i[:nq], bo[:nq], c[:nq]
+        row = torch.cat([d.view(torch.int32), i, c[:, None], bo], dim=1)
+        g = all_gather_rows(row, nq, self.world, self.group)   # the one collective
+        return (g[:, :k].contiguous().view(torch.float32), g[:, k:2 * k].contiguous(), g[:, 2 * k + 1:].contiguous(),
+                g[:, 2 * k].contiguous())
+
+    def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks"):
+        import torch
+
+        _check_merge(merge)
+        if merge == "union":
+            return self._search_union(qn_t, qs_t, nb, k)
         nq = qn_t.shape[0]
         kout = self.index.kout(nb, k)
         per, lo, hi = row_slice(nq, self.rank, self.world)

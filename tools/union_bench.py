@@ -13,6 +13,10 @@ sends an object to its cluster and a query to the 4 nearest) -- ms per batch, de
 and recall@k of the union results against lmi_knn over the first --recall-queries queries.  lmi_knn, lmi_search and both of its
 modes are the code the union scan was added beside; nothing here is a pass/fail gate.  A record of the machine it runs on.
 
+The sharded leg (profiles/union_sharded.txt) follows the union rows on the same index and bucket order, batches timed one by one:
+lmi_scan_union and lmi_scan_union_part (a rank's part: the same launches, five planes written instead of two), and
+lmi_merge_union_parts alone on the parts of emulated worlds of 2 and 8 ranks (rank r owns the buckets b with b % world == r).
+
   python tools/union_bench.py                          # the full shape: about 80 GB of device memory
   python tools/union_bench.py --n 400000 --nq 2000     # a quick look"""
 import argparse
@@ -110,6 +114,46 @@ def main():
         recall = float(np.mean([len(set(t_) & set(f)) / float(k) for t_, f in zip(truth[:, :k].tolist(), got.tolist())]))
         print(f"lmi_search_union | {k} | {ms:.2f} | {recall:.4f} | groups {plan['GROUPS']} waves {plan['WAVES']} slab {plan['SLAB_BYTES'] >> 20} MiB "
               f"workspace {plan['WORKSPACE_BYTES'] >> 20} MiB; mean results {float(c_t.float().mean().item()):.1f}", flush=True)
+
+    # ---- the sharded leg: a rank's part beside lmi_scan_union, and the merge kernel alone for emulated worlds ----
+    def timed_each(fn, steps):
+        """(min, mean, max) ms over `steps` batches timed one by one, after one warm-up batch."""
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(steps):
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append(1e3 * (time.perf_counter() - t))
+        return min(ms), sum(ms) / len(ms), max(ms)
+
+    print("# sharded leg: call | k | ms per batch min / mean / max | note")
+    steps = max(a.steps, 5)
+    for k in a.ks:
+        d_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        i_t = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        c_t = torch.empty((nq,), dtype=torch.int32, device=dev)
+        part = torch.empty((5, nq, k), dtype=torch.int32, device=dev)
+        c_p = torch.empty((nq,), dtype=torch.int32, device=dev)
+        lo, mean, hi = timed_each(lambda: eng.scan_union_device(Q, bo, nb, k, d_t, i_t, c_t), steps)
+        print(f"lmi_scan_union | {k} | {lo:.2f} / {mean:.2f} / {hi:.2f} |", flush=True)
+        lo, mean, hi = timed_each(lambda: eng.scan_union_part_device(Q, bo, nb, k, part, c_p), steps)
+        ok = torch.equal(part[1], d_t.view(torch.int32)) and torch.equal(part[2], i_t) and torch.equal(c_p, c_t)
+        print(f"lmi_scan_union_part | {k} | {lo:.2f} / {mean:.2f} / {hi:.2f} | dist, id, counts {'equal' if ok else 'DIFFER from'} lmi_scan_union's",
+              flush=True)
+        for world in (2, 8):
+            # rank r of the emulated world owns the buckets b with b % world == r: the others are struck out of its order, which is what
+            # an `owned` mask does to them (no rows), and leaves every rank t where it is
+            parts = torch.empty((world, 5, nq, k), dtype=torch.int32, device=dev)
+            for r in range(world):
+                eng.scan_union_part_device(Q, torch.where(bo % world == r, bo, torch.full_like(bo, -1)), nb, k, parts[r])
+            m_d, m_i, m_c = torch.empty_like(d_t), torch.empty_like(i_t), torch.empty_like(c_t)
+            lo, mean, hi = timed_each(lambda: eng.merge_union_parts(parts, world, nq, k, m_d, m_i, m_c), steps)
+            ok = torch.equal(m_d.view(torch.int32), d_t.view(torch.int32)) and torch.equal(m_i, i_t) and torch.equal(m_c, c_t)
+            print(f"lmi_merge_union_parts, world {world} | {k} | {lo:.3f} / {mean:.3f} / {hi:.3f} | {world * 20 * nq * k >> 20} MiB of parts; "
+                  f"{'equal to' if ok else 'DIFFERS from'} lmi_scan_union", flush=True)
+            del parts
 
     d_t = torch.empty((nq, 10), dtype=torch.float32, device=dev)
     i_t = torch.empty((nq, 10), dtype=torch.int32, device=dev)
