@@ -588,6 +588,63 @@ enum {
  * min(n, LMI_UNION_PLAN_COUNT) words. */
 LMI_API int lmi_debug_union_plan(int64_t *out, int n);
 
+/* The filtered union scan (no reference counterpart): the union scan with every query's candidates restricted to a set of ids -- a
+ * tenant, a category, "not these" -- without a second index (lmi_subset makes one; a filter set is one bit per (filter, stored row)).
+ * A FILTER SET holds nf filters over one built index.  Filter j is an id list plus a mode: LMI_FILTER_KEEP -- a stored row is ALLOWED
+ * iff its id is in the list; LMI_FILTER_DROP -- iff it is not.  The library sorts and de-duplicates the lists; ids the index does not
+ * hold are ignored; rows that share an id all follow it; an empty KEEP list allows nothing, an empty DROP list everything.
+ * Query q uses filter filter_of[q], an int32 ON THE HOST (also with on_device) in [-1, nf): -1 = unfiltered; a NULL filter_of = every
+ * query uses filter 0.
+ * Contract: lmi_scan_union's, with the candidate set reduced to the allowed rows.  Ordinals stay the positions in the UNFILTERED
+ * concatenation, scores the unsplit canonical chains; selection takes the first k ALLOWED candidates in (score descending with
+ * -0 == +0, ordinal ascending) among the scores > -FLT_MAX; dist, id, padding and counts as there.  Restated twice:
+ *   oracle.knn_ip / knn_l2 of the query against the concatenation of its buckets' allowed rows;
+ *   for a batch that uses one filter: lmi_subset(h, list, mode) followed by lmi_scan_union with the same order, bit for bit.
+ * The filter acts on the SCAN, not on the routing: lmi_set_stop_rows, lmi_set_stop_mass and lmi_set_path_mass count live bucket
+ * sizes and model probabilities exactly as before -- a bucket whose rows are all disallowed still uses up the budget.
+ * A (query, rank) whose (filter, bucket) pair allows no row is neither scored nor selected (lmi_debug_filter_plan counts them).
+ * Validity: the masks are keyed by slab position.  A filter set fits the handle it was made from and that handle's clone views, until
+ * the layout changes: after lmi_buckets_insert / lmi_buckets_delete, on lmi_subset's output and on any other index it is refused --
+ * the message says "stale" -- and must be made again.  It may outlive the handle; it holds nf * (rows / 8, per row-block of 32) bytes
+ * of device memory.
+ * lmi_filter_create: all pointers are HOST pointers; ids holds the lists back to back, filter j's at [offsets[j], offsets[j + 1]).
+ * Refused: a NULL handle or out; an index that is not built; nf outside 1..LMI_FILTER_MAX; offsets[0] != 0, offsets that are not
+ * non-decreasing, 2^31 ids or more in all; a mode other than KEEP / DROP; an index of more than 65535 buckets.
+ * lmi_filter_counts: out [nf][L] <- the allowed rows per (filter, bucket).  lmi_filter_bucket_mask: out [n_b] <- one byte (0 / 1) per
+ * row of the bucket, in lmi_bucket_read's order (for tests and diagnostics).
+ * The filtered calls take their parent's arguments plus (f, filter_of).  Refused before any launch: everything the parent refuses
+ * (an index that is not stored row-major included); a NULL filter; a stale or foreign filter; a filter_of entry outside [-1, nf).
+ * Not offered: filters on lmi_search's rank merge, a filtered lmi_scan_union_part, _f16 query forms, lmi_pipeline_submit. */
+typedef struct lmi_filter lmi_filter;
+#define LMI_FILTER_KEEP 0   /* the list names the allowed ids    */
+#define LMI_FILTER_DROP 1   /* the list names the disallowed ids */
+#define LMI_FILTER_MAX 1024 /* filters of one set                */
+LMI_API int lmi_filter_create(lmi_index *h, const uint32_t *ids, const int64_t *offsets /* [nf + 1] */, int nf,
+                              const int32_t *modes /* [nf] */, lmi_filter **out);
+LMI_API int lmi_filter_destroy(lmi_filter *f);
+LMI_API int lmi_filter_counts(lmi_filter *f, int64_t *out /* [nf][L] */);
+LMI_API int lmi_filter_bucket_mask(lmi_filter *f, int j, int bucket, uint8_t *out /* [n_b] */);
+LMI_API int lmi_scan_union_filtered(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb, int k,
+                                    float *dists, uint32_t *ids, int32_t *counts, int on_device, const lmi_filter *f,
+                                    const int32_t *filter_of /* host [nq], nullable */);
+LMI_API int lmi_search_union_filtered(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb, int k,
+                                      float *dists, uint32_t *ids, int32_t *counts, int32_t *bucket_order, int on_device,
+                                      const lmi_filter *f, const int32_t *filter_of /* host [nq], nullable */);
+LMI_API int lmi_search_tree_union_filtered(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb, int k,
+                                           float *dists, uint32_t *ids, int32_t *counts, int32_t *slab_ids, int32_t *entries,
+                                           int on_device, const lmi_filter *f, const int32_t *filter_of /* host [nq], nullable */);
+enum {
+    LMI_FILTER_PLAN_FILTERS = 0,      /* filters of the set the call was given                                                */
+    LMI_FILTER_PLAN_MASK_BYTES,       /* bytes of the set's masks on the device                                               */
+    LMI_FILTER_PLAN_SLOTS,            /* (query, rank) slots of the last group that were scored and selected                  */
+    LMI_FILTER_PLAN_SKIPPED,          /* slots of the whole call left out because their (filter, bucket) pair allows no row   */
+    LMI_FILTER_PLAN_COUNT
+};
+/* What the last filtered union call on this thread did (all zero before the first, after a refused call, after one with nq == 0
+ * and after an unfiltered union call); writes min(n, LMI_FILTER_PLAN_COUNT) words.  lmi_debug_union_plan reports the same call's
+ * geometry. */
+LMI_API int lmi_debug_filter_plan(int64_t *out, int n);
+
 /* The union scan across the ranks of a bucket-sharded index (no reference counterpart): every rank scans the buckets it owns and
  * hands on a PART; the merge of the parts is what lmi_scan_union returns on one handle that holds the whole index, bit for bit, for
  * any assignment of the buckets (each owned by exactly one part) and any world size.

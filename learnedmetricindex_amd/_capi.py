@@ -34,6 +34,10 @@ UNION_MAX_K = 1024   # LMI_UNION_MAX_K: the largest k of the union scan (`Index.
 UNION_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "LIST_ROWS", "LISTS_PER_QUERY", "WORKSPACE_BYTES", "VEC_ROWS")
 UNION_PART_PLANES = 5   # LMI_UNION_PART_PLANES: a part of the union scan is int32 [5, nq, k] -- the LMI_UPART_* planes, in their order:
 UPART_SCORE, UPART_DIST, UPART_ID, UPART_RANK, UPART_ROW = range(5)
+FILTER_KEEP, FILTER_DROP = 0, 1   # LMI_FILTER_KEEP, LMI_FILTER_DROP: the list names the allowed / the disallowed ids
+FILTER_MAX = 1024                 # LMI_FILTER_MAX: filters of one set (`Filter`)
+#: the LMI_FILTER_PLAN_* words, in their order (lmi_debug_filter_plan)
+FILTER_PLAN_FIELDS = ("FILTERS", "MASK_BYTES", "SLOTS", "SKIPPED")
 
 _lib = None
 
@@ -103,6 +107,17 @@ SIGNATURES = {
     "lmi_scan_union_part": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_merge_union_parts": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_allgather_merge_union": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    # filter sets and the filtered union scan: the parent call's arguments, then (filter, filter_of on the host)
+    "lmi_filter_create": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "lmi_filter_destroy": (ctypes.c_int, [_vp]),
+    "lmi_filter_counts": (ctypes.c_int, [_vp, _vp]),
+    "lmi_filter_bucket_mask": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "lmi_scan_union_filtered": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "lmi_search_union_filtered": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                 _vp, _vp]),
+    "lmi_search_tree_union_filtered": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
+                                                      ctypes.c_int, _vp, _vp]),
+    "lmi_debug_filter_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -676,9 +691,33 @@ class Index:
         if len(rows) > 1:
             raise ValueError(f"{who}: the arrays disagree about the number of queries ({sorted(rows)})")
 
-    def scan_union(self, queries_search, bucket_order, k: int = 10):
+    @staticmethod
+    def _filter_args(who: str, filter, filter_of, nq: int):
+        """(filter handle, filter_of i32[nq] or None) of a filtered union call; argument errors are raised before the library loads.
+        `filter_of` stays on the host also for the `_device` forms."""
+        if filter is None:
+            if filter_of is not None:
+                raise ValueError(f"{who}: filter_of without a filter")
+            return None, None
+        if not isinstance(filter, Filter):
+            raise ValueError(f"{who}: filter must be a _capi.Filter, not {type(filter).__name__}")
+        if getattr(filter, "_f", None) is None:
+            raise ValueError(f"{who}: the filter is closed")
+        if filter_of is None:
+            return filter._f, None
+        fo = np.asarray(filter_of.cpu().numpy() if hasattr(filter_of, "cpu") else filter_of)
+        if fo.ndim != 1 or fo.shape[0] != nq or fo.dtype.kind not in "iu":
+            raise ValueError(f"{who}: filter_of must be one integer per query ([{nq}]), not {fo.dtype}{tuple(fo.shape)}")
+        if fo.size and (fo.min() < -1 or fo.max() >= filter.nf):
+            raise ValueError(f"{who}: filter_of holds a value outside [-1, {filter.nf})")
+        return filter._f, _np(fo, np.int32)
+
+    def scan_union(self, queries_search, bucket_order, k: int = 10, filter=None, filter_of=None):
         """(dists f32[nq,k], ids u32[nq,k], counts i32[nq]) of `lmi_scan_union`: per query the k best objects of the union of the
-        buckets `bucket_order[q]` lists (-1: none); behind `counts[q]` real results dist = +inf, id = 0."""
+        buckets `bucket_order[q]` lists (-1: none); behind `counts[q]` real results dist = +inf, id = 0.
+        `filter` (a `Filter` made on this index) restricts every query's candidates to the rows its filter allows
+        (`lmi_scan_union_filtered`): query q uses filter `filter_of[q]` (int, -1 = unfiltered; None = all use filter 0).  The same two
+        keywords on `search_union`, `search_tree_union` and the `_device` forms, where `filter_of` stays a host array."""
         if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
             raise ValueError("scan_union: bucket_order must be a two-dimensional array")
         nb = int(bucket_order.shape[1])
@@ -689,11 +728,15 @@ class Index:
         d = np.empty((nq, k), dtype=np.float32)
         i = np.empty((nq, k), dtype=np.uint32)
         c = np.empty((nq,), dtype=np.int32)
-        _check(lib().lmi_scan_union(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0))
+        f, fo = self._filter_args("scan_union", filter, filter_of, nq)
+        if f is None:
+            _check(lib().lmi_scan_union(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0))
+        else:
+            _check(lib().lmi_scan_union_filtered(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0, f, _ptr(fo)))
         return d, i, c
 
-    def search_union(self, queries_nav, queries_search, nb: int, k: int = 10):
-        """`lmi_search_union`: (dists, ids, counts, bucket order i32[nq,nb])."""
+    def search_union(self, queries_nav, queries_search, nb: int, k: int = 10, filter=None, filter_of=None):
+        """`lmi_search_union`: (dists, ids, counts, bucket order i32[nq,nb]).  `filter`, `filter_of`: as in `scan_union`."""
         self._union_args("search_union", k, nb, queries_nav=queries_nav, queries_search=queries_search)
         same = queries_search is queries_nav
         qn = _np(queries_nav, np.float32)
@@ -703,11 +746,17 @@ class Index:
         i = np.empty((nq, k), dtype=np.uint32)
         c = np.empty((nq,), dtype=np.int32)
         bo = np.empty((nq, nb), dtype=np.int32)
-        _check(lib().lmi_search_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0))
+        f, fo = self._filter_args("search_union", filter, filter_of, nq)
+        if f is None:
+            _check(lib().lmi_search_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0))
+        else:
+            _check(lib().lmi_search_union_filtered(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0,
+                                                   f, _ptr(fo)))
         return d, i, c, bo
 
-    def search_tree_union(self, queries_nav, queries_search, nb: int, k: int = 10):
-        """`lmi_search_tree_union`: (dists, ids, counts, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb])."""
+    def search_tree_union(self, queries_nav, queries_search, nb: int, k: int = 10, filter=None, filter_of=None):
+        """`lmi_search_tree_union`: (dists, ids, counts, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb]).  `filter`,
+        `filter_of`: as in `scan_union`."""
         self._union_args("search_tree_union", k, nb, queries_nav=queries_nav, queries_search=queries_search)
         same = queries_search is queries_nav
         qn = _np(queries_nav, np.float32)
@@ -718,23 +767,47 @@ class Index:
         c = np.empty((nq,), dtype=np.int32)
         slab = np.empty((nq, nb), dtype=np.int32)
         ent = np.empty((nq, nb), dtype=np.int32)
-        _check(lib().lmi_search_tree_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab), _ptr(ent), 0))
+        f, fo = self._filter_args("search_tree_union", filter, filter_of, nq)
+        if f is None:
+            _check(lib().lmi_search_tree_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab), _ptr(ent), 0))
+        else:
+            _check(lib().lmi_search_tree_union_filtered(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab),
+                                                        _ptr(ent), 0, f, _ptr(fo)))
         return d, i, c, slab, ent
 
-    def scan_union_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, counts_t=None) -> None:
+    def scan_union_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, counts_t=None, filter=None, filter_of=None) -> None:
         """Device tensors (float32 queries, int32 order, float32 / uint32-sized / int32 outputs); returns when they have landed."""
         self._union_args("scan_union_device", k, nb, queries_search=qs_t, bucket_order=bo_t)
-        _check(lib().lmi_scan_union(self._h, _ptr(qs_t), int(qs_t.shape[0]), _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1))
+        nq = int(qs_t.shape[0])
+        f, fo = self._filter_args("scan_union_device", filter, filter_of, nq)
+        if f is None:
+            _check(lib().lmi_scan_union(self._h, _ptr(qs_t), nq, _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1))
+        else:
+            _check(lib().lmi_scan_union_filtered(self._h, _ptr(qs_t), nq, _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1,
+                                                 f, _ptr(fo)))
 
-    def search_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, bo_t=None) -> None:
+    def search_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, bo_t=None, filter=None, filter_of=None) -> None:
         self._union_args("search_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
-        _check(lib().lmi_search_union(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
-                                      _ptr(counts_t), _ptr(bo_t), 1))
+        nq = int(qn_t.shape[0])
+        f, fo = self._filter_args("search_union_device", filter, filter_of, nq)
+        if f is None:
+            _check(lib().lmi_search_union(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
+                                          _ptr(counts_t), _ptr(bo_t), 1))
+        else:
+            _check(lib().lmi_search_union_filtered(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
+                                                   _ptr(counts_t), _ptr(bo_t), 1, f, _ptr(fo)))
 
-    def search_tree_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, slab_t=None, ent_t=None) -> None:
+    def search_tree_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, slab_t=None, ent_t=None, filter=None,
+                                 filter_of=None) -> None:
         self._union_args("search_tree_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
-        _check(lib().lmi_search_tree_union(self._h, _ptr(qn_t), _ptr(qs_t), int(qn_t.shape[0]), int(nb), int(k), _ptr(d_t), _ptr(i_t),
-                                           _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1))
+        nq = int(qn_t.shape[0])
+        f, fo = self._filter_args("search_tree_union_device", filter, filter_of, nq)
+        if f is None:
+            _check(lib().lmi_search_tree_union(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
+                                               _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1))
+        else:
+            _check(lib().lmi_search_tree_union_filtered(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
+                                                        _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1, f, _ptr(fo)))
 
     # ---- the union scan across ranks: a rank's part and the merge of the parts (include/lmi_hip.h, lmi_scan_union_part) ----
     @staticmethod
@@ -973,6 +1046,86 @@ def knn_last_plan() -> dict:
     w = (ctypes.c_int64 * len(KNN_PLAN_FIELDS))()
     _check(lib().lmi_debug_knn_plan(w, len(KNN_PLAN_FIELDS)))
     return dict(zip(KNN_PLAN_FIELDS, (int(v) for v in w)))
+
+
+class Filter:
+    """A filter set over one built `Index` (`lmi_filter_create`): `lists[j]` holds filter j's ids, `modes[j]` is "keep" / FILTER_KEEP
+    (a stored row is allowed iff its id is listed; the default) or "drop" / FILTER_DROP (iff it is not).  Duplicates and ids the
+    index does not hold are ignored; an empty keep list allows nothing, an empty drop list everything.  Passed as `filter=` to
+    `Index.scan_union`, `search_union`, `search_tree_union` and their `_device` forms, on the index it was made on or a clone
+    view of it; after `insert` / `delete`, and on a `subset`, the library refuses it as stale and it has to be made again.
+    Argument errors raise ValueError before the library loads."""
+
+    MODES = {"keep": FILTER_KEEP, "drop": FILTER_DROP, FILTER_KEEP: FILTER_KEEP, FILTER_DROP: FILTER_DROP}
+
+    def __init__(self, index: "Index", lists, modes=None):
+        self._f = None   # (closed until the library has made it)
+        ids, offsets, modes_a = self.pack(lists, modes)
+        self.nf = int(modes_a.shape[0])
+        f = _vp()
+        _check(lib().lmi_filter_create(index._h, _ptr(ids), _ptr(offsets), self.nf, _ptr(modes_a), ctypes.byref(f)))
+        self._f = f
+        self.L = int(index.L)
+        self._sizes = index.bucket_sizes()
+
+    @classmethod
+    def pack(cls, lists, modes=None):
+        """(ids u32[total], offsets i64[nf + 1], modes i32[nf]): the arguments of `lmi_filter_create`."""
+        if isinstance(lists, np.ndarray) and lists.ndim == 1:
+            raise ValueError("Filter: lists must be a sequence of id lists (one per filter), not one flat array")
+        lists = [np.asarray(a).reshape(-1) for a in lists]
+        nf = len(lists)
+        if nf < 1 or nf > FILTER_MAX:
+            raise ValueError(f"Filter: {nf} filters outside [1, {FILTER_MAX}]")
+        modes = ["keep"] * nf if modes is None else list(modes)
+        if len(modes) != nf:
+            raise ValueError(f"Filter: {len(modes)} modes for {nf} lists")
+        for m in modes:
+            if isinstance(m, (bool, float)) or m not in cls.MODES:
+                raise ValueError(f"Filter: mode {m!r} is neither 'keep' / FILTER_KEEP nor 'drop' / FILTER_DROP")
+        for j, a in enumerate(lists):
+            if a.size and a.dtype.kind not in "iu":   # (an empty list is float64 and has nothing to truncate)
+                raise ValueError(f"Filter: the ids of filter {j} must be integers, not {a.dtype}")
+            if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+                raise ValueError(f"Filter: the ids of filter {j} must fit uint32")
+        offsets = np.zeros(nf + 1, dtype=np.int64)
+        np.cumsum([a.size for a in lists], out=offsets[1:])
+        if offsets[-1] >= 2 ** 31:
+            raise ValueError("Filter: 2^31 ids or more in all")
+        ids = _np(np.concatenate(lists), np.uint32) if offsets[-1] else np.zeros(0, dtype=np.uint32)
+        return ids, offsets, np.asarray([cls.MODES[m] for m in modes], dtype=np.int32)
+
+    def counts(self) -> np.ndarray:
+        """i64[nf, L]: the allowed rows per (filter, bucket) (`lmi_filter_counts`)."""
+        out = np.zeros((self.nf, self.L), dtype=np.int64)
+        _check(lib().lmi_filter_counts(self._f, _ptr(out)))
+        return out
+
+    def bucket_mask(self, j: int, bucket: int) -> np.ndarray:
+        """u8[n_b]: 1 where filter j allows the row, in `read_bucket`'s order (`lmi_filter_bucket_mask`)."""
+        if not 0 <= int(j) < self.nf or not 0 <= int(bucket) < self.L:
+            raise ValueError(f"bucket_mask: (filter {j}, bucket {bucket}) outside ({self.nf}, {self.L})")
+        out = np.zeros(int(self._sizes[bucket]), dtype=np.uint8)
+        _check(lib().lmi_filter_bucket_mask(self._f, int(j), int(bucket), _ptr(out)))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "_f", None) is not None:
+            f, self._f = self._f, None
+            lib().lmi_filter_destroy(f)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def filter_last_plan() -> dict:
+    """What the last filtered union call on this thread did (`lmi_debug_filter_plan`): `FILTER_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(FILTER_PLAN_FIELDS))()
+    _check(lib().lmi_debug_filter_plan(w, len(FILTER_PLAN_FIELDS)))
+    return dict(zip(FILTER_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -169,6 +170,10 @@ struct Buckets {
     std::vector<unsigned char> h_owned;  // lmi_buckets_begin's `owned` (empty: every bucket)
     std::vector<unsigned char> h_any;    // per bucket: holds rows on some rank (n_nonempty)
     int64_t mut_paths[4] = {0, 0, 0, 0}; // lmi_debug_layout: buckets filled in their slack, buckets relocated, growth re-packs, hole re-packs
+    // which layout this is (next_layout_stamp: lmi_buckets_end, every lmi_buckets_insert / _delete that changes the slab, lmi_subset's
+    // output).  Copied with the struct: a clone view carries its parent's.  Read by the filters only (lmi_host_filter.h): a filter's
+    // masks are keyed by slab position and hold for the handles that carry the stamp it was made under
+    uint64_t layout_stamp = 0;
     // lmi_index_bytes: what is held for the index right now: the vector images, the ids, the per-bucket tables (a clone view: its parent's)
     int64_t index_bytes() const {
         int64_t t = 0;
@@ -179,6 +184,12 @@ struct Buckets {
 };
 
 struct lmi_index;
+
+// a value no other layout of this process carries (never 0: a handle without a built index)
+inline uint64_t next_layout_stamp() {
+    static std::atomic<uint64_t> counter{0};
+    return ++counter;
+}
 
 // ---- per handle: workspaces, staging, streams, events, timing and statistics.  Never copied: a clone view starts with a fresh one ----
 struct CallState {

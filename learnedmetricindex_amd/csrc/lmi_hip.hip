@@ -19,7 +19,8 @@
 #include "lmi_knn.h"          // the kernels of lmi_knn
 #include "lmi_host_knn.h"     // lmi_knn, lmi_knn_set_geometry, lmi_debug_knn_plan
 #include "lmi_union.h"        // the kernels of the union scan
-#include "lmi_host_union.h"   // lmi_scan_union / lmi_scan_union_part / lmi_search_union / lmi_search_tree_union, geometry and plan hooks
+#include "lmi_filter.h"       // the kernels of the filter sets and the masked select of the filtered union scan
+#include "lmi_host_union.h"   // lmi_scan_union / lmi_scan_union_part / lmi_search_union / lmi_search_tree_union, geometry and plan hooks; the *_filtered forms (lmi_host_filter.h)
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

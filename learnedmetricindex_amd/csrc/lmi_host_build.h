@@ -333,6 +333,7 @@ extern "C" LMI_API int lmi_buckets_end(lmi_index* h) {
     } else if (h->prefilter && h->n_rb_total > 0) CHK(prefilter_images(h));
     h->building = false;
     h->built = true;
+    h->layout_stamp = next_layout_stamp();
     return 0;
 }
 

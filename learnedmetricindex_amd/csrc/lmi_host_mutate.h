@@ -259,6 +259,7 @@ static int insert_impl(lmi_index* h, const void* rows, int src16, const int64_t*
     CHK(set_dev(h));
     CHK(insert_reserve(h, nrows, src16, on_device));
     HIPCHK(hipStreamSynchronize(h->stream));   // searches enqueued before the call read the index as it was
+    h->layout_stamp = next_layout_stamp();     // from here on the slab changes: the filters made before the call are stale
     CHK(insert_relocate(h, plan));
     CHK(insert_scatter(h, rows, src16, labels, ids, nrows, on_device));
     const RangeList ranges = insert_ranges(h, add, labels, nrows);
@@ -352,6 +353,7 @@ extern "C" LMI_API int lmi_buckets_delete(lmi_index* h, const uint32_t* ids, int
             removed += h->h_nb_rows[b] - kept[b];
         }
     if (removed == 0) return 0;
+    h->layout_stamp = next_layout_stamp();   // from here on the slab changes: the filters made before the call are stale
     CHK(delete_compact(h, hit, span));
     // 5: the tables, then the hit buckets' fp16 row-blocks and maxima from their rows as they are now
     for (int b : hit) {

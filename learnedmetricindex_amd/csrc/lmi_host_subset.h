@@ -134,6 +134,7 @@ static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t 
     for (DevBuf* b : {&c->mut_ids, &c->mut_keep, &c->mut_src, &c->mut_word, &c->mut_list, &c->mut_stage}) b->release();   // the call's maps
     c->building = false;
     c->built = true;
+    c->layout_stamp = next_layout_stamp();   // its own layout: no filter of the source fits it
     if (n_kept) *n_kept = kept;
     return 0;
 }

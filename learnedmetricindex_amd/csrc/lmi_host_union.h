@@ -2,9 +2,12 @@
 // the handle's stream.  The bucket order comes back to the host once (that is the call's internal synchronisation): per query group the
 // host sorts the slots by bucket, cuts them into waves and writes the item tables; per wave pack, score, select; per group one finish.
 // lmi_scan_union, lmi_scan_union_part, lmi_search_union, lmi_search_tree_union, lmi_union_set_geometry, lmi_debug_union_plan.
+// The filtered forms (lmi_scan_union_filtered, lmi_search_union_filtered, lmi_search_tree_union_filtered; lmi_host_filter.h) are the
+// same schedule with two differences: a slot whose (filter, bucket) pair allows no row is left out, and the select is the masked one.
 #pragma once
 #include "lmi_host.h"
 #include "lmi_host_call.h"
+#include "lmi_host_filter.h"
 #include "lmi_host_model.h"
 #include "lmi_host_scan.h"
 #include "lmi_union.h"
@@ -50,8 +53,12 @@ int union_check(lmi_index* h, const char* who, int nq, int nb, int k) {
 
 // d_qs [nq][d_user] and d_order [nq][nb] on the device, already enqueued on h->stream; dists / ids / counts as the caller gave them.
 // part != nullptr (lmi_scan_union_part): the caller's [LMI_UNION_PART_PLANES][nq][k] block is written instead of dists / ids.
+// f != nullptr (the filtered forms; filter_check has passed): query q's candidates are the rows filter filter_of[q] allows (host [nq];
+// nullptr: filter 0; -1: all rows).  A slot whose (filter, bucket) pair allows no row gets slot_n = 0 and no slot -- it is not packed,
+// scored or selected -- while slot_base still advances by the bucket's rows: ordinals stay the unfiltered concatenation's, the finish
+// kernel skips the rank, and no entry carries an ordinal of the gap.  Without f nothing differs from the unfiltered call.
 int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const int* d_order, int nb, int k, float* dists, uint32_t* ids,
-               int32_t* counts, int on_device, int32_t* part = nullptr) {
+               int32_t* counts, int on_device, int32_t* part = nullptr, const lmi_filter* f = nullptr, const int32_t* filter_of = nullptr) {
     namespace up = lmi_union_plan;
     hipStream_t st = h->stream;
     const int L = h->L;
@@ -82,9 +89,11 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
         std::vector<int> rowq, tile_cnt, slot_n;
         std::vector<long long> tile_off, slot_pos0;
         std::vector<unsigned> slot_base;
+        std::vector<long long> slot_mask;   // filtered: beside `slots`, the word offset of each slot's mask row (-1: unfiltered query)
     };
     std::vector<Group> groups((size_t)p.query_groups);
-    int64_t max_slab = 0, max_tiles = 0, max_items = 0, max_slots = 0;
+    int64_t max_slab = 0, max_tiles = 0, max_items = 0, max_slots = 0, skipped = 0;
+    auto filter_of_query = [&](int64_t q) -> int { return f ? (filter_of ? filter_of[q] : 0) : -1; };
     std::vector<int64_t> rows64(nrows.begin(), nrows.end());
     for (int64_t g = 0; g < p.query_groups; ++g) {
         Group& G = groups[g];
@@ -96,12 +105,16 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
         std::vector<int64_t> cnt(L, 0);
         for (int64_t q = 0; q < gq; ++q) {
             int64_t base = 0;
+            const int fj = filter_of_query(G.q0 + q);
             for (int t = 0; t < nb; ++t) {
                 const int b = order[(size_t)(G.q0 + q) * nb + t];
                 const int n = b >= 0 && b < L ? nrows[b] : 0;
+                const bool dead = fj >= 0 && n > 0 && f->counts[(size_t)fj * L + b] == 0;   // the filter allows no row of the bucket
                 G.slot_base[q * nb + t] = (unsigned)base;
-                G.slot_n[q * nb + t] = n;
-                if (n > 0) { G.slot_pos0[q * nb + t] = (long long)rbs[b] * 32; cnt[b]++; base += n; }
+                G.slot_n[q * nb + t] = dead ? 0 : n;
+                if (n > 0) base += n;
+                if (dead) ++skipped;
+                else if (n > 0) { G.slot_pos0[q * nb + t] = (long long)rbs[b] * 32; cnt[b]++; }
             }
         }
         // a bucket's slots in (query, rank) order
@@ -128,6 +141,10 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
                 const int64_t s = real ? by_bucket[start[c.bucket] + c.slot0 + i] : -1;
                 G.rowq.push_back(real ? (int)(G.q0 + s / nb) : -1);
                 if (real) G.slots.push_back(UnionSlot{c.slab_off + i * pitch, s * LR, (int)c.n, G.slot_base[s]});
+                if (real && f) {
+                    const int fj = filter_of_query(G.q0 + s / nb);
+                    G.slot_mask.push_back(fj < 0 ? -1ll : (long long)lmi_filter_plan::mask_word(fj, f->n_rb_total, rbs[c.bucket], 0));
+                }
             }
             for (int64_t t = 0; t < tiles; ++t) {
                 G.tile_off.push_back(c.slab_off + t * 32 * pitch);
@@ -177,6 +194,8 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     CHK(mem.alloc(&d_slot_n, (size_t)Q * nb * 4, "slot rows"));
     CHK(mem.alloc(&d_slot_base, (size_t)Q * nb * 4, "slot bases"));
     CHK(mem.alloc(&d_slot_pos0, (size_t)Q * nb * 8, "slot positions"));
+    long long* d_slot_mask = nullptr;
+    if (f) CHK(mem.alloc(&d_slot_mask, (size_t)max_slots * 8, "slot masks"));
     if (!on_device) {
         if (part) CHK(mem.alloc(&d_P, (size_t)LMI_UNION_PART_PLANES * Q * k * 4, "part"));
         else {
@@ -193,6 +212,12 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     g_union_last[LMI_UNION_PLAN_LISTS_PER_QUERY] = p.lists_per_query;
     g_union_last[LMI_UNION_PLAN_WORKSPACE_BYTES] = mem.total;
     g_union_last[LMI_UNION_PLAN_VEC_ROWS] = vec;
+    if (f) {
+        g_filter_last[LMI_FILTER_PLAN_FILTERS] = f->nf;
+        g_filter_last[LMI_FILTER_PLAN_MASK_BYTES] = f->mask_bytes();
+        g_filter_last[LMI_FILTER_PLAN_SLOTS] = (int64_t)groups.back().slots.size();
+        g_filter_last[LMI_FILTER_PLAN_SKIPPED] = skipped;
+    }
 
     const size_t lds = (size_t)2 * LR * sizeof(knn_entry);
     auto up_async = [&](void* dst, const void* src, size_t bytes) -> int {
@@ -209,6 +234,7 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
         CHK(up_async(d_slot_n, G.slot_n.data(), G.slot_n.size() * 4));
         CHK(up_async(d_slot_base, G.slot_base.data(), G.slot_base.size() * 4));
         CHK(up_async(d_slot_pos0, G.slot_pos0.data(), G.slot_pos0.size() * 8));
+        if (f) CHK(up_async(d_slot_mask, G.slot_mask.data(), G.slot_mask.size() * 8));
         for (const Wave& W : G.waves) {
             if (W.slots == 0) continue;
             union_pack_kernel<<<cdiv(W.tiles * 32 * KG, 256), 256, 0, st>>>(C.q, d_rowq + W.tile0 * 32, h->d, (int)W.tiles, KG, d_qf);
@@ -217,7 +243,8 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
                                                   d_tile_off + W.tile0, d_tile_cnt + W.tile0, d_S));
             else CHK(union_score_launch<false>(W.ct, (int)W.items, st, d_items + W.item0, h->rowmajor.as<float>(), h->dp, h->d, d_qf, KG,
                                                d_tile_off + W.tile0, d_tile_cnt + W.tile0, d_S));
-            union_select_kernel<<<(int)W.slots, 64, lds, st>>>(d_S, d_slots + W.slot0, k, LR, d_lists);
+            if (f) union_select_masked_kernel<<<(int)W.slots, 64, lds, st>>>(d_S, d_slots + W.slot0, d_slot_mask + W.slot0, f->mask.as<unsigned>(), k, LR, d_lists);
+            else union_select_kernel<<<(int)W.slots, 64, lds, st>>>(d_S, d_slots + W.slot0, k, LR, d_lists);
             HIPCHK(hipGetLastError());
         }
         int* oC = on_device ? (counts ? counts + G.q0 : nullptr) : d_C;
@@ -250,6 +277,22 @@ int union_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     return 0;
 }
 
+// the filter of a call: none (the unfiltered entry points) or the (f, filter_of) pair of a *_filtered one, which must then be valid
+struct UnionFilter {
+    bool asked = false;
+    const lmi_filter* f = nullptr;
+    const int32_t* filter_of = nullptr;
+};
+// how every form except the part begins: the plan words cleared, then the refusals that need no pointer
+int union_begin(lmi_index* h, const char* who, int nq, int nb, int k, const UnionFilter& uf) {
+    for (int64_t& w : g_union_last) w = 0;
+    for (int64_t& w : g_filter_last) w = 0;
+    if (!h) return fail("%s: NULL handle", who);
+    CHK(union_check(h, who, nq, nb, k));
+    if (uf.asked) CHK(filter_check(h, who, uf.f, uf.filter_of, nq));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" LMI_API int lmi_union_set_geometry(int64_t query_rows, int64_t slab_bytes) {
@@ -266,12 +309,9 @@ extern "C" LMI_API int lmi_debug_union_plan(int64_t* out, int n) {
     return 0;
 }
 
-extern "C" LMI_API int lmi_scan_union(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, int k,
-                                      float* dists, uint32_t* ids, int32_t* counts, int on_device) {
-    const char* who = "lmi_scan_union";
-    for (int64_t& w : g_union_last) w = 0;
-    if (!h) return fail("%s: NULL handle", who);
-    CHK(union_check(h, who, nq, nb, k));
+static int scan_union_impl(const char* who, lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, int k,
+                           float* dists, uint32_t* ids, int32_t* counts, int on_device, const UnionFilter& uf) {
+    CHK(union_begin(h, who, nq, nb, k, uf));
     if (nq == 0) return 0;
     if (!queries_search || !bucket_order || !dists || !ids) return fail("%s: queries_search, bucket_order, dists and ids must not be NULL", who);
     CHK(set_dev(h));
@@ -280,13 +320,25 @@ extern "C" LMI_API int lmi_scan_union(lmi_index* h, const float* queries_search,
     CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
     CHK(input_ptr(h, bucket_order, (size_t)nq * nb * 4, on_device, h->order, &d_order));
     begin_call(h);
-    return union_core(h, who, static_cast<const float*>(d_qs), nq, static_cast<const int*>(d_order), nb, k, dists, ids, counts, on_device);
+    return union_core(h, who, static_cast<const float*>(d_qs), nq, static_cast<const int*>(d_order), nb, k, dists, ids, counts, on_device,
+                      nullptr, uf.f, uf.filter_of);
+}
+extern "C" LMI_API int lmi_scan_union(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, int k,
+                                      float* dists, uint32_t* ids, int32_t* counts, int on_device) {
+    return scan_union_impl("lmi_scan_union", h, queries_search, nq, bucket_order, nb, k, dists, ids, counts, on_device, UnionFilter{});
+}
+extern "C" LMI_API int lmi_scan_union_filtered(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, int k,
+                                               float* dists, uint32_t* ids, int32_t* counts, int on_device, const lmi_filter* f,
+                                               const int32_t* filter_of) {
+    return scan_union_impl("lmi_scan_union_filtered", h, queries_search, nq, bucket_order, nb, k, dists, ids, counts, on_device,
+                           UnionFilter{true, f, filter_of});
 }
 
 extern "C" LMI_API int lmi_scan_union_part(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, int k,
                                            int32_t* part, int32_t* counts, int on_device) {
     const char* who = "lmi_scan_union_part";
     for (int64_t& w : g_union_last) w = 0;
+    for (int64_t& w : g_filter_last) w = 0;
     if (!h) return fail("%s: NULL handle", who);
     CHK(union_check(h, who, nq, nb, k));
     if (nq == 0) return 0;
@@ -301,12 +353,9 @@ extern "C" LMI_API int lmi_scan_union_part(lmi_index* h, const float* queries_se
                       part);
 }
 
-extern "C" LMI_API int lmi_search_union(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
-                                        float* dists, uint32_t* ids, int32_t* counts, int32_t* bucket_order, int on_device) {
-    const char* who = "lmi_search_union";
-    for (int64_t& w : g_union_last) w = 0;
-    if (!h) return fail("%s: NULL handle", who);
-    CHK(union_check(h, who, nq, nb, k));
+static int search_union_impl(const char* who, lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                             float* dists, uint32_t* ids, int32_t* counts, int32_t* bucket_order, int on_device, const UnionFilter& uf) {
+    CHK(union_begin(h, who, nq, nb, k, uf));
     if (h->root().n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
     if (h->root().dims.back() != h->L) return fail("%s: MLP has %d classes, index has %d buckets", who, h->root().dims.back(), h->L);
     if (nq == 0) return 0;
@@ -321,17 +370,25 @@ extern "C" LMI_API int lmi_search_union(lmi_index* h, const float* queries_nav, 
     if (!on_device || !bucket_order) { CHK(h->order.reserve((size_t)nq * nb * 4)); d_order = h->order.as<int>(); }
     begin_call(h);
     CHK(mlp_enqueue(h, static_cast<const float*>(d_qn), nq, nb, d_order, nullptr));
-    CHK(union_core(h, who, static_cast<const float*>(d_qs), nq, d_order, nb, k, dists, ids, counts, on_device));
+    CHK(union_core(h, who, static_cast<const float*>(d_qs), nq, d_order, nb, k, dists, ids, counts, on_device, nullptr, uf.f, uf.filter_of));
     if (!on_device) CHK(copy_back(h, {{bucket_order, d_order, (size_t)nq * nb * 4}}));
     return 0;
 }
+extern "C" LMI_API int lmi_search_union(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                                        float* dists, uint32_t* ids, int32_t* counts, int32_t* bucket_order, int on_device) {
+    return search_union_impl("lmi_search_union", h, queries_nav, queries_search, nq, nb, k, dists, ids, counts, bucket_order, on_device, UnionFilter{});
+}
+extern "C" LMI_API int lmi_search_union_filtered(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                                                 float* dists, uint32_t* ids, int32_t* counts, int32_t* bucket_order, int on_device,
+                                                 const lmi_filter* f, const int32_t* filter_of) {
+    return search_union_impl("lmi_search_union_filtered", h, queries_nav, queries_search, nq, nb, k, dists, ids, counts, bucket_order, on_device,
+                             UnionFilter{true, f, filter_of});
+}
 
-extern "C" LMI_API int lmi_search_tree_union(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
-                                             float* dists, uint32_t* ids, int32_t* counts, int32_t* slab_ids, int32_t* entries, int on_device) {
-    const char* who = "lmi_search_tree_union";
-    for (int64_t& w : g_union_last) w = 0;
-    if (!h) return fail("%s: NULL handle", who);
-    CHK(union_check(h, who, nq, nb, k));
+static int search_tree_union_impl(const char* who, lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                                  float* dists, uint32_t* ids, int32_t* counts, int32_t* slab_ids, int32_t* entries, int on_device,
+                                  const UnionFilter& uf) {
+    CHK(union_begin(h, who, nq, nb, k, uf));
     if (nq == 0) return 0;
     if (!queries_nav || !queries_search || !dists || !ids) return fail("%s: queries_nav, queries_search, dists and ids must not be NULL", who);
     CHK(nav_check(h, nq, nb, who));
@@ -346,7 +403,18 @@ extern "C" LMI_API int lmi_search_tree_union(lmi_index* h, const float* queries_
     int* d_ent = (on_device && entries) ? entries : h->nav_ent.as<int>();
     begin_call(h);
     CHK(nav_enqueue(h, static_cast<const float*>(d_qn), nq, nb, d_slab, d_ent));
-    CHK(union_core(h, who, static_cast<const float*>(d_qs), nq, d_slab, nb, k, dists, ids, counts, on_device));
+    CHK(union_core(h, who, static_cast<const float*>(d_qs), nq, d_slab, nb, k, dists, ids, counts, on_device, nullptr, uf.f, uf.filter_of));
     if (!on_device) CHK(copy_back(h, {{slab_ids, d_slab, (size_t)nq * nb * 4}, {entries, d_ent, (size_t)nq * nb * 4}}));
     return 0;
+}
+extern "C" LMI_API int lmi_search_tree_union(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                                             float* dists, uint32_t* ids, int32_t* counts, int32_t* slab_ids, int32_t* entries, int on_device) {
+    return search_tree_union_impl("lmi_search_tree_union", h, queries_nav, queries_search, nq, nb, k, dists, ids, counts, slab_ids, entries, on_device,
+                                  UnionFilter{});
+}
+extern "C" LMI_API int lmi_search_tree_union_filtered(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, int k,
+                                                      float* dists, uint32_t* ids, int32_t* counts, int32_t* slab_ids, int32_t* entries,
+                                                      int on_device, const lmi_filter* f, const int32_t* filter_of) {
+    return search_tree_union_impl("lmi_search_tree_union_filtered", h, queries_nav, queries_search, nq, nb, k, dists, ids, counts, slab_ids, entries,
+                                  on_device, UnionFilter{true, f, filter_of});
 }

@@ -23,6 +23,7 @@ are (inf, 0) (Q2); the per-bucket k is always 10 and a single-bucket search retu
 whatever `k` is (Q3); buckets with < 10 objects are padded like faiss does (Q4); dist = 1 - ip in
 float32 stored as float64 (Q5/Q6).
 """
+import functools
 import time
 from collections import defaultdict
 from logging import INFO
@@ -271,16 +272,17 @@ class LearnedIndex(Logger):
 
     def search_resident(self, queries_navigation, queries_search, n_categories: List[int], n_buckets: int = 1,
                         k: int = 10, stop_mass: Optional[float] = None, path_mass: Optional[float] = None,
-                        stop_rows: Optional[int] = None, merge: str = "ranks"):
+                        stop_rows: Optional[int] = None, merge: str = "ranks", filter=None, filter_of=None):
         """`search` against the index already resident in HBM (after `prepare`, a previous `search`
-        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass`, `path_mass`, `stop_rows`
-        and `merge` as there."""
+        or `index_io.load_index`): no DataFrames needed.  Same return values as `search`; `stop_mass`, `path_mass`, `stop_rows`,
+        `merge`, `filter` and `filter_of` as there."""
         self._check_merge(merge)
+        self._check_filter(filter, filter_of, merge)
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         assert self._engine is not None, "no resident index: call prepare()/search() or index_io.load_index()"
         return self._search_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, k,
-                                 time.time(), stop_mass, path_mass, stop_rows, merge)
+                                 time.time(), stop_mass, path_mass, stop_rows, merge, filter, filter_of)
 
     MERGES = ("ranks", "union")
 
@@ -289,6 +291,15 @@ class LearnedIndex(Logger):
         if merge not in cls.MERGES:
             raise ValueError(f"merge {merge!r} unknown: 'ranks' (at most 10 results per visited bucket, merged by rank; the reference) "
                              "or 'union' (the k best objects of all visited buckets)")
+
+    @staticmethod
+    def _check_filter(filter, filter_of, merge) -> None:
+        """A filter restricts the candidates of the union scan: the rank merge has no filtered form.  Refused before any work is
+        done."""
+        if filter is None and filter_of is not None:
+            raise ValueError("filter_of without a filter")
+        if filter is not None and merge != "union":
+            raise ValueError("a filter needs merge='union' (the rank merge has no filtered form)")
 
     @staticmethod
     def _check_stop_mass(stop_mass, n_categories) -> None:
@@ -400,6 +411,8 @@ class LearnedIndex(Logger):
         storage: str = "f32",
         stop_rows: Optional[int] = None,
         merge: str = "ranks",
+        filter=None,
+        filter_of=None,
     ) -> Tuple[npt.NDArray, npt.NDArray[np.uint32], Dict[str, float]]:
         """Searches for `k` nearest neighbors of every query in its `n_buckets` most probable buckets.
         Parameters and return values as the reference (LearnedIndex.py:41-83).  `metric` (an extension; the
@@ -422,18 +435,33 @@ class LearnedIndex(Logger):
         k <= 20 for n_buckets >= 2.  "union" returns the `k` best objects of the union of the visited buckets (`lmi_search_union` /
         `lmi_search_tree_union`): k up to 1024, results [nq, k] for any n_buckets; a query whose buckets hold fewer than k objects
         is padded with dist = +inf, id = 0.  The stops compose with it.  It needs the default storage ("f32", prefilter on).
-        ValueError for anything else."""
+        ValueError for anything else.
+        `filter` (an extension, with merge="union" only; `lmi_search_union_filtered` / `lmi_search_tree_union_filtered`): None = off;
+        a list of ids (DataFrame index labels): only those objects may be returned; or a `_capi.Filter` made on the resident engine
+        (several filters, keep or drop), with `filter_of` [nq] naming each query's filter (-1 = unfiltered; None = all use filter 0).
+        The filter acts on the scan, not on the routing: the stops count whole buckets as before.  ValueError with merge="ranks"."""
         self._check_merge(merge)
+        self._check_filter(filter, filter_of, merge)
         self._check_stop_mass(stop_mass, n_categories)
         self._check_path_mass(path_mass, n_categories)
         s = time.time()
         eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged,
                            storage=storage)
-        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass, stop_rows, merge)
+        return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass, stop_rows, merge,
+                                 filter, filter_of)
 
     def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None,
-                     stop_rows=None, merge="ranks"):
+                     stop_rows=None, merge="ranks", filter=None, filter_of=None):
+        if filter is not None and not isinstance(filter, _capi.Filter):   # an id list: one keep filter, made for this call
+            made = _capi.Filter(eng, [np.asarray(filter).reshape(-1)])
+            try:
+                return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass,
+                                         stop_rows, merge, made, filter_of)
+            finally:
+                made.close()
         run = self._search_union if merge == "union" else self._search_chunks
+        if filter is not None:
+            run = functools.partial(self._search_union, filter=filter, filter_of=filter_of)
         if stop_mass is None and path_mass is None and stop_rows is None:
             return run(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         # the engine's own settings come back afterwards: a later call without the arguments is as before
@@ -451,9 +479,10 @@ class LearnedIndex(Logger):
             eng.set_path_mass(before[1])
             eng.set_stop_rows(before[2])
 
-    def _search_union(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
+    def _search_union(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, filter=None, filter_of=None):
         """merge="union": the batch goes to the library whole (it groups the queries itself); a multi-level index is walked in
-        pieces of `_nav_chunk()` queries, the walk's queue limit."""
+        pieces of `_nav_chunk()` queries, the walk's queue limit.  `filter` (a `_capi.Filter`) and `filter_of` go with the calls."""
+        fo = None if filter_of is None else np.asarray(filter_of).reshape(-1)
         measured_time = defaultdict(float)
         qn = np.ascontiguousarray(_query_array(queries_navigation), dtype=np.float32)   # the union calls take binary32 queries
         qs = qn if queries_search is queries_navigation else np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
@@ -465,10 +494,11 @@ class LearnedIndex(Logger):
             return np.empty((0, k)), np.empty((0, k), dtype=np.uint32), measured_time
         t0 = time.time()
         if len(n_categories) == 1:
-            d32, nns = eng.search_union(qn, qs, n_buckets, k)[:2]
+            d32, nns = eng.search_union(qn, qs, n_buckets, k, filter=filter, filter_of=fo)[:2]
         else:
             step = self._nav_chunk()
-            parts = [eng.search_tree_union(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets, k)[:2]
+            parts = [eng.search_tree_union(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets, k,
+                                           filter=filter, filter_of=None if fo is None else fo[lo: lo + step])[:2]
                      for lo in range(0, nq, step)]
             d32 = parts[0][0] if len(parts) == 1 else np.concatenate([p[0] for p in parts])
             nns = parts[0][1] if len(parts) == 1 else np.concatenate([p[1] for p in parts])

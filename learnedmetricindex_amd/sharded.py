@@ -161,9 +161,11 @@ def merge_union_parts_numpy(gathered: np.ndarray):
     return d, i, sel.sum(axis=1).astype(np.int32)
 
 
-def _check_merge(merge) -> None:
+def _check_merge(merge, filter=None) -> None:
     if merge not in ("ranks", "union"):
         raise ValueError(f"merge must be 'ranks' or 'union', not {merge!r}")
+    if filter is not None:   # (the part form of the union scan has no filtered counterpart yet: DESIGN.md section 5.14.2)
+        raise ValueError("a filter is not supported by the sharded searchers (use Index.search_union(filter=...) on one handle)")
 
 
 class ShardedSearcher:
@@ -304,10 +306,10 @@ class ShardedSearcher:
         self._timed("result_allgather_merge", exchange, part.is_cuda)
         return out_d, out_i, bo, cnt
 
-    def search_routed(self, qs_t, bo_loc, nb: int, k: int, merge: str = "ranks"):
+    def search_routed(self, qs_t, bo_loc, nb: int, k: int, merge: str = "ranks", filter=None):
         """The rest of a sharded search: all-gather of the bucket order, scan of the owned buckets, all-gather + merge.
         merge="union": the union scan, k <= 1024 -> (dists [nq, k], ids, bucket order, counts)."""
-        _check_merge(merge)
+        _check_merge(merge, filter)
         nq = qs_t.shape[0]
         if merge == "union":
             bo = self._timed("bucket_order_allgather", lambda: all_gather_rows(bo_loc, nq, self.world, self.group), bo_loc.is_cuda)
@@ -336,9 +338,9 @@ class ShardedSearcher:
         self._timed("result_allgather_merge", exchange, blk.is_cuda)
         return out_d, out_i, bo
 
-    def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks"):
+    def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks", filter=None):
         """(dists, ids, bucket order); merge="union": the union scan, k <= 1024 -> (dists [nq, k], ids, bucket order, counts)."""
-        _check_merge(merge)
+        _check_merge(merge, filter)
         nq = qn_t.shape[0]
         if self.shard_inference:
             if self._bo_loc is None or self._bo_loc.shape[1] != nb or self._bo_loc.shape[0] != row_slice(nq, self.rank, self.world)[0]:
@@ -413,10 +415,10 @@ class ReplicaSearcher:
         return (g[:, :k].contiguous().view(torch.float32), g[:, k:2 * k].contiguous(), g[:, 2 * k + 1:].contiguous(),
                 g[:, 2 * k].contiguous())
 
-    def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks"):
+    def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks", filter=None):
         import torch
 
-        _check_merge(merge)
+        _check_merge(merge, filter)
         if merge == "union":
             return self._search_union(qn_t, qs_t, nb, k)
         nq = qn_t.shape[0]
