@@ -712,6 +712,13 @@ class Index:
             raise ValueError(f"{who}: filter_of holds a value outside [-1, {filter.nf})")
         return filter._f, _np(fo, np.int32)
 
+    def _union_call(self, name: str, args: tuple, f, fo) -> None:
+        """`name(handle, *args)`, or with a filter `name_filtered(handle, *args, filter, filter_of)`."""
+        if f is None:
+            _check(getattr(lib(), name)(self._h, *args))
+        else:
+            _check(getattr(lib(), name + "_filtered")(self._h, *args, f, _ptr(fo)))
+
     def scan_union(self, queries_search, bucket_order, k: int = 10, filter=None, filter_of=None):
         """(dists f32[nq,k], ids u32[nq,k], counts i32[nq]) of `lmi_scan_union`: per query the k best objects of the union of the
         buckets `bucket_order[q]` lists (-1: none); behind `counts[q]` real results dist = +inf, id = 0.
@@ -729,10 +736,7 @@ class Index:
         i = np.empty((nq, k), dtype=np.uint32)
         c = np.empty((nq,), dtype=np.int32)
         f, fo = self._filter_args("scan_union", filter, filter_of, nq)
-        if f is None:
-            _check(lib().lmi_scan_union(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0))
-        else:
-            _check(lib().lmi_scan_union_filtered(self._h, _ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0, f, _ptr(fo)))
+        self._union_call("lmi_scan_union", (_ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0), f, fo)
         return d, i, c
 
     def search_union(self, queries_nav, queries_search, nb: int, k: int = 10, filter=None, filter_of=None):
@@ -747,11 +751,7 @@ class Index:
         c = np.empty((nq,), dtype=np.int32)
         bo = np.empty((nq, nb), dtype=np.int32)
         f, fo = self._filter_args("search_union", filter, filter_of, nq)
-        if f is None:
-            _check(lib().lmi_search_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0))
-        else:
-            _check(lib().lmi_search_union_filtered(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0,
-                                                   f, _ptr(fo)))
+        self._union_call("lmi_search_union", (_ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0), f, fo)
         return d, i, c, bo
 
     def search_tree_union(self, queries_nav, queries_search, nb: int, k: int = 10, filter=None, filter_of=None):
@@ -768,11 +768,7 @@ class Index:
         slab = np.empty((nq, nb), dtype=np.int32)
         ent = np.empty((nq, nb), dtype=np.int32)
         f, fo = self._filter_args("search_tree_union", filter, filter_of, nq)
-        if f is None:
-            _check(lib().lmi_search_tree_union(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab), _ptr(ent), 0))
-        else:
-            _check(lib().lmi_search_tree_union_filtered(self._h, _ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab),
-                                                        _ptr(ent), 0, f, _ptr(fo)))
+        self._union_call("lmi_search_tree_union", (_ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab), _ptr(ent), 0), f, fo)
         return d, i, c, slab, ent
 
     def scan_union_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, counts_t=None, filter=None, filter_of=None) -> None:
@@ -780,34 +776,21 @@ class Index:
         self._union_args("scan_union_device", k, nb, queries_search=qs_t, bucket_order=bo_t)
         nq = int(qs_t.shape[0])
         f, fo = self._filter_args("scan_union_device", filter, filter_of, nq)
-        if f is None:
-            _check(lib().lmi_scan_union(self._h, _ptr(qs_t), nq, _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1))
-        else:
-            _check(lib().lmi_scan_union_filtered(self._h, _ptr(qs_t), nq, _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1,
-                                                 f, _ptr(fo)))
+        self._union_call("lmi_scan_union", (_ptr(qs_t), nq, _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1), f, fo)
 
     def search_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, bo_t=None, filter=None, filter_of=None) -> None:
         self._union_args("search_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
         nq = int(qn_t.shape[0])
         f, fo = self._filter_args("search_union_device", filter, filter_of, nq)
-        if f is None:
-            _check(lib().lmi_search_union(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
-                                          _ptr(counts_t), _ptr(bo_t), 1))
-        else:
-            _check(lib().lmi_search_union_filtered(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
-                                                   _ptr(counts_t), _ptr(bo_t), 1, f, _ptr(fo)))
+        self._union_call("lmi_search_union", (_ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), _ptr(bo_t), 1), f, fo)
 
     def search_tree_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, slab_t=None, ent_t=None, filter=None,
                                  filter_of=None) -> None:
         self._union_args("search_tree_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
         nq = int(qn_t.shape[0])
         f, fo = self._filter_args("search_tree_union_device", filter, filter_of, nq)
-        if f is None:
-            _check(lib().lmi_search_tree_union(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
-                                               _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1))
-        else:
-            _check(lib().lmi_search_tree_union_filtered(self._h, _ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t),
-                                                        _ptr(counts_t), _ptr(slab_t), _ptr(ent_t), 1, f, _ptr(fo)))
+        self._union_call("lmi_search_tree_union", (_ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t),
+                                                   _ptr(slab_t), _ptr(ent_t), 1), f, fo)
 
     # ---- the union scan across ranks: a rank's part and the merge of the parts (include/lmi_hip.h, lmi_scan_union_part) ----
     @staticmethod

@@ -1,8 +1,8 @@
 // lmi_union.h -- device code of the union scan (lmi_scan_union, lmi_search_union, lmi_search_tree_union): for every query the k best
 // objects of the union of its visited buckets, k up to 1024 (include/lmi_hip.h states the contract).
 //
-// A slot is one (query, rank) whose bucket has rows.  The host (lmi_host_union.h) sorts a query group's slots by bucket and cuts them
-// into waves (lmi_union_plan.h); per wave:
+// A slot is one (query, rank) whose bucket has rows.  The host sorts a query group's slots by bucket, cuts them into waves and writes
+// the tables the kernels below are launched from (lmi_union_plan.h, build_tables; lmi_host_union.h uploads them and launches); per wave:
 //   union_pack_kernel    the wave's slot queries, gathered by an index list, into fragment order (dense_pack_kernel with the list);
 //   union_score_kernel   one block per item = (bucket, 256 rows of it, CT query tiles): S = Q . X^T by v_mfma_f32_32x32x2_f32,
 //                        knn_score_kernel's loop (the two and km_assign_kernel are kept equal: lmi_dense.h) with B straight from the
@@ -15,24 +15,12 @@
 // writing a part (lmi_scan_union_part: score, dist, id, rank, row per result) for the merge across ranks (lmi_union_merge.h).
 #pragma once
 #include "lmi_knn.h"
+#include "lmi_union_plan.h"
 
 namespace lmi {
 
-// one block of union_score_kernel
-struct UnionItem {
-    long long pos0;   // slab position (row of the row-major image) of the bucket's row 0
-    int n;            // rows of the bucket (> 0: no item is emitted for an empty bucket -- the row clamp below needs n - 1 >= 0)
-    int blk;          // which 256 rows of it
-    int tile0;        // first query tile (of the wave's packed queries)
-    int ntiles;       // 1 .. CT
-};
-// one block of union_select_kernel
-struct UnionSlot {
-    long long s_off;  // the slot's row of the slab (floats)
-    long long list;   // its list (entries)
-    int n;            // scores in the row = rows of the bucket
-    unsigned base;    // ordinal of the bucket's row 0 for this query
-};
+// UnionItem (one block of union_score_kernel) and UnionSlot (one block of union_select_kernel) are declared in lmi_union_plan.h, in
+// this namespace, beside the pure host code that builds the tables of them.
 
 // dense_pack_kernel with an index list: fragment row p holds query rowq[p] (rowq[p] < 0: zeros) of src [.][d]; links >= d: zeros.
 __global__ void union_pack_kernel(const float* __restrict__ src, const int* __restrict__ rowq, int d, int nct, int KG,

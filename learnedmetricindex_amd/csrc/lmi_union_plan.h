@@ -1,16 +1,47 @@
 // lmi_union_plan.h -- the geometry of one union scan (lmi_scan_union and the two search forms): how the batch is cut into query
-// groups, a group's (bucket, slots) work into waves that share one score slab, and the device bytes the call allocates for that.
-// Host only and pure: the standard library, no HIP call, no kernel header -- lmi_host_union.h passes the sizes, the free memory and
-// the forced values in and acts on what comes back; tests/host/union_plan_selftest.cpp checks it on the CPU.
+// groups, a group's (bucket, slots) work into waves that share one score slab, the device bytes the call allocates for that, and
+// (build_tables) every table a group's kernels are launched from.
+// Host only and pure: the standard library, no HIP call, no kernel header -- lmi_host_union.h passes the sizes, the free memory, the
+// forced values, the bucket order and the layout in, uploads what comes back and launches from it; tests/host/union_plan_selftest.cpp
+// checks all of it on the CPU.
 //
 // A slot is one (query, rank) whose bucket has rows.  A slot is scored against its whole bucket in one piece and owns one sorted list,
-// so nothing here can change a result (include/lmi_hip.h, lmi_scan_union); the geometry decides memory and speed only.
+// so nothing here can change a result (include/lmi_hip.h, lmi_scan_union); the geometry decides memory and speed only -- but the
+// tables are addresses the kernels trust.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <vector>
 
+#include "lmi_filter_plan.h"
+
+// ---- the launch records.  They stay in namespace lmi, beside the kernels that take them (lmi_union.h): a kernel's symbol carries the
+// namespace of its parameter types. ----
+namespace lmi {
+
+// one block of union_score_kernel
+struct UnionItem {
+    long long pos0;   // slab position (row of the row-major image) of the bucket's row 0
+    int n;            // rows of the bucket (> 0: no item is emitted for an empty bucket -- the kernel's row clamp needs n - 1 >= 0)
+    int blk;          // which 256 rows of it
+    int tile0;        // first query tile (of the wave's packed queries)
+    int ntiles;       // 1 .. CT
+};
+// one block of union_select_kernel
+struct UnionSlot {
+    long long s_off;  // the slot's row of the slab (floats)
+    long long list;   // its list (entries)
+    int n;            // scores in the row = rows of the bucket
+    unsigned base;    // ordinal of the bucket's row 0 for this query
+};
+static_assert(sizeof(UnionItem) == 24 && sizeof(UnionSlot) == 24, "the kernels read these records as the host lays them out");
+
+}  // namespace lmi
+
 namespace lmi_union_plan {
+
+using lmi::UnionItem;
+using lmi::UnionSlot;
 
 constexpr int MAX_K = 1024;          // LMI_UNION_MAX_K (lmi_host_union.h asserts that they agree)
 constexpr int MIN_LIST = 128;        // a slot's sorted list holds max(MIN_LIST, k rounded up to a power of two) entries
@@ -117,6 +148,123 @@ inline std::vector<Chunk> cut_waves(const Plan& p, const std::vector<int64_t>& r
     }
     *n_waves = out.empty() ? 0 : wave + 1;
     return out;
+}
+
+constexpr int ITEM_ROWS = 256;   // rows of a bucket per item: KNN_ROWS (lmi_host_union.h asserts that they agree)
+
+// A wave of a group: its ranges of the group's item, slot and tile tables, the floats of the slab it writes, and the query tiles an
+// item spans (the CT of union_score_kernel).
+struct Wave { int64_t item0 = 0, items = 0, slot0 = 0, slots = 0, tile0 = 0, tiles = 0, slab_floats = 0; int ct = 1; };
+
+// Everything the kernels of query group [q0, q1) are launched from.  With gq = q1 - q0:
+//   slot_n, slot_base, slot_pos0 [gq][nb]   per (query, rank), for the finish: rows to merge (0: none), ordinal of the bucket's row 0,
+//                                           slab position of the bucket's row 0;
+//   slots, slot_mask                        one per scanned slot, wave after wave, inside a wave by (bucket, query, rank);
+//                                           slot_mask[i]: the word offset of slot i's mask row, -1 for an unfiltered query (empty
+//                                           without a filter);
+//   rowq, tile_off, tile_cnt                per 32-query tile of a wave's packed queries: rowq [tiles][32] the global query of each
+//                                           fragment row (-1: padding), the tile's first slab row (floats), its real slots;
+//   items                                   wave after wave; inside a wave by chunk, tile group, 256-row block (blocks of one bucket
+//                                           and tile group run back to back: that order is speed);
+//   skipped                                 the slots a filter left out.
+struct Tables {
+    int64_t q0 = 0, q1 = 0;
+    std::vector<Wave> waves;
+    std::vector<UnionItem> items;
+    std::vector<UnionSlot> slots;
+    std::vector<int> rowq, tile_cnt, slot_n;
+    std::vector<long long> tile_off, slot_pos0, slot_mask;
+    std::vector<unsigned> slot_base;
+    int64_t skipped = 0;
+};
+
+// the live layout: rows and first 32-row block of each of the L buckets
+struct Layout { int L; const int* nb_rows; const int* rb_start; };
+// a filter set as the tables need it: counts [nf][L] allowed rows; filter_of [nq] (nullptr: every query uses filter 0; -1: unfiltered);
+// n_rb_total: the words of one filter's mask row
+struct FilterView { const int32_t* counts; const int32_t* filter_of; int64_t n_rb_total; };
+
+// The tables of query group `group` of plan p.  order [p.nq][p.nb]: the buckets each query visits, by rank; fv: nullptr without a filter.
+// The rules:
+//   - a bucket id outside [0, L) or an empty bucket is no slot and advances no ordinal;
+//   - a slot whose (filter, bucket) pair allows no row gets slot_n = 0 and no UnionSlot -- it is not packed, scored or selected -- but
+//     still advances slot_base by the bucket's rows: ordinals stay the unfiltered concatenation's, the finish skips the rank, and no
+//     entry carries an ordinal of the gap;
+//   - a query that lists a bucket twice gets two slots;
+//   - a wave's ct is 1, 2 or 4, from the widest chunk of the wave (a chunk of 3 or more tiles takes 4).
+inline Tables build_tables(const Plan& p, int64_t group, const int* order, const Layout& lay, const FilterView* fv) {
+    Tables T;
+    group_range(p, group, &T.q0, &T.q1);
+    const int nb = p.nb, L = lay.L;
+    const int64_t gq = T.q1 - T.q0;
+    const int* ord = order + T.q0 * nb;   // the group's rows of order: slot s = q * nb + t visits ord[s]
+    auto filter_of_slot = [&](int64_t s) -> int { return fv ? (fv->filter_of ? fv->filter_of[T.q0 + s / nb] : 0) : -1; };
+    T.slot_n.assign((size_t)(gq * nb), 0);
+    T.slot_base.assign((size_t)(gq * nb), 0u);
+    T.slot_pos0.assign((size_t)(gq * nb), 0);
+    std::vector<int64_t> rows(lay.nb_rows, lay.nb_rows + L), cnt((size_t)L, 0);
+    for (int64_t q = 0; q < gq; ++q) {
+        int64_t base = 0;
+        const int fj = filter_of_slot(q * nb);
+        for (int t = 0; t < nb; ++t) {
+            const int64_t s = q * nb + t;
+            const int b = ord[s];
+            const int n = b >= 0 && b < L ? lay.nb_rows[b] : 0;
+            const bool dead = fj >= 0 && n > 0 && fv->counts[(size_t)fj * L + b] == 0;   // the filter allows no row of the bucket
+            T.slot_base[s] = (unsigned)base;
+            T.slot_n[s] = dead ? 0 : n;
+            if (n > 0) base += n;
+            if (dead) ++T.skipped;
+            else if (n > 0) { T.slot_pos0[s] = (long long)lay.rb_start[b] * 32; cnt[b]++; }
+        }
+    }
+    // a bucket's slots in (query, rank) order
+    std::vector<int64_t> start((size_t)L + 1, 0);
+    for (int b = 0; b < L; ++b) start[b + 1] = start[b] + cnt[b];
+    std::vector<int64_t> by_bucket((size_t)start[L]), fill(start.begin(), start.end() - 1);
+    for (int64_t s = 0; s < gq * nb; ++s)
+        if (T.slot_n[s] > 0) by_bucket[fill[ord[s]]++] = s;
+    int n_waves = 0;
+    const std::vector<Chunk> chunks = cut_waves(p, rows, cnt, &n_waves);
+    T.waves.assign((size_t)n_waves, Wave{});
+    // cut_waves gives a wave's chunks back to back; a chunk's tile0 and slab_off count from its wave's start
+    for (size_t c0 = 0, c1 = 0; c0 < chunks.size(); c0 = c1) {
+        Wave& W = T.waves[chunks[c0].wave];
+        for (c1 = c0; c1 < chunks.size() && chunks[c1].wave == chunks[c0].wave; ++c1) {
+            const int64_t tiles = cdiv(chunks[c1].slots, 32);
+            W.ct = std::max(W.ct, tiles >= 3 ? 4 : (int)tiles);
+        }
+        W.item0 = (int64_t)T.items.size();
+        W.slot0 = (int64_t)T.slots.size();
+        W.tile0 = (int64_t)T.tile_cnt.size();
+        for (size_t ci = c0; ci < c1; ++ci) {
+            const Chunk& c = chunks[ci];
+            const int64_t tiles = cdiv(c.slots, 32), pitch = slab_pitch(c.n), blocks = cdiv(c.n, ITEM_ROWS);
+            const long long pos0 = (long long)lay.rb_start[c.bucket] * 32;
+            W.tiles += tiles;
+            W.slots += c.slots;
+            W.slab_floats = std::max(W.slab_floats, c.slab_off + c.slots * pitch);
+            for (int64_t i = 0; i < tiles * 32; ++i) {
+                if (i >= c.slots) { T.rowq.push_back(-1); continue; }
+                const int64_t s = by_bucket[start[c.bucket] + c.slot0 + i];
+                T.rowq.push_back((int)(T.q0 + s / nb));
+                T.slots.push_back(UnionSlot{c.slab_off + i * pitch, s * p.list_rows, (int)c.n, T.slot_base[s]});
+                if (fv) {
+                    const int fj = filter_of_slot(s);
+                    T.slot_mask.push_back(fj < 0 ? -1ll : (long long)lmi_filter_plan::mask_word(fj, fv->n_rb_total, lay.rb_start[c.bucket], 0));
+                }
+            }
+            for (int64_t t = 0; t < tiles; ++t) {
+                T.tile_off.push_back(c.slab_off + t * 32 * pitch);
+                T.tile_cnt.push_back((int)std::min<int64_t>(32, c.slots - t * 32));
+            }
+            for (int64_t t0 = 0; t0 < tiles; t0 += W.ct)
+                for (int64_t blk = 0; blk < blocks; ++blk)
+                    T.items.push_back(UnionItem{pos0, (int)c.n, (int)blk, (int)(c.tile0 + t0), (int)std::min<int64_t>(W.ct, tiles - t0)});
+        }
+        W.items = (int64_t)T.items.size() - W.item0;
+    }
+    return T;
 }
 
 }  // namespace lmi_union_plan

@@ -2,11 +2,16 @@
 // for -fsanitize=address,undefined (tests/test_union_host.py builds and runs it).  For a grid of (nq, nb, k, d, pointers, forced values,
 // free memory) and several bucket / slot-count profiles: budgets are respected (a wave goes past its slab budget only as one lone tile
 // of 32 slots), forced values are honoured, the query groups tile [0, nq), and the waves' chunks cover every slot of every bucket
-// exactly once, with slab rows and query tiles that do not overlap inside a wave.
+// exactly once, with slab rows and query tiles that do not overlap inside a wave.  check_tables: for small explicit layouts, bucket
+// orders and filter tables, what build_tables hands the kernels -- every live (query, rank) owns exactly one slot with the right list,
+// rows and ordinal base, a wave's slab rows are disjoint and inside its slab, fragment rows, tile tables and slots agree, the items
+// cover every (tile, 256-row block) exactly once, and the mask offsets are the filter's -- derived here from the inputs alone.
 #include "lmi_union_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <utility>
 
 using namespace lmi_union_plan;
 
@@ -82,6 +87,158 @@ static void check_waves(const Plan& p, const std::vector<int64_t>& rows, const s
     EXPECT(n_waves == (ch.empty() ? 0 : wave + 1));
 }
 
+// build_tables for every group of p, against properties worked out from (order, layout, filter) alone
+static void check_tables(const Plan& p, const std::vector<int>& order, const Layout& lay, const FilterView* fv) {
+    const int nb = p.nb, L = lay.L, LR = p.list_rows;
+    for (int64_t g = 0; g < p.query_groups; ++g) {
+        const Tables T = build_tables(p, g, order.data(), lay, fv);
+        int64_t q0, q1;
+        group_range(p, g, &q0, &q1);
+        EXPECT(T.q0 == q0 && T.q1 == q1);
+        const int64_t gq = q1 - q0, ns = gq * nb;
+        EXPECT((int64_t)T.slot_n.size() == ns && (int64_t)T.slot_base.size() == ns && (int64_t)T.slot_pos0.size() == ns);
+        // per (query, rank): what it must be
+        std::vector<int> want_n((size_t)ns, 0), bucket_of((size_t)ns, -1), filter_of_slot((size_t)ns, -1);
+        int64_t want_slots = 0, want_skipped = 0;
+        for (int64_t q = 0; q < gq; ++q) {
+            const int fj = fv ? (fv->filter_of ? fv->filter_of[q0 + q] : 0) : -1;
+            int64_t base = 0;
+            for (int t = 0; t < nb; ++t) {
+                const int64_t s = q * nb + t;
+                const int b = order[(size_t)((q0 + q) * nb + t)];
+                const bool live = b >= 0 && b < L && lay.nb_rows[b] > 0;
+                const bool dead = live && fj >= 0 && fv->counts[(size_t)fj * L + b] == 0;
+                EXPECT(T.slot_base[s] == (unsigned)base);   // earlier ranks' rows: dead ones included, absent and empty ones not
+                if (live) base += lay.nb_rows[b];
+                if (dead) ++want_skipped;
+                if (live && !dead) {
+                    want_n[s] = lay.nb_rows[b];
+                    bucket_of[s] = b;
+                    filter_of_slot[s] = fj;
+                    ++want_slots;
+                    EXPECT(T.slot_pos0[s] == (long long)lay.rb_start[b] * 32);
+                }
+                EXPECT(T.slot_n[s] == want_n[s]);
+            }
+        }
+        EXPECT(T.skipped == want_skipped);
+        // every live (q, t) owns exactly one UnionSlot, nothing else owns one
+        EXPECT((int64_t)T.slots.size() == want_slots);
+        EXPECT(T.slot_mask.size() == (fv ? T.slots.size() : 0));
+        std::vector<int> owned((size_t)ns, 0);
+        for (size_t i = 0; i < T.slots.size(); ++i) {
+            const UnionSlot& sl = T.slots[i];
+            EXPECT(sl.list >= 0 && sl.list % LR == 0 && sl.list / LR < ns);
+            const int64_t s = sl.list / LR;
+            EXPECT(owned[s]++ == 0 && want_n[s] > 0 && sl.n == want_n[s] && sl.base == T.slot_base[s] && sl.s_off >= 0);
+            if (fv) {
+                const int fj = filter_of_slot[s];
+                EXPECT(T.slot_mask[i] == (fj < 0 ? -1 : (long long)lmi_filter_plan::mask_word(fj, fv->n_rb_total, lay.rb_start[bucket_of[s]], 0)));
+            }
+        }
+        // the waves tile the group's arrays
+        EXPECT(T.rowq.size() == T.tile_cnt.size() * 32 && T.tile_off.size() == T.tile_cnt.size());
+        int64_t item_at = 0, slot_at = 0, tile_at = 0;
+        for (const Wave& W : T.waves) {
+            EXPECT(W.item0 == item_at && W.slot0 == slot_at && W.tile0 == tile_at);
+            EXPECT(W.items > 0 && W.slots > 0 && W.tiles > 0 && W.slab_floats > 0 && (W.ct == 1 || W.ct == 2 || W.ct == 4));
+            item_at += W.items; slot_at += W.slots; tile_at += W.tiles;
+            EXPECT(item_at <= (int64_t)T.items.size() && slot_at <= (int64_t)T.slots.size() && tile_at <= (int64_t)T.tile_cnt.size());
+            // tile by tile: the wave's slots in order fill the tiles' real rows; slab row, fragment row and bucket agree
+            std::vector<int> tile_bucket((size_t)W.tiles, -1);
+            std::vector<std::pair<int64_t, int64_t>> ranges;
+            std::map<int, int64_t> tiles_of_bucket;
+            int64_t cur = W.slot0;
+            for (int64_t t = 0; t < W.tiles; ++t) {
+                const int64_t gt = W.tile0 + t;
+                const int cnt = T.tile_cnt[gt];
+                EXPECT(cnt >= 1 && cnt <= 32 && cur + cnt <= W.slot0 + W.slots);
+                for (int j = 0; j < 32; ++j) {
+                    if (j >= cnt) { EXPECT(T.rowq[gt * 32 + j] == -1); continue; }
+                    const UnionSlot& sl = T.slots[cur++];
+                    const int64_t s = sl.list / LR;
+                    if (j == 0) tile_bucket[t] = bucket_of[s];
+                    EXPECT(bucket_of[s] == tile_bucket[t]);
+                    EXPECT(sl.s_off == T.tile_off[gt] + j * slab_pitch(sl.n));
+                    EXPECT(T.rowq[gt * 32 + j] == (int)(q0 + s / nb));
+                    EXPECT(sl.s_off + sl.n <= W.slab_floats);
+                    ranges.push_back({sl.s_off, sl.s_off + sl.n});
+                }
+                ++tiles_of_bucket[tile_bucket[t]];
+            }
+            EXPECT(cur == W.slot0 + W.slots);
+            std::sort(ranges.begin(), ranges.end());
+            for (size_t i = 1; i < ranges.size(); ++i) EXPECT(ranges[i - 1].second <= ranges[i].first);
+            int64_t widest = 0;
+            for (const auto& kv : tiles_of_bucket) widest = std::max(widest, kv.second);
+            EXPECT(W.ct == (widest >= 3 ? 4 : (int)widest));
+            // the items: every (tile, 256-row block of the tile's bucket) exactly once
+            std::map<std::pair<int64_t, int>, int> covered;
+            for (int64_t i = W.item0; i < W.item0 + W.items; ++i) {
+                const UnionItem& it = T.items[i];
+                EXPECT(it.ntiles >= 1 && it.ntiles <= W.ct && it.tile0 >= 0 && it.tile0 + it.ntiles <= W.tiles);
+                const int b = tile_bucket[it.tile0];
+                EXPECT(it.pos0 == (long long)lay.rb_start[b] * 32 && it.n == lay.nb_rows[b] && it.blk >= 0 && (int64_t)it.blk * 256 < it.n);
+                for (int t = it.tile0; t < it.tile0 + it.ntiles; ++t) {
+                    EXPECT(tile_bucket[t] == b);   // one bucket per wave is one chunk: no item spans two
+                    ++covered[{t, it.blk}];
+                }
+            }
+            int64_t want_cover = 0;
+            for (int64_t t = 0; t < W.tiles; ++t) want_cover += cdiv(lay.nb_rows[tile_bucket[t]], 256);
+            EXPECT((int64_t)covered.size() == want_cover);
+            for (const auto& kv : covered) EXPECT(kv.second == 1);
+        }
+        EXPECT(item_at == (int64_t)T.items.size() && slot_at == (int64_t)T.slots.size() && tile_at == (int64_t)T.tile_cnt.size());
+    }
+}
+
+// the grid of check_tables: two layouts x (nq, nb, k) x forced geometry x bucket orders x filters
+static void check_tables_grid() {
+    struct Lay { std::vector<int> rows, rbs; };
+    Lay lays[2] = {{{0, 1, 33, 257, 2000, 640, 0, 5, 64, 65, 900, 1203}, {}}, {{40, 0, 700}, {}}};
+    for (Lay& l : lays) {   // buckets start on 32-row blocks, with a gap in front of each
+        int at = 3;
+        for (int n : l.rows) { l.rbs.push_back(at); at += (int)cdiv(n, 32) + 2; }
+        l.rbs.push_back(at);
+    }
+    const Forced forced[] = {{0, 0}, {32, 64 << 10}, {7, 4096}};
+    uint32_t rng = 12345u;
+    auto next = [&rng]() { rng = rng * 1664525u + 1013904223u; return rng >> 8; };
+    for (const Lay& l : lays) {
+        const int L = (int)l.rows.size();
+        const Layout lay{L, l.rows.data(), l.rbs.data()};
+        const int64_t n_rb_total = l.rbs.back();
+        // three filters: 0 empties the buckets b % 3 == 1, 1 the even ones, 2 all of them
+        std::vector<int32_t> counts((size_t)3 * L);
+        for (int b = 0; b < L; ++b) {
+            counts[0 * L + b] = b % 3 == 1 ? 0 : std::max(1, l.rows[b] / 2);
+            counts[1 * L + b] = b % 2 == 0 ? 0 : l.rows[b];
+            counts[2 * L + b] = 0;
+        }
+        for (int64_t nq : {1, 33, 150})
+            for (int nb : {1, 3, 8})
+                for (int k : {10, 129, 1024})
+                    for (const Forced& f : forced) {
+                        const Plan p = make_plan(nq, nb, k, 64, false, 0, f);
+                        std::vector<int> mixed((size_t)nq * nb), twice((size_t)nq * nb), one((size_t)nq * nb, L - 1);
+                        for (size_t i = 0; i < mixed.size(); ++i) {
+                            const uint32_t r = next() % (uint32_t)(L + 3);   // -1, 0 .. L-1, L, L+1
+                            mixed[i] = (int)r - 1;
+                            twice[i] = i % (size_t)nb < 2 ? 2 % L : (int)(next() % (uint32_t)L);   // ranks 0 and 1 list the same bucket
+                        }
+                        std::vector<int32_t> mix((size_t)nq), all_dead((size_t)nq, 2);
+                        for (int64_t q = 0; q < nq; ++q) mix[q] = (int32_t)(next() % 4u) - 1;
+                        const FilterView views[] = {{counts.data(), nullptr, n_rb_total}, {counts.data(), mix.data(), n_rb_total},
+                                                    {counts.data(), all_dead.data(), n_rb_total}};
+                        for (const std::vector<int>* o : {&mixed, &twice, &one}) {
+                            check_tables(p, *o, lay, nullptr);
+                            for (const FilterView& v : views) check_tables(p, *o, lay, &v);
+                        }
+                    }
+    }
+}
+
 int main() {
     const int64_t nqs[] = {1, 33, 150, 10000, ((int64_t)1 << 31) / 1024 - 1};
     const int nbs[] = {1, 3, 8, 120, 1024};
@@ -126,6 +283,7 @@ int main() {
         const Plan s = make_plan(150, 8, 100, 64, false, 0, Forced{32, 64 << 10});
         EXPECT(s.query_groups == 5 && s.query_rows == 32 && s.slab_bytes == (64 << 10));
     }
+    check_tables_grid();
     std::printf("union plan selftest: clean (%ld checks)\n", g_checks);
     return 0;
 }
