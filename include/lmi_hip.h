@@ -645,6 +645,76 @@ enum {
  * geometry. */
 LMI_API int lmi_debug_filter_plan(int64_t *out, int n);
 
+/* The range search (no reference counterpart): for every query ALL objects of its visited buckets within distance radius[q] -- the
+ * second standard query of a metric index; the length of a query's result is decided by the data, not by a k.  It is the union scan
+ * with another last stage: a threshold and a compaction instead of a selection.  tests/range_ref.py restates it in numpy.
+ * Contract
+ *   candidates, ordinals, scores   lmi_scan_union's, word for word: the concatenation of the rows of the query's ranks in
+ *                lmi_bucket_read's order; a rank of -1 contributes nothing, a bucket listed twice contributes twice; the row counts
+ *                are the live ones; the score is the unsplit canonical chain (L2: the stored -|x|^2/2 column inside it).
+ *   admission    a candidate is admitted iff its score is > -FLT_MAX (the union scan's rule: NaN never passes) AND
+ *                sim_to_dist(score) <= radius[q], compared in binary32, where sim_to_dist is the distance the scan writes:
+ *                IP 1.0f - s, L2 fmaf(-2, key, |q|^2).  radius is a HOST float [nq], also with on_device.  A NaN or -inf radius
+ *                admits nothing; +inf admits every candidate that passes the first rule.
+ *   filter       f (nullable; filter_of nullable, HOST int32 [nq], as in lmi_scan_union_filtered): only the rows query q's filter
+ *                allows are candidates; ordinals stay the unfiltered ones.  A filter_of without f is refused.
+ *   result       a query's admitted candidates in ASCENDING ORDINAL order (by rank, then by row): no sort, and the order is total.
+ *                lims int64 [nq + 1] with lims[0] = 0; dists float [lims[nq]]; ids uint32 [lims[nq]]; query q owns
+ *                [lims[q], lims[q + 1]).  The same bit for bit for any query grouping, wave cut, grid or pointer kind;
+ *                lmi_union_set_geometry applies to these calls and never changes a bit.
+ * The stops (lmi_set_stop_mass, lmi_set_path_mass, lmi_set_stop_rows) act through the bucket order exactly as in the union forms:
+ * lmi_search_range routes as lmi_search_union does, lmi_search_tree_range as lmi_search_tree_union; lmi_scan_range takes the caller's
+ * order as given.  on_device: queries (and the order arrays) are all device pointers or all host pointers.
+ * The result is an opaque lmi_range_result that owns the device arrays and the host lims.  It holds no pointer to its handle and may
+ * outlive it.  lmi_range_result_total: lims[nq].  _lims: lims [nq + 1] <- the limits.  _read: dists, ids [total] <- the arrays (device
+ * pointers with on_device, else host; both may be NULL where total is 0).  _destroy: frees it (NULL: nothing).
+ * max_total: the most results the whole call may produce; 0 = only memory limits it.  When the running count passes max_total the
+ * call fails, says how many results had been counted when it stopped, launches nothing further and produces no result object
+ * (*result = NULL); the handle stays usable.
+ * Every (query, bucket) pair is multiplied once: the scores of a wave stay in its slab while they are counted and then emitted.  The
+ * counts of every wave come back to the host to size the wave's chunk exactly: the call synchronises the handle's stream ONCE PER
+ * WAVE (and once per query group, and once behind the final gather), and returns when the result is complete.
+ * Device memory of a call: the union scan's slab, packed queries and tables (no lists) + 28 bytes per slot of a group + 20 per slot
+ * of the call (the gather) + 4 nq; the results twice while the call runs -- 8 bytes per result in exact-size per-wave chunks, 8 per
+ * result in the final arrays, allocated once behind the last group -- and once afterwards.
+ * Refused before any launch: everything lmi_scan_union refuses apart from k -- an index that is not built; nb < 1, nb > 1024,
+ * nq * nb >= 2^31; nb * (largest bucket) >= 2^32 - 1; an index that is not stored row-major (lmi_set_prefilter(0), LMI_STORAGE_F16);
+ * a needed pointer that is NULL -- everything the filtered forms refuse of a filter (stale, foreign, filter_of outside [-1, nf)); a
+ * NULL radius; a NULL result pointer; a negative max_total.  nq == 0 succeeds with an empty result (lims = {0}).
+ * Not offered: sharded ranks, _f16 query forms, lmi_pipeline_submit, a device-side sort by distance. */
+typedef struct lmi_range_result lmi_range_result;
+LMI_API int lmi_scan_range(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb,
+                           const float *radius /* host [nq] */, const lmi_filter *f /* nullable */,
+                           const int32_t *filter_of /* host [nq], nullable */, int64_t max_total, lmi_range_result **result,
+                           int on_device);
+/* lmi_mlp_topk followed by lmi_scan_range; bucket_order (nullable) [nq][nb] <- the order that was scanned. */
+LMI_API int lmi_search_range(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb,
+                             const float *radius /* host [nq] */, const lmi_filter *f /* nullable */,
+                             const int32_t *filter_of /* host [nq], nullable */, int64_t max_total, lmi_range_result **result,
+                             int32_t *bucket_order /* nullable */, int on_device);
+/* lmi_nav_order followed by lmi_scan_range; slab_ids, entries (nullable) [nq][nb] as lmi_search_tree returns them. */
+LMI_API int lmi_search_tree_range(lmi_index *h, const float *queries_nav, const float *queries_search, int nq, int nb,
+                                  const float *radius /* host [nq] */, const lmi_filter *f /* nullable */,
+                                  const int32_t *filter_of /* host [nq], nullable */, int64_t max_total, lmi_range_result **result,
+                                  int32_t *slab_ids /* nullable */, int32_t *entries /* nullable */, int on_device);
+LMI_API int lmi_range_result_total(const lmi_range_result *r, int64_t *total);
+LMI_API int lmi_range_result_lims(const lmi_range_result *r, int64_t *lims /* [nq + 1] */);
+LMI_API int lmi_range_result_read(const lmi_range_result *r, float *dists, uint32_t *ids, int on_device);
+LMI_API int lmi_range_result_destroy(lmi_range_result *r);
+enum {
+    LMI_RANGE_PLAN_GROUPS = 0,        /* groups the queries were taken in                                                     */
+    LMI_RANGE_PLAN_QUERY_ROWS,        /* queries per group (the last may be smaller)                                          */
+    LMI_RANGE_PLAN_WAVES,             /* waves of the last group (0: none of its slots had rows)                              */
+    LMI_RANGE_PLAN_SLAB_BYTES,        /* bytes of the score slab (the largest wave's)                                         */
+    LMI_RANGE_PLAN_RESULTS,           /* results of the call: lims[nq]                                                        */
+    LMI_RANGE_PLAN_CHUNK_BYTES,       /* bytes of the per-wave result chunks, all together (8 per result)                     */
+    LMI_RANGE_PLAN_WORKSPACE_BYTES,   /* device bytes the call allocated beside the chunks and the result                     */
+    LMI_RANGE_PLAN_COUNT
+};
+/* What the last range call on this thread did (all zero before the first, after a refused or failed call and after one with
+ * nq == 0); writes min(n, LMI_RANGE_PLAN_COUNT) words. */
+LMI_API int lmi_debug_range_plan(int64_t *out, int n);
+
 /* The union scan across the ranks of a bucket-sharded index (no reference counterpart): every rank scans the buckets it owns and
  * hands on a PART; the merge of the parts is what lmi_scan_union returns on one handle that holds the whole index, bit for bit, for
  * any assignment of the buckets (each owned by exactly one part) and any world size.

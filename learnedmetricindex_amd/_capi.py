@@ -38,6 +38,8 @@ FILTER_KEEP, FILTER_DROP = 0, 1   # LMI_FILTER_KEEP, LMI_FILTER_DROP: the list n
 FILTER_MAX = 1024                 # LMI_FILTER_MAX: filters of one set (`Filter`)
 #: the LMI_FILTER_PLAN_* words, in their order (lmi_debug_filter_plan)
 FILTER_PLAN_FIELDS = ("FILTERS", "MASK_BYTES", "SLOTS", "SKIPPED")
+#: the LMI_RANGE_PLAN_* words, in their order (lmi_debug_range_plan)
+RANGE_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "RESULTS", "CHUNK_BYTES", "WORKSPACE_BYTES")
 
 _lib = None
 
@@ -118,6 +120,18 @@ SIGNATURES = {
     "lmi_search_tree_union_filtered": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
                                                       ctypes.c_int, _vp, _vp]),
     "lmi_debug_filter_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    # the range search: (.., radius on the host, filter, filter_of on the host, max_total, &result, [order outputs,] on_device)
+    "lmi_scan_range": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, ctypes.POINTER(_vp),
+                                      ctypes.c_int]),
+    "lmi_search_range": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, ctypes.POINTER(_vp),
+                                        _vp, ctypes.c_int]),
+    "lmi_search_tree_range": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64,
+                                             ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int]),
+    "lmi_range_result_total": (ctypes.c_int, [_vp, _i64p]),
+    "lmi_range_result_lims": (ctypes.c_int, [_vp, _vp]),
+    "lmi_range_result_read": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),
+    "lmi_range_result_destroy": (ctypes.c_int, [_vp]),
+    "lmi_debug_range_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -792,6 +806,89 @@ class Index:
         self._union_call("lmi_search_tree_union", (_ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t),
                                                    _ptr(slab_t), _ptr(ent_t), 1), f, fo)
 
+    # ---- the range search: every object of the visited buckets within a radius, in ordinal order (include/lmi_hip.h, lmi_scan_range) ----
+    @staticmethod
+    def _range_args(who: str, nb: int, radius, max_total, **arrays) -> np.ndarray:
+        """radius f32[nq] of a range call (a scalar serves every query); argument errors are raised before the library loads."""
+        Index._union_args(who, 1, nb, **arrays)
+        nq = int(next(iter(arrays.values())).shape[0])
+        if radius is None:
+            raise ValueError(f"{who}: radius is None")
+        r = np.asarray(radius.cpu().numpy() if hasattr(radius, "cpu") else radius)
+        if r.dtype.kind not in "fiu" or r.ndim > 1 or (r.ndim == 1 and r.shape[0] != nq):
+            raise ValueError(f"{who}: radius must be a number or one number per query ([{nq}]), not {r.dtype}{tuple(r.shape)}")
+        if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
+            raise ValueError(f"{who}: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
+        return np.ascontiguousarray(np.broadcast_to(r.astype(np.float32), (nq,)))
+
+    def _range_call(self, name: str, head: tuple, radius, f, fo, max_total: int, tail: tuple) -> "RangeResult":
+        res = _vp()
+        _check(getattr(lib(), name)(self._h, *head, _ptr(radius), f, _ptr(fo), int(max_total), ctypes.byref(res), *tail))
+        return RangeResult(res, int(radius.shape[0]))
+
+    def scan_range(self, queries_search, bucket_order, radius, filter=None, filter_of=None, max_total: int = 0):
+        """(lims i64[nq + 1], dists f32[total], ids u32[total]) of `lmi_scan_range`: per query every object of the buckets
+        `bucket_order[q]` lists (-1: none) whose distance is <= `radius` (a number, or one per query), in (rank, row) order; query q owns
+        [lims[q], lims[q + 1]).  `filter`, `filter_of`: as in `scan_union`.  `max_total` > 0: the call fails (LmiError) once more results
+        than that have been counted."""
+        if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
+            raise ValueError("scan_range: bucket_order must be a two-dimensional array")
+        nb = int(bucket_order.shape[1])
+        r = self._range_args("scan_range", nb, radius, max_total, queries_search=queries_search, bucket_order=bucket_order)
+        q = _np(queries_search, np.float32)
+        bo = _np(bucket_order, np.int32)
+        f, fo = self._filter_args("scan_range", filter, filter_of, q.shape[0])
+        with self._range_call("lmi_scan_range", (_ptr(q), q.shape[0], _ptr(bo), nb), r, f, fo, max_total, (0,)) as res:
+            return (res.lims,) + res.read()
+
+    def search_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0):
+        """`lmi_search_range`: (lims, dists, ids, bucket order i32[nq,nb])."""
+        r = self._range_args("search_range", nb, radius, max_total, queries_nav=queries_nav, queries_search=queries_search)
+        same = queries_search is queries_nav
+        qn = _np(queries_nav, np.float32)
+        qs = qn if same else _np(queries_search, np.float32)
+        nq = qn.shape[0]
+        bo = np.empty((nq, nb), dtype=np.int32)
+        f, fo = self._filter_args("search_range", filter, filter_of, nq)
+        with self._range_call("lmi_search_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total, (_ptr(bo), 0)) as res:
+            return (res.lims,) + res.read() + (bo,)
+
+    def search_tree_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0):
+        """`lmi_search_tree_range`: (lims, dists, ids, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb])."""
+        r = self._range_args("search_tree_range", nb, radius, max_total, queries_nav=queries_nav, queries_search=queries_search)
+        same = queries_search is queries_nav
+        qn = _np(queries_nav, np.float32)
+        qs = qn if same else _np(queries_search, np.float32)
+        nq = qn.shape[0]
+        slab = np.empty((nq, nb), dtype=np.int32)
+        ent = np.empty((nq, nb), dtype=np.int32)
+        f, fo = self._filter_args("search_tree_range", filter, filter_of, nq)
+        with self._range_call("lmi_search_tree_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total,
+                              (_ptr(slab), _ptr(ent), 0)) as res:
+            return (res.lims,) + res.read() + (slab, ent)
+
+    def scan_range_device(self, qs_t, bo_t, nb: int, radius, filter=None, filter_of=None, max_total: int = 0) -> "RangeResult":
+        """Device tensors (float32 queries, int32 order); `radius` and `filter_of` stay on the host.  Returns the `RangeResult`, whose
+        arrays stay on the device until `read()` / `read_into()`."""
+        r = self._range_args("scan_range_device", nb, radius, max_total, queries_search=qs_t, bucket_order=bo_t)
+        nq = int(qs_t.shape[0])
+        f, fo = self._filter_args("scan_range_device", filter, filter_of, nq)
+        return self._range_call("lmi_scan_range", (_ptr(qs_t), nq, _ptr(bo_t), int(nb)), r, f, fo, max_total, (1,))
+
+    def search_range_device(self, qn_t, qs_t, nb: int, radius, bo_t=None, filter=None, filter_of=None, max_total: int = 0) -> "RangeResult":
+        r = self._range_args("search_range_device", nb, radius, max_total, queries_nav=qn_t, queries_search=qs_t)
+        nq = int(qn_t.shape[0])
+        f, fo = self._filter_args("search_range_device", filter, filter_of, nq)
+        return self._range_call("lmi_search_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total, (_ptr(bo_t), 1))
+
+    def search_tree_range_device(self, qn_t, qs_t, nb: int, radius, slab_t=None, ent_t=None, filter=None, filter_of=None,
+                                 max_total: int = 0) -> "RangeResult":
+        r = self._range_args("search_tree_range_device", nb, radius, max_total, queries_nav=qn_t, queries_search=qs_t)
+        nq = int(qn_t.shape[0])
+        f, fo = self._filter_args("search_tree_range_device", filter, filter_of, nq)
+        return self._range_call("lmi_search_tree_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total,
+                                (_ptr(slab_t), _ptr(ent_t), 1))
+
     # ---- the union scan across ranks: a rank's part and the merge of the parts (include/lmi_hip.h, lmi_scan_union_part) ----
     @staticmethod
     def _union_merge_args(who: str, world, nq, k) -> None:
@@ -1109,6 +1206,62 @@ def filter_last_plan() -> dict:
     w = (ctypes.c_int64 * len(FILTER_PLAN_FIELDS))()
     _check(lib().lmi_debug_filter_plan(w, len(FILTER_PLAN_FIELDS)))
     return dict(zip(FILTER_PLAN_FIELDS, (int(v) for v in w)))
+
+
+class RangeResult:
+    """The results of one range call (`lmi_range_result`): `lims` i64[nq + 1] and `total` = lims[nq] on the host, the distances and ids
+    on the device until they are read.  It does not refer to the `Index` it came from and may outlive it.  A context manager: leaving
+    the block closes it."""
+
+    def __init__(self, handle, nq: int):
+        self._r = handle
+        self.nq = int(nq)
+        self.lims = np.zeros(self.nq + 1, dtype=np.int64)
+        _check(lib().lmi_range_result_lims(self._r, _ptr(self.lims)))
+        self.total = int(self.lims[-1])
+
+    def _open(self):
+        if getattr(self, "_r", None) is None:
+            raise ValueError("RangeResult: the result is closed")
+        return self._r
+
+    def read(self):
+        """(dists f32[total], ids u32[total]) on the host."""
+        d = np.empty(self.total, dtype=np.float32)
+        i = np.empty(self.total, dtype=np.uint32)
+        _check(lib().lmi_range_result_read(self._open(), _ptr(d), _ptr(i), 0))
+        return d, i
+
+    def read_into(self, d_t, i_t) -> None:
+        """Device tensors of at least `total` 4-byte elements each (float32; int32 or uint32-sized) <- the distances and the ids."""
+        for name, t in (("d_t", d_t), ("i_t", i_t)):
+            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() >= self.total):
+                raise ValueError(f"RangeResult.read_into: {name} must be a contiguous device tensor of >= {self.total} 4-byte elements")
+        _check(lib().lmi_range_result_read(self._open(), _ptr(d_t), _ptr(i_t), 1))
+
+    def close(self) -> None:
+        if getattr(self, "_r", None) is not None:
+            r, self._r = self._r, None
+            lib().lmi_range_result_destroy(r)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def range_last_plan() -> dict:
+    """What the last range call on this thread did (`lmi_debug_range_plan`): `RANGE_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(RANGE_PLAN_FIELDS))()
+    _check(lib().lmi_debug_range_plan(w, len(RANGE_PLAN_FIELDS)))
+    return dict(zip(RANGE_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

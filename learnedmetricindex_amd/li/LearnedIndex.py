@@ -506,6 +506,143 @@ class LearnedIndex(Logger):
         measured_time["search"] = time.time() - s
         return d32.astype(np.float64), nns, measured_time
 
+    # ---- range search (an extension; no reference counterpart): every object of the visited buckets within a radius ----
+    @staticmethod
+    def _check_range(radius, max_total, storage) -> None:
+        """Refused before any work is done."""
+        if radius is None:
+            raise ValueError("range_search: radius is None")
+        if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
+            raise ValueError(f"range_search: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
+        if storage != "f32":
+            raise ValueError(f"range_search needs the default storage ('f32', prefilter on): the candidates are read from the row-major "
+                             f"image, which storage={storage!r} does not keep")
+
+    def range_search(
+        self,
+        data_navigation: pd.DataFrame,
+        queries_navigation: npt.NDArray[np.float32],
+        data_search: pd.DataFrame,
+        queries_search: npt.NDArray[np.float32],
+        data_prediction: npt.NDArray[np.int64],
+        n_categories: List[int],
+        radius,
+        n_buckets: int = 1,
+        metric: str = "ip",
+        sort: bool = False,
+        max_total: int = 0,
+        assume_unchanged: bool = False,
+        stop_mass: Optional[float] = None,
+        path_mass: Optional[float] = None,
+        stop_rows: Optional[int] = None,
+        filter=None,
+        filter_of=None,
+        storage: str = "f32",
+    ):
+        """Every object of each query's `n_buckets` most probable buckets whose distance to the query is <= `radius` (a number, or one
+        per query): `lmi_search_range` / `lmi_search_tree_range`.  Returns (lims i64[nq + 1], dists f64[total], nns u32[total],
+        measured_time): query q owns [lims[q], lims[q + 1]), its results in (rank, row) order -- or, with `sort=True`, stably sorted
+        by distance on the host.  `metric`, `assume_unchanged`, the stops, `filter` and `filter_of` as in `search` (the filter needs no
+        `merge`); `max_total` > 0 makes the call fail (`_capi.LmiError`) once more results than that have been counted -- on a
+        multi-level index per piece of `_nav_chunk()` queries, less what the earlier pieces returned.  It needs the default storage:
+        ValueError otherwise, before any work."""
+        self._check_range(radius, max_total, storage)
+        self._check_filter(filter, filter_of, "union")
+        self._check_stop_mass(stop_mass, n_categories)
+        self._check_path_mass(path_mass, n_categories)
+        s = time.time()
+        eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged,
+                           storage=storage)
+        return self._range_with(eng, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total, s, stop_mass,
+                                path_mass, stop_rows, filter, filter_of)
+
+    def range_search_resident(self, queries_navigation, queries_search, n_categories: List[int], radius, n_buckets: int = 1,
+                              sort: bool = False, max_total: int = 0, stop_mass: Optional[float] = None,
+                              path_mass: Optional[float] = None, stop_rows: Optional[int] = None, filter=None, filter_of=None):
+        """`range_search` against the index already resident in HBM: no DataFrames needed.  Same return values."""
+        assert self._engine is not None, "no resident index: call prepare()/search() or index_io.load_index()"
+        self._check_range(radius, max_total, getattr(self._engine, "storage", "f32"))
+        self._check_filter(filter, filter_of, "union")
+        self._check_stop_mass(stop_mass, n_categories)
+        self._check_path_mass(path_mass, n_categories)
+        return self._range_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total,
+                                time.time(), stop_mass, path_mass, stop_rows, filter, filter_of)
+
+    def _range_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total, s, stop_mass,
+                    path_mass, stop_rows, filter, filter_of):
+        if filter is not None and not isinstance(filter, _capi.Filter):   # an id list: one keep filter, made for this call
+            made = _capi.Filter(eng, [np.asarray(filter).reshape(-1)])
+            try:
+                return self._range_with(eng, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total, s,
+                                        stop_mass, path_mass, stop_rows, made, filter_of)
+            finally:
+                made.close()
+        run = functools.partial(self._range_run, eng, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total,
+                                s, filter, filter_of)
+        if stop_mass is None and path_mass is None and stop_rows is None:
+            return run()
+        before = eng.stop_mass, eng.path_mass, eng.stop_rows   # the engine's own settings come back afterwards
+        try:
+            if stop_mass is not None:
+                eng.set_stop_mass(stop_mass)
+            if path_mass is not None:
+                eng.set_path_mass(path_mass)
+            if stop_rows is not None:
+                eng.set_stop_rows(stop_rows)
+            return run()
+        finally:
+            eng.set_stop_mass(before[0])
+            eng.set_path_mass(before[1])
+            eng.set_stop_rows(before[2])
+
+    def _range_run(self, eng, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total, s, filter, filter_of):
+        """The batch goes to the library whole on a 1-level index; a multi-level index is walked in pieces of `_nav_chunk()` queries and
+        the pieces' lims are joined."""
+        fo = None if filter_of is None else np.asarray(filter_of).reshape(-1)
+        measured_time = defaultdict(float)
+        qn = np.ascontiguousarray(_query_array(queries_navigation), dtype=np.float32)
+        qs = qn if queries_search is queries_navigation else np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
+        assert qn.shape[0] == qs.shape[0]
+        nq = qs.shape[0]
+        r = np.asarray(radius, dtype=np.float32)
+        if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != nq):
+            raise ValueError(f"range_search: radius must be a number or one number per query ([{nq}]), not {tuple(r.shape)}")
+        r = np.ascontiguousarray(np.broadcast_to(r, (nq,)))
+        if len(n_categories) == 1:
+            assert n_buckets <= eng.n_classes, "n_buckets exceeds the number of classes"
+        if nq == 0:
+            return np.zeros(1, dtype=np.int64), np.empty(0), np.empty(0, dtype=np.uint32), measured_time
+        t0 = time.time()
+        if len(n_categories) == 1:
+            lims, d32, nns = eng.search_range(qn, qs, n_buckets, r, filter=filter, filter_of=fo, max_total=max_total)[:3]
+        else:
+            step = self._nav_chunk()
+            parts, got = [], 0
+            for lo in range(0, nq, step):
+                # what is left of the budget (a 0 would mean "no limit" to the library: 1 then, and the sum is checked below)
+                left = max(1, max_total - got) if max_total > 0 else 0
+                part = eng.search_tree_range(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets,
+                                             r[lo: lo + step], filter=filter, filter_of=None if fo is None else fo[lo: lo + step],
+                                             max_total=left)[:3]
+                if max_total > 0 and got + int(part[0][-1]) > max_total:
+                    raise _capi.LmiError(f"range_search: more than max_total = {max_total} results: {got + int(part[0][-1])} had been "
+                                         f"counted when the call stopped")
+                got += int(part[0][-1])
+                parts.append(part)
+            lims = np.concatenate([parts[0][0][:1]] + [p[0][1:] + off for p, off in
+                                                       zip(parts, np.cumsum([0] + [int(p[0][-1]) for p in parts[:-1]]))]).astype(np.int64)
+            d32 = np.concatenate([p[1] for p in parts])
+            nns = np.concatenate([p[2] for p in parts])
+        if sort:
+            for q in range(nq):
+                a, b = int(lims[q]), int(lims[q + 1])
+                if b - a > 1:
+                    o = np.argsort(d32[a:b], kind="stable")
+                    d32[a:b], nns[a:b] = d32[a:b][o], nns[a:b][o]
+        measured_time["search_within_buckets"] = time.time() - t0   # wall time of the calls: the library times no phase of them
+        measured_time["search"] = time.time() - s
+        return lims, d32.astype(np.float64), nns, measured_time
+
     def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
         measured_time = defaultdict(float)
         qn = _query_array(queries_navigation)   # float16 arrays stay halves: the engine uploads them as they are

@@ -79,6 +79,7 @@ class Experiment:
     storage: str = "f32"
     trainer: str = "torch"
     merge: str = "ranks"
+    range_radius: Optional[float] = None
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -119,6 +120,9 @@ class Experiment:
                        help="ranks = at most 10 results per visited bucket, merged by rank (the reference; k <= 20); union = the k best "
                             "objects of all visited buckets, k up to 1024 -- with --eval, recall@k then measures what the index returned "
                             "for that k")
+        p.add_argument("--range-radius", type=float, default=None,
+                       help="also run a range search per budget: every object of the visited buckets within this distance of the "
+                            "query; the results per query (mean, max) are reported")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -136,6 +140,10 @@ class Experiment:
             p.error("--merge union takes --k from 1 to 1024")
         if a["merge"] == "union" and a["storage"] != "f32":
             p.error("--merge union needs --storage f32 (the union scan reads the row-major f32 image)")
+        if a["range_radius"] is not None and a["storage"] != "f32":
+            p.error("--range-radius needs --storage f32 (the range search reads the row-major f32 image)")
+        if a["range_radius"] is not None and a["range_radius"] != a["range_radius"]:
+            p.error("--range-radius must be a number")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -310,6 +318,13 @@ def run(exp: Experiment) -> Dict:
         sink.write(exp.dataset, exp.size, stem, dists, knns, algo="Learned-index", data=src.stamp(exp.dataset),
                    buildtime=build_s, querytime=clock["search"], size=exp.size, params=stem)
         out[budget] = (dists, knns, clock)
+        if exp.range_radius is not None:
+            lims, _, _, rclock = index.range_search_resident(nav_q, scan_q, exp.n_categories, exp.range_radius, n_buckets=budget,
+                                                             stop_mass=exp.stop_mass, path_mass=exp.path_mass, stop_rows=exp.stop_rows)
+            per_query = np.diff(lims)
+            out[f"range_{budget}"] = (float(per_query.mean()) if per_query.size else 0.0, int(per_query.max(initial=0)))
+            LOG.info("%d buckets: range search within %g: %.4fs, results per query mean %.2f, max %d", budget, exp.range_radius,
+                     rclock["search"], *out[f"range_{budget}"])
     index.close()
     return out
 

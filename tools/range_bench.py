@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""What the range search (lmi_search_range) costs beside the union scan it shares its score stage with (developer aid).
+
+On tools/union_bench.py's shape -- 10M x 768 unit-norm rows in 120 Gaussian clusters, 10 000 queries, the 4 most probable buckets each;
+the routing model's logits are the inner products with the cluster centres -- ms per batch, device tensors in, batches timed one by
+one after one warm-up, in ONE run on one index:
+
+  lmi_search_union at k = 10 and k = 1000        the call beside it: pack, score, select, merge
+  lmi_search_range, per-query radii              radius[q] = the query's k-th distance of the union call: k results per query
+  lmi_search_range, one radius                   the median of those radii for every query: about k per query, uneven runs
+
+A range row also says how many results came back (mean and max per query), the plan, and whether every query's run, stably sorted
+by distance, begins with the union's ids.  Nothing here is a pass/fail gate.  A record of the machine it runs on.
+
+  python tools/range_bench.py                          # the full shape: about 80 GB of device memory
+  python tools/range_bench.py --n 400000 --nq 2000     # a quick look"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+
+CHUNK = 1 << 18
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--n", type=int, default=10_000_000)
+    ap.add_argument("--d", type=int, default=768)
+    ap.add_argument("--leaves", type=int, default=120)
+    ap.add_argument("--nq", type=int, default=10_000)
+    ap.add_argument("--nb", type=int, default=4)
+    ap.add_argument("--ks", type=int, nargs="+", default=[10, 1000])
+    ap.add_argument("--steps", type=int, default=5, help="timed batches per row (after one warm-up batch)")
+    ap.add_argument("--seed", type=int, default=2023)
+    a = ap.parse_args()
+    import torch
+
+    from learnedmetricindex_amd import _capi
+
+    dev = torch.device("cuda", 0)
+    N, d, L, nq, nb = a.n, a.d, a.leaves, a.nq, a.nb
+    t0 = time.time()
+    centres = torch.randn(L, d, generator=torch.Generator().manual_seed(a.seed)).to(dev)
+
+    def gen_rows(tag, piece, n):
+        g = torch.Generator(device=dev).manual_seed(a.seed * 1_000_003 + tag * 100_003 + piece)
+        c = torch.randint(0, L, (n,), generator=g, device=dev)
+        return torch.nn.functional.normalize(centres[c] + torch.randn(n, d, generator=g, device=dev), dim=1).contiguous()
+
+    X = torch.empty((N, d), dtype=torch.float32, device=dev)
+    for p in range(0, N, CHUNK):
+        X[p: p + CHUNK] = gen_rows(1, p // CHUNK, min(CHUNK, N - p))
+    Q = gen_rows(7, 0, nq)
+    cn = centres.cpu().numpy()
+    layers = [(cn, np.full(L, float(np.linalg.norm(cn, axis=1).max()) + 1.0, np.float32)),
+              (np.eye(L, dtype=np.float32), np.zeros(L, np.float32))]
+    eng = _capi.Index(0)
+    eng.set_stream(torch.cuda.current_stream().cuda_stream)
+    eng.set_mlp(layers)
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    for p in range(0, N, CHUNK):
+        eng.mlp_topk_device(X[p: p + CHUNK], 1, labels[p: p + CHUNK])
+    torch.cuda.synchronize()
+    eng.buckets_begin(labels.cpu().numpy().astype(np.int64), d, L)
+    for p in range(0, N, CHUNK):
+        eng.add_rows(X[p: p + CHUNK], p)
+        torch.cuda.synchronize()
+    eng.buckets_end()
+    del X
+
+    def timed_each(fn, steps):
+        """(min, mean, max) ms over `steps` batches timed one by one, after one warm-up batch."""
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(steps):
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append(1e3 * (time.perf_counter() - t))
+        return min(ms), sum(ms) / len(ms), max(ms)
+
+    sizes = eng.bucket_sizes()
+    print(f"# {N} x {d}, {L} buckets (sizes min/median/max {sizes.min()}/{int(np.median(sizes))}/{sizes.max()}), {nq} queries, n_buckets {nb}; "
+          f"device tensors; {a.steps} batches per row timed one by one after one warm-up; setup {time.time() - t0:.0f} s", flush=True)
+    print("# call | k or radius | ms per batch min / mean / max | results per query mean / max | note", flush=True)
+    bo = torch.empty((nq, nb), dtype=torch.int32, device=dev)
+    for k in a.ks:
+        d_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        i_t = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        c_t = torch.empty((nq,), dtype=torch.int32, device=dev)
+        lo, mean, hi = timed_each(lambda: eng.search_union_device(Q, Q, nb, k, d_t, i_t, c_t, bo), a.steps)
+        plan = _capi.union_last_plan()
+        print(f"lmi_search_union | k {k} | {lo:.2f} / {mean:.2f} / {hi:.2f} | {float(c_t.float().mean().item()):.1f} / {int(c_t.max().item())} | "
+              f"groups {plan['GROUPS']} waves {plan['WAVES']} slab {plan['SLAB_BYTES'] >> 20} MiB workspace {plan['WORKSPACE_BYTES'] >> 20} MiB",
+              flush=True)
+        du, iu = d_t.cpu().numpy(), i_t.cpu().numpy().view(np.uint32)
+        per_query = np.ascontiguousarray(du[:, k - 1])
+        for what, radius in ((f"radius[q] = the k = {k} distance", per_query),
+                             (f"radius {float(np.median(per_query)):.6f}", np.full(nq, np.median(per_query), np.float32))):
+            keep = []
+
+            def call():
+                for r in keep:
+                    r.close()
+                keep[:] = [eng.search_range_device(Q, Q, nb, radius, bo)]
+
+            lo, mean, hi = timed_each(call, a.steps)
+            res = keep[0]
+            plan = _capi.range_last_plan()
+            n = np.diff(res.lims)
+            dd, ii = res.read()
+            res.close()
+            agree = 0   # queries whose run, stably sorted by distance, begins with the union's ids (as far as both go)
+            for q in range(nq):
+                lo_q, hi_q = int(res.lims[q]), int(res.lims[q + 1])
+                o = np.argsort(dd[lo_q:hi_q], kind="stable")[:k]
+                m = min(k, hi_q - lo_q)
+                agree += bool(np.array_equal(ii[lo_q:hi_q][o][:m], iu[q, :m]))
+            print(f"lmi_search_range | {what} | {lo:.2f} / {mean:.2f} / {hi:.2f} | {n.mean():.1f} / {n.max()} | groups {plan['GROUPS']} waves "
+                  f"{plan['WAVES']} slab {plan['SLAB_BYTES'] >> 20} MiB workspace {plan['WORKSPACE_BYTES'] >> 20} MiB chunks "
+                  f"{plan['CHUNK_BYTES'] >> 10} KiB; sorted runs begin with the union's ids for {agree} of {nq} queries", flush=True)
+    eng.set_stream(0)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
