@@ -681,7 +681,7 @@ LMI_API int lmi_debug_filter_plan(int64_t *out, int n);
  * nq * nb >= 2^31; nb * (largest bucket) >= 2^32 - 1; an index that is not stored row-major (lmi_set_prefilter(0), LMI_STORAGE_F16);
  * a needed pointer that is NULL -- everything the filtered forms refuse of a filter (stale, foreign, filter_of outside [-1, nf)); a
  * NULL radius; a NULL result pointer; a negative max_total.  nq == 0 succeeds with an empty result (lims = {0}).
- * Not offered: sharded ranks, _f16 query forms, lmi_pipeline_submit, a device-side sort by distance. */
+ * Not offered: _f16 query forms, lmi_pipeline_submit, a device-side sort by distance.  Sharded ranks: lmi_join_range_parts below. */
 typedef struct lmi_range_result lmi_range_result;
 LMI_API int lmi_scan_range(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb,
                            const float *radius /* host [nq] */, const lmi_filter *f /* nullable */,
@@ -700,6 +700,11 @@ LMI_API int lmi_search_tree_range(lmi_index *h, const float *queries_nav, const 
 LMI_API int lmi_range_result_total(const lmi_range_result *r, int64_t *total);
 LMI_API int lmi_range_result_lims(const lmi_range_result *r, int64_t *lims /* [nq + 1] */);
 LMI_API int lmi_range_result_read(const lmi_range_result *r, float *dists, uint32_t *ids, int on_device);
+/* The counts behind lims: *nb (nullable) <- the nb of the call that made the result; counts (nullable, HOST int32 [nq][nb]) <- the
+ * results of every (query, rank t of the bucket in the query's order) -- 0 for a rank of -1, an empty bucket, one the filter emptied or
+ * one the handle does not own.  Row q sums to lims[q + 1] - lims[q].  A result of nq == 0 reports its call's nb and no counts. */
+LMI_API int lmi_range_result_pair_counts(const lmi_range_result *r, int32_t *nb /* nullable */,
+                                         int32_t *counts /* [nq][nb], nullable */);
 LMI_API int lmi_range_result_destroy(lmi_range_result *r);
 enum {
     LMI_RANGE_PLAN_GROUPS = 0,        /* groups the queries were taken in                                                     */
@@ -756,6 +761,61 @@ LMI_API int lmi_merge_union_parts(lmi_index *h, const int32_t *parts /* [world][
  * cleanly when RCCL is absent. */
 LMI_API int lmi_allgather_merge_union(lmi_index *h, void *comm, int rank, int world, const int32_t *part /* device */, int nq, int k,
                                       float *dists, uint32_t *ids, int32_t *counts /* nullable */);
+
+/* The range search across the ranks of a bucket-sharded index (no reference counterpart): every rank calls lmi_scan_range on its
+ * handle (built with an `owned` mask: an unowned bucket has no rows there, so the rank answers for exactly the buckets it owns) with
+ * the SAME queries, bucket order and radius, and hands on its result as a PART: its pair counts (lmi_range_result_pair_counts) and
+ * its dists / ids (lmi_range_result_read).  The join of the parts is what lmi_scan_range returns on one handle that holds all the
+ * buckets, bit for bit, for any assignment of the buckets (each owned by exactly one part) and any world size.
+ * Why a gather suffices: a range result is in (query, rank t, row) order; every (query, t) names one bucket and one part owns it, so
+ * the run of (query, t) comes whole from its owner and no ordering by score is needed (unlike lmi_merge_union_parts).
+ * Contract
+ *   counts       HOST int32 [world][nq][nb], always: counts[r][q][t] = results of part r for (q, t).
+ *   dists, ids   [world] pointers: part r's arrays in (q, t, row) order as lmi_range_result_read gives them, counts[r] summed long.
+ *                on_device: all device pointers, or all host pointers -- a host part's arrays are uploaded once each.  A part whose
+ *                total is 0 may pass NULL for both.
+ *   result       the run of (q, t) is the run of the one part whose counts[r][q][t] > 0, copied unchanged, at the exclusive sum of
+ *                the summed counts in (q, t) order; lims[q] = that sum at (q, 0).  The result's pair counts are the sum over the
+ *                parts.  It is an lmi_range_result like any other (device arrays, host lims; it may outlive the handle) and is
+ *                complete when the call returns (the handle's stream is synchronised once).
+ * The handle needs no built index: it provides the device and the stream.  The host plans the join (lmi_range_join_plan.h: pure
+ * arithmetic) and range_join_kernel copies: runs are cut into pieces of at most piece_rows results (default 4 096), one block of 256
+ * lanes per piece, 4-byte loads and stores (source and target share no alignment), no LDS, no atomic, nothing written outside a
+ * piece's target.  Device memory of a call: the result (8 bytes per result), 24 bytes per piece, 16 per part; with host pointers
+ * the staged parts (8 bytes per result) while the call runs.
+ * Refused before any launch or allocation: a NULL handle; world outside 1..64; nq < 0; nb outside 1..1024; nq * nb >= 2^31; NULL
+ * counts, dists or ids with nq > 0; a negative count (names the part, query and t); a (query, t) that two parts both claim (names
+ * the query, t and both parts: the parts' ownerships overlap); a part whose total is > 0 with a NULL array; a NULL result pointer;
+ * a negative max_total; a grand total above max_total when max_total > 0 (says the total).  *result = NULL after a refusal.
+ * nq == 0 succeeds with an empty result (lims = {0}). */
+LMI_API int lmi_join_range_parts(lmi_index *h, int world, int nq, int nb, const int32_t *counts /* host, [world][nq][nb] */,
+                                 const float *const *dists /* [world] */, const uint32_t *const *ids /* [world] */,
+                                 int64_t max_total, lmi_range_result **result, int on_device);
+/* The exchange through RCCL inside the library: every rank passes its part (the lmi_range_result of its lmi_scan_range) -> ONE
+ * ncclAllGather of the part's nq * nb counts on the handle's stream -> ONE stream synchronisation, so that the host can size the
+ * payload and plan the join -> ONE ncclAllGather of [dists | ids], each padded to the largest part's total Tmax (ncclAllGather is the
+ * only collective the library resolves and it moves equal blocks: 8 * world * Tmax bytes are received where 8 * total are needed) ->
+ * the join, as above.  The joined result is identical on every rank.  nq and nb are the part's; ALL RANKS MUST PASS PARTS OF THE SAME
+ * nq AND nb: a mismatch the gathered counts cannot show (they are exchanged in blocks of this rank's nq * nb) is the caller's
+ * responsibility.  A part whose total differs from what its gathered counts sum to is refused.
+ * Refusals as lmi_join_range_parts, and a NULL part, a NULL communicator, a rank outside 0..world-1; fails cleanly when RCCL is
+ * absent.  nq == 0 succeeds with an empty result and no collective. */
+LMI_API int lmi_allgather_join_range(lmi_index *h, void *comm, int rank, int world, const lmi_range_result *part, int64_t max_total,
+                                     lmi_range_result **result);
+/* Test hook: the most results of one copy piece of the joins on this thread; 0 = the default (4 096).  Never changes a bit of a
+ * result.  Refused: a negative value, one above 2^30. */
+LMI_API int lmi_range_join_set_geometry(int64_t piece_rows);
+enum {
+    LMI_RANGE_JOIN_PARTS = 0,         /* parts joined: world                                                                  */
+    LMI_RANGE_JOIN_RUNS,              /* non-empty (query, t) runs                                                            */
+    LMI_RANGE_JOIN_PIECES,            /* copy pieces = blocks of the kernel's grid                                            */
+    LMI_RANGE_JOIN_RESULTS,           /* results of the join: lims[nq]                                                        */
+    LMI_RANGE_JOIN_LARGEST_PART,      /* the largest part's total (Tmax: what lmi_allgather_join_range pads every part to)    */
+    LMI_RANGE_JOIN_COUNT
+};
+/* What the last join on this thread did (all zero before the first, after a refused or failed call and after one with nq == 0);
+ * writes min(n, LMI_RANGE_JOIN_COUNT) words. */
+LMI_API int lmi_debug_range_join_plan(int64_t *out, int n);
 
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);

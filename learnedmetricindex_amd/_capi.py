@@ -40,6 +40,8 @@ FILTER_MAX = 1024                 # LMI_FILTER_MAX: filters of one set (`Filter`
 FILTER_PLAN_FIELDS = ("FILTERS", "MASK_BYTES", "SLOTS", "SKIPPED")
 #: the LMI_RANGE_PLAN_* words, in their order (lmi_debug_range_plan)
 RANGE_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "RESULTS", "CHUNK_BYTES", "WORKSPACE_BYTES")
+#: the LMI_RANGE_JOIN_* words, in their order (lmi_debug_range_join_plan)
+RANGE_JOIN_FIELDS = ("PARTS", "RUNS", "PIECES", "RESULTS", "LARGEST_PART")
 
 _lib = None
 
@@ -132,6 +134,13 @@ SIGNATURES = {
     "lmi_range_result_read": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),
     "lmi_range_result_destroy": (ctypes.c_int, [_vp]),
     "lmi_debug_range_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    # the range search across ranks: a result's per-(query, rank) counts, the join of the ranks' parts, its exchange through RCCL
+    "lmi_range_result_pair_counts": (ctypes.c_int, [_vp, _i32p, _vp]),
+    "lmi_join_range_parts": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                            ctypes.c_int64, ctypes.POINTER(_vp), ctypes.c_int]),
+    "lmi_allgather_join_range": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64, ctypes.POINTER(_vp)]),
+    "lmi_range_join_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
+    "lmi_debug_range_join_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -889,6 +898,79 @@ class Index:
         return self._range_call("lmi_search_tree_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total,
                                 (_ptr(slab_t), _ptr(ent_t), 1))
 
+    # ---- the range search across ranks: the join of the ranks' parts (include/lmi_hip.h, lmi_join_range_parts) ----
+    @staticmethod
+    def _range_join_args(who: str, counts, dists, ids, max_total):
+        """(counts i32[world, nq, nb] contiguous, on_device) of a join; argument errors are raised before the library loads."""
+        if not isinstance(counts, np.ndarray) or counts.ndim != 3 or counts.dtype.kind not in "iu":
+            raise ValueError(f"{who}: counts must be an integer numpy array [world, nq, nb] on the host")
+        world, nq, nb = (int(x) for x in counts.shape)
+        if world < 1 or world > 64:
+            raise ValueError(f"{who}: world {world} outside [1, 64]")
+        if nb < 1 or nb > 1024:
+            raise ValueError(f"{who}: nb {nb} outside [1, 1024]")
+        if nq * nb >= 1 << 31:
+            raise ValueError(f"{who}: nq * nb = {nq * nb} is too large")
+        if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
+            raise ValueError(f"{who}: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
+        for name, arrs in (("dists", dists), ("ids", ids)):
+            if not isinstance(arrs, (list, tuple)) or len(arrs) != world:
+                raise ValueError(f"{who}: {name} must be a list of {world} arrays, one per part (None for a part without results)")
+        present = [a for a in list(dists) + list(ids) if a is not None]
+        host = [isinstance(a, np.ndarray) for a in present]
+        if any(host) and not all(host):
+            raise ValueError(f"{who}: the parts must be all numpy arrays or all tensors on the device")
+        totals = counts.astype(np.int64).reshape(world, -1).sum(axis=1)
+        for r in range(world):
+            for name, a in (("dists", dists[r]), ("ids", ids[r])):
+                if a is None:
+                    if totals[r] > 0:
+                        raise ValueError(f"{who}: part {r} holds {int(totals[r])} results and its {name} is None")
+                    continue
+                if not isinstance(a, np.ndarray) and not (hasattr(a, "is_cuda") and a.is_cuda and a.is_contiguous() and a.element_size() == 4):
+                    raise ValueError(f"{who}: {name}[{r}] must be a numpy array or a contiguous tensor of 4-byte elements on the device")
+                if len(a.shape) != 1 or int(a.shape[0]) < totals[r]:
+                    raise ValueError(f"{who}: {name}[{r}] must be one-dimensional with >= {int(totals[r])} elements, not {tuple(a.shape)}")
+        return np.ascontiguousarray(counts, dtype=np.int32), (0 if all(host) else 1)
+
+    def join_range_parts(self, counts, dists, ids, max_total: int = 0) -> "RangeResult":
+        """`lmi_join_range_parts`: counts i32[world, nq, nb] (host), `dists` / `ids` lists of the parts' arrays (all numpy: host pointers;
+        all tensors: device pointers; None for a part without results) -> the `RangeResult` one handle holding every bucket returns."""
+        c, on_device = self._range_join_args("join_range_parts", counts, dists, ids, max_total)
+        world, nq, nb = c.shape
+        if on_device == 0:
+            dists = [None if a is None else _np(a, np.float32) for a in dists]
+            ids = [None if a is None else _np(a, np.uint32) for a in ids]
+        pd = (_vp * world)(*[_ptr(a) for a in dists])
+        pi = (_vp * world)(*[_ptr(a) for a in ids])
+        res = _vp()
+        _check(lib().lmi_join_range_parts(self._h, world, nq, nb, _ptr(c), pd, pi, int(max_total), ctypes.byref(res), on_device))
+        return RangeResult(res, nq)
+
+    def allgather_join_range(self, comm, rank: int, world: int, part: "RangeResult", max_total: int = 0) -> "RangeResult":
+        """This rank's `RangeResult` (of `scan_range_device` on its owned buckets) -> the joined result on every rank
+        (`lmi_allgather_join_range`: two ncclAllGather calls and one stream synchronisation between them)."""
+        who = "allgather_join_range"
+        if not isinstance(world, (int, np.integer)) or world < 1 or world > 64:
+            raise ValueError(f"{who}: world {world!r} outside [1, 64]")
+        if not isinstance(rank, (int, np.integer)) or rank < 0 or rank >= world:
+            raise ValueError(f"{who}: rank {rank!r} of {world}")
+        if comm is None or not isinstance(part, RangeResult):
+            raise ValueError(f"{who}: comm must not be None and part must be a RangeResult")
+        if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
+            raise ValueError(f"{who}: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
+        res = _vp()
+        _check(lib().lmi_allgather_join_range(self._h, comm, int(rank), int(world), part._open(), int(max_total), ctypes.byref(res)))
+        return RangeResult(res, part.nq)
+
+    @staticmethod
+    def set_range_join_geometry(piece_rows: int = 0) -> None:
+        """Test hook (`lmi_range_join_set_geometry`): the most results of one copy piece of the joins on this thread; 0 = the default.
+        Never changes a result."""
+        if isinstance(piece_rows, bool) or not isinstance(piece_rows, (int, np.integer)) or piece_rows < 0 or piece_rows > 1 << 30:
+            raise ValueError(f"set_range_join_geometry: piece_rows {piece_rows!r} outside [0, 2^30]")
+        _check(lib().lmi_range_join_set_geometry(int(piece_rows)))
+
     # ---- the union scan across ranks: a rank's part and the merge of the parts (include/lmi_hip.h, lmi_scan_union_part) ----
     @staticmethod
     def _union_merge_args(who: str, world, nq, k) -> None:
@@ -1232,6 +1314,16 @@ class RangeResult:
         _check(lib().lmi_range_result_read(self._open(), _ptr(d), _ptr(i), 0))
         return d, i
 
+    def pair_counts(self) -> np.ndarray:
+        """i32[nq, nb]: the results of every (query, rank t of the bucket in the query's order) (`lmi_range_result_pair_counts`); row q
+        sums to lims[q + 1] - lims[q].  What a rank hands on beside its arrays for `Index.join_range_parts`."""
+        nb = ctypes.c_int32(0)
+        _check(lib().lmi_range_result_pair_counts(self._open(), ctypes.byref(nb), None))
+        c = np.zeros((self.nq, int(nb.value)), dtype=np.int32)
+        if self.nq > 0:
+            _check(lib().lmi_range_result_pair_counts(self._r, None, _ptr(c)))
+        return c
+
     def read_into(self, d_t, i_t) -> None:
         """Device tensors of at least `total` 4-byte elements each (float32; int32 or uint32-sized) <- the distances and the ids."""
         for name, t in (("d_t", d_t), ("i_t", i_t)):
@@ -1262,6 +1354,13 @@ def range_last_plan() -> dict:
     w = (ctypes.c_int64 * len(RANGE_PLAN_FIELDS))()
     _check(lib().lmi_debug_range_plan(w, len(RANGE_PLAN_FIELDS)))
     return dict(zip(RANGE_PLAN_FIELDS, (int(v) for v in w)))
+
+
+def range_join_last_plan() -> dict:
+    """What the last join of range parts on this thread did (`lmi_debug_range_join_plan`): `RANGE_JOIN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(RANGE_JOIN_FIELDS))()
+    _check(lib().lmi_debug_range_join_plan(w, len(RANGE_JOIN_FIELDS)))
+    return dict(zip(RANGE_JOIN_FIELDS, (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

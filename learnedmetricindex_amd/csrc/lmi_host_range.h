@@ -4,7 +4,8 @@
 // wave's counts come back to the host (ONE synchronisation per wave); a chunk of exactly the wave's results is allocated, the slots'
 // offsets go up, emit.  Behind the last group the final arrays are allocated once at lims[nq] and every wave's runs are gathered (one
 // descriptor table for all of them, one synchronisation).
-// lmi_scan_range, lmi_search_range, lmi_search_tree_range, lmi_range_result_*, lmi_debug_range_plan.
+// lmi_scan_range, lmi_search_range, lmi_search_tree_range, lmi_range_result_*, lmi_debug_range_plan.  A result keeps the call's nb and
+// the counts of every (query, rank): what the join of the ranks' parts (lmi_host_range_join.h) is planned from.
 #pragma once
 #include "lmi_host_union.h"
 #include "lmi_range.h"
@@ -14,6 +15,8 @@
 struct lmi_range_result {
     int device = 0;
     std::vector<int64_t> lims;   // [nq + 1]
+    int nb = 0;                  // the ranks per query of the call that made it
+    std::vector<int> pair_count; // [nq][nb]: the results of every (query, rank); row q sums to lims[q + 1] - lims[q]
     float* dists = nullptr;      // [lims[nq]], device
     uint32_t* ids = nullptr;
     ~lmi_range_result() {
@@ -41,9 +44,10 @@ int range_begin(lmi_index* h, const char* who, int nq, int nb, const float* radi
     return 0;
 }
 
-int range_empty(lmi_index* h, int nq, lmi_range_result** out) {
+int range_empty(lmi_index* h, int nq, int nb, lmi_range_result** out) {
     lmi_range_result* r = new lmi_range_result();
     r->device = h->device;
+    r->nb = nb;
     r->lims.assign((size_t)nq + 1, 0);
     *out = r;
     return 0;
@@ -180,6 +184,8 @@ int range_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     lmi_range_result* r = new lmi_range_result();
     r->device = h->device;
     r->lims = rp::make_lims(tot, first);
+    r->nb = nb;
+    r->pair_count = tot.pair_count;
     const int64_t total = r->lims.back();
     // the gathers: every wave's descriptors back to back in one table, one upload, one launch per wave that produced results
     auto finish = [&]() -> int {
@@ -246,7 +252,7 @@ extern "C" LMI_API int lmi_scan_range(lmi_index* h, const float* queries_search,
                                       int on_device) {
     const char* who = "lmi_scan_range";
     CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
-    if (nq == 0) return range_empty(h, nq, result);
+    if (nq == 0) return range_empty(h, nq, nb, result);
     if (!queries_search || !bucket_order) return fail("%s: queries_search and bucket_order must not be NULL", who);
     CHK(set_dev(h));
     const void* d_qs = nullptr;
@@ -264,7 +270,7 @@ extern "C" LMI_API int lmi_search_range(lmi_index* h, const float* queries_nav, 
     CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
     if (h->root().n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
     if (h->root().dims.back() != h->L) return fail("%s: MLP has %d classes, index has %d buckets", who, h->root().dims.back(), h->L);
-    if (nq == 0) return range_empty(h, nq, result);
+    if (nq == 0) return range_empty(h, nq, nb, result);
     if (!queries_nav || !queries_search) return fail("%s: queries_nav and queries_search must not be NULL", who);
     CHK(set_dev(h));
     const float *d_qn = nullptr, *d_qs = nullptr;
@@ -287,7 +293,7 @@ extern "C" LMI_API int lmi_search_tree_range(lmi_index* h, const float* queries_
                                              lmi_range_result** result, int32_t* slab_ids, int32_t* entries, int on_device) {
     const char* who = "lmi_search_tree_range";
     CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
-    if (nq == 0) return range_empty(h, nq, result);
+    if (nq == 0) return range_empty(h, nq, nb, result);
     if (!queries_nav || !queries_search) return fail("%s: queries_nav and queries_search must not be NULL", who);
     CHK(nav_check(h, nq, nb, who));
     const float *d_qn = nullptr, *d_qs = nullptr;
@@ -315,6 +321,12 @@ extern "C" LMI_API int lmi_range_result_total(const lmi_range_result* r, int64_t
 extern "C" LMI_API int lmi_range_result_lims(const lmi_range_result* r, int64_t* lims) {
     if (!r || !lims) return fail("lmi_range_result_lims: NULL argument");
     std::copy(r->lims.begin(), r->lims.end(), lims);
+    return 0;
+}
+extern "C" LMI_API int lmi_range_result_pair_counts(const lmi_range_result* r, int32_t* nb, int32_t* counts) {
+    if (!r) return fail("lmi_range_result_pair_counts: NULL result");
+    if (nb) *nb = r->nb;
+    if (counts) std::copy(r->pair_count.begin(), r->pair_count.end(), counts);
     return 0;
 }
 extern "C" LMI_API int lmi_range_result_read(const lmi_range_result* r, float* dists, uint32_t* ids, int on_device) {

@@ -13,6 +13,10 @@ Two layouts of the routing step (`ShardedSearcher(shard_inference=...)`):
 buckets.  A rank's scan writes a PART (`Index.scan_union_part_device`: score bits | dist bits | ids | ranks | rows, int32 [5, nq, k]); the
 one result collective moves 20*nq*k bytes per rank and the merge orders by (score, bucket rank, row) -- by score, not by distance, whose
 rounding can make two scores one; by (rank, row), which orders as the single handle's ordinal does and needs no other rank's bucket sizes.
+`range_search` (both searchers) answers the range query -- every object of the visited buckets within a radius.
+A rank's `Index.scan_range_device` answers for the buckets it owns; its per-(query, bucket rank) counts and its [dists | ids] block (padded
+to the largest rank's total) are all-gathered, and the join is a gather (`Index.join_range_parts`): a result is in (query, bucket rank, row)
+order, every (query, bucket rank) names one bucket and one rank owns it, so every run comes whole from its owner -- no ordering by score.
 `ReplicaSearcher` is the other mode SURVEY section 8e names: QUERY-sharded replicas -- every rank holds the whole
 index and answers its 1/world slice of the batch; one all-gather of [dists | ids | bucket order] rows.  A query's
 answer does not depend on the rest of its batch, so the result is again byte-identical for every world size.  It
@@ -159,6 +163,75 @@ def merge_union_parts_numpy(gathered: np.ndarray):
     d = np.where(sel, np.take_along_axis(dist, order, 1), np.float32(np.inf)).astype(np.float32)
     i = np.where(sel, np.take_along_axis(ids, order, 1), 0).astype(np.uint32)
     return d, i, sel.sum(axis=1).astype(np.int32)
+
+
+def join_range_parts_numpy(counts, dists, ids):
+    """Host restatement of `lmi_join_range_parts`, used by the CPU tests and their stand-in index: counts int [world, nq, nb], `dists` /
+    `ids` lists of the parts' arrays in (query, t, row) order (None for a part without results) -> (lims i64[nq + 1], dists f32[total],
+    ids u32[total]).  The run of (q, t) is the run of the one part whose count is > 0, copied unchanged; a (q, t) two parts both claim
+    means overlapping ownership: ValueError, as the library refuses it."""
+    counts = np.asarray(counts)
+    if counts.ndim != 3:
+        raise ValueError("join_range_parts_numpy: counts must be [world, nq, nb]")
+    world, nq, nb = counts.shape
+    c = counts.astype(np.int64).reshape(world, nq * nb)
+    if (c < 0).any():
+        r, s = (int(x[0]) for x in np.nonzero(c < 0))
+        raise ValueError(f"join_range_parts_numpy: the count of part {r} at query {s // nb}, t {s % nb} is negative")
+    claimed = (c > 0).sum(axis=0)
+    if (claimed > 1).any():
+        s = int(np.flatnonzero(claimed > 1)[0])
+        a, b = (int(x) for x in np.flatnonzero(c[:, s] > 0)[:2])
+        raise ValueError(f"join_range_parts_numpy: query {s // nb}, t {s % nb} has results in part {a} and in part {b}: the parts' "
+                         "buckets overlap")
+    src = np.cumsum(c, axis=1) - c                      # a part's exclusive run offsets
+    n = c.sum(axis=0)
+    first = np.concatenate([[0], np.cumsum(n)])         # the joined result's
+    total = int(first[-1])
+    owner = np.argmax(c > 0, axis=0)
+    out_d, out_i = np.empty(total, np.float32), np.empty(total, np.uint32)
+    for r in range(world):
+        if c[r].sum() == 0:
+            continue
+        pd = np.asarray(dists[r]).view(np.float32).reshape(-1)
+        pi = np.asarray(ids[r]).view(np.uint32).reshape(-1)
+        for s in np.flatnonzero((owner == r) & (n > 0)):
+            out_d[first[s]: first[s] + n[s]] = pd[src[r, s]: src[r, s] + n[s]]
+            out_i[first[s]: first[s] + n[s]] = pi[src[r, s]: src[r, s] + n[s]]
+    return first[::nb].astype(np.int64), out_d, out_i   # lims[q] = first[q * nb]
+
+
+def _radius_rows(radius, nq: int) -> np.ndarray:
+    """radius f32[nq] of a sharded range search: a scalar serves every query (the same on every rank)."""
+    r = np.asarray(radius.cpu().numpy() if hasattr(radius, "cpu") else radius)
+    if r.dtype.kind not in "fiu" or r.ndim > 1 or (r.ndim == 1 and r.shape[0] != nq):
+        raise ValueError(f"range_search: radius must be a number or one number per query ([{nq}])")
+    return np.ascontiguousarray(np.broadcast_to(r.astype(np.float32), (nq,)))
+
+
+def _read_range(res, dev):
+    """(lims, dists tensor, ids tensor) of a range result on `dev`; the result is closed."""
+    import torch
+
+    d = torch.empty(res.total, dtype=torch.float32, device=dev)
+    i = torch.empty(res.total, dtype=torch.int32, device=dev)
+    if res.total > 0:
+        res.read_into(d, i)
+    lims = np.array(res.lims, dtype=np.int64)
+    res.close()
+    return lims, d, i
+
+
+def _read_empty(dev):
+    import torch
+
+    return torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+
+
+def _over_total(who: str, max_total: int, total: int):
+    from ._capi import LmiError
+
+    return LmiError(f"{who}: more than max_total = {max_total} results: the ranks hold {total}")
 
 
 def _check_merge(merge, filter=None) -> None:
@@ -357,6 +430,85 @@ class ShardedSearcher:
         self.index.search_device(qn_t, qs_t, nb, k, blk[0], blk[1], blk[2], bo)
         return self._exchange(blk, out_d, out_i, bo, nq, kout)
 
+    # ---- the range search: every object of the visited buckets within a radius, joined across the ranks ----
+    def _scan_exchange_range(self, qs_t, bo, nb: int, radius, max_total: int):
+        """Behind the routing: this rank's `scan_range_device` over `bo` (its owned buckets answer), then the exchange -- none for a
+        world of one without a communicator; `lmi_allgather_join_range` with a `lib_comm`; else one all-gather of the nq*nb counts,
+        one of the [2, Tmax] block (dists | ids, padded to the largest part) and `lmi_join_range_parts` on pointers into the gathered
+        buffer.  `max_total` limits the joined result on every path, checked on the gathered counts, which every rank sees alike; a
+        rank whose own part already exceeds it says so to the others through the counts, so that no rank waits in a collective."""
+        import torch
+
+        from ._capi import LmiError
+
+        nq, dev = qs_t.shape[0], qs_t.device
+        radius = _radius_rows(radius, nq)
+        if self.world == 1 and self.lib_comm is None:
+            return _read_range(self.index.scan_range_device(qs_t, bo, nb, radius, max_total=max_total), dev) + (bo,)
+        if self.lib_comm is not None:
+            part = self.index.scan_range_device(qs_t, bo, nb, radius)
+            try:
+                joined = self._timed("result_allgather_merge",
+                                     lambda: self.index.allgather_join_range(self.lib_comm, self.rank, self.world, part, max_total), qs_t.is_cuda)
+            finally:
+                part.close()
+            return _read_range(joined, dev) + (bo,)
+        try:
+            part = self.index.scan_range_device(qs_t, bo, nb, radius, max_total=max_total)
+            counts = torch.from_numpy(part.pair_counts()).to(dev)
+        except LmiError:
+            if max_total == 0:
+                raise
+            part, counts = None, torch.full((nq, nb), -1, dtype=torch.int32, device=dev)   # this rank alone is over max_total
+
+        def exchange():
+            g_counts = _all_gather_cat(counts, self.world, self.group).cpu().numpy().reshape(self.world, nq, nb)
+            if (g_counts < 0).any():
+                raise LmiError(f"range_search: more than max_total = {max_total} results on rank {int(np.nonzero(g_counts < 0)[0][0])} alone")
+            totals = g_counts.astype(np.int64).reshape(self.world, -1).sum(axis=1)
+            if max_total > 0 and totals.sum() > max_total:
+                raise _over_total("range_search", max_total, int(totals.sum()))
+            tmax = int(totals.max())
+            if tmax == 0:
+                return self.index.join_range_parts(g_counts, [None] * self.world, [None] * self.world, max_total)
+            blk = torch.zeros((2, tmax), dtype=torch.int32, device=dev)
+            if part.total > 0:
+                part.read_into(blk[0], blk[1])
+            g = all_gather_blocks(blk, self.world, self.group)   # [world, 2, tmax]
+            return self.index.join_range_parts(g_counts, [g[r, 0] for r in range(self.world)], [g[r, 1] for r in range(self.world)], max_total)
+
+        try:
+            joined = self._timed("result_allgather_merge", exchange, qs_t.is_cuda)
+        finally:
+            if part is not None:
+                part.close()
+        return _read_range(joined, dev) + (bo,)
+
+    def range_search_routed(self, qs_t, bo_loc, nb: int, radius, max_total: int = 0):
+        """The rest of a sharded range search behind `route_local`: all-gather of the bucket order (as `search_routed`), scan of the
+        owned buckets, exchange and join -> (lims i64 numpy [nq + 1], dists tensor [total], ids tensor [total], bucket order)."""
+        nq = qs_t.shape[0]
+        radius = _radius_rows(radius, nq)
+        bo = self._timed("bucket_order_allgather", lambda: all_gather_rows(bo_loc, nq, self.world, self.group), bo_loc.is_cuda)
+        return self._scan_exchange_range(qs_t, bo.contiguous(), nb, radius, max_total)
+
+    def range_search(self, qn_t, qs_t, nb: int, radius, max_total: int = 0):
+        """Per query every object of its nb visited buckets within `radius` (a number, or one per query; the same on every rank), in
+        (bucket rank, row) order: what `Index.search_range` returns on one handle that holds the whole index, bit for bit, on every
+        rank.  Routing as `search(merge="union")`.  -> (lims i64 numpy [nq + 1], dists tensor, ids tensor, bucket order)."""
+        import torch
+
+        nq = qn_t.shape[0]
+        radius = _radius_rows(radius, nq)   # (argument errors before any work)
+        if self.shard_inference:
+            if self._bo_loc is None or self._bo_loc.shape[1] != nb or self._bo_loc.shape[0] != row_slice(nq, self.rank, self.world)[0]:
+                self._bo_loc = self.new_route_buffer(nq, nb, qn_t.device)
+            self.route_local(qn_t, nb, self._bo_loc)
+            return self.range_search_routed(qs_t, self._bo_loc, nb, radius, max_total)
+        bo = torch.empty((nq, nb), dtype=torch.int32, device=qn_t.device)
+        self.index.mlp_topk_device(qn_t, nb, bo)
+        return self._scan_exchange_range(qs_t, bo, nb, radius, max_total)
+
 
 class ReplicaSearcher:
     """Query-sharded replicas: the index is whole on every rank (`set_buckets` / `add_rows` without an `owned`
@@ -414,6 +566,58 @@ class ReplicaSearcher:
         g = all_gather_rows(row, nq, self.world, self.group)   # the one collective
         return (g[:, :k].contiguous().view(torch.float32), g[:, k:2 * k].contiguous(), g[:, 2 * k + 1:].contiguous(),
                 g[:, 2 * k].contiguous())
+
+    def range_search(self, qn_t, qs_t, nb: int, radius, max_total: int = 0):
+        """Same signature and return value as `ShardedSearcher.range_search`.  `search_range_device` on the rank's slice with that slice
+        of `radius`; one all-gather of [count | nb buckets] rows and one of the [2, Tmax] payload (dists | ids, padded to the largest
+        slice's total).  The slices are contiguous runs of queries, so the batch's result is their concatenation in rank order: no
+        kernel.  `max_total` limits the batch's total, checked on the gathered counts (alike on every rank)."""
+        import torch
+
+        from ._capi import LmiError
+
+        nq, dev = qn_t.shape[0], qn_t.device
+        radius = _radius_rows(radius, nq)
+        per, lo, hi = row_slice(nq, self.rank, self.world)
+        n = hi - lo
+        bo = torch.full((per, nb), -1, dtype=torch.int32, device=dev)
+        cnt = torch.zeros((per,), dtype=torch.int64, device=dev)
+        part = None
+        if n > 0:
+            try:
+                part = self.index.search_range_device(qn_t[lo:hi], qs_t[lo:hi], nb, radius[lo:hi], bo_t=bo[:n], max_total=max_total)
+                cnt[:n] = torch.from_numpy(np.diff(part.lims)).to(dev)
+            except LmiError:
+                if max_total == 0 or self.world == 1:
+                    raise
+                cnt[:n] = -1   # this rank's slice alone is over max_total: the others learn it from the counts
+        if self.world == 1:
+            if part is None:   # an empty batch
+                return (np.zeros(1, np.int64),) + _read_empty(dev) + (bo[:nq],)
+            return _read_range(part, dev) + (bo[:nq],)
+        try:
+            row = torch.cat([cnt.view(torch.int32).view(per, 2), bo], dim=1)
+            g = _all_gather_cat(row, self.world, self.group)           # [world * per, 2 + nb]
+            counts = g[:, :2].contiguous().view(torch.int64).view(-1).cpu().numpy()
+            if (counts < 0).any():
+                raise LmiError(f"range_search: more than max_total = {max_total} results on rank {int(np.flatnonzero(counts < 0)[0]) // per} alone")
+            totals = counts.reshape(self.world, per).sum(axis=1)
+            if max_total > 0 and totals.sum() > max_total:
+                raise _over_total("range_search", max_total, int(totals.sum()))
+            lims = np.concatenate([[0], np.cumsum(counts[:nq])]).astype(np.int64)
+            tmax = int(totals.max())
+            if tmax == 0:
+                return (lims,) + _read_empty(dev) + (g[:nq, 2:].contiguous(),)
+            blk = torch.zeros((2, tmax), dtype=torch.int32, device=dev)
+            if part is not None and part.total > 0:
+                part.read_into(blk[0], blk[1])
+            p = all_gather_blocks(blk, self.world, self.group)          # [world, 2, tmax]
+            d = torch.cat([p[r, 0, : int(totals[r])] for r in range(self.world)]).view(torch.float32)
+            i = torch.cat([p[r, 1, : int(totals[r])] for r in range(self.world)])
+            return lims, d, i, g[:nq, 2:].contiguous()
+        finally:
+            if part is not None:
+                part.close()
 
     def search(self, qn_t, qs_t, nb: int, k: int, merge: str = "ranks", filter=None):
         import torch

@@ -12,6 +12,11 @@ one after one warm-up, in ONE run on one index:
 A range row also says how many results came back (mean and max per query), the plan, and whether every query's run, stably sorted
 by distance, begins with the union's ids.  Nothing here is a pass/fail gate.  A record of the machine it runs on.
 
+The sharded leg (profiles/range_sharded.txt) follows on the same index and bucket order, batches timed one by one: lmi_scan_range on
+the whole handle, the same call on the buckets of one rank of emulated worlds of 2 and 8 ranks (rank r owns the buckets b with
+b % world == r; the slowest rank's row is printed), and lmi_join_range_parts alone on those ranks' parts, with what a padded all-gather
+of them would move.  One card plays every rank; nothing is said about several GPUs.
+
   python tools/range_bench.py                          # the full shape: about 80 GB of device memory
   python tools/range_bench.py --n 400000 --nq 2000     # a quick look"""
 import argparse
@@ -125,6 +130,85 @@ def main():
             print(f"lmi_search_range | {what} | {lo:.2f} / {mean:.2f} / {hi:.2f} | {n.mean():.1f} / {n.max()} | groups {plan['GROUPS']} waves "
                   f"{plan['WAVES']} slab {plan['SLAB_BYTES'] >> 20} MiB workspace {plan['WORKSPACE_BYTES'] >> 20} MiB chunks "
                   f"{plan['CHUNK_BYTES'] >> 10} KiB; sorted runs begin with the union's ids for {agree} of {nq} queries", flush=True)
+    # ---- the sharded leg (profiles/range_sharded.txt): a rank's part call beside lmi_scan_range, and the join alone, for emulated worlds ----
+    # Rank r of an emulated world owns the buckets b with b % world == r: the others are struck out of its order, which is what an
+    # `owned` mask does to them (no rows), and leaves every rank t where it is.  One card plays every rank: no multi-GPU claim is made.
+    print("# sharded leg: call | radius | ms per batch min / mean / max | note", flush=True)
+    steps = max(a.steps, 5)
+    stalls = []   # (row, batch times) of the rows in which one batch took more than three times the fastest
+
+    def timed_row(row, fn):
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(steps):
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append(1e3 * (time.perf_counter() - t))
+        if max(ms) > 3 * min(ms):
+            stalls.append((row, ms))
+        return min(ms), sum(ms) / len(ms), max(ms)
+
+    for k in a.ks:
+        d_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        i_t = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        eng.search_union_device(Q, Q, nb, k, d_t, i_t, None, bo)
+        torch.cuda.synchronize()
+        radius = np.ascontiguousarray(d_t[:, k - 1].cpu().numpy())
+        what = f"radius[q] = the k = {k} distance"
+        keep = []
+
+        def call(order):
+            for r in keep:
+                r.close()
+            keep[:] = [eng.scan_range_device(Q, order, nb, radius)]
+
+        lo, mean, hi = timed_row(f"lmi_scan_range, k {k}", lambda: call(bo))
+        whole = keep.pop()
+        wd = torch.empty(whole.total, dtype=torch.float32, device=dev)
+        wi = torch.empty(whole.total, dtype=torch.int32, device=dev)
+        whole.read_into(wd, wi)
+        print(f"lmi_scan_range | {what} | {lo:.2f} / {mean:.2f} / {hi:.2f} | {whole.total} results", flush=True)
+        for world in (2, 8):
+            counts, ds, is_, rows = [], [], [], []
+            for r in range(world):
+                order = torch.where(bo % world == r, bo, torch.full_like(bo, -1))
+                rows.append(timed_row(f"rank {r} of {world}, k {k}", lambda: call(order)))
+                part = keep.pop()
+                counts.append(part.pair_counts())
+                ds.append(torch.empty(part.total, dtype=torch.float32, device=dev))
+                is_.append(torch.empty(part.total, dtype=torch.int32, device=dev))
+                if part.total:
+                    part.read_into(ds[-1], is_[-1])
+                part.close()
+            counts = np.stack(counts)
+            totals = counts.reshape(world, -1).sum(axis=1)
+            slow = max(rows, key=lambda t: t[1])
+            print(f"lmi_scan_range on a rank's buckets, world {world} | {what} | {slow[0]:.2f} / {slow[1]:.2f} / {slow[2]:.2f} | the slowest of "
+                  f"the {world} ranks (the fastest: mean {min(t[1] for t in rows):.2f}); part totals min / max {totals.min()} / {totals.max()}",
+                  flush=True)
+
+            def join():
+                for r in keep:
+                    r.close()
+                keep[:] = [eng.join_range_parts(counts, ds, is_)]
+
+            lo, mean, hi = timed_row(f"join, world {world}, k {k}", join)
+            res = keep.pop()
+            jd, ji = torch.empty_like(wd), torch.empty_like(wi)
+            ok = res.total == whole.total and np.array_equal(res.lims, whole.lims)
+            if ok and res.total:
+                res.read_into(jd, ji)
+                ok = torch.equal(jd.view(torch.int32), wd.view(torch.int32)) and torch.equal(ji, wi)
+            res.close()
+            plan = _capi.range_join_last_plan()
+            print(f"lmi_join_range_parts, world {world} | {what} | {lo:.3f} / {mean:.3f} / {hi:.3f} | {plan['RUNS']} runs in {plan['PIECES']} "
+                  f"pieces, {8 * plan['RESULTS'] >> 10} KiB of results; a padded all-gather would receive {8 * world * plan['LARGEST_PART'] >> 10} "
+                  f"KiB; {'equal to' if ok else 'DIFFERS from'} lmi_scan_range", flush=True)
+        whole.close()
+    for row, ms in stalls:
+        print(f"# a stalled batch in: {row}: " + " ".join(f"{t:.2f}" for t in ms), flush=True)
     eng.set_stream(0)
     eng.close()
 
