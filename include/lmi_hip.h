@@ -681,7 +681,8 @@ LMI_API int lmi_debug_filter_plan(int64_t *out, int n);
  * nq * nb >= 2^31; nb * (largest bucket) >= 2^32 - 1; an index that is not stored row-major (lmi_set_prefilter(0), LMI_STORAGE_F16);
  * a needed pointer that is NULL -- everything the filtered forms refuse of a filter (stale, foreign, filter_of outside [-1, nf)); a
  * NULL radius; a NULL result pointer; a negative max_total.  nq == 0 succeeds with an empty result (lims = {0}).
- * Not offered: _f16 query forms, lmi_pipeline_submit, a device-side sort by distance.  Sharded ranks: lmi_join_range_parts below. */
+ * Not offered: _f16 query forms, lmi_pipeline_submit.  Nearest first: lmi_range_result_sort below.  Sharded ranks:
+ * lmi_join_range_parts below. */
 typedef struct lmi_range_result lmi_range_result;
 LMI_API int lmi_scan_range(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order, int nb,
                            const float *radius /* host [nq] */, const lmi_filter *f /* nullable */,
@@ -816,6 +817,67 @@ enum {
 /* What the last join on this thread did (all zero before the first, after a refused or failed call and after one with nq == 0);
  * writes min(n, LMI_RANGE_JOIN_COUNT) words. */
 LMI_API int lmi_debug_range_join_plan(int64_t *out, int n);
+
+/* A range result sorted by distance, on the device and in place (no reference counterpart): nearest first, for callers that read the
+ * result (lmi_range_result_read, host or device pointers) after the sort.  h provides the device and the stream only and needs no
+ * built index, like lmi_join_range_parts; r is any result of that device: a scan's or a join's.  tests/range_sort_ref.py restates the
+ * contract in numpy.
+ * Contract
+ *   order        for every query q with segment [a, b) = [lims[q], lims[q + 1]): dists[a:b] and ids[a:b] are permuted TOGETHER so that
+ *                the pairs (key(dist), position the entry had in the segment before the call) ascend.  key orders binary32 values
+ *                numerically with -0 == +0; every NaN, of either sign and any payload, sorts behind +inf; equal keys keep their
+ *                earlier relative order.  This is numpy's argsort(dists[a:b], kind="stable") applied to both arrays.
+ *   bits         the bits of dists and ids are MOVED, never recomputed: -0 stays -0, a NaN keeps its payload.
+ *   unchanged    lims, nb and the pair counts.  After a sort the pair counts still say how many results every (query, rank t)
+ *                contributed, NOT where they lie: the runs of the ranks are interleaved by distance.
+ *   determinism  (key, position) is a total order without equal elements, so the result is the same bit for bit for any tile length,
+ *                grouping, grid or algorithm; lmi_range_sort_set_geometry never changes a bit.  Sorting a sorted result is allowed
+ *                and changes nothing.
+ *   flag         the result remembers that it was sorted: lmi_range_result_sorted writes 1, else 0.  lmi_allgather_join_range refuses
+ *                a sorted part by name, because the join needs (rank, row) order: sort the JOINED result.  lmi_join_range_parts takes
+ *                raw arrays and cannot know: passing it arrays read from a sorted result is the caller's mistake.
+ * How: an entry becomes ONE 64-bit word, (order-preserving image of the key << 32) | position; the words of a segment are unique, so an
+ * unstable network yields the stable order.  The host picks a form per segment from lims alone (lmi_range_sort_plan.h):
+ *   skipped      0 or 1 entries
+ *   wave form    2 .. 256 entries: one wave per segment, four per block, the words in registers
+ *   tile form    up to tile_rows = T entries (default 8 192: 64 KiB of words, two blocks per CU): one block per segment, sorted in LDS
+ *   long form    above T: tiles of T sorted in LDS into a key buffer, then ceil(log2(tiles)) merge passes between two key buffers, every
+ *                pass cut by merge path into output pieces of min(T, 2 048) words, one block each
+ * (a T below 512 lowers the wave form's limit to T / 2).  The kernels write a permuted COPY, which is copied back over the segments.
+ * Memory: the scratch is allocated and freed by the call, per GROUP of whole consecutive segments: 8 bytes per entry of the group
+ * (the copy) + 16 bytes per entry of the group's longest long-form segment (the two key buffers) + 12 bytes per wave- or tile-form
+ * segment (the tables).  Groups are cut so that 24 bytes per entry of a group stay within scratch_bytes (default 1 GiB): a bound on
+ * the copy and the key buffers.  A segment is never split; one that alone exceeds the budget is a group of its own.  Nothing is kept
+ * between calls.  All work is enqueued on h's stream; the call synchronises that stream ONCE PER GROUP and returns when the result is
+ * sorted.
+ * Failure: a failed allocation names the bytes it wanted, frees what the call allocated and leaves the flag unset.  A group's segments
+ * are written back only after all of its kernels were enqueued, so after a failed allocation or launch every segment is either as it
+ * was or fully sorted, and a repeated call finishes the job.
+ * Refused before any launch or allocation, each by name: a NULL h or r; r on another device than h's; a segment of 2^32 entries or
+ * more.  nq == 0, a total of 0 and a result whose segments all hold 0 or 1 entries succeed, launch nothing and set the flag. */
+LMI_API int lmi_range_result_sort(lmi_index *h, lmi_range_result *r);
+LMI_API int lmi_range_result_sorted(const lmi_range_result *r, int *sorted);
+/* Test hook, per thread: tile_rows = T of the sorts on this thread (a power of two in [64, 8 192]) and scratch_bytes = the groups'
+ * budget (at most 2^40); 0 = the default.  Never changes a bit of a result.  Refused: a negative value, a tile_rows that is not a
+ * power of two in [64, 8 192], scratch_bytes above 2^40; nothing is set then. */
+LMI_API int lmi_range_sort_set_geometry(int64_t tile_rows, int64_t scratch_bytes);
+enum {
+    LMI_RANGE_SORT_PLAN_GROUPS = 0,        /* groups with something to sort = stream synchronisations                          */
+    LMI_RANGE_SORT_PLAN_WAVE_SEGMENTS,     /* segments sorted in the wave form                                                 */
+    LMI_RANGE_SORT_PLAN_TILE_SEGMENTS,     /* segments sorted in the tile form                                                 */
+    LMI_RANGE_SORT_PLAN_LONG_SEGMENTS,     /* segments sorted in the long form                                                 */
+    LMI_RANGE_SORT_PLAN_SKIPPED_SEGMENTS,  /* segments of 0 or 1 entries                                                       */
+    LMI_RANGE_SORT_PLAN_TILE_ROWS,         /* T                                                                                */
+    LMI_RANGE_SORT_PLAN_WAVE_ROWS,         /* the wave form's limit: min(256, T / 2)                                           */
+    LMI_RANGE_SORT_PLAN_MERGE_ROWS,        /* words of one merge piece: min(T, 2 048)                                          */
+    LMI_RANGE_SORT_PLAN_MAX_PASSES,        /* the most merge passes any segment took (0: no long form)                         */
+    LMI_RANGE_SORT_PLAN_SCRATCH_BYTES,     /* copy + key buffers of the largest group                                          */
+    LMI_RANGE_SORT_PLAN_RESULTS,           /* entries of the result: lims[nq]                                                  */
+    LMI_RANGE_SORT_PLAN_COUNT
+};
+/* What the last lmi_range_result_sort on this thread did (all zero before the first and after a refused or failed call); writes
+ * min(n, LMI_RANGE_SORT_PLAN_COUNT) words. */
+LMI_API int lmi_debug_range_sort_plan(int64_t *out, int n);
 
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);

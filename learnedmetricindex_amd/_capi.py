@@ -42,6 +42,10 @@ FILTER_PLAN_FIELDS = ("FILTERS", "MASK_BYTES", "SLOTS", "SKIPPED")
 RANGE_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "RESULTS", "CHUNK_BYTES", "WORKSPACE_BYTES")
 #: the LMI_RANGE_JOIN_* words, in their order (lmi_debug_range_join_plan)
 RANGE_JOIN_FIELDS = ("PARTS", "RUNS", "PIECES", "RESULTS", "LARGEST_PART")
+#: the LMI_RANGE_SORT_PLAN_* words, in their order (lmi_debug_range_sort_plan)
+RANGE_SORT_PLAN_FIELDS = ("GROUPS", "WAVE_SEGMENTS", "TILE_SEGMENTS", "LONG_SEGMENTS", "SKIPPED_SEGMENTS", "TILE_ROWS", "WAVE_ROWS",
+                          "MERGE_ROWS", "MAX_PASSES", "SCRATCH_BYTES", "RESULTS")
+RANGE_SORT_MIN_TILE_ROWS, RANGE_SORT_MAX_TILE_ROWS = 64, 8192   # what lmi_range_sort_set_geometry takes for tile_rows (a power of two)
 
 _lib = None
 
@@ -141,6 +145,11 @@ SIGNATURES = {
     "lmi_allgather_join_range": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64, ctypes.POINTER(_vp)]),
     "lmi_range_join_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
     "lmi_debug_range_join_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    # a range result sorted by distance on the device
+    "lmi_range_result_sort": (ctypes.c_int, [_vp, _vp]),
+    "lmi_range_result_sorted": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "lmi_range_sort_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
+    "lmi_debug_range_sort_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_kmeans": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
@@ -830,16 +839,27 @@ class Index:
             raise ValueError(f"{who}: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
         return np.ascontiguousarray(np.broadcast_to(r.astype(np.float32), (nq,)))
 
-    def _range_call(self, name: str, head: tuple, radius, f, fo, max_total: int, tail: tuple) -> "RangeResult":
+    #: the range calls take `sort=True`: every query's results come back nearest first, sorted on the device (`lmi_range_result_sort`)
+    range_sort = True
+
+    def _range_call(self, name: str, head: tuple, radius, f, fo, max_total: int, tail: tuple, sort: bool = False) -> "RangeResult":
         res = _vp()
         _check(getattr(lib(), name)(self._h, *head, _ptr(radius), f, _ptr(fo), int(max_total), ctypes.byref(res), *tail))
-        return RangeResult(res, int(radius.shape[0]))
+        out = RangeResult(res, int(radius.shape[0]))
+        if sort:
+            try:
+                out.sort(self)
+            except Exception:
+                out.close()
+                raise
+        return out
 
-    def scan_range(self, queries_search, bucket_order, radius, filter=None, filter_of=None, max_total: int = 0):
+    def scan_range(self, queries_search, bucket_order, radius, filter=None, filter_of=None, max_total: int = 0, sort: bool = False):
         """(lims i64[nq + 1], dists f32[total], ids u32[total]) of `lmi_scan_range`: per query every object of the buckets
         `bucket_order[q]` lists (-1: none) whose distance is <= `radius` (a number, or one per query), in (rank, row) order; query q owns
         [lims[q], lims[q + 1]).  `filter`, `filter_of`: as in `scan_union`.  `max_total` > 0: the call fails (LmiError) once more results
-        than that have been counted."""
+        than that have been counted.  `sort=True` (all six range calls): every query's results stably sorted by distance on the device
+        (`RangeResult.sort`) before they are read or returned."""
         if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
             raise ValueError("scan_range: bucket_order must be a two-dimensional array")
         nb = int(bucket_order.shape[1])
@@ -847,10 +867,11 @@ class Index:
         q = _np(queries_search, np.float32)
         bo = _np(bucket_order, np.int32)
         f, fo = self._filter_args("scan_range", filter, filter_of, q.shape[0])
-        with self._range_call("lmi_scan_range", (_ptr(q), q.shape[0], _ptr(bo), nb), r, f, fo, max_total, (0,)) as res:
+        with self._range_call("lmi_scan_range", (_ptr(q), q.shape[0], _ptr(bo), nb), r, f, fo, max_total, (0,), sort) as res:
             return (res.lims,) + res.read()
 
-    def search_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0):
+    def search_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0,
+                     sort: bool = False):
         """`lmi_search_range`: (lims, dists, ids, bucket order i32[nq,nb])."""
         r = self._range_args("search_range", nb, radius, max_total, queries_nav=queries_nav, queries_search=queries_search)
         same = queries_search is queries_nav
@@ -859,10 +880,11 @@ class Index:
         nq = qn.shape[0]
         bo = np.empty((nq, nb), dtype=np.int32)
         f, fo = self._filter_args("search_range", filter, filter_of, nq)
-        with self._range_call("lmi_search_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total, (_ptr(bo), 0)) as res:
+        with self._range_call("lmi_search_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total, (_ptr(bo), 0), sort) as res:
             return (res.lims,) + res.read() + (bo,)
 
-    def search_tree_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0):
+    def search_tree_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0,
+                          sort: bool = False):
         """`lmi_search_tree_range`: (lims, dists, ids, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb])."""
         r = self._range_args("search_tree_range", nb, radius, max_total, queries_nav=queries_nav, queries_search=queries_search)
         same = queries_search is queries_nav
@@ -873,30 +895,32 @@ class Index:
         ent = np.empty((nq, nb), dtype=np.int32)
         f, fo = self._filter_args("search_tree_range", filter, filter_of, nq)
         with self._range_call("lmi_search_tree_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total,
-                              (_ptr(slab), _ptr(ent), 0)) as res:
+                              (_ptr(slab), _ptr(ent), 0), sort) as res:
             return (res.lims,) + res.read() + (slab, ent)
 
-    def scan_range_device(self, qs_t, bo_t, nb: int, radius, filter=None, filter_of=None, max_total: int = 0) -> "RangeResult":
+    def scan_range_device(self, qs_t, bo_t, nb: int, radius, filter=None, filter_of=None, max_total: int = 0,
+                          sort: bool = False) -> "RangeResult":
         """Device tensors (float32 queries, int32 order); `radius` and `filter_of` stay on the host.  Returns the `RangeResult`, whose
         arrays stay on the device until `read()` / `read_into()`."""
         r = self._range_args("scan_range_device", nb, radius, max_total, queries_search=qs_t, bucket_order=bo_t)
         nq = int(qs_t.shape[0])
         f, fo = self._filter_args("scan_range_device", filter, filter_of, nq)
-        return self._range_call("lmi_scan_range", (_ptr(qs_t), nq, _ptr(bo_t), int(nb)), r, f, fo, max_total, (1,))
+        return self._range_call("lmi_scan_range", (_ptr(qs_t), nq, _ptr(bo_t), int(nb)), r, f, fo, max_total, (1,), sort)
 
-    def search_range_device(self, qn_t, qs_t, nb: int, radius, bo_t=None, filter=None, filter_of=None, max_total: int = 0) -> "RangeResult":
+    def search_range_device(self, qn_t, qs_t, nb: int, radius, bo_t=None, filter=None, filter_of=None, max_total: int = 0,
+                            sort: bool = False) -> "RangeResult":
         r = self._range_args("search_range_device", nb, radius, max_total, queries_nav=qn_t, queries_search=qs_t)
         nq = int(qn_t.shape[0])
         f, fo = self._filter_args("search_range_device", filter, filter_of, nq)
-        return self._range_call("lmi_search_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total, (_ptr(bo_t), 1))
+        return self._range_call("lmi_search_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total, (_ptr(bo_t), 1), sort)
 
     def search_tree_range_device(self, qn_t, qs_t, nb: int, radius, slab_t=None, ent_t=None, filter=None, filter_of=None,
-                                 max_total: int = 0) -> "RangeResult":
+                                 max_total: int = 0, sort: bool = False) -> "RangeResult":
         r = self._range_args("search_tree_range_device", nb, radius, max_total, queries_nav=qn_t, queries_search=qs_t)
         nq = int(qn_t.shape[0])
         f, fo = self._filter_args("search_tree_range_device", filter, filter_of, nq)
         return self._range_call("lmi_search_tree_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total,
-                                (_ptr(slab_t), _ptr(ent_t), 1))
+                                (_ptr(slab_t), _ptr(ent_t), 1), sort)
 
     # ---- the range search across ranks: the join of the ranks' parts (include/lmi_hip.h, lmi_join_range_parts) ----
     @staticmethod
@@ -1324,6 +1348,23 @@ class RangeResult:
             _check(lib().lmi_range_result_pair_counts(self._r, None, _ptr(c)))
         return c
 
+    def sort(self, index) -> "RangeResult":
+        """Every query's results stably sorted by distance, on the device and in place (`lmi_range_result_sort`): what
+        `np.argsort(dists[a:b], kind="stable")` makes of each segment, -0 == +0 and NaNs last.  `index` is any open `Index` on the
+        result's device (it provides the stream; it needs no built index).  `lims` and `pair_counts()` stay as they are.  Returns self."""
+        if not isinstance(index, Index) or getattr(index, "_h", None) is None:
+            raise ValueError("RangeResult.sort: index must be an open Index")
+        r = self._open()
+        _check(lib().lmi_range_result_sort(index._h, r))
+        return self
+
+    @property
+    def sorted(self) -> bool:
+        """True once `sort` has run on this result (`lmi_range_result_sorted`): its segments are no longer in (rank, row) order."""
+        r, flag = self._open(), ctypes.c_int(0)
+        _check(lib().lmi_range_result_sorted(r, ctypes.byref(flag)))
+        return bool(flag.value)
+
     def read_into(self, d_t, i_t) -> None:
         """Device tensors of at least `total` 4-byte elements each (float32; int32 or uint32-sized) <- the distances and the ids."""
         for name, t in (("d_t", d_t), ("i_t", i_t)):
@@ -1361,6 +1402,27 @@ def range_join_last_plan() -> dict:
     w = (ctypes.c_int64 * len(RANGE_JOIN_FIELDS))()
     _check(lib().lmi_debug_range_join_plan(w, len(RANGE_JOIN_FIELDS)))
     return dict(zip(RANGE_JOIN_FIELDS, (int(v) for v in w)))
+
+
+def range_sort_set_geometry(tile_rows: int = 0, scratch_bytes: int = 0) -> None:
+    """Test hook (`lmi_range_sort_set_geometry`): the tile length (a power of two in [64, 8192]) and the groups' scratch budget in bytes
+    (at most 2^40) of `RangeResult.sort` on this thread; 0 = the default.  Never changes a result."""
+    for name, v in (("tile_rows", tile_rows), ("scratch_bytes", scratch_bytes)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"range_sort_set_geometry: {name} {v!r} must be an integer >= 0 (0: the default)")
+    if tile_rows and (tile_rows & (tile_rows - 1) or not RANGE_SORT_MIN_TILE_ROWS <= tile_rows <= RANGE_SORT_MAX_TILE_ROWS):
+        raise ValueError(f"range_sort_set_geometry: tile_rows {tile_rows} is not a power of two in "
+                         f"[{RANGE_SORT_MIN_TILE_ROWS}, {RANGE_SORT_MAX_TILE_ROWS}]")
+    if scratch_bytes > 1 << 40:
+        raise ValueError(f"range_sort_set_geometry: scratch_bytes {scratch_bytes} above 2^40")
+    _check(lib().lmi_range_sort_set_geometry(int(tile_rows), int(scratch_bytes)))
+
+
+def range_sort_last_plan() -> dict:
+    """What the last `RangeResult.sort` on this thread did (`lmi_debug_range_sort_plan`): `RANGE_SORT_PLAN_FIELDS` (lower case) -> int."""
+    w = (ctypes.c_int64 * len(RANGE_SORT_PLAN_FIELDS))()
+    _check(lib().lmi_debug_range_sort_plan(w, len(RANGE_SORT_PLAN_FIELDS)))
+    return dict(zip((n.lower() for n in RANGE_SORT_PLAN_FIELDS), (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

@@ -25,6 +25,8 @@
 #include "lmi_host_range.h"   // lmi_scan_range / lmi_search_range / lmi_search_tree_range, lmi_range_result_*, lmi_debug_range_plan
 #include "lmi_range_join.h"   // the kernel of the join of range parts
 #include "lmi_host_range_join.h"   // lmi_join_range_parts / lmi_allgather_join_range, lmi_range_join_set_geometry, lmi_debug_range_join_plan
+#include "lmi_range_sort.h"   // the kernels of the sort of a range result by distance
+#include "lmi_host_range_sort.h"   // lmi_range_result_sort / lmi_range_result_sorted, lmi_range_sort_set_geometry, lmi_debug_range_sort_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

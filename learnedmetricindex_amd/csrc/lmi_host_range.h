@@ -19,6 +19,7 @@ struct lmi_range_result {
     std::vector<int> pair_count; // [nq][nb]: the results of every (query, rank); row q sums to lims[q + 1] - lims[q]
     float* dists = nullptr;      // [lims[nq]], device
     uint32_t* ids = nullptr;
+    bool sorted = false;         // lmi_range_result_sort has run: every segment is in distance order, no longer in (rank, row) order
     ~lmi_range_result() {
         if (dists) (void)hipFree(dists);
         if (ids) (void)hipFree(ids);

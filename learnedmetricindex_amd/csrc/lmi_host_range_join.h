@@ -156,6 +156,9 @@ extern "C" LMI_API int lmi_allgather_join_range(lmi_index* h, void* comm, int ra
     const int nb = part ? part->nb : 1;
     CHK(range_join_check(who, h, world, nq, nb, max_total, result));
     if (!part) return fail("%s: NULL part", who);
+    if (part->sorted)
+        return fail("%s: the part is sorted by distance (lmi_range_result_sort): the join needs its (rank, row) order; sort the joined "
+                    "result instead", who);
     if (!comm) return fail("%s: NULL communicator", who);
     if (rank < 0 || rank >= world) return fail("%s: rank %d of %d", who, rank, world);
     if (!rccl()->ok) return fail("%s: RCCL (librccl.so) is not available in this process", who);

@@ -24,6 +24,7 @@ whatever `k` is (Q3); buckets with < 10 objects are padded like faiss does (Q4);
 float32 stored as float64 (Q5/Q6).
 """
 import functools
+import inspect
 import time
 from collections import defaultdict
 from logging import INFO
@@ -542,8 +543,8 @@ class LearnedIndex(Logger):
         """Every object of each query's `n_buckets` most probable buckets whose distance to the query is <= `radius` (a number, or one
         per query): `lmi_search_range` / `lmi_search_tree_range`.  Returns (lims i64[nq + 1], dists f64[total], nns u32[total],
         measured_time): query q owns [lims[q], lims[q + 1]), its results in (rank, row) order -- or, with `sort=True`, stably sorted
-        by distance on the host.  `metric`, `assume_unchanged`, the stops, `filter` and `filter_of` as in `search` (the filter needs no
-        `merge`); `max_total` > 0 makes the call fail (`_capi.LmiError`) once more results than that have been counted -- on a
+        by distance (on the device when the engine has `range_sort`: `lmi_range_result_sort`).  `metric`, `assume_unchanged`, the
+        stops, `filter` and `filter_of` as in `search` (the filter needs no `merge`); `max_total` > 0 makes the call fail (`_capi.LmiError`) once more results than that have been counted -- on a
         multi-level index per piece of `_nav_chunk()` queries, less what the earlier pieces returned.  It needs the default storage:
         ValueError otherwise, before any work."""
         self._check_range(radius, max_total, storage)
@@ -613,8 +614,13 @@ class LearnedIndex(Logger):
         if nq == 0:
             return np.zeros(1, dtype=np.int64), np.empty(0), np.empty(0, dtype=np.uint32), measured_time
         t0 = time.time()
+        call = eng.search_range if len(n_categories) == 1 else eng.search_tree_range
+        # an engine that sorts on the device (`range_sort`) is asked to; any other, and a call that takes no `sort`, is called as ever
+        # and its results are ordered below
+        engine_sorts = bool(sort) and bool(getattr(eng, "range_sort", False)) and "sort" in inspect.signature(call).parameters
+        how = {"sort": True} if engine_sorts else {}
         if len(n_categories) == 1:
-            lims, d32, nns = eng.search_range(qn, qs, n_buckets, r, filter=filter, filter_of=fo, max_total=max_total)[:3]
+            lims, d32, nns = eng.search_range(qn, qs, n_buckets, r, filter=filter, filter_of=fo, max_total=max_total, **how)[:3]
         else:
             step = self._nav_chunk()
             parts, got = [], 0
@@ -623,7 +629,7 @@ class LearnedIndex(Logger):
                 left = max(1, max_total - got) if max_total > 0 else 0
                 part = eng.search_tree_range(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets,
                                              r[lo: lo + step], filter=filter, filter_of=None if fo is None else fo[lo: lo + step],
-                                             max_total=left)[:3]
+                                             max_total=left, **how)[:3]   # segments never span pieces: each is sorted by its call
                 if max_total > 0 and got + int(part[0][-1]) > max_total:
                     raise _capi.LmiError(f"range_search: more than max_total = {max_total} results: {got + int(part[0][-1])} had been "
                                          f"counted when the call stopped")
@@ -633,7 +639,7 @@ class LearnedIndex(Logger):
                                                        zip(parts, np.cumsum([0] + [int(p[0][-1]) for p in parts[:-1]]))]).astype(np.int64)
             d32 = np.concatenate([p[1] for p in parts])
             nns = np.concatenate([p[2] for p in parts])
-        if sort:
+        if sort and not engine_sorts:
             for q in range(nq):
                 a, b = int(lims[q]), int(lims[q + 1])
                 if b - a > 1:

@@ -80,6 +80,7 @@ class Experiment:
     trainer: str = "torch"
     merge: str = "ranks"
     range_radius: Optional[float] = None
+    range_sort: bool = False
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -123,6 +124,8 @@ class Experiment:
         p.add_argument("--range-radius", type=float, default=None,
                        help="also run a range search per budget: every object of the visited buckets within this distance of the "
                             "query; the results per query (mean, max) are reported")
+        p.add_argument("--range-sort", action="store_true",
+                       help="with --range-radius: every query's range results nearest first, sorted on the device")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -144,6 +147,8 @@ class Experiment:
             p.error("--range-radius needs --storage f32 (the range search reads the row-major f32 image)")
         if a["range_radius"] is not None and a["range_radius"] != a["range_radius"]:
             p.error("--range-radius must be a number")
+        if a["range_sort"] and a["range_radius"] is None:
+            p.error("--range-sort needs --range-radius")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -320,7 +325,8 @@ def run(exp: Experiment) -> Dict:
         out[budget] = (dists, knns, clock)
         if exp.range_radius is not None:
             lims, _, _, rclock = index.range_search_resident(nav_q, scan_q, exp.n_categories, exp.range_radius, n_buckets=budget,
-                                                             stop_mass=exp.stop_mass, path_mass=exp.path_mass, stop_rows=exp.stop_rows)
+                                                             sort=exp.range_sort, stop_mass=exp.stop_mass, path_mass=exp.path_mass,
+                                                             stop_rows=exp.stop_rows)
             per_query = np.diff(lims)
             out[f"range_{budget}"] = (float(per_query.mean()) if per_query.size else 0.0, int(per_query.max(initial=0)))
             LOG.info("%d buckets: range search within %g: %.4fs, results per query mean %.2f, max %d", budget, exp.range_radius,

@@ -16,7 +16,8 @@ rounding can make two scores one; by (rank, row), which orders as the single han
 `range_search` (both searchers) answers the range query -- every object of the visited buckets within a radius.
 A rank's `Index.scan_range_device` answers for the buckets it owns; its per-(query, bucket rank) counts and its [dists | ids] block (padded
 to the largest rank's total) are all-gathered, and the join is a gather (`Index.join_range_parts`): a result is in (query, bucket rank, row)
-order, every (query, bucket rank) names one bucket and one rank owns it, so every run comes whole from its owner -- no ordering by score.
+order, every (query, bucket rank) names one bucket and one rank owns it, so every run comes whole from its owner -- no ordering by score.  `sort=True` sorts the JOINED result
+by distance on the device (`RangeResult.sort`); the parts stay in (rank, row) order, which the join needs.
 `ReplicaSearcher` is the other mode SURVEY section 8e names: QUERY-sharded replicas -- every rank holds the whole
 index and answers its 1/world slice of the batch; one all-gather of [dists | ids | bucket order] rows.  A query's
 answer does not depend on the rest of its batch, so the result is again byte-identical for every world size.  It
@@ -431,12 +432,13 @@ class ShardedSearcher:
         return self._exchange(blk, out_d, out_i, bo, nq, kout)
 
     # ---- the range search: every object of the visited buckets within a radius, joined across the ranks ----
-    def _scan_exchange_range(self, qs_t, bo, nb: int, radius, max_total: int):
+    def _scan_exchange_range(self, qs_t, bo, nb: int, radius, max_total: int, sort: bool = False):
         """Behind the routing: this rank's `scan_range_device` over `bo` (its owned buckets answer), then the exchange -- none for a
         world of one without a communicator; `lmi_allgather_join_range` with a `lib_comm`; else one all-gather of the nq*nb counts,
         one of the [2, Tmax] block (dists | ids, padded to the largest part) and `lmi_join_range_parts` on pointers into the gathered
         buffer.  `max_total` limits the joined result on every path, checked on the gathered counts, which every rank sees alike; a
-        rank whose own part already exceeds it says so to the others through the counts, so that no rank waits in a collective."""
+        rank whose own part already exceeds it says so to the others through the counts, so that no rank waits in a collective.
+        `sort`: the JOINED result is sorted by distance (`RangeResult.sort`) -- the parts must stay in (rank, row) order for the join."""
         import torch
 
         from ._capi import LmiError
@@ -444,7 +446,8 @@ class ShardedSearcher:
         nq, dev = qs_t.shape[0], qs_t.device
         radius = _radius_rows(radius, nq)
         if self.world == 1 and self.lib_comm is None:
-            return _read_range(self.index.scan_range_device(qs_t, bo, nb, radius, max_total=max_total), dev) + (bo,)
+            how = {"sort": True} if sort else {}
+            return _read_range(self.index.scan_range_device(qs_t, bo, nb, radius, max_total=max_total, **how), dev) + (bo,)
         if self.lib_comm is not None:
             part = self.index.scan_range_device(qs_t, bo, nb, radius)
             try:
@@ -452,7 +455,7 @@ class ShardedSearcher:
                                      lambda: self.index.allgather_join_range(self.lib_comm, self.rank, self.world, part, max_total), qs_t.is_cuda)
             finally:
                 part.close()
-            return _read_range(joined, dev) + (bo,)
+            return _read_range(joined.sort(self.index) if sort else joined, dev) + (bo,)
         try:
             part = self.index.scan_range_device(qs_t, bo, nb, radius, max_total=max_total)
             counts = torch.from_numpy(part.pair_counts()).to(dev)
@@ -482,20 +485,21 @@ class ShardedSearcher:
         finally:
             if part is not None:
                 part.close()
-        return _read_range(joined, dev) + (bo,)
+        return _read_range(joined.sort(self.index) if sort else joined, dev) + (bo,)
 
-    def range_search_routed(self, qs_t, bo_loc, nb: int, radius, max_total: int = 0):
+    def range_search_routed(self, qs_t, bo_loc, nb: int, radius, max_total: int = 0, sort: bool = False):
         """The rest of a sharded range search behind `route_local`: all-gather of the bucket order (as `search_routed`), scan of the
         owned buckets, exchange and join -> (lims i64 numpy [nq + 1], dists tensor [total], ids tensor [total], bucket order)."""
         nq = qs_t.shape[0]
         radius = _radius_rows(radius, nq)
         bo = self._timed("bucket_order_allgather", lambda: all_gather_rows(bo_loc, nq, self.world, self.group), bo_loc.is_cuda)
-        return self._scan_exchange_range(qs_t, bo.contiguous(), nb, radius, max_total)
+        return self._scan_exchange_range(qs_t, bo.contiguous(), nb, radius, max_total, sort)
 
-    def range_search(self, qn_t, qs_t, nb: int, radius, max_total: int = 0):
+    def range_search(self, qn_t, qs_t, nb: int, radius, max_total: int = 0, sort: bool = False):
         """Per query every object of its nb visited buckets within `radius` (a number, or one per query; the same on every rank), in
         (bucket rank, row) order: what `Index.search_range` returns on one handle that holds the whole index, bit for bit, on every
-        rank.  Routing as `search(merge="union")`.  -> (lims i64 numpy [nq + 1], dists tensor, ids tensor, bucket order)."""
+        rank.  Routing as `search(merge="union")`.  `sort=True`: nearest first -- the joined result is sorted on the device after the
+        join, alike on every rank.  -> (lims i64 numpy [nq + 1], dists tensor, ids tensor, bucket order)."""
         import torch
 
         nq = qn_t.shape[0]
@@ -504,10 +508,10 @@ class ShardedSearcher:
             if self._bo_loc is None or self._bo_loc.shape[1] != nb or self._bo_loc.shape[0] != row_slice(nq, self.rank, self.world)[0]:
                 self._bo_loc = self.new_route_buffer(nq, nb, qn_t.device)
             self.route_local(qn_t, nb, self._bo_loc)
-            return self.range_search_routed(qs_t, self._bo_loc, nb, radius, max_total)
+            return self.range_search_routed(qs_t, self._bo_loc, nb, radius, max_total, sort)
         bo = torch.empty((nq, nb), dtype=torch.int32, device=qn_t.device)
         self.index.mlp_topk_device(qn_t, nb, bo)
-        return self._scan_exchange_range(qs_t, bo, nb, radius, max_total)
+        return self._scan_exchange_range(qs_t, bo, nb, radius, max_total, sort)
 
 
 class ReplicaSearcher:
@@ -567,8 +571,9 @@ class ReplicaSearcher:
         return (g[:, :k].contiguous().view(torch.float32), g[:, k:2 * k].contiguous(), g[:, 2 * k + 1:].contiguous(),
                 g[:, 2 * k].contiguous())
 
-    def range_search(self, qn_t, qs_t, nb: int, radius, max_total: int = 0):
-        """Same signature and return value as `ShardedSearcher.range_search`.  `search_range_device` on the rank's slice with that slice
+    def range_search(self, qn_t, qs_t, nb: int, radius, max_total: int = 0, sort: bool = False):
+        """Same signature and return value as `ShardedSearcher.range_search` (`sort=True`: a rank sorts its slice's result before the
+        exchange -- a query's results all lie in one slice).  `search_range_device` on the rank's slice with that slice
         of `radius`; one all-gather of [count | nb buckets] rows and one of the [2, Tmax] payload (dists | ids, padded to the largest
         slice's total).  The slices are contiguous runs of queries, so the batch's result is their concatenation in rank order: no
         kernel.  `max_total` limits the batch's total, checked on the gathered counts (alike on every rank)."""
@@ -585,7 +590,8 @@ class ReplicaSearcher:
         part = None
         if n > 0:
             try:
-                part = self.index.search_range_device(qn_t[lo:hi], qs_t[lo:hi], nb, radius[lo:hi], bo_t=bo[:n], max_total=max_total)
+                part = self.index.search_range_device(qn_t[lo:hi], qs_t[lo:hi], nb, radius[lo:hi], bo_t=bo[:n], max_total=max_total,
+                                                      **({"sort": True} if sort else {}))
                 cnt[:n] = torch.from_numpy(np.diff(part.lims)).to(dev)
             except LmiError:
                 if max_total == 0 or self.world == 1:

@@ -17,8 +17,15 @@ the whole handle, the same call on the buckets of one rank of emulated worlds of
 b % world == r; the slowest rank's row is printed), and lmi_join_range_parts alone on those ranks' parts, with what a padded all-gather
 of them would move.  One card plays every rank; nothing is said about several GPUs.
 
+The sort leg (--sort; profiles/range_sort.txt) runs INSTEAD of the rows above, on the same index: per-query radii that yield about
+--sort-k results per query, then per repeat lmi_scan_range, lmi_range_result_sort on its result, and the host route to the same
+order (read() and one stable argsort per query), each timed on its own; and one skewed result -- a single query that owns a segment
+of --skew entries among the others' hundred -- so that the long form is timed.  Medians of the repeats; both sorts are compared with
+numpy bit for bit.
+
   python tools/range_bench.py                          # the full shape: about 80 GB of device memory
-  python tools/range_bench.py --n 400000 --nq 2000     # a quick look"""
+  python tools/range_bench.py --n 400000 --nq 2000     # a quick look
+  python tools/range_bench.py --sort                   # the sort leg alone"""
 import argparse
 import os
 import sys
@@ -42,6 +49,9 @@ def main():
     ap.add_argument("--ks", type=int, nargs="+", default=[10, 1000])
     ap.add_argument("--steps", type=int, default=5, help="timed batches per row (after one warm-up batch)")
     ap.add_argument("--seed", type=int, default=2023)
+    ap.add_argument("--sort", action="store_true", help="run the sort leg (lmi_range_result_sort) instead of the other rows")
+    ap.add_argument("--sort-k", type=int, default=100, help="sort leg: results per query (the radius is the query's k-th distance)")
+    ap.add_argument("--skew", type=int, default=1_000_000, help="sort leg: entries of the one long segment of the skewed result")
     a = ap.parse_args()
     import torch
 
@@ -93,8 +103,13 @@ def main():
     sizes = eng.bucket_sizes()
     print(f"# {N} x {d}, {L} buckets (sizes min/median/max {sizes.min()}/{int(np.median(sizes))}/{sizes.max()}), {nq} queries, n_buckets {nb}; "
           f"device tensors; {a.steps} batches per row timed one by one after one warm-up; setup {time.time() - t0:.0f} s", flush=True)
-    print("# call | k or radius | ms per batch min / mean / max | results per query mean / max | note", flush=True)
     bo = torch.empty((nq, nb), dtype=torch.int32, device=dev)
+    if a.sort:
+        sort_leg(a, _capi, eng, Q, bo, dev)
+        eng.set_stream(0)
+        eng.close()
+        return
+    print("# call | k or radius | ms per batch min / mean / max | results per query mean / max | note", flush=True)
     for k in a.ks:
         d_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
         i_t = torch.empty((nq, k), dtype=torch.int32, device=dev)
@@ -211,6 +226,84 @@ def main():
         print(f"# a stalled batch in: {row}: " + " ".join(f"{t:.2f}" for t in ms), flush=True)
     eng.set_stream(0)
     eng.close()
+
+
+def host_sort(lims, dd, ii):
+    """The parent commit's route to the ordered result: one stable argsort per query (li.range_search(sort=True) before the device sort)."""
+    for q in range(len(lims) - 1):
+        lo, hi = int(lims[q]), int(lims[q + 1])
+        if hi - lo > 1:
+            o = np.argsort(dd[lo:hi], kind="stable")
+            dd[lo:hi], ii[lo:hi] = dd[lo:hi][o], ii[lo:hi][o]
+    return dd, ii
+
+
+def sort_leg(a, _capi, eng, Q, bo, dev):
+    import torch
+
+    nq, nb, k, steps = a.nq, a.nb, a.sort_k, max(a.steps, 5)
+    d_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    i_t = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    eng.search_union_device(Q, Q, nb, k, d_t, i_t, None, bo)
+    torch.cuda.synchronize()
+    radius = np.ascontiguousarray(d_t[:, k - 1].cpu().numpy())
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t), out
+
+    def row(name, ms, note):
+        print(f"{name} | {np.median(ms):.3f} | {min(ms):.3f} / {max(ms):.3f} | {note}", flush=True)
+
+    print(f"# sort leg: radius[q] = the k = {k} distance; {steps} repeats after one warm-up, each call timed on its own", flush=True)
+    print("# call | ms median | min / max | note", flush=True)
+    scan_ms, sort_ms, read_ms, loop_ms, ok = [], [], [], [], True
+    for step in range(steps + 1):
+        t_scan, res = clock(lambda: eng.scan_range_device(Q, bo, nb, radius))
+        t_read, (dd, ii) = clock(res.read)
+        t0 = time.perf_counter()
+        hd, hi_ = host_sort(res.lims, dd, ii)
+        t_loop = 1e3 * (time.perf_counter() - t0)
+        t_sort, _ = clock(lambda: res.sort(eng))
+        plan = _capi.range_sort_last_plan()
+        gd, gi = res.read()
+        ok = ok and gd.view(np.uint32).tobytes() == hd.view(np.uint32).tobytes() and gi.tobytes() == hi_.tobytes()
+        n = np.diff(res.lims)
+        res.close()
+        if step:   # the first is the warm-up
+            scan_ms.append(t_scan), sort_ms.append(t_sort), read_ms.append(t_read), loop_ms.append(t_loop)
+    what = (f"{int(n.sum())} results, per query mean {n.mean():.1f} max {n.max()}; groups {plan['groups']} wave {plan['wave_segments']} tile "
+            f"{plan['tile_segments']} long {plan['long_segments']} skipped {plan['skipped_segments']} scratch {plan['scratch_bytes'] >> 10} KiB")
+    row("(a) lmi_range_result_sort", sort_ms, what + f"; {'equal to' if ok else 'DIFFERS from'} the host order")
+    row("(b) lmi_scan_range before it", scan_ms, "device pointers")
+    row("(c) read() + one stable argsort per query", [x + y for x, y in zip(read_ms, loop_ms)],
+        f"read() median {np.median(read_ms):.3f}, the loop median {np.median(loop_ms):.3f}")
+    # the skewed result: no index needed, lmi_join_range_parts makes a result of any host arrays
+    rs = np.random.RandomState(a.seed)
+    lens = np.full(nq, k, np.int32)
+    lens[nq // 2] = a.skew
+    total = int(lens.sum())
+    sd = rs.rand(total).astype(np.float32)
+    si = np.arange(total, dtype=np.uint32)
+    lims = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+    skew_ms, ok = [], True
+    for step in range(steps + 1):
+        res = eng.join_range_parts(lens.reshape(1, nq, 1), [sd], [si])
+        t_sort, _ = clock(lambda: res.sort(eng))
+        plan = _capi.range_sort_last_plan()
+        if step == 0:
+            gd, gi = res.read()
+            hd, hi_ = host_sort(lims, sd.copy(), si.copy())
+            ok = gd.view(np.uint32).tobytes() == hd.view(np.uint32).tobytes() and gi.tobytes() == hi_.tobytes()
+        else:
+            skew_ms.append(t_sort)
+        res.close()
+    row(f"(d) lmi_range_result_sort, one segment of {a.skew}", skew_ms,
+        f"{total} results; wave {plan['wave_segments']} long {plan['long_segments']} passes {plan['max_passes']} scratch "
+        f"{plan['scratch_bytes'] >> 20} MiB; {'equal to' if ok else 'DIFFERS from'} the host order")
 
 
 if __name__ == "__main__":
