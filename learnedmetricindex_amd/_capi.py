@@ -751,6 +751,38 @@ class Index:
         else:
             _check(getattr(lib(), name + "_filtered")(self._h, *args, f, _ptr(fo)))
 
+    #: the three forms of a union or range call: what the library's name begins with, what its two arrays are called, its order outputs
+    _FORMS = {"scan": ("lmi_scan", ("queries_search", "bucket_order"), 0),
+              "search": ("lmi_search", ("queries_nav", "queries_search"), 1),
+              "search_tree": ("lmi_search_tree", ("queries_nav", "queries_search"), 2)}
+
+    @staticmethod
+    def _form_inputs(form: str, first, second, nb: int, orders):
+        """(head, orders, nq, keep) of a union or range call whose argument checks have passed.  `first`, `second`: the form's two arrays
+        (`_FORMS`).  `orders` None: host arrays -- float32 queries (one array where the caller passed one twice), an int32 bucket order, and
+        the form's order outputs i32[nq,nb] are made here; otherwise device tensors, taken as they are, with the caller's order outputs.
+        `head`: the library's arguments up to n_buckets; `keep`: the arrays `head` points into."""
+        if orders is None:
+            same = second is first
+            first = _np(first, np.float32)
+            second = _np(second, np.int32) if form == "scan" else first if same else _np(second, np.float32)
+            orders = tuple(np.empty((first.shape[0], nb), dtype=np.int32) for _ in range(Index._FORMS[form][2]))
+        nq = int(first.shape[0])
+        head = (_ptr(first), nq, _ptr(second), int(nb)) if form == "scan" else (_ptr(first), _ptr(second), nq, int(nb))
+        return head, orders, nq, (first, second)
+
+    def _union(self, form: str, first, second, nb: int, k: int, filter, filter_of, outs=None, orders=None):
+        """A union call of one form: on host arrays (`outs` None) the outputs are made here and returned with the form's orders."""
+        host = outs is None
+        who = f"{form}_union" if host else f"{form}_union_device"
+        self._union_args(who, k, nb, **dict(zip(self._FORMS[form][1], (first, second))))
+        head, orders, nq, _keep = self._form_inputs(form, first, second, nb, None if host else orders)   # (_keep: alive until the call returns)
+        if host:
+            outs = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.uint32), np.empty((nq,), dtype=np.int32))
+        f, fo = self._filter_args(who, filter, filter_of, nq)
+        self._union_call(self._FORMS[form][0] + "_union", head + (int(k),) + tuple(_ptr(x) for x in outs + orders) + (0 if host else 1,), f, fo)
+        return outs + orders if host else None
+
     def scan_union(self, queries_search, bucket_order, k: int = 10, filter=None, filter_of=None):
         """(dists f32[nq,k], ids u32[nq,k], counts i32[nq]) of `lmi_scan_union`: per query the k best objects of the union of the
         buckets `bucket_order[q]` lists (-1: none); behind `counts[q]` real results dist = +inf, id = 0.
@@ -759,70 +791,27 @@ class Index:
         keywords on `search_union`, `search_tree_union` and the `_device` forms, where `filter_of` stays a host array."""
         if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
             raise ValueError("scan_union: bucket_order must be a two-dimensional array")
-        nb = int(bucket_order.shape[1])
-        self._union_args("scan_union", k, nb, queries_search=queries_search, bucket_order=bucket_order)
-        q = _np(queries_search, np.float32)
-        bo = _np(bucket_order, np.int32)
-        nq = q.shape[0]
-        d = np.empty((nq, k), dtype=np.float32)
-        i = np.empty((nq, k), dtype=np.uint32)
-        c = np.empty((nq,), dtype=np.int32)
-        f, fo = self._filter_args("scan_union", filter, filter_of, nq)
-        self._union_call("lmi_scan_union", (_ptr(q), nq, _ptr(bo), nb, int(k), _ptr(d), _ptr(i), _ptr(c), 0), f, fo)
-        return d, i, c
+        return self._union("scan", queries_search, bucket_order, int(bucket_order.shape[1]), k, filter, filter_of)
 
     def search_union(self, queries_nav, queries_search, nb: int, k: int = 10, filter=None, filter_of=None):
         """`lmi_search_union`: (dists, ids, counts, bucket order i32[nq,nb]).  `filter`, `filter_of`: as in `scan_union`."""
-        self._union_args("search_union", k, nb, queries_nav=queries_nav, queries_search=queries_search)
-        same = queries_search is queries_nav
-        qn = _np(queries_nav, np.float32)
-        qs = qn if same else _np(queries_search, np.float32)
-        nq = qn.shape[0]
-        d = np.empty((nq, k), dtype=np.float32)
-        i = np.empty((nq, k), dtype=np.uint32)
-        c = np.empty((nq,), dtype=np.int32)
-        bo = np.empty((nq, nb), dtype=np.int32)
-        f, fo = self._filter_args("search_union", filter, filter_of, nq)
-        self._union_call("lmi_search_union", (_ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(bo), 0), f, fo)
-        return d, i, c, bo
+        return self._union("search", queries_nav, queries_search, nb, k, filter, filter_of)
 
     def search_tree_union(self, queries_nav, queries_search, nb: int, k: int = 10, filter=None, filter_of=None):
         """`lmi_search_tree_union`: (dists, ids, counts, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb]).  `filter`,
         `filter_of`: as in `scan_union`."""
-        self._union_args("search_tree_union", k, nb, queries_nav=queries_nav, queries_search=queries_search)
-        same = queries_search is queries_nav
-        qn = _np(queries_nav, np.float32)
-        qs = qn if same else _np(queries_search, np.float32)
-        nq = qn.shape[0]
-        d = np.empty((nq, k), dtype=np.float32)
-        i = np.empty((nq, k), dtype=np.uint32)
-        c = np.empty((nq,), dtype=np.int32)
-        slab = np.empty((nq, nb), dtype=np.int32)
-        ent = np.empty((nq, nb), dtype=np.int32)
-        f, fo = self._filter_args("search_tree_union", filter, filter_of, nq)
-        self._union_call("lmi_search_tree_union", (_ptr(qn), _ptr(qs), nq, int(nb), int(k), _ptr(d), _ptr(i), _ptr(c), _ptr(slab), _ptr(ent), 0), f, fo)
-        return d, i, c, slab, ent
+        return self._union("search_tree", queries_nav, queries_search, nb, k, filter, filter_of)
 
     def scan_union_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, counts_t=None, filter=None, filter_of=None) -> None:
         """Device tensors (float32 queries, int32 order, float32 / uint32-sized / int32 outputs); returns when they have landed."""
-        self._union_args("scan_union_device", k, nb, queries_search=qs_t, bucket_order=bo_t)
-        nq = int(qs_t.shape[0])
-        f, fo = self._filter_args("scan_union_device", filter, filter_of, nq)
-        self._union_call("lmi_scan_union", (_ptr(qs_t), nq, _ptr(bo_t), int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), 1), f, fo)
+        self._union("scan", qs_t, bo_t, nb, k, filter, filter_of, (d_t, i_t, counts_t), ())
 
     def search_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, bo_t=None, filter=None, filter_of=None) -> None:
-        self._union_args("search_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
-        nq = int(qn_t.shape[0])
-        f, fo = self._filter_args("search_union_device", filter, filter_of, nq)
-        self._union_call("lmi_search_union", (_ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t), _ptr(bo_t), 1), f, fo)
+        self._union("search", qn_t, qs_t, nb, k, filter, filter_of, (d_t, i_t, counts_t), (bo_t,))
 
     def search_tree_union_device(self, qn_t, qs_t, nb: int, k: int, d_t, i_t, counts_t=None, slab_t=None, ent_t=None, filter=None,
                                  filter_of=None) -> None:
-        self._union_args("search_tree_union_device", k, nb, queries_nav=qn_t, queries_search=qs_t)
-        nq = int(qn_t.shape[0])
-        f, fo = self._filter_args("search_tree_union_device", filter, filter_of, nq)
-        self._union_call("lmi_search_tree_union", (_ptr(qn_t), _ptr(qs_t), nq, int(nb), int(k), _ptr(d_t), _ptr(i_t), _ptr(counts_t),
-                                                   _ptr(slab_t), _ptr(ent_t), 1), f, fo)
+        self._union("search_tree", qn_t, qs_t, nb, k, filter, filter_of, (d_t, i_t, counts_t), (slab_t, ent_t))
 
     # ---- the range search: every object of the visited buckets within a radius, in ordinal order (include/lmi_hip.h, lmi_scan_range) ----
     @staticmethod
@@ -854,6 +843,20 @@ class Index:
                 raise
         return out
 
+    def _range(self, form: str, first, second, nb: int, radius, filter, filter_of, max_total, sort, orders=None):
+        """A range call of one form: on host arrays (`orders` None) the result is read, closed and returned with the form's orders; on
+        device tensors the `RangeResult` is returned."""
+        host = orders is None
+        who = f"{form}_range" if host else f"{form}_range_device"
+        r = self._range_args(who, nb, radius, max_total, **dict(zip(self._FORMS[form][1], (first, second))))
+        head, orders, nq, _keep = self._form_inputs(form, first, second, nb, orders)
+        f, fo = self._filter_args(who, filter, filter_of, nq)
+        res = self._range_call(self._FORMS[form][0] + "_range", head, r, f, fo, max_total, tuple(_ptr(x) for x in orders) + (0 if host else 1,), sort)
+        if not host:
+            return res
+        with res:
+            return (res.lims,) + res.read() + orders
+
     def scan_range(self, queries_search, bucket_order, radius, filter=None, filter_of=None, max_total: int = 0, sort: bool = False):
         """(lims i64[nq + 1], dists f32[total], ids u32[total]) of `lmi_scan_range`: per query every object of the buckets
         `bucket_order[q]` lists (-1: none) whose distance is <= `radius` (a number, or one per query), in (rank, row) order; query q owns
@@ -862,65 +865,31 @@ class Index:
         (`RangeResult.sort`) before they are read or returned."""
         if not hasattr(bucket_order, "shape") or len(bucket_order.shape) != 2:
             raise ValueError("scan_range: bucket_order must be a two-dimensional array")
-        nb = int(bucket_order.shape[1])
-        r = self._range_args("scan_range", nb, radius, max_total, queries_search=queries_search, bucket_order=bucket_order)
-        q = _np(queries_search, np.float32)
-        bo = _np(bucket_order, np.int32)
-        f, fo = self._filter_args("scan_range", filter, filter_of, q.shape[0])
-        with self._range_call("lmi_scan_range", (_ptr(q), q.shape[0], _ptr(bo), nb), r, f, fo, max_total, (0,), sort) as res:
-            return (res.lims,) + res.read()
+        return self._range("scan", queries_search, bucket_order, int(bucket_order.shape[1]), radius, filter, filter_of, max_total, sort)
 
     def search_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0,
                      sort: bool = False):
         """`lmi_search_range`: (lims, dists, ids, bucket order i32[nq,nb])."""
-        r = self._range_args("search_range", nb, radius, max_total, queries_nav=queries_nav, queries_search=queries_search)
-        same = queries_search is queries_nav
-        qn = _np(queries_nav, np.float32)
-        qs = qn if same else _np(queries_search, np.float32)
-        nq = qn.shape[0]
-        bo = np.empty((nq, nb), dtype=np.int32)
-        f, fo = self._filter_args("search_range", filter, filter_of, nq)
-        with self._range_call("lmi_search_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total, (_ptr(bo), 0), sort) as res:
-            return (res.lims,) + res.read() + (bo,)
+        return self._range("search", queries_nav, queries_search, nb, radius, filter, filter_of, max_total, sort)
 
     def search_tree_range(self, queries_nav, queries_search, nb: int, radius, filter=None, filter_of=None, max_total: int = 0,
                           sort: bool = False):
         """`lmi_search_tree_range`: (lims, dists, ids, slab bucket ids i32[nq,nb], flat child indices i32[nq,nb])."""
-        r = self._range_args("search_tree_range", nb, radius, max_total, queries_nav=queries_nav, queries_search=queries_search)
-        same = queries_search is queries_nav
-        qn = _np(queries_nav, np.float32)
-        qs = qn if same else _np(queries_search, np.float32)
-        nq = qn.shape[0]
-        slab = np.empty((nq, nb), dtype=np.int32)
-        ent = np.empty((nq, nb), dtype=np.int32)
-        f, fo = self._filter_args("search_tree_range", filter, filter_of, nq)
-        with self._range_call("lmi_search_tree_range", (_ptr(qn), _ptr(qs), nq, int(nb)), r, f, fo, max_total,
-                              (_ptr(slab), _ptr(ent), 0), sort) as res:
-            return (res.lims,) + res.read() + (slab, ent)
+        return self._range("search_tree", queries_nav, queries_search, nb, radius, filter, filter_of, max_total, sort)
 
     def scan_range_device(self, qs_t, bo_t, nb: int, radius, filter=None, filter_of=None, max_total: int = 0,
                           sort: bool = False) -> "RangeResult":
         """Device tensors (float32 queries, int32 order); `radius` and `filter_of` stay on the host.  Returns the `RangeResult`, whose
         arrays stay on the device until `read()` / `read_into()`."""
-        r = self._range_args("scan_range_device", nb, radius, max_total, queries_search=qs_t, bucket_order=bo_t)
-        nq = int(qs_t.shape[0])
-        f, fo = self._filter_args("scan_range_device", filter, filter_of, nq)
-        return self._range_call("lmi_scan_range", (_ptr(qs_t), nq, _ptr(bo_t), int(nb)), r, f, fo, max_total, (1,), sort)
+        return self._range("scan", qs_t, bo_t, nb, radius, filter, filter_of, max_total, sort, ())
 
     def search_range_device(self, qn_t, qs_t, nb: int, radius, bo_t=None, filter=None, filter_of=None, max_total: int = 0,
                             sort: bool = False) -> "RangeResult":
-        r = self._range_args("search_range_device", nb, radius, max_total, queries_nav=qn_t, queries_search=qs_t)
-        nq = int(qn_t.shape[0])
-        f, fo = self._filter_args("search_range_device", filter, filter_of, nq)
-        return self._range_call("lmi_search_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total, (_ptr(bo_t), 1), sort)
+        return self._range("search", qn_t, qs_t, nb, radius, filter, filter_of, max_total, sort, (bo_t,))
 
     def search_tree_range_device(self, qn_t, qs_t, nb: int, radius, slab_t=None, ent_t=None, filter=None, filter_of=None,
                                  max_total: int = 0, sort: bool = False) -> "RangeResult":
-        r = self._range_args("search_tree_range_device", nb, radius, max_total, queries_nav=qn_t, queries_search=qs_t)
-        nq = int(qn_t.shape[0])
-        f, fo = self._filter_args("search_tree_range_device", filter, filter_of, nq)
-        return self._range_call("lmi_search_tree_range", (_ptr(qn_t), _ptr(qs_t), nq, int(nb)), r, f, fo, max_total,
-                                (_ptr(slab_t), _ptr(ent_t), 1), sort)
+        return self._range("search_tree", qn_t, qs_t, nb, radius, filter, filter_of, max_total, sort, (slab_t, ent_t))
 
     # ---- the range search across ranks: the join of the ranks' parts (include/lmi_hip.h, lmi_join_range_parts) ----
     @staticmethod

@@ -20,7 +20,8 @@
 #include "lmi_host_knn.h"     // lmi_knn, lmi_knn_set_geometry, lmi_debug_knn_plan
 #include "lmi_union.h"        // the kernels of the union scan
 #include "lmi_filter.h"       // the kernels of the filter sets and the masked select of the filtered union scan
-#include "lmi_host_union.h"   // lmi_scan_union / lmi_scan_union_part / lmi_search_union / lmi_search_tree_union, geometry and plan hooks; the *_filtered forms (lmi_host_filter.h)
+#include "lmi_host_candidates.h"   // the candidate stage of the union scan and the range search: plan, tables, buffers, pack and score
+#include "lmi_host_union.h"   // lmi_scan_union / lmi_scan_union_part / lmi_search_union / lmi_search_tree_union, geometry and plan hooks; the *_filtered forms (lmi_host_filter.h); the front of the three forms
 #include "lmi_range.h"        // the kernels of the range search
 #include "lmi_host_range.h"   // lmi_scan_range / lmi_search_range / lmi_search_tree_range, lmi_range_result_*, lmi_debug_range_plan
 #include "lmi_range_join.h"   // the kernel of the join of range parts

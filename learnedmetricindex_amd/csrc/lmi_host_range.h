@@ -1,9 +1,10 @@
 // lmi_host_range.h -- the range search: every candidate of the union scan within a radius, in ordinal order (kernels: lmi_range.h;
-// the offsets, lims and gathers: lmi_range_plan.h; include/lmi_hip.h states the contract).  The schedule and the tables are the union
-// scan's (lmi_union_plan.h, make_plan / build_tables, read and never changed); no lists are kept.  Per wave: pack, score, count; the
-// wave's counts come back to the host (ONE synchronisation per wave); a chunk of exactly the wave's results is allocated, the slots'
-// offsets go up, emit.  Behind the last group the final arrays are allocated once at lims[nq] and every wave's runs are gathered (one
-// descriptor table for all of them, one synchronisation).
+// the offsets, lims and gathers: lmi_range_plan.h; include/lmi_hip.h states the contract).  The plan, the tables and the scores are the
+// candidate stage's (lmi_host_candidates.h), opened with the smallest list since no lists are kept; the front of the three forms is
+// the union scan's (UnionFront, lmi_host_union.h).  Per wave: the stage's scores, count; the wave's counts come back to the host (ONE
+// synchronisation per wave); a chunk of exactly the wave's results is allocated, the slots' offsets go up, emit.  Behind the last
+// group the final arrays are allocated once at lims[nq] and every wave's runs are gathered (one descriptor table for all of them, one
+// synchronisation).
 // lmi_scan_range, lmi_search_range, lmi_search_tree_range, lmi_range_result_*, lmi_debug_range_plan.  A result keeps the call's nb and
 // the counts of every (query, rank): what the join of the ranks' parts (lmi_host_range_join.h) is planned from.
 #pragma once
@@ -60,64 +61,22 @@ int range_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     namespace up = lmi_union_plan;
     namespace rp = lmi_range_plan;
     hipStream_t st = h->stream;
-    const int L = h->L;
-    ScanCall C;
-    C.P.nq = nq;
-    CHK(scan_augment_l2(h, C, d_qs));
-    std::vector<int> order((size_t)nq * nb), nrows(L), rbs(L + 1);
-    HIPCHK(hipMemcpyAsync(order.data(), d_order, order.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(nrows.data(), h->d_nb_rows.p, (size_t)L * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(rbs.data(), h->d_rb_start.p, (size_t)(L + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const up::Plan p = up::make_plan(nq, nb, rp::PLAN_K, h->d, true, (int64_t)free_b, g_union_forced);
-    const int KG = p.kg;
-    const bool vec = h->d % 4 == 0;
-
-    const up::Layout layout{L, nrows.data(), rbs.data()};
-    const up::FilterView fview{f ? f->counts.data() : nullptr, filter_of, f ? f->n_rb_total : 0};
-    std::vector<up::Tables> groups;
-    groups.reserve((size_t)p.query_groups);
-    int64_t max_slab = 0, max_tiles = 0, max_group_tiles = 0, max_items = 0, max_slots = 0;
-    for (int64_t g = 0; g < p.query_groups; ++g) {
-        groups.push_back(up::build_tables(p, g, order.data(), layout, f ? &fview : nullptr));
-        const up::Tables& G = groups.back();
-        for (const up::Wave& W : G.waves) {
-            max_slab = std::max(max_slab, W.slab_floats * 4);
-            max_tiles = std::max(max_tiles, W.tiles);
-        }
-        max_group_tiles = std::max<int64_t>(max_group_tiles, (int64_t)G.tile_cnt.size());
-        max_items = std::max<int64_t>(max_items, (int64_t)G.items.size());
-        max_slots = std::max<int64_t>(max_slots, (int64_t)G.slots.size());
-    }
-    CallScratch mem(who), chunks(who);
-    float *d_S = nullptr, *d_radius = nullptr;
-    float4* d_qf = nullptr;
-    UnionItem* d_items = nullptr;
-    UnionSlot* d_slots = nullptr;
-    int *d_rowq = nullptr, *d_tile_cnt = nullptr, *d_slot_q = nullptr, *d_counts = nullptr;
-    long long *d_tile_off = nullptr, *d_slot_mask = nullptr, *d_slot_pos0 = nullptr, *d_slot_off = nullptr;
-    CHK(mem.alloc(&d_S, (size_t)max_slab, "score slab"));
-    CHK(mem.alloc(&d_qf, (size_t)max_tiles * KG * 1024, "query fragments"));
-    CHK(mem.alloc(&d_items, (size_t)max_items * sizeof(UnionItem), "items"));
-    CHK(mem.alloc(&d_slots, (size_t)max_slots * sizeof(UnionSlot), "slots"));
-    CHK(mem.alloc(&d_rowq, (size_t)max_group_tiles * 32 * 4, "fragment rows"));
-    CHK(mem.alloc(&d_tile_cnt, (size_t)max_group_tiles * 4, "tile counts"));
-    CHK(mem.alloc(&d_tile_off, (size_t)max_group_tiles * 8, "tile offsets"));
-    CHK(mem.alloc(&d_slot_q, (size_t)max_slots * 4, "slot queries"));
-    CHK(mem.alloc(&d_slot_pos0, (size_t)max_slots * 8, "slot positions"));
-    CHK(mem.alloc(&d_slot_off, (size_t)max_slots * 8, "slot offsets"));
-    CHK(mem.alloc(&d_counts, (size_t)max_slots * 4, "slot counts"));
-    CHK(mem.alloc(&d_radius, (size_t)nq * 4, "radius"));
-    if (f) CHK(mem.alloc(&d_slot_mask, (size_t)max_slots * 8, "slot masks"));
+    CandidateStage S(h, who);
+    CHK(S.open(d_qs, nq, d_order, nb, rp::PLAN_K, true, f, filter_of));
+    const up::Plan& p = S.p;
+    const std::vector<up::Tables>& groups = S.groups;
+    const int64_t max_slots = S.ext.group_slots;
+    CallScratch chunks(who);
+    float* d_radius = nullptr;
+    int *d_slot_q = nullptr, *d_counts = nullptr;
+    long long *d_slot_pos0 = nullptr, *d_slot_off = nullptr;
+    CHK(S.mem.alloc(&d_slot_q, (size_t)max_slots * 4, "slot queries"));
+    CHK(S.mem.alloc(&d_slot_pos0, (size_t)max_slots * 8, "slot positions"));
+    CHK(S.mem.alloc(&d_slot_off, (size_t)max_slots * 8, "slot offsets"));
+    CHK(S.mem.alloc(&d_counts, (size_t)max_slots * 4, "slot counts"));
+    CHK(S.mem.alloc(&d_radius, (size_t)nq * 4, "radius"));
     HIPCHK(hipMemcpyAsync(d_radius, radius, (size_t)nq * 4, hipMemcpyHostToDevice, st));
 
-    auto up_async = [&](void* dst, const void* src, size_t bytes) -> int {
-        if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
-        return 0;
-    };
     // what a wave leaves behind for the gather: its chunk and, per slot, the count and the offset inside the chunk
     struct WaveOut {
         float* D = nullptr;
@@ -132,28 +91,17 @@ int range_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     const unsigned* d_mask = f ? f->mask.as<unsigned>() : nullptr;
     for (size_t g = 0; g < groups.size(); ++g) {
         const up::Tables& G = groups[g];
-        const rp::SlotArrays A = rp::slot_arrays(p, G);
-        CHK(up_async(d_items, G.items.data(), G.items.size() * sizeof(UnionItem)));
-        CHK(up_async(d_slots, G.slots.data(), G.slots.size() * sizeof(UnionSlot)));
-        CHK(up_async(d_rowq, G.rowq.data(), G.rowq.size() * 4));
-        CHK(up_async(d_tile_cnt, G.tile_cnt.data(), G.tile_cnt.size() * 4));
-        CHK(up_async(d_tile_off, G.tile_off.data(), G.tile_off.size() * 8));
-        CHK(up_async(d_slot_q, A.q.data(), A.q.size() * 4));
-        CHK(up_async(d_slot_pos0, A.pos0.data(), A.pos0.size() * 8));
-        if (f) CHK(up_async(d_slot_mask, G.slot_mask.data(), G.slot_mask.size() * 8));
+        CHK(S.upload(G));
+        CHK(S.up(d_slot_q, G.scan_q.data(), G.scan_q.size() * 4));
+        CHK(S.up(d_slot_pos0, G.scan_pos0.data(), G.scan_pos0.size() * 8));
         outs[g].resize(G.waves.size());
         for (size_t w = 0; w < G.waves.size(); ++w) {
             const up::Wave& W = G.waves[w];
             WaveOut& O = outs[g][w];
             if (W.slots == 0) continue;
-            union_pack_kernel<<<cdiv(W.tiles * 32 * KG, 256), 256, 0, st>>>(C.q, d_rowq + W.tile0 * 32, h->d, (int)W.tiles, KG, d_qf);
-            HIPCHK(hipGetLastError());
-            if (vec) CHK(union_score_launch<true>(W.ct, (int)W.items, st, d_items + W.item0, h->rowmajor.as<float>(), h->dp, h->d, d_qf, KG,
-                                                  d_tile_off + W.tile0, d_tile_cnt + W.tile0, d_S));
-            else CHK(union_score_launch<false>(W.ct, (int)W.items, st, d_items + W.item0, h->rowmajor.as<float>(), h->dp, h->d, d_qf, KG,
-                                               d_tile_off + W.tile0, d_tile_cnt + W.tile0, d_S));
-            const long long* smask = f ? d_slot_mask + W.slot0 : nullptr;
-            range_count_kernel<<<(int)W.slots, 64, 0, st>>>(d_S, d_slots + W.slot0, d_slot_q + W.slot0, smask, d_mask, C.qn2, d_radius,
+            CHK(S.score(W));
+            const long long* smask = f ? S.d_slot_mask + W.slot0 : nullptr;
+            range_count_kernel<<<(int)W.slots, 64, 0, st>>>(S.d_S, S.d_slots + W.slot0, d_slot_q + W.slot0, smask, d_mask, S.C.qn2, d_radius,
                                                            d_counts + W.slot0);
             HIPCHK(hipGetLastError());
             O.counts.assign((size_t)W.slots, 0);
@@ -171,14 +119,13 @@ int range_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
             CHK(chunks.alloc(&O.D, (size_t)O.total * 4, "result chunk (dists)"));
             CHK(chunks.alloc(&O.I, (size_t)O.total * 4, "result chunk (ids)"));
             chunk_bytes += O.total * 8;
-            CHK(up_async(d_slot_off + W.slot0, O.off.data(), (size_t)W.slots * 8));
-            range_emit_kernel<<<(int)W.slots, 64, 0, st>>>(d_S, d_slots + W.slot0, d_slot_q + W.slot0, smask, d_mask, C.qn2, d_radius,
+            CHK(S.up(d_slot_off + W.slot0, O.off.data(), (size_t)W.slots * 8));
+            range_emit_kernel<<<(int)W.slots, 64, 0, st>>>(S.d_S, S.d_slots + W.slot0, d_slot_q + W.slot0, smask, d_mask, S.C.qn2, d_radius,
                                                           d_counts + W.slot0, d_slot_off + W.slot0, d_slot_pos0 + W.slot0,
                                                           h->ids_slab.as<unsigned>(), O.D, O.I);
             HIPCHK(hipGetLastError());
         }
-        // the next group rewrites the tables; the host tables above live until the call returns
-        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipStreamSynchronize(st));   // the next group rewrites the tables
     }
 
     const std::vector<int64_t> first = rp::run_starts(tot);
@@ -207,12 +154,12 @@ int range_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
             }
         long long *d_src = nullptr, *d_dst = nullptr;
         int* d_n = nullptr;
-        CHK(mem.alloc(&d_src, all.src.size() * 8, "run sources"));
-        CHK(mem.alloc(&d_dst, all.dst.size() * 8, "run targets"));
-        CHK(mem.alloc(&d_n, all.n.size() * 4, "run lengths"));
-        CHK(up_async(d_src, all.src.data(), all.src.size() * 8));
-        CHK(up_async(d_dst, all.dst.data(), all.dst.size() * 8));
-        CHK(up_async(d_n, all.n.data(), all.n.size() * 4));
+        CHK(S.mem.alloc(&d_src, all.src.size() * 8, "run sources"));
+        CHK(S.mem.alloc(&d_dst, all.dst.size() * 8, "run targets"));
+        CHK(S.mem.alloc(&d_n, all.n.size() * 4, "run lengths"));
+        CHK(S.up(d_src, all.src.data(), all.src.size() * 8));
+        CHK(S.up(d_dst, all.dst.data(), all.dst.size() * 8));
+        CHK(S.up(d_n, all.n.data(), all.n.size() * 4));
         for (size_t g = 0; g < groups.size(); ++g)
             for (size_t w = 0; w < groups[g].waves.size(); ++w) {
                 const WaveOut& O = outs[g][w];
@@ -232,10 +179,10 @@ int range_core(lmi_index* h, const char* who, const float* d_qs, int nq, const i
     g_range_last[LMI_RANGE_PLAN_GROUPS] = p.query_groups;
     g_range_last[LMI_RANGE_PLAN_QUERY_ROWS] = p.query_rows;
     g_range_last[LMI_RANGE_PLAN_WAVES] = (int64_t)groups.back().waves.size();
-    g_range_last[LMI_RANGE_PLAN_SLAB_BYTES] = max_slab;
+    g_range_last[LMI_RANGE_PLAN_SLAB_BYTES] = S.ext.slab_bytes;
     g_range_last[LMI_RANGE_PLAN_RESULTS] = total;
     g_range_last[LMI_RANGE_PLAN_CHUNK_BYTES] = chunk_bytes;
-    g_range_last[LMI_RANGE_PLAN_WORKSPACE_BYTES] = mem.total;
+    g_range_last[LMI_RANGE_PLAN_WORKSPACE_BYTES] = S.mem.total;
     *out = r;
     return 0;
 }
@@ -248,70 +195,39 @@ extern "C" LMI_API int lmi_debug_range_plan(int64_t* out, int n) {
     return 0;
 }
 
+// every range entry point: a, b as UnionFront states them.  A copy back that fails takes the result with it.
+static int range_call(UnionForm form, const char* who, lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb,
+                      const float* radius, const lmi_filter* f, const int32_t* filter_of, int64_t max_total, lmi_range_result** result,
+                      int32_t* a, int32_t* b, int on_device) {
+    CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
+    UnionFront F{form, a, b};
+    CHK(F.open(h, who, queries_nav, queries_search, nq, nb, on_device, true, nullptr));
+    if (nq == 0) return range_empty(h, nq, nb, result);
+    CHK(range_core(h, who, F.d_qs, nq, F.d_order, nb, radius, f, filter_of, max_total, result));
+    if (F.close(h, on_device) != 0) {
+        delete *result;
+        *result = nullptr;
+        return -1;
+    }
+    return 0;
+}
 extern "C" LMI_API int lmi_scan_range(lmi_index* h, const float* queries_search, int nq, const int32_t* bucket_order, int nb, const float* radius,
                                       const lmi_filter* f, const int32_t* filter_of, int64_t max_total, lmi_range_result** result,
                                       int on_device) {
-    const char* who = "lmi_scan_range";
-    CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
-    if (nq == 0) return range_empty(h, nq, nb, result);
-    if (!queries_search || !bucket_order) return fail("%s: queries_search and bucket_order must not be NULL", who);
-    CHK(set_dev(h));
-    const void* d_qs = nullptr;
-    const void* d_order = nullptr;
-    CHK(input_ptr(h, queries_search, (size_t)nq * h->d_user * 4, on_device, h->q_srch, &d_qs));
-    CHK(input_ptr(h, bucket_order, (size_t)nq * nb * 4, on_device, h->order, &d_order));
-    begin_call(h);
-    return range_core(h, who, static_cast<const float*>(d_qs), nq, static_cast<const int*>(d_order), nb, radius, f, filter_of, max_total, result);
+    return range_call(ORDER_GIVEN, "lmi_scan_range", h, nullptr, queries_search, nq, nb, radius, f, filter_of, max_total, result,
+                      const_cast<int32_t*>(bucket_order), nullptr, on_device);
 }
-
 extern "C" LMI_API int lmi_search_range(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb, const float* radius,
                                         const lmi_filter* f, const int32_t* filter_of, int64_t max_total, lmi_range_result** result,
                                         int32_t* bucket_order, int on_device) {
-    const char* who = "lmi_search_range";
-    CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
-    if (h->root().n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
-    if (h->root().dims.back() != h->L) return fail("%s: MLP has %d classes, index has %d buckets", who, h->root().dims.back(), h->L);
-    if (nq == 0) return range_empty(h, nq, nb, result);
-    if (!queries_nav || !queries_search) return fail("%s: queries_nav and queries_search must not be NULL", who);
-    CHK(set_dev(h));
-    const float *d_qn = nullptr, *d_qs = nullptr;
-    CHK(union_queries(h, queries_nav, queries_search, nq, on_device, &d_qn, &d_qs));
-    int* d_order = bucket_order;
-    if (!on_device || !bucket_order) { CHK(h->order.reserve((size_t)nq * nb * 4)); d_order = h->order.as<int>(); }
-    begin_call(h);
-    CHK(mlp_enqueue(h, d_qn, nq, nb, d_order, nullptr));
-    CHK(range_core(h, who, d_qs, nq, d_order, nb, radius, f, filter_of, max_total, result));
-    if (!on_device && copy_back(h, {{bucket_order, d_order, (size_t)nq * nb * 4}}) != 0) {
-        delete *result;
-        *result = nullptr;
-        return -1;
-    }
-    return 0;
+    return range_call(ORDER_MLP, "lmi_search_range", h, queries_nav, queries_search, nq, nb, radius, f, filter_of, max_total, result, bucket_order,
+                      nullptr, on_device);
 }
-
 extern "C" LMI_API int lmi_search_tree_range(lmi_index* h, const float* queries_nav, const float* queries_search, int nq, int nb,
                                              const float* radius, const lmi_filter* f, const int32_t* filter_of, int64_t max_total,
                                              lmi_range_result** result, int32_t* slab_ids, int32_t* entries, int on_device) {
-    const char* who = "lmi_search_tree_range";
-    CHK(range_begin(h, who, nq, nb, radius, f, filter_of, max_total, result));
-    if (nq == 0) return range_empty(h, nq, nb, result);
-    if (!queries_nav || !queries_search) return fail("%s: queries_nav and queries_search must not be NULL", who);
-    CHK(nav_check(h, nq, nb, who));
-    const float *d_qn = nullptr, *d_qs = nullptr;
-    CHK(union_queries(h, queries_nav, queries_search, nq, on_device, &d_qn, &d_qs));
-    CHK(h->nav_slab.reserve((size_t)nq * nb * 4));
-    CHK(h->nav_ent.reserve((size_t)nq * nb * 4));
-    int* d_slab = (on_device && slab_ids) ? slab_ids : h->nav_slab.as<int>();
-    int* d_ent = (on_device && entries) ? entries : h->nav_ent.as<int>();
-    begin_call(h);
-    CHK(nav_enqueue(h, d_qn, nq, nb, d_slab, d_ent));
-    CHK(range_core(h, who, d_qs, nq, d_slab, nb, radius, f, filter_of, max_total, result));
-    if (!on_device && copy_back(h, {{slab_ids, d_slab, (size_t)nq * nb * 4}, {entries, d_ent, (size_t)nq * nb * 4}}) != 0) {
-        delete *result;
-        *result = nullptr;
-        return -1;
-    }
-    return 0;
+    return range_call(ORDER_TREE, "lmi_search_tree_range", h, queries_nav, queries_search, nq, nb, radius, f, filter_of, max_total, result, slab_ids,
+                      entries, on_device);
 }
 
 extern "C" LMI_API int lmi_range_result_total(const lmi_range_result* r, int64_t* total) {

@@ -1,6 +1,6 @@
 // lmi_range_plan.h -- the host arithmetic of a range search (lmi_scan_range and the two search forms; include/lmi_hip.h): which
-// query a slot of the union scan's tables belongs to, where a slot's results lie inside its wave's chunk, how the counts of every
-// (query, rank) become lims, where every slot's run goes in the final arrays, and the max_total test.
+// (query, rank) a slot of the union scan's tables belongs to, where a slot's results lie inside its wave's chunk, how the counts of
+// every (query, rank) become lims, where every slot's run goes in the final arrays, and the max_total test.
 // Host only and pure: the standard library and lmi_union_plan.h (whose plan and tables it reads and never changes), no HIP call, no
 // handle -- lmi_host_range.h passes the counts in and launches from what comes back; tests/host/range_plan_selftest.cpp checks all of
 // it on the CPU.
@@ -20,23 +20,8 @@ constexpr int PLAN_K = 1;
 // Slot i of a group's slot table is (query, rank) pair s = q * nb + t of the group (build_tables numbers a slot's list by it).
 inline int64_t slot_pair(const up::Plan& p, const up::Tables& T, int64_t i) { return T.slots[(size_t)i].list / p.list_rows; }
 
-// The arrays parallel to a group's slot table that the range kernels read: q[i] the GLOBAL query of slot i, pos0[i] the slab position
-// of its bucket's row 0.
-struct SlotArrays {
-    std::vector<int> q;
-    std::vector<long long> pos0;
-};
-inline SlotArrays slot_arrays(const up::Plan& p, const up::Tables& T) {
-    SlotArrays A;
-    A.q.reserve(T.slots.size());
-    A.pos0.reserve(T.slots.size());
-    for (int64_t i = 0; i < (int64_t)T.slots.size(); ++i) {
-        const int64_t s = slot_pair(p, T, i);
-        A.q.push_back((int)(T.q0 + s / p.nb));
-        A.pos0.push_back(T.slot_pos0[(size_t)s]);
-    }
-    return A;
-}
+// (The arrays parallel to a group's slot table that the range kernels read -- the global query of slot i and the slab position of its
+// bucket's row 0 -- are the tables' own scan_q and scan_pos0.)
 
 // A wave's chunk: slot i of the wave (counts[i] results) owns [off[i], off[i] + counts[i]) of it; returns the chunk's length.
 inline int64_t chunk_offsets(const int* counts, int64_t slots, long long* off) {

@@ -1,9 +1,10 @@
 // lmi_union_plan.h -- the geometry of one union scan (lmi_scan_union and the two search forms): how the batch is cut into query
 // groups, a group's (bucket, slots) work into waves that share one score slab, the device bytes the call allocates for that, and
-// (build_tables) every table a group's kernels are launched from.
-// Host only and pure: the standard library, no HIP call, no kernel header -- lmi_host_union.h passes the sizes, the free memory, the
-// forced values, the bucket order and the layout in, uploads what comes back and launches from it; tests/host/union_plan_selftest.cpp
-// checks all of it on the CPU.
+// (build_tables) every table a group's kernels are launched from, and (build_groups) the tables of all groups with the extents the
+// call's buffers are sized by.
+// Host only and pure: the standard library, no HIP call, no kernel header -- lmi_host_candidates.h passes the sizes, the free memory,
+// the forced values, the bucket order and the layout in, uploads what comes back and launches from it, for the union scan and the range
+// search alike; tests/host/union_plan_selftest.cpp checks all of it on the CPU.
 //
 // A slot is one (query, rank) whose bucket has rows.  A slot is scored against its whole bucket in one piece and owns one sorted list,
 // so nothing here can change a result (include/lmi_hip.h, lmi_scan_union); the geometry decides memory and speed only -- but the
@@ -159,9 +160,10 @@ struct Wave { int64_t item0 = 0, items = 0, slot0 = 0, slots = 0, tile0 = 0, til
 // Everything the kernels of query group [q0, q1) are launched from.  With gq = q1 - q0:
 //   slot_n, slot_base, slot_pos0 [gq][nb]   per (query, rank), for the finish: rows to merge (0: none), ordinal of the bucket's row 0,
 //                                           slab position of the bucket's row 0;
-//   slots, slot_mask                        one per scanned slot, wave after wave, inside a wave by (bucket, query, rank);
+//   slots, slot_mask, scan_q, scan_pos0     one per scanned slot, wave after wave, inside a wave by (bucket, query, rank);
 //                                           slot_mask[i]: the word offset of slot i's mask row, -1 for an unfiltered query (empty
-//                                           without a filter);
+//                                           without a filter); scan_q[i]: the GLOBAL query of slot i; scan_pos0[i]: the slab position
+//                                           of its bucket's row 0 (the range kernels read these two);
 //   rowq, tile_off, tile_cnt                per 32-query tile of a wave's packed queries: rowq [tiles][32] the global query of each
 //                                           fragment row (-1: padding), the tile's first slab row (floats), its real slots;
 //   items                                   wave after wave; inside a wave by chunk, tile group, 256-row block (blocks of one bucket
@@ -172,8 +174,8 @@ struct Tables {
     std::vector<Wave> waves;
     std::vector<UnionItem> items;
     std::vector<UnionSlot> slots;
-    std::vector<int> rowq, tile_cnt, slot_n;
-    std::vector<long long> tile_off, slot_pos0, slot_mask;
+    std::vector<int> rowq, tile_cnt, slot_n, scan_q;
+    std::vector<long long> tile_off, slot_pos0, slot_mask, scan_pos0;
     std::vector<unsigned> slot_base;
     int64_t skipped = 0;
 };
@@ -249,6 +251,8 @@ inline Tables build_tables(const Plan& p, int64_t group, const int* order, const
                 const int64_t s = by_bucket[start[c.bucket] + c.slot0 + i];
                 T.rowq.push_back((int)(T.q0 + s / nb));
                 T.slots.push_back(UnionSlot{c.slab_off + i * pitch, s * p.list_rows, (int)c.n, T.slot_base[s]});
+                T.scan_q.push_back(T.rowq.back());
+                T.scan_pos0.push_back(pos0);
                 if (fv) {
                     const int fj = filter_of_slot(s);
                     T.slot_mask.push_back(fj < 0 ? -1ll : (long long)lmi_filter_plan::mask_word(fj, fv->n_rb_total, lay.rb_start[c.bucket], 0));
@@ -265,6 +269,31 @@ inline Tables build_tables(const Plan& p, int64_t group, const int* order, const
         W.items = (int64_t)T.items.size() - W.item0;
     }
     return T;
+}
+
+// What a call's device buffers are sized by: the largest wave (its slab in bytes, its tiles), the largest group (its tiles, items and
+// scanned slots) and, over all groups, the slots the filters left out.
+struct Extents { int64_t slab_bytes = 0, wave_tiles = 0, group_tiles = 0, group_items = 0, group_slots = 0, skipped = 0; };
+struct Groups { std::vector<Tables> groups; Extents ext; };
+
+// The tables of every query group of plan p, in order, and their extents.
+inline Groups build_groups(const Plan& p, const int* order, const Layout& lay, const FilterView* fv) {
+    Groups R;
+    R.groups.reserve((size_t)p.query_groups);
+    Extents& e = R.ext;
+    for (int64_t g = 0; g < p.query_groups; ++g) {
+        R.groups.push_back(build_tables(p, g, order, lay, fv));
+        const Tables& T = R.groups.back();
+        for (const Wave& W : T.waves) {
+            e.slab_bytes = std::max(e.slab_bytes, W.slab_floats * 4);
+            e.wave_tiles = std::max(e.wave_tiles, W.tiles);
+        }
+        e.group_tiles = std::max(e.group_tiles, (int64_t)T.tile_cnt.size());
+        e.group_items = std::max(e.group_items, (int64_t)T.items.size());
+        e.group_slots = std::max(e.group_slots, (int64_t)T.slots.size());
+        e.skipped += T.skipped;
+    }
+    return R;
 }
 
 }  // namespace lmi_union_plan

@@ -2,7 +2,7 @@
 // CPU, meant for -fsanitize=address,undefined (tests/test_range_host.py builds and runs it).  For random layouts, bucket orders (holes,
 // buckets listed twice, ids outside the index, empty buckets), filter tables with emptied (filter, bucket) pairs and forced geometries
 // that give several groups and waves, with random per-slot counts:
-//   - a slot's parallel arrays name its query and its bucket's slab position;
+//   - a slot's parallel arrays (the tables' scan_q and scan_pos0) name its query and its bucket's slab position;
 //   - a wave's offsets tile its chunk exactly once, in slot order;
 //   - lims starts at 0, is monotone and ends at the sum of all counts;
 //   - the gathered runs tile [0, total) exactly once, every run inside its query's [lims[q], lims[q + 1]), a query's runs in rank order;
@@ -49,22 +49,21 @@ static void check_case(std::mt19937& rng, int64_t nq, int nb, int L, int nf, int
 
     Totals tot(nq, nb);
     struct WaveOut { std::vector<int> counts; std::vector<long long> off; int64_t total; };
-    std::vector<up::Tables> groups;
+    const up::Groups all = up::build_groups(p, order.data(), lay, nf > 0 ? &fv : nullptr);
+    const std::vector<up::Tables>& groups = all.groups;
     std::vector<std::vector<WaveOut>> outs;
     int64_t counted = 0;
     std::vector<char> is_slot((size_t)(nq * nb), 0);
-    for (int64_t g = 0; g < p.query_groups; ++g) {
-        groups.push_back(up::build_tables(p, g, order.data(), lay, nf > 0 ? &fv : nullptr));
-        const up::Tables& T = groups.back();
-        const SlotArrays A = slot_arrays(p, T);
-        EXPECT(A.q.size() == T.slots.size() && A.pos0.size() == T.slots.size());
+    EXPECT((int64_t)groups.size() == p.query_groups);
+    for (const up::Tables& T : groups) {
+        EXPECT(T.scan_q.size() == T.slots.size() && T.scan_pos0.size() == T.slots.size());
         for (size_t i = 0; i < T.slots.size(); ++i) {
             const int64_t s = slot_pair(p, T, (int64_t)i);
             EXPECT(s >= 0 && s < (T.q1 - T.q0) * nb);
             const int64_t q = T.q0 + s / nb, t = s % nb;
             const int b = order[(size_t)(q * nb + t)];
-            EXPECT(A.q[i] == q && b >= 0 && b < L && T.slots[i].n == nrows[(size_t)b] && T.slots[i].n > 0);
-            EXPECT(A.pos0[i] == (long long)rbs[(size_t)b] * 32);
+            EXPECT(T.scan_q[i] == q && b >= 0 && b < L && T.slots[i].n == nrows[(size_t)b] && T.slots[i].n > 0);
+            EXPECT(T.scan_pos0[i] == (long long)rbs[(size_t)b] * 32);
             EXPECT(!is_slot[(size_t)(q * nb + t)]);   // every (query, rank) owns at most one slot
             is_slot[(size_t)(q * nb + t)] = 1;
             if (nf > 0 && filter_of[(size_t)q] >= 0) EXPECT(fcounts[(size_t)filter_of[(size_t)q] * L + b] > 0);

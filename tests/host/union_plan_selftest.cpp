@@ -6,10 +6,12 @@
 // orders and filter tables, what build_tables hands the kernels -- every live (query, rank) owns exactly one slot with the right list,
 // rows and ordinal base, a wave's slab rows are disjoint and inside its slab, fragment rows, tile tables and slots agree, the items
 // cover every (tile, 256-row block) exactly once, and the mask offsets are the filter's -- derived here from the inputs alone.
+// check_groups: on the same grid, build_groups is build_tables group by group, and its extents are the brute-force maxima.
 #include "lmi_union_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <utility>
 
@@ -125,12 +127,14 @@ static void check_tables(const Plan& p, const std::vector<int>& order, const Lay
         // every live (q, t) owns exactly one UnionSlot, nothing else owns one
         EXPECT((int64_t)T.slots.size() == want_slots);
         EXPECT(T.slot_mask.size() == (fv ? T.slots.size() : 0));
+        EXPECT(T.scan_q.size() == T.slots.size() && T.scan_pos0.size() == T.slots.size());
         std::vector<int> owned((size_t)ns, 0);
         for (size_t i = 0; i < T.slots.size(); ++i) {
             const UnionSlot& sl = T.slots[i];
             EXPECT(sl.list >= 0 && sl.list % LR == 0 && sl.list / LR < ns);
             const int64_t s = sl.list / LR;
             EXPECT(owned[s]++ == 0 && want_n[s] > 0 && sl.n == want_n[s] && sl.base == T.slot_base[s] && sl.s_off >= 0);
+            EXPECT(T.scan_q[i] == (int)(q0 + s / nb) && T.scan_pos0[i] == (long long)lay.rb_start[bucket_of[s]] * 32);
             if (fv) {
                 const int fj = filter_of_slot[s];
                 EXPECT(T.slot_mask[i] == (fj < 0 ? -1 : (long long)lmi_filter_plan::mask_word(fj, fv->n_rb_total, lay.rb_start[bucket_of[s]], 0)));
@@ -193,6 +197,49 @@ static void check_tables(const Plan& p, const std::vector<int>& order, const Lay
     }
 }
 
+template <class V>
+static bool same_bytes(const std::vector<V>& a, const std::vector<V>& b) {
+    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(V)) == 0);
+}
+
+// build_groups: the group list is build_tables called group by group, the extents are the maxima (skipped: the sum) over those tables
+static void check_groups(const Plan& p, const std::vector<int>& order, const Layout& lay, const FilterView* fv) {
+    const Groups R = build_groups(p, order.data(), lay, fv);
+    EXPECT((int64_t)R.groups.size() == p.query_groups);
+    Extents want;
+    for (int64_t g = 0; g < p.query_groups; ++g) {
+        const Tables T = build_tables(p, g, order.data(), lay, fv);
+        const Tables& G = R.groups[(size_t)g];
+        EXPECT(G.q0 == T.q0 && G.q1 == T.q1 && G.skipped == T.skipped);
+        EXPECT(same_bytes(G.items, T.items) && same_bytes(G.slots, T.slots) && G.waves.size() == T.waves.size());   // (records without padding)
+        for (size_t w = 0; w < T.waves.size(); ++w) {
+            const Wave &a = G.waves[w], &b = T.waves[w];
+            EXPECT(a.item0 == b.item0 && a.items == b.items && a.slot0 == b.slot0 && a.slots == b.slots && a.tile0 == b.tile0 &&
+                   a.tiles == b.tiles && a.slab_floats == b.slab_floats && a.ct == b.ct);
+        }
+        EXPECT(G.rowq == T.rowq && G.tile_cnt == T.tile_cnt && G.tile_off == T.tile_off);
+        EXPECT(G.slot_n == T.slot_n && G.slot_base == T.slot_base && G.slot_pos0 == T.slot_pos0 && G.slot_mask == T.slot_mask);
+        EXPECT(G.scan_q == T.scan_q && G.scan_pos0 == T.scan_pos0);
+        for (const Wave& W : T.waves) {
+            want.slab_bytes = std::max(want.slab_bytes, W.slab_floats * 4);
+            want.wave_tiles = std::max(want.wave_tiles, W.tiles);
+        }
+        want.group_tiles = std::max<int64_t>(want.group_tiles, (int64_t)T.tile_cnt.size());
+        want.group_items = std::max<int64_t>(want.group_items, (int64_t)T.items.size());
+        want.group_slots = std::max<int64_t>(want.group_slots, (int64_t)T.slots.size());
+        want.skipped += T.skipped;
+    }
+    const Extents& e = R.ext;
+    EXPECT(e.slab_bytes == want.slab_bytes && e.wave_tiles == want.wave_tiles && e.group_tiles == want.group_tiles);
+    EXPECT(e.group_items == want.group_items && e.group_slots == want.group_slots && e.skipped == want.skipped);
+    // every buffer sized by the extents holds every wave and group that is uploaded into it or written by it
+    for (const Tables& G : R.groups) {
+        EXPECT((int64_t)G.items.size() <= e.group_items && (int64_t)G.slots.size() <= e.group_slots && (int64_t)G.tile_cnt.size() <= e.group_tiles);
+        EXPECT(G.slot_mask.size() <= (size_t)e.group_slots && G.rowq.size() <= (size_t)e.group_tiles * 32);
+        for (const Wave& W : G.waves) EXPECT(W.slab_floats * 4 <= e.slab_bytes && W.tiles <= e.wave_tiles);
+    }
+}
+
 // the grid of check_tables: two layouts x (nq, nb, k) x forced geometry x bucket orders x filters
 static void check_tables_grid() {
     struct Lay { std::vector<int> rows, rbs; };
@@ -233,7 +280,11 @@ static void check_tables_grid() {
                                                     {counts.data(), all_dead.data(), n_rb_total}};
                         for (const std::vector<int>* o : {&mixed, &twice, &one}) {
                             check_tables(p, *o, lay, nullptr);
-                            for (const FilterView& v : views) check_tables(p, *o, lay, &v);
+                            check_groups(p, *o, lay, nullptr);
+                            for (const FilterView& v : views) {
+                                check_tables(p, *o, lay, &v);
+                                check_groups(p, *o, lay, &v);
+                            }
                         }
                     }
     }

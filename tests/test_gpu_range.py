@@ -247,6 +247,31 @@ def test_the_shared_filters(capi, index_of, oracle, metric):
         filt.close()
 
 
+def test_union_and_range_sit_on_one_candidate_stage(capi, index_of):
+    """A filtered union scan (k = 10) and a filtered range search have lists of 128 rows both, so the one stage they share cuts the
+    same batch into the same groups and waves with the same slab: several of each under the forced geometry, on device pointers."""
+    d, nb, metric = 64, 8, "l2"
+    idx, Q = index_of(d, metric), ur.case(d)[1]
+    fo = fr.filter_of()
+    filt = capi.Filter(idx, fr.filter_lists(d), fr.MODES)
+    q_t, bo_t = torch.from_numpy(np.array(Q)).cuda(), torch.from_numpy(np.array(ur.random_order(nb))).cuda()
+    d_t = torch.empty((ur.NQ, 10), dtype=torch.float32, device="cuda")
+    i_t = torch.empty((ur.NQ, 10), dtype=torch.int32, device="cuda")
+    try:
+        capi.union_set_geometry(32, 256 << 10)
+        idx.scan_union_device(q_t, bo_t, nb, 10, d_t, i_t, filter=filt, filter_of=fo)
+        union_plan = capi.union_last_plan()
+        with idx.scan_range_device(q_t, bo_t, nb, FIXED[metric], filter=filt, filter_of=fo):
+            range_plan = capi.range_last_plan()
+    finally:
+        capi.union_set_geometry(0, 0)
+        filt.close()
+    assert union_plan["LIST_ROWS"] == 128
+    for word in ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES"):
+        assert union_plan[word] == range_plan[word], (word, union_plan, range_plan)
+    assert union_plan["GROUPS"] == 5 and union_plan["QUERY_ROWS"] == 32 and union_plan["WAVES"] > 1 and union_plan["SLAB_BYTES"] > 0
+
+
 @pytest.mark.parametrize("metric", ur.METRICS)
 def test_search_range_with_the_stops(index_of, oracle, metric):
     """lmi_search_range equals the reference applied to the bucket order it returns, and that order is lmi_search_union's."""
