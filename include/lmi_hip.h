@@ -274,6 +274,59 @@ LMI_API int lmi_buckets_delete(lmi_index *h, const uint32_t *ids, int64_t n, int
 #define LMI_SUBSET_KEEP 0   /* ids lists the objects the new index holds      */
 #define LMI_SUBSET_DROP 1   /* ids lists the objects the new index leaves out */
 LMI_API int lmi_subset(lmi_index *h, const uint32_t *ids, int64_t n, int mode, lmi_index **out, int64_t *n_kept /* nullable */);
+/* A re-bucketed copy of a built index, derived on the device (no reference counterpart: the reference re-labels its DataFrames and
+ * rebuilds).  lmi_subset is "same labels, fewer objects"; this is "same objects, new labels, any new L".
+ * The new label of a stored object: labels[i] if its id is ids[i] (host arrays, n entries, every id listed once); otherwise
+ * bucket_map[its bucket] (host, [L of h]; NULL: the identity, which needs L_new >= L).  A map entry of -1 says "this bucket must be
+ * emptied by the list".  Two stored objects that carry the same id both take that id's label; ids that no object carries are
+ * ignored; *n_named (nullable) <- the OBJECTS (not list entries) that took their label from the list.  One call is a split (name one
+ * bucket's objects: lmi_bucket_read gives their ids), a merge (a many-to-one map, n == 0), a new empty bucket between existing ones
+ * (an injective map into a larger L_new) or a complete re-placement after retraining (name everything).
+ * THE ORDER RULE: *out holds exactly what lmi_create + h's settings + lmi_buckets_begin(.., L_new, new labels ..) / add_rows / end
+ * would hold for the object list "h's objects in the order h holds them -- old bucket ascending, then row within the bucket -- each
+ * with its new label".  So a new bucket's objects are ordered by (old bucket, old row), whatever the order of the list or the map:
+ * every search returns the same dists, ids and keys bit for bit, lmi_bucket_sizes / lmi_bucket_read / lmi_bucket_read_f16 /
+ * lmi_index_bytes return the same, and lmi_debug_layout shows a fresh build's layout with all four counters zero.  The identity call
+ * (n == 0, NULL map, L_new == L) is h's compaction, equal to lmi_subset(h, NULL, 0, LMI_SUBSET_DROP, ..).  The order is that of the
+ * unique words (new label << 32) | ordinal, ordinal = the object's dense position in h's order (NOT its slab row: an insert may have
+ * moved a bucket behind later ones); no position depends on the arrival order of an atomic, on the sort's tile length or on a grid.
+ * *out is a NEW, INDEPENDENT handle on h's device, as lmi_subset's: no clone view, h may be destroyed first, either may be mutated
+ * without the other noticing.  It carries h's settings, storage and chunk rule (lmi_subset's list) and copies of ALL of h's models,
+ * but NOT the tree tables (their child_bucket entries name h's buckets): set what changed with lmi_set_mlp / lmi_nav_set_model /
+ * lmi_nav_set_tree, which work on a built handle.  lmi_search refuses a root model whose class count is not L_new, as ever; the
+ * explicit-order calls (lmi_scan_topk, lmi_scan_union, lmi_scan_range) work at once.  Its layout is its own: a filter of h is refused.
+ * All three stored forms: row-major f32 (both metrics; the -|x|^2/2 column of L2 travels with the row), f32 fragments
+ * (lmi_set_prefilter(0)) and LMI_STORAGE_F16, whose halves are moved as stored under h's scale (the object set is h's, so the absmax
+ * is) -- no binary32 image exists at any point.  The fp16 fragments, norms and bounds are derived from the new handle's own rows.
+ * The call synchronises h's stream first, only READS h -- allowed while clone views live, and on one -- and returns when the new
+ * index is complete.  Peak device memory: h's images + the new index's + the call's maps: 20 bytes per object of h (two buffers of
+ * 8-byte words -- one when a single sort tile holds them all -- and the 4-byte slab row of each ordinal) + 4 bytes per slab row of the
+ * new index (the gathers' source positions) + 8 bytes per list entry (its id and its label); the maps are freed before the call
+ * returns.
+ * Refused before any launch, with *out left NULL and h untouched, each by name: NULL h or out; h not built or being built; L_new < 1
+ * or >= 2^20; n < 0, or n > 0 with a NULL ids or labels; a label outside [0, L_new); a map entry outside [-1, L_new); a NULL map with
+ * L_new < L; an id listed twice (the message says which); a handle built with an `owned` mask (a new partition needs a new
+ * ownership).  Refused after the labelling pass: an object that is not named and whose bucket maps to -1 (the message names the first
+ * such bucket and how many of its objects were left); a layout past the 32-bit slab positions; a failed allocation (the message says
+ * how many bytes it wanted).  Then no index is made and everything the call allocated is freed. */
+LMI_API int lmi_regroup(lmi_index *h, const uint32_t *ids, const int64_t *labels, int64_t n, const int32_t *bucket_map /* nullable */,
+                        int L_new, lmi_index **out, int64_t *n_named /* nullable */);
+/* Test hook, per thread: the tile length of lmi_regroup's sort (0: the default 8 192; a power of two in [64, 8192]).  Objects up to
+ * one tile are sorted in LDS alone; above it tiles are sorted and merge passes double the runs.  Never changes a bit of the result. */
+LMI_API int lmi_regroup_set_geometry(int64_t tile_rows);
+enum {
+    LMI_REGROUP_PLAN_ROWS = 0,     /* objects of the source = words sorted                              */
+    LMI_REGROUP_PLAN_TILE_ROWS,    /* T                                                                 */
+    LMI_REGROUP_PLAN_TILES,        /* tiles sorted in LDS: ceil(rows / T)                               */
+    LMI_REGROUP_PLAN_MERGE_ROWS,   /* words of one merge piece: min(T, 2 048)                           */
+    LMI_REGROUP_PLAN_PASSES,       /* merge passes (0: one tile held every word)                        */
+    LMI_REGROUP_PLAN_MAP_BYTES,    /* device bytes of the call's maps                                   */
+    LMI_REGROUP_PLAN_NAMED,        /* *n_named                                                          */
+    LMI_REGROUP_PLAN_COUNT
+};
+/* What the last lmi_regroup on this thread did (all zero after a refused call): out[0..n) <- the first
+ * min(n, LMI_REGROUP_PLAN_COUNT) words. */
+LMI_API int lmi_debug_regroup_plan(int64_t *out, int n);
 /* sizes[L] <- number of objects per bucket (0 for buckets not owned). */
 LMI_API int lmi_bucket_sizes(lmi_index *h, int64_t *sizes);
 /* Reads one bucket back to the host in bucket order (what `data_search.loc[g.index].to_numpy()`

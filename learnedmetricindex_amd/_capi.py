@@ -46,6 +46,10 @@ RANGE_JOIN_FIELDS = ("PARTS", "RUNS", "PIECES", "RESULTS", "LARGEST_PART")
 RANGE_SORT_PLAN_FIELDS = ("GROUPS", "WAVE_SEGMENTS", "TILE_SEGMENTS", "LONG_SEGMENTS", "SKIPPED_SEGMENTS", "TILE_ROWS", "WAVE_ROWS",
                           "MERGE_ROWS", "MAX_PASSES", "SCRATCH_BYTES", "RESULTS")
 RANGE_SORT_MIN_TILE_ROWS, RANGE_SORT_MAX_TILE_ROWS = 64, 8192   # what lmi_range_sort_set_geometry takes for tile_rows (a power of two)
+#: the LMI_REGROUP_PLAN_* words, in their order (lmi_debug_regroup_plan)
+REGROUP_PLAN_FIELDS = ("ROWS", "TILE_ROWS", "TILES", "MERGE_ROWS", "PASSES", "MAP_BYTES", "NAMED")
+REGROUP_MIN_TILE_ROWS, REGROUP_MAX_TILE_ROWS = 64, 8192   # what lmi_regroup_set_geometry takes (a power of two)
+REGROUP_MAX_LABELS = 1 << 20                              # lmi_regroup: L_new stays below it
 
 _lib = None
 
@@ -83,6 +87,9 @@ SIGNATURES = {
     "lmi_buckets_insert": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _i64p]),
     "lmi_buckets_delete": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _i64p]),
     "lmi_subset": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp), _i64p]),
+    "lmi_regroup": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int, ctypes.POINTER(_vp), _i64p]),
+    "lmi_regroup_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
+    "lmi_debug_regroup_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_bucket_sizes": (ctypes.c_int, [_vp, _vp]),
     "lmi_mlp_topk": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_mlp_proba": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -656,6 +663,26 @@ class Index:
         kept = ctypes.c_int64(0)
         _check(lib().lmi_subset(self._h, _ptr(ids_a), int(ids_a.shape[0]), 1 if drop else 0, ctypes.byref(v._h), ctypes.byref(kept)))
         v.N, v.bytes_in = kept.value, 0
+        return v
+
+    def regroup(self, ids, labels, L_new: int, bucket_map=None) -> "Index":
+        """A new, independent `Index` that holds this one's objects under new bucket labels, derived on the device (`lmi_regroup`).
+        An object whose id is `ids[i]` goes to bucket `labels[i]`; every other object goes to `bucket_map[its bucket]` (int [L];
+        None: it keeps its bucket, which needs `L_new >= L`; an entry of -1: "this bucket must be emptied by the list").  Two objects
+        that share an id both move; ids that no object carries are ignored; an id listed twice raises.  The result holds exactly what
+        a fresh build of "this index's objects in the order held here (bucket ascending, then row), each with its new label" would:
+        a new bucket's objects are ordered by (old bucket, old row), whatever the order of the list -- same search results bit for
+        bit, same layout.  It owns its images and copies of the models, carries this one's settings, but NOT the tree tables (they
+        name this index's buckets): call `set_mlp` / `nav_set_model` / `nav_set_tree` for what changed; `search` refuses a root model
+        whose class count is not `L_new`, the explicit-order scans work at once.  `.n_named` on the result is the number of objects
+        (not list entries) that took their label from the list.  This index is only read; works on every storage, while clone views
+        live, and on one.  Bad arguments raise ValueError before the library is called (`regroup_args`)."""
+        ids_a, lab_a, map_a, L_new = regroup_args(ids, labels, L_new, bucket_map, self.L)
+        v = self._derived()
+        named = ctypes.c_int64(0)
+        _check(lib().lmi_regroup(self._h, _ptr(ids_a), _ptr(lab_a), int(ids_a.shape[0]), _ptr(map_a), L_new, ctypes.byref(v._h),
+                                 ctypes.byref(named)))
+        v.L, v.N, v.bytes_in, v.n_named = L_new, getattr(self, "N", None), 0, named.value
         return v
 
     def bucket_sizes(self) -> np.ndarray:
@@ -1392,6 +1419,61 @@ def range_sort_last_plan() -> dict:
     w = (ctypes.c_int64 * len(RANGE_SORT_PLAN_FIELDS))()
     _check(lib().lmi_debug_range_sort_plan(w, len(RANGE_SORT_PLAN_FIELDS)))
     return dict(zip((n.lower() for n in RANGE_SORT_PLAN_FIELDS), (int(v) for v in w)))
+
+
+def regroup_args(ids, labels, L_new, bucket_map, L):
+    """`Index.regroup`'s arguments as the library takes them -- (ids uint32 [n], labels int64 [n], bucket_map int32 [L] or None, L_new)
+    -- or ValueError; needs no library.  What it cannot see (which objects the index holds) the library checks."""
+    if isinstance(L_new, bool) or not isinstance(L_new, (int, np.integer)) or not 1 <= L_new < REGROUP_MAX_LABELS:
+        raise ValueError(f"regroup: L_new {L_new!r} must be an integer in [1, {REGROUP_MAX_LABELS})")
+    a, lab = np.asarray(ids).reshape(-1), np.asarray(labels).reshape(-1)
+    if a.shape[0] != lab.shape[0]:
+        raise ValueError(f"regroup: {a.shape[0]} ids but {lab.shape[0]} labels")
+    for name, x in (("ids", a), ("labels", lab)):
+        if x.size and x.dtype.kind not in "iu":   # (an empty list is float64 and has nothing to truncate)
+            raise ValueError(f"regroup: {name} must be integers, not {x.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+        raise ValueError("regroup: ids must fit uint32")
+    if lab.size and (lab.min() < 0 or lab.max() >= L_new):
+        bad = int(np.flatnonzero((lab < 0) | (lab >= L_new))[0])
+        raise ValueError(f"regroup: labels[{bad}] = {int(lab[bad])} outside [0, {L_new})")
+    ids_a = _np(a, np.uint32)
+    if ids_a.size > 1:
+        srt = np.sort(ids_a)
+        dup = np.flatnonzero(srt[1:] == srt[:-1])
+        if dup.size:
+            raise ValueError(f"regroup: id {int(srt[dup[0]])} is listed twice")
+    map_a = None
+    if bucket_map is None:
+        if L_new < L:
+            raise ValueError(f"regroup: without a bucket_map every unnamed object keeps its bucket, which needs L_new >= L ({L_new} < {L})")
+    else:
+        m = np.asarray(bucket_map).reshape(-1)
+        if m.shape[0] != L or (m.size and m.dtype.kind not in "iu"):
+            raise ValueError(f"regroup: bucket_map must be {L} integers (one per bucket of this index)")
+        if m.size and (m.min() < -1 or m.max() >= L_new):
+            bad = int(np.flatnonzero((m < -1) | (m >= L_new))[0])
+            raise ValueError(f"regroup: bucket_map[{bad}] = {int(m[bad])} outside [-1, {L_new})")
+        map_a = _np(m, np.int32)
+    return ids_a, _np(lab, np.int64), map_a, int(L_new)
+
+
+def regroup_set_geometry(tile_rows: int = 0) -> None:
+    """Test hook (`lmi_regroup_set_geometry`): the tile length (a power of two in [64, 8192]; 0 = the default) of the sort inside
+    `Index.regroup` on this thread.  Never changes a result."""
+    if isinstance(tile_rows, bool) or not isinstance(tile_rows, (int, np.integer)) or tile_rows < 0:
+        raise ValueError(f"regroup_set_geometry: tile_rows {tile_rows!r} must be an integer >= 0 (0: the default)")
+    if tile_rows and (tile_rows & (tile_rows - 1) or not REGROUP_MIN_TILE_ROWS <= tile_rows <= REGROUP_MAX_TILE_ROWS):
+        raise ValueError(f"regroup_set_geometry: tile_rows {tile_rows} is not a power of two in "
+                         f"[{REGROUP_MIN_TILE_ROWS}, {REGROUP_MAX_TILE_ROWS}]")
+    _check(lib().lmi_regroup_set_geometry(int(tile_rows)))
+
+
+def regroup_last_plan() -> dict:
+    """What the last `Index.regroup` on this thread did (`lmi_debug_regroup_plan`): `REGROUP_PLAN_FIELDS` (lower case) -> int."""
+    w = (ctypes.c_int64 * len(REGROUP_PLAN_FIELDS))()
+    _check(lib().lmi_debug_regroup_plan(w, len(REGROUP_PLAN_FIELDS)))
+    return dict(zip((n.lower() for n in REGROUP_PLAN_FIELDS), (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

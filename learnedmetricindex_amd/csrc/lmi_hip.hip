@@ -28,6 +28,8 @@
 #include "lmi_host_range_join.h"   // lmi_join_range_parts / lmi_allgather_join_range, lmi_range_join_set_geometry, lmi_debug_range_join_plan
 #include "lmi_range_sort.h"   // the kernels of the sort of a range result by distance
 #include "lmi_host_range_sort.h"   // lmi_range_result_sort / lmi_range_result_sorted, lmi_range_sort_set_geometry, lmi_debug_range_sort_plan
+#include "lmi_regroup.h"        // the kernels of lmi_regroup (its sort merges with lmi_range_sort.h's kernel)
+#include "lmi_host_regroup.h"   // lmi_regroup, lmi_regroup_set_geometry, lmi_debug_regroup_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

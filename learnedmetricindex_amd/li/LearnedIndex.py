@@ -318,7 +318,7 @@ class LearnedIndex(Logger):
 
     # ------------------------------------------------------------------------------------------
     def insert(self, data_navigation_new: pd.DataFrame, data_search_new: Optional[pd.DataFrame] = None,
-               ids=None) -> npt.NDArray[np.int64]:
+               ids=None, create_buckets: bool = False) -> npt.NDArray[np.int64]:
         """Adds objects to the HBM-resident index (an extension: the reference rebuilds).  Each object is placed the way
         `LearnedIndexBuilder.build` places it -- argmax of the root model, then argmax of each internal node's model down the
         tree, through the HIP MLP -- and goes after the last object of its bucket (`lmi_buckets_insert`; refused by the library,
@@ -326,8 +326,10 @@ class LearnedIndex(Logger):
         (default: `data_navigation_new`) holds the scan vectors, `ids` (default: `data_navigation_new.index`) the labels.
         Returns the objects' `data_prediction` rows (int64 [n, n_levels]) for the caller to append to their own frames.
         A multi-level placement onto a leaf path that holds no bucket would need a new bucket: the whole call is refused
-        with ValueError before anything changes.  Afterwards `search_resident` answers from the mutated index; `search`
-        keeps answering from the frames it is given (they no longer match the resident copy, which it rebuilds)."""
+        with ValueError before anything changes -- unless `create_buckets=True`: then the missing leaf paths are opened first
+        as empty buckets (a `regroup` that names no object: the resident engine is replaced by the re-bucketed one and closed,
+        the paths join `bucket_paths`) and the insert goes on as usual.  Afterwards `search_resident` answers from the mutated
+        index; `search` keeps answering from the frames it is given (they no longer match the resident copy, which it rebuilds)."""
         eng = self._resident("insert")
         nav = data_navigation_new
         srch = nav if data_search_new is None else data_search_new
@@ -352,7 +354,10 @@ class LearnedIndex(Logger):
         else:
             bucket_of = np.asarray([self._path_ids.get(tuple(int(v) for v in p), -1) for p in dp], dtype=np.int64)
             missing = int((bucket_of < 0).sum())
-            if missing:
+            if missing and create_buckets:
+                eng = self._open_buckets(np.unique(dp[bucket_of < 0], axis=0))
+                bucket_of = np.asarray([self._path_ids[tuple(int(v) for v in p)] for p in dp], dtype=np.int64)
+            elif missing:
                 raise ValueError(f"{missing} of {dp.shape[0]} object(s) fall on a leaf path that holds no bucket; creating buckets "
                                  "is not supported (rebuild the index): nothing was inserted")
         cols = _feature_columns(srch)
@@ -384,6 +389,90 @@ class LearnedIndex(Logger):
         other._engine_key = self._mutated_key()
         other._path_ids, other._entry_paths, other._nav_cap = self._path_ids, self._entry_paths, self._nav_cap
         return other
+
+    def regroup(self, ids, data_prediction, root_model: Optional[NeuralNetwork] = None,
+                internal_models: Optional[Dict[Tuple, NeuralNetwork]] = None,
+                bucket_paths: Optional[List[Tuple]] = None) -> "LearnedIndex":
+        """A new `LearnedIndex` over the SAME resident objects under a new partition (an extension; `lmi_regroup`): the object
+        whose id (DataFrame index label) is `ids[i]` takes the path `data_prediction[i]` (int64 [n, n_levels_new], n_levels_new >=
+        the current depth); every other object keeps its path, padded with EMPTY_VALUE where the tree got deeper.  `root_model`,
+        `internal_models` and `bucket_paths` default to this object's; pass what the new partition changes (a split's child model,
+        a retrained root).  The copy is derived on the device -- no DataFrame is needed, nothing is uploaded again -- is independent
+        of this object's resident index, is laid out like a fresh build of the same objects in the order held here, and is answered
+        by `search_resident` / `range_search_resident`; it saves and loads through `index_io` like any mutated index.  This object
+        is unchanged.
+        Bucket ids: on a 1-level index bucket id == class id and the new index has as many buckets as the (new) root model has
+        classes.  Otherwise the buckets are the distinct paths among this index's bucket paths and the rows of `data_prediction`,
+        numbered in sorted order as a build numbers them; a path left without objects stays, as an empty bucket.
+        When to split or merge, with which clustering and how many epochs is the caller's policy: INTEGRATION.md has the recipe."""
+        other = LearnedIndex(self.root_model if root_model is None else root_model,
+                             self.internal_models if internal_models is None else internal_models,
+                             self.bucket_paths if bucket_paths is None else bucket_paths)
+        self._regroup_into(other, ids, data_prediction)
+        return other
+
+    def _current_paths(self, eng) -> npt.NDArray[np.int64]:
+        """[L, depth]: the path of every bucket id of the resident engine."""
+        if self._path_ids is None:
+            return np.arange(eng.L, dtype=np.int64)[:, None]
+        return np.asarray([p for p, _ in sorted(self._path_ids.items(), key=lambda kv: kv[1])], dtype=np.int64).reshape(eng.L, -1)
+
+    def _regroup_into(self, other: "LearnedIndex", ids, data_prediction, extra_paths=None) -> None:
+        """`regroup` into `other` (which holds the new models and bucket paths): the new path set, its sorted ids, the old id -> new
+        id shift as the engine's `bucket_map`, the named objects' labels; then the new engine's models and tree.  `extra_paths`
+        [m, n_levels]: paths that become buckets although no object is placed there (`insert(create_buckets=True)`)."""
+        eng = self._resident("regroup")
+        ids = np.asarray(ids).reshape(-1)
+        old = self._current_paths(eng)
+        dp = np.asarray(data_prediction, dtype=np.int64)
+        if dp.ndim == 1:
+            dp = dp[:, None] if dp.size else dp.reshape(0, old.shape[1])
+        if dp.ndim != 2 or dp.shape[0] != ids.shape[0]:
+            raise ValueError(f"regroup: data_prediction {tuple(dp.shape)} must hold one path per id ({ids.shape[0]})")
+        n_levels = dp.shape[1]
+        if n_levels < old.shape[1]:
+            raise ValueError(f"regroup: data_prediction has {n_levels} level(s), the index has {old.shape[1]}")
+        if n_levels == 1 and self._path_ids is None:
+            # bucket id == class id; a bucket past the new model's classes has to be emptied by the list
+            L_new = int(linear_layers(other.root_model.model)[-1][0].shape[0])
+            bucket_map = None if L_new >= eng.L else np.where(np.arange(eng.L) < L_new, np.arange(eng.L), -1).astype(np.int32)
+            new = eng.regroup(ids, dp[:, 0], L_new, bucket_map)
+            try:
+                new.set_mlp(linear_layers(other.root_model.model))
+            except BaseException:
+                new.close()
+                raise
+            other._path_ids = None
+        else:
+            padded = np.full((old.shape[0], n_levels), EMPTY_VALUE, dtype=np.int64)
+            padded[:, : old.shape[1]] = old
+            stack = [padded, dp] + ([] if extra_paths is None else [np.asarray(extra_paths, dtype=np.int64).reshape(-1, n_levels)])
+            paths, inv = np.unique(np.concatenate(stack), axis=0, return_inverse=True)
+            inv = np.asarray(inv).reshape(-1)
+            L = old.shape[0]
+            new = eng.regroup(ids, inv[L: L + dp.shape[0]], int(paths.shape[0]), inv[:L].astype(np.int32))
+            other._path_ids = {tuple(int(v) for v in p): i for i, p in enumerate(paths)}
+            try:
+                other._upload_tree(new, n_levels)
+            except BaseException:
+                new.close()
+                raise
+        other._engine, other._engine_key = new, self._mutated_key()
+
+    def _open_buckets(self, missing_paths):
+        """`insert(create_buckets=True)`: the resident engine re-bucketed with `missing_paths` as empty buckets; this object now
+        answers from the new engine, the old one is closed.  Returns the new engine."""
+        known = {tuple(int(v) for v in p) for p in self.bucket_paths}
+        more = [tuple(int(v) for v in p) for p in missing_paths]
+        other = LearnedIndex(self.root_model, self.internal_models, list(self.bucket_paths) + [p for p in more if p not in known])
+        self._regroup_into(other, [], np.empty((0, missing_paths.shape[1]), dtype=np.int64), extra_paths=missing_paths)
+        old = self._engine
+        self.bucket_paths = other.bucket_paths
+        self._engine, self._engine_key = other._engine, other._engine_key
+        self._path_ids, self._entry_paths, self._nav_cap = other._path_ids, other._entry_paths, other._nav_cap
+        other._engine = None
+        old.close()
+        return self._engine
 
     def _resident(self, what: str):
         assert self._engine is not None, f"{what}: no resident index: call prepare()/search() or index_io.load_index()"
