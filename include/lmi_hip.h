@@ -577,6 +577,57 @@ enum {
  * min(n, LMI_KNN_PLAN_COUNT) words. */
 LMI_API int lmi_debug_knn_plan(int64_t *out, int n);
 
+/* Exact brute-force RANGE query on the device: for every query ALL rows of xb within distance radius[q] -- the ground truth of the
+ * range search (lmi_scan_range below), as lmi_knn is the ground truth of search(k).  It is lmi_knn with another last stage: a
+ * threshold and a compaction instead of the selection.  No handle: the work runs on the NULL stream of `device` and the call returns
+ * when the result is complete.  on_device covers xq [nq][d] and xb [nb][d], read as lmi_knn reads them (host pointers: xb goes up in
+ * pieces and is never resident as a whole); radius is a HOST float [nq], also with on_device.
+ * Contract
+ *   score        lmi_knn's, word for word.  LMI_METRIC_IP: the chain acc = fmaf(q[t], x[t], acc) from +0, t = 0..d-1.  LMI_METRIC_L2:
+ *                xn, qn = the same chain on <x,x> and <q,q>; key = the chain continued by one link fmaf(1.0f, -0.5f * xn, s).  No
+ *                chain is split over t and nothing is added atomically (the chains run in v_mfma_f32_32x32x2_f32, padded as in lmi_knn).
+ *   distance     IP 1.0f - s; L2 fmaf(-2.0f, key, qn): what lmi_knn writes in D for L2 and what lmi_scan_range writes for IP.
+ *   admission    a row is admitted iff its score is > -FLT_MAX (NaN never passes) AND its distance is <= radius[q], compared in
+ *                binary32: lmi_scan_range's rule without a filter.  A NaN or -inf radius admits nothing; +inf admits every row that
+ *                passes the first rule.
+ *   result       an lmi_range_result on `device` (lmi_scan_range below states the object): lims int64 [nq + 1]; dists float; ids
+ *                uint32 = the row's number in xb; every query's results in ASCENDING ROW order.  Its nb is 1 and its pair counts are
+ *                [nq][1], the per-query totals, so lmi_range_result_total, _lims, _read, _pair_counts, _sort and _destroy work on it
+ *                as on any other.  The same bit for bit for any pieces, splits, query groups, grid or pointer kind.
+ *   geometry     lmi_knn_set_geometry applies: piece_rows and query_rows as in lmi_knn; splits = the stretches of a piece that
+ *                separate waves count and emit.  It never changes a bit.
+ * max_total: as in lmi_scan_range -- the most results the whole call may produce; 0 = only memory limits it.  The running count is
+ * tested after every piece; when it passes max_total the call fails, says how many results had been counted when it stopped,
+ * launches nothing further and produces no result object (*result = NULL).  The next call works.
+ * Every (query, row) pair is multiplied once: a piece's scores stay in the slab while they are counted and then emitted.  The counts
+ * of every (group, piece) come back to the host to size its chunk exactly: the call synchronises ONCE PER PIECE of every query group,
+ * and once behind the final gather.
+ * Refused with nothing launched and *result = NULL: d outside 1..4096; nq or nb < 0 or >= 2^31; an unknown metric; a NULL result
+ * pointer; a NULL radius or xq with nq > 0; a NULL xb with nq > 0 and nb > 0; a negative max_total.  nq == 0 succeeds with an empty
+ * result (lims = {0}); nb == 0 with lims all 0.  A failure at any point frees all the call allocated and leaves *result = NULL.
+ * Device memory of a call, with Q, Q', P, d' as in lmi_knn: 4 Q' roundup(P, 64) (scores) + 4 Q' d' (query fragments) + 4 Q + 4 P
+ * (norms) + 4 nq (radii) + 12 Q splits (counts and offsets) + 20 per non-empty (query, piece) run (the gather); with host pointers
+ * 4 Q d + 4 P d more for the queries and the piece; no lists.  The results twice while the call runs -- 8 bytes per result in
+ * exact-size per-piece chunks, 8 per result in the final arrays, allocated once behind the last group -- and once afterwards. */
+struct lmi_range_result;
+LMI_API int lmi_knn_range(int device, const float *xq, int64_t nq, const float *xb, int64_t nb, int d, int metric,
+                          const float *radius /* HOST [nq], also with on_device */, int64_t max_total,
+                          struct lmi_range_result **result, int on_device);
+enum {
+    LMI_KNN_RANGE_PLAN_PIECES = 0,       /* pieces the base was scanned in (0: nb == 0)                                        */
+    LMI_KNN_RANGE_PLAN_PIECE_ROWS,       /* rows per piece (the last may be shorter)                                          */
+    LMI_KNN_RANGE_PLAN_SPLITS,           /* stretches per piece, each counted and emitted by a wave of its own                */
+    LMI_KNN_RANGE_PLAN_QUERY_GROUPS,     /* groups the queries were taken in                                                  */
+    LMI_KNN_RANGE_PLAN_QUERY_ROWS,       /* queries per group (the last may be smaller)                                       */
+    LMI_KNN_RANGE_PLAN_RESULTS,          /* results of the call: lims[nq]                                                     */
+    LMI_KNN_RANGE_PLAN_CHUNK_BYTES,      /* bytes of the per-piece result chunks, all together (8 per result)                 */
+    LMI_KNN_RANGE_PLAN_WORKSPACE_BYTES,  /* device bytes the call allocated beside the chunks and the result                  */
+    LMI_KNN_RANGE_PLAN_COUNT
+};
+/* What the last lmi_knn_range on this thread did (all zero before the first, after a refused or failed call and after one with
+ * nq == 0); writes min(n, LMI_KNN_RANGE_PLAN_COUNT) words. */
+LMI_API int lmi_debug_knn_range_plan(int64_t *out, int n);
+
 /* The union scan: for every query the k best objects of the UNION of its visited buckets, k up to LMI_UNION_MAX_K -- what any
  * inverted-file index answers to search(k).  (lmi_scan_topk keeps the reference's semantics: at most LMI_K_PER_BUCKET per bucket,
  * merged by rank, k <= LMI_MAX_K; nothing about it changes.)  oracle.knn_ip / oracle.knn_l2 of a query against the concatenated

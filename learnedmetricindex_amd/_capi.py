@@ -29,6 +29,8 @@ MLP_PLAN_FIELDS = ("num_cus", "fm_ok", "logits_lds", "lds_bytes", "fused", "mode
 #: the LMI_KNN_PLAN_* words, in their order (lmi_debug_knn_plan)
 KNN_PLAN_FIELDS = ("PIECES", "PIECE_ROWS", "SPLITS", "QUERY_GROUPS", "QUERY_ROWS", "VEC_XQ", "VEC_XB", "WORKSPACE_BYTES", "LIST_ROWS")
 KNN_METRICS = {"ip": 0, "l2": 1}   # LMI_METRIC_IP, LMI_METRIC_L2
+#: the LMI_KNN_RANGE_PLAN_* words, in their order (lmi_debug_knn_range_plan)
+KNN_RANGE_PLAN_FIELDS = ("PIECES", "PIECE_ROWS", "SPLITS", "QUERY_GROUPS", "QUERY_ROWS", "RESULTS", "CHUNK_BYTES", "WORKSPACE_BYTES")
 UNION_MAX_K = 1024   # LMI_UNION_MAX_K: the largest k of the union scan (`Index.scan_union`, `search_union`, `search_tree_union`)
 #: the LMI_UNION_PLAN_* words, in their order (lmi_debug_union_plan)
 UNION_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "WAVES", "SLAB_BYTES", "LIST_ROWS", "LISTS_PER_QUERY", "WORKSPACE_BYTES", "VEC_ROWS")
@@ -114,6 +116,9 @@ SIGNATURES = {
                                _vp, _vp, ctypes.c_int]),
     "lmi_knn_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "lmi_debug_knn_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    "lmi_knn_range": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
+                                     ctypes.POINTER(_vp), ctypes.c_int]),
+    "lmi_debug_knn_range_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_scan_union": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_search_union": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_search_tree_union": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
@@ -1391,6 +1396,50 @@ def range_last_plan() -> dict:
     w = (ctypes.c_int64 * len(RANGE_PLAN_FIELDS))()
     _check(lib().lmi_debug_range_plan(w, len(RANGE_PLAN_FIELDS)))
     return dict(zip(RANGE_PLAN_FIELDS, (int(v) for v in w)))
+
+
+def range_knn(xq, xb, radius, metric: str = "ip", max_total: int = 0, device: int = 0) -> "RangeResult":
+    """Exact brute-force range query on the device (`lmi_knn_range`): the `RangeResult` of, per query, every row of `xb` within
+    distance `radius` (a number, or one per query) -- metric "ip": 1 - the inner product, "l2": the squared Euclidean distance, as
+    `knn` computes them -- in ascending row order; `ids` are row numbers in `xb`.  A NaN or -inf radius admits nothing.  `xq`, `xb`:
+    float32 numpy arrays or contiguous float32 torch tensors on the device, both of one kind, as `knn` takes them; `radius` stays on
+    the host.  `max_total` > 0: the call fails (LmiError) once more results than that have been counted.  The same input gives the
+    same result bit for bit.  Argument errors raise ValueError before the library is loaded."""
+    is_np = _array_arg("range_knn", "xq", xq, "float32", "2d"), _array_arg("range_knn", "xb", xb, "float32", "2d")
+    if is_np[0] != is_np[1]:
+        raise ValueError("range_knn: xq and xb must both be numpy arrays or both be torch tensors on the device")
+    if metric not in KNN_METRICS:
+        raise ValueError(f"range_knn: metric {metric!r} unknown ('ip' or 'l2')")
+    nq, d, nb = int(xq.shape[0]), int(xq.shape[1]), int(xb.shape[0])
+    if int(xb.shape[1]) != d:
+        raise ValueError(f"range_knn: xq has {d} columns, xb {int(xb.shape[1])}")
+    if d < 1 or d > 4096:
+        raise ValueError(f"range_knn: d {d} outside [1, 4096]")
+    if radius is None:
+        raise ValueError("range_knn: radius is None")
+    r = np.asarray(radius.cpu().numpy() if hasattr(radius, "cpu") else radius)
+    if r.dtype.kind not in "fiu" or r.ndim > 1 or (r.ndim == 1 and r.shape[0] != nq):
+        raise ValueError(f"range_knn: radius must be a number or one number per query ([{nq}]), not {r.dtype}{tuple(r.shape)}")
+    if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
+        raise ValueError(f"range_knn: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
+    r = np.ascontiguousarray(np.broadcast_to(r.astype(np.float32), (nq,)))
+    if is_np[0]:
+        xq, xb, on_device = np.ascontiguousarray(xq), np.ascontiguousarray(xb), 0
+    else:
+        if not (xq.is_cuda and xb.is_cuda and xq.is_contiguous() and xb.is_contiguous()) or xq.device != xb.device:
+            raise ValueError("range_knn: torch xq and xb must be contiguous tensors on one device")
+        device, on_device = _sync_device(xq), 1
+    res = _vp()
+    _check(lib().lmi_knn_range(int(device), _ptr(xq), nq, _ptr(xb), nb, d, KNN_METRICS[metric], _ptr(r), int(max_total), ctypes.byref(res),
+                               on_device))
+    return RangeResult(res, nq)
+
+
+def knn_range_last_plan() -> dict:
+    """What the last `range_knn` on this thread did (`lmi_debug_knn_range_plan`): `KNN_RANGE_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(KNN_RANGE_PLAN_FIELDS))()
+    _check(lib().lmi_debug_knn_range_plan(w, len(KNN_RANGE_PLAN_FIELDS)))
+    return dict(zip(KNN_RANGE_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def range_join_last_plan() -> dict:

@@ -24,6 +24,8 @@
 #include "lmi_host_union.h"   // lmi_scan_union / lmi_scan_union_part / lmi_search_union / lmi_search_tree_union, geometry and plan hooks; the *_filtered forms (lmi_host_filter.h); the front of the three forms
 #include "lmi_range.h"        // the kernels of the range search
 #include "lmi_host_range.h"   // lmi_scan_range / lmi_search_range / lmi_search_tree_range, lmi_range_result_*, lmi_debug_range_plan
+#include "lmi_knn_range.h"    // the kernels of lmi_knn_range
+#include "lmi_host_knn_range.h"   // lmi_knn_range, lmi_debug_knn_range_plan
 #include "lmi_range_join.h"   // the kernel of the join of range parts
 #include "lmi_host_range_join.h"   // lmi_join_range_parts / lmi_allgather_join_range, lmi_range_join_set_geometry, lmi_debug_range_join_plan
 #include "lmi_range_sort.h"   // the kernels of the sort of a range result by distance

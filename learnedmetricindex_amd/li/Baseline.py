@@ -4,6 +4,7 @@ Cosine distance by brute force: rows are L2-normalised on the host, then ONE `lm
 `faiss.knn(..., METRIC_INNER_PRODUCT)` replacement: fp16-MFMA prefilter + exact binary32 re-rank over a
 single-bucket index in HBM) yields the k largest inner products per query; distance = 1 - similarity.
 `k` above 10, up to `MAX_K`, goes through `lmi_knn` instead (exact binary32 brute force, no index).
+`range_search` (an extension) is the range query's ground truth the same way: `lmi_knn_range` on the unit rows.
 Same call surface as the reference class: `search(queries, data, k) -> (dists, ids 1-based, seconds)`,
 `build(data) -> seconds`.  There is no CPU path here; `li.utils.pairwise_cosine` remains for callers that
 want the sklearn form."""
@@ -44,3 +45,18 @@ class Baseline(Logger):
         found = rows >= 0  # fewer than k objects: faiss-style padding (-1)
         dists = np.where(found, np.float32(1) - sims, np.float32(np.inf))
         return dists, np.where(found, rows + 1, 0), time.time() - t0
+
+    def range_search(self, queries, data, radius, sort: bool = False, max_total: int = 0, device: int = 0):
+        """Every object within cosine distance `radius` (a number, or one per query) of each query, by brute force (`lmi_knn_range`
+        on unit rows, like `search`): (lims i64[nq + 1], dists f32[total], ids 1-based [total], seconds); query q owns
+        [lims[q], lims[q + 1]), in ascending id order, or nearest first with `sort=True` (sorted on the device)."""
+        t0 = time.time()
+        with _capi.range_knn(_unit(queries), _unit(data), radius, metric="ip", max_total=max_total, device=device) as res:
+            if sort:
+                index = _capi.Index(device)   # provides the stream of the sort only
+                try:
+                    res.sort(index)
+                finally:
+                    index.close()
+            dists, rows = res.read()
+            return res.lims, dists, rows.astype(np.int64) + 1, time.time() - t0

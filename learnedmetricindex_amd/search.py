@@ -40,6 +40,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:  # `li` importable next to this file, as in the reference layout
     sys.path.insert(0, _HERE)
 
+import _capi  # noqa: E402  (the module `li` binds when it is imported as a top-level package)
 from li.Baseline import Baseline  # noqa: E402
 from li.BuildConfiguration import BuildConfiguration  # noqa: E402
 from li.clustering import algorithms  # noqa: E402
@@ -123,7 +124,8 @@ class Experiment:
                             "for that k")
         p.add_argument("--range-radius", type=float, default=None,
                        help="also run a range search per budget: every object of the visited buckets within this distance of the "
-                            "query; the results per query (mean, max) are reported")
+                            "query; the results per query (mean, max) are reported -- with --eval also the recall against the "
+                            "exhaustive range query over all objects (GPU brute force)")
         p.add_argument("--range-sort", action="store_true",
                        help="with --range-radius: every query's range results nearest first, sorted on the device")
         a = vars(p.parse_args(argv))
@@ -276,6 +278,30 @@ def recall_against_bruteforce(queries: np.ndarray, objects: pd.DataFrame, knns: 
     return float(np.mean([len(set(t) & set(f)) / kk for t, f in zip(truth.tolist(), knns[:m, :k].tolist())]))
 
 
+def range_recall(lims_found, ids_found, lims_true, ids_true) -> float:
+    """Recall of a range search against the exhaustive one: sum |found & true| / sum |true| over the queries of `lims_true`, found
+    and true being the SETS of object ids of a query (query q owns [lims[q], lims[q + 1]) of its ids; an id found twice counts once);
+    1.0 where the truth is empty.  `lims_found` may cover more queries than `lims_true`: the first ones are compared."""
+    lf, lt = np.asarray(lims_found, dtype=np.int64), np.asarray(lims_true, dtype=np.int64)
+    found, true = np.asarray(ids_found), np.asarray(ids_true)
+    assert lf.shape[0] >= lt.shape[0] >= 1
+    hit = total = 0
+    for q in range(lt.shape[0] - 1):
+        t = set(true[lt[q]:lt[q + 1]].tolist())
+        hit += len(t & set(found[lf[q]:lf[q + 1]].tolist()))
+        total += len(t)
+    return hit / total if total else 1.0
+
+
+def range_truth(queries: np.ndarray, objects: pd.DataFrame, radius: float, sample: int = 1000):
+    """(lims, object ids) of the exhaustive range query (`lmi_knn_range`) of the first `sample` queries over the scan vectors AS THE
+    INDEX HOLDS THEM -- not re-normalised: a radius is an absolute distance.  Rows map to ids through `objects.index`."""
+    m = min(sample, queries.shape[0])
+    with _capi.range_knn(np.ascontiguousarray(queries[:m], dtype=np.float32), objects.to_numpy(dtype=np.float32), radius, metric="ip") as res:
+        _, rows = res.read()
+        return res.lims, objects.index.to_numpy()[rows.astype(np.int64)]
+
+
 def run(exp: Experiment) -> Dict:
     LOG.info("experiment: %s", dataclasses.asdict(exp))
     src = VectorSource(exp.size, exp.synthetic)
@@ -307,7 +333,7 @@ def run(exp: Experiment) -> Dict:
         save_as_pickle(os.path.join("models", exp.tag(f"{exp.dataset}-{exp.size}", prep=exp.preprocess) + ".pkl"), index)
 
     index.prepare(nav, scan, placement, exp.n_categories, storage=exp.storage)  # one upload; every budget below reuses the resident slab
-    sink, out = ResultSink(), {}
+    sink, out, truth = ResultSink(), {}, None
     for budget in bucket_budgets(exp.buckets_perc, n_buckets_in_index):
         dists, knns, clock = index.search_resident(nav_q, scan_q, exp.n_categories, n_buckets=budget, k=exp.k, stop_mass=exp.stop_mass,
                                                      path_mass=exp.path_mass, stop_rows=exp.stop_rows, merge=exp.merge)
@@ -324,13 +350,19 @@ def run(exp: Experiment) -> Dict:
                    buildtime=build_s, querytime=clock["search"], size=exp.size, params=stem)
         out[budget] = (dists, knns, clock)
         if exp.range_radius is not None:
-            lims, _, _, rclock = index.range_search_resident(nav_q, scan_q, exp.n_categories, exp.range_radius, n_buckets=budget,
+            lims, _, found, rclock = index.range_search_resident(nav_q, scan_q, exp.n_categories, exp.range_radius, n_buckets=budget,
                                                              sort=exp.range_sort, stop_mass=exp.stop_mass, path_mass=exp.path_mass,
                                                              stop_rows=exp.stop_rows)
             per_query = np.diff(lims)
             out[f"range_{budget}"] = (float(per_query.mean()) if per_query.size else 0.0, int(per_query.max(initial=0)))
             LOG.info("%d buckets: range search within %g: %.4fs, results per query mean %.2f, max %d", budget, exp.range_radius,
                      rclock["search"], *out[f"range_{budget}"])
+            if exp.evaluate:
+                if truth is None:   # one exhaustive scan serves every budget
+                    truth = range_truth(scan_q, scan, exp.range_radius)
+                out[f"range_recall_{budget}"] = range_recall(lims, found, *truth)
+                LOG.info("%d buckets: range recall within %g = %.5f (%d true results over %d queries)", budget, exp.range_radius,
+                         out[f"range_recall_{budget}"], int(truth[0][-1]), len(truth[0]) - 1)
     index.close()
     return out
 
