@@ -345,7 +345,9 @@ LMI_API int lmi_bucket_read(lmi_index *h, int bucket, float *rows, uint32_t *ids
  *        device and ingested like a float piece.  Half and float pieces may be mixed freely within one build, piece by piece; the
  *        rule that add_rows and add_owned_rows are not mixed covers all four calls.  lmi_buckets_end's verdict is unchanged (a half
  *        piece can only fail it by inf / NaN or by the scale).
- * lmi_buckets_insert_f16: as lmi_buckets_insert, its checks and refusals included (an LMI_STORAGE_F16 index is refused). */
+ * lmi_buckets_insert_f16: as lmi_buckets_insert, its checks and refusals included (an LMI_STORAGE_F16 index is refused).
+ * lmi_knn_f16 / lmi_knn_range_f16 (declared beside lmi_knn and lmi_knn_range below): the exact ground truths on queries AND base
+ *        as halves; the same contract, and the base is never widened into a buffer. */
 LMI_API int lmi_buckets_add_rows_f16(lmi_index *h, const uint16_t *rows, int64_t row0, int64_t nrows, int on_device);
 LMI_API int lmi_buckets_add_owned_rows_f16(lmi_index *h, const uint16_t *rows, const int64_t *index, int64_t nrows,
                                    int on_device);
@@ -557,6 +559,22 @@ LMI_API int lmi_train(int device, const float *x, int64_t n, const int32_t *labe
 #define LMI_KNN_MAX_K 1024
 LMI_API int lmi_knn(int device, const float *xq, int64_t nq, const float *xb, int64_t nb, int d, int k, int metric,
                     float *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
+/* lmi_knn on binary16 inputs: xq [nq][d] and xb [nb][d] are halves (bit patterns), both of them; D and I are typed and laid out as in
+ * lmi_knn.  faiss.knn(xq.astype(float32), xb.astype(float32), k, metric) without the widened copies (li/Baseline.py:7-21 on data that is
+ * distributed as 16-bit floats).  The contract of every *_f16 entry point (lmi_buckets_add_rows_f16 above): D and I are bit for bit
+ * what lmi_knn returns for the same values widened to binary32 -- widening is exact, every half is widened where the kernels load it
+ * (the queries into their fragments, the base rows straight into the product's operands) and from there on the arithmetic, the
+ * selection and the padding are lmi_knn's; no base row is ever widened into a buffer.
+ * Pointers need 2-byte alignment only, on the host and with on_device.  xb is read with 16-byte loads where d % 8 == 0 and the
+ * scanned base -- the call's piece buffer with host pointers, the caller's pointer with on_device -- is 16-byte aligned, element by
+ * element otherwise (d = 44 is a multiple of 4 and not of 8: element by element); xq always element by element.
+ * Host pointers upload halves: 2 Q d + 2 P d instead of 4 Q d + 4 P d in lmi_knn's memory formula; everything else there stands, and
+ * the pieces, splits and query groups are the ones lmi_knn makes for the same sizes, forced or not.
+ * Refusals and limits: lmi_knn's, with the message naming lmi_knn_f16.  lmi_knn_set_geometry and lmi_debug_knn_plan serve both forms:
+ * the plan words are those of the last call of either; VEC_XB reports the 16-byte loads of the form that ran.
+ * Not offered: one half array beside a binary32 one; halves in lmi_kmeans / lmi_train. */
+LMI_API int lmi_knn_f16(int device, const uint16_t *xq, int64_t nq, const uint16_t *xb, int64_t nb, int d, int k, int metric,
+                        float *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
 /* Tuning / test hook: rows of xb per uploaded or scanned piece (< 2^31), base splits per piece (<= 1024; their partial lists are
  * merged afterwards), queries per group (<= 2^20).  0 = chosen by the library.  Thread-local, like lmi_last_error; never changes a
  * result. */
@@ -568,12 +586,12 @@ enum {
     LMI_KNN_PLAN_QUERY_GROUPS,     /* groups the queries were taken in                                                       */
     LMI_KNN_PLAN_QUERY_ROWS,       /* queries per group (the last may be smaller)                                            */
     LMI_KNN_PLAN_VEC_XQ,           /* 16-byte loads of xq: always 0, the queries are packed element by element               */
-    LMI_KNN_PLAN_VEC_XB,           /* 16-byte loads of xb                                                                    */
+    LMI_KNN_PLAN_VEC_XB,           /* 16-byte loads of xb (lmi_knn_f16: by its own rule, d % 8 == 0)                         */
     LMI_KNN_PLAN_WORKSPACE_BYTES,  /* device bytes the call allocated                                                        */
     LMI_KNN_PLAN_LIST_ROWS,        /* entries of a query's sorted list (LR above)                                            */
     LMI_KNN_PLAN_COUNT
 };
-/* What the last lmi_knn on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
+/* What the last lmi_knn or lmi_knn_f16 on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
  * min(n, LMI_KNN_PLAN_COUNT) words. */
 LMI_API int lmi_debug_knn_plan(int64_t *out, int n);
 
@@ -613,6 +631,16 @@ struct lmi_range_result;
 LMI_API int lmi_knn_range(int device, const float *xq, int64_t nq, const float *xb, int64_t nb, int d, int metric,
                           const float *radius /* HOST [nq], also with on_device */, int64_t max_total,
                           struct lmi_range_result **result, int on_device);
+/* lmi_knn_range on binary16 inputs: xq and xb are halves (bit patterns), both of them; radius stays a HOST float [nq].  What
+ * lmi_knn_f16 is to lmi_knn: the range ground truth of data distributed as 16-bit floats without a widened copy of it (the reference
+ * has no range query; lmi_knn_range's place is taken).  The contract of every *_f16 entry point: the result -- lims, dists, ids, pair
+ * counts -- is bit for bit lmi_knn_range's for the same values widened to binary32, and it is the same lmi_range_result, so _read,
+ * _sort, _pair_counts and _destroy work on it unchanged.  Alignment, the 16-byte rule, the upload (halves) and the geometry as in
+ * lmi_knn_f16; max_total, the refusals and the limits as in lmi_knn_range, with the message naming lmi_knn_range_f16.
+ * lmi_debug_knn_range_plan reports the last call of either form. */
+LMI_API int lmi_knn_range_f16(int device, const uint16_t *xq, int64_t nq, const uint16_t *xb, int64_t nb, int d, int metric,
+                              const float *radius /* HOST [nq], also with on_device */, int64_t max_total,
+                              struct lmi_range_result **result, int on_device);
 enum {
     LMI_KNN_RANGE_PLAN_PIECES = 0,       /* pieces the base was scanned in (0: nb == 0)                                        */
     LMI_KNN_RANGE_PLAN_PIECE_ROWS,       /* rows per piece (the last may be shorter)                                          */
@@ -624,7 +652,7 @@ enum {
     LMI_KNN_RANGE_PLAN_WORKSPACE_BYTES,  /* device bytes the call allocated beside the chunks and the result                  */
     LMI_KNN_RANGE_PLAN_COUNT
 };
-/* What the last lmi_knn_range on this thread did (all zero before the first, after a refused or failed call and after one with
+/* What the last lmi_knn_range or lmi_knn_range_f16 on this thread did (all zero before the first, after a refused or failed call and after one with
  * nq == 0); writes min(n, LMI_KNN_RANGE_PLAN_COUNT) words. */
 LMI_API int lmi_debug_knn_range_plan(int64_t *out, int n);
 

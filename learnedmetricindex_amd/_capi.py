@@ -114,10 +114,14 @@ SIGNATURES = {
                                   ctypes.c_int, _vp, _vp]),
     "lmi_knn": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                _vp, _vp, ctypes.c_int]),
+    "lmi_knn_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   _vp, _vp, ctypes.c_int]),
     "lmi_knn_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "lmi_debug_knn_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_knn_range": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
                                      ctypes.POINTER(_vp), ctypes.c_int]),
+    "lmi_knn_range_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp,
+                                         ctypes.c_int64, ctypes.POINTER(_vp), ctypes.c_int]),
     "lmi_debug_knn_range_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_scan_union": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_search_union": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
@@ -1186,17 +1190,29 @@ def knn_ip(xq, xb, k: int = 10, device: int = 0):
     return D, I
 
 
+def _knn_inputs(who: str, xq, xb):
+    """(is numpy, is float16) of the two arrays of `knn` / `range_knn`: both float32 or both float16 (then the `_f16` entry point takes
+    them as they are: nothing is widened on the host), both numpy or both torch.  Anything else -- one float16 array beside a float32
+    one included -- is a ValueError."""
+    f16 = _is_f16(xq) and _is_f16(xb)
+    dtype = "float16" if f16 else "float32"   # a mixed pair: the float16 array is told that it must be float32
+    is_np = _array_arg(who, "xq", xq, dtype, "2d"), _array_arg(who, "xb", xb, dtype, "2d")
+    if is_np[0] != is_np[1]:
+        raise ValueError(f"{who}: xq and xb must both be numpy arrays or both be torch tensors on the device")
+    return is_np[0], f16
+
+
 def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
     """Exact brute-force k-NN on the device for k up to KNN_MAX_K (`lmi_knn`): (D f32[nq,k], I i64[nq,k]).  metric "ip": the k
     largest inner products, descending; "l2": the k smallest squared Euclidean distances, ascending; ties go to the lower row; fewer
     than k rows pad with I = -1 and D = -FLT_MAX (l2: FLT_MAX).  The same input gives the same result bit for bit
     (include/lmi_hip.h states the arithmetic; oracle.knn_ip / oracle.knn_l2 restate it).  `xq`, `xb`: float32 numpy arrays -- `xb`
     is uploaded in pieces and never resident as a whole -- or contiguous float32 torch tensors on the device, both of one kind; D and
-    I then come back as tensors on that device and the inputs are only read.  Argument errors raise ValueError before the library is
-    loaded."""
-    is_np = _array_arg("knn", "xq", xq, "float32", "2d"), _array_arg("knn", "xb", xb, "float32", "2d")
-    if is_np[0] != is_np[1]:
-        raise ValueError("knn: xq and xb must both be numpy arrays or both be torch tensors on the device")
+    I then come back as tensors on that device and the inputs are only read.  Both float16 (numpy, or contiguous torch.float16 tensors
+    on one device): `lmi_knn_f16` takes the halves as they are -- half the upload, no widened copy anywhere -- and returns bit for bit
+    what the call on the arrays widened to float32 returns.  One float16 array beside a float32 one is refused.  Argument errors raise
+    ValueError before the library is loaded."""
+    is_np, f16 = _knn_inputs("knn", xq, xb)
     if metric not in KNN_METRICS:
         raise ValueError(f"knn: metric {metric!r} unknown ('ip' or 'l2')")
     nq, d, nb, k = int(xq.shape[0]), int(xq.shape[1]), int(xb.shape[0]), int(k)
@@ -1206,11 +1222,12 @@ def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
         raise ValueError(f"knn: d {d} outside [1, 4096]")
     if k < 1 or k > KNN_MAX_K:
         raise ValueError(f"knn: k {k} outside [1, {KNN_MAX_K}]")
-    if is_np[0]:
+    if is_np:
         xq, xb = np.ascontiguousarray(xq), np.ascontiguousarray(xb)
         D = np.empty((nq, k), dtype=np.float32)
         I = np.empty((nq, k), dtype=np.int64)
-        _check(lib().lmi_knn(int(device), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 0))
+        call = lib().lmi_knn_f16 if f16 else lib().lmi_knn
+        _check(call(int(device), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 0))
         return D, I
     if not (xq.is_cuda and xb.is_cuda and xq.is_contiguous() and xb.is_contiguous()) or xq.device != xb.device:
         raise ValueError("knn: torch xq and xb must be contiguous tensors on one device")
@@ -1218,7 +1235,8 @@ def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
 
     D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
     I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
-    _check(lib().lmi_knn(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
+    call = lib().lmi_knn_f16 if f16 else lib().lmi_knn
+    _check(call(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
     return D, I
 
 
@@ -1229,7 +1247,7 @@ def knn_set_geometry(piece_rows: int = 0, splits: int = 0, query_rows: int = 0) 
 
 
 def knn_last_plan() -> dict:
-    """What the last `knn` on this thread did (`lmi_debug_knn_plan`): `KNN_PLAN_FIELDS` -> int."""
+    """What the last `knn` on this thread did, float32 or float16 (`lmi_debug_knn_plan`): `KNN_PLAN_FIELDS` -> int."""
     w = (ctypes.c_int64 * len(KNN_PLAN_FIELDS))()
     _check(lib().lmi_debug_knn_plan(w, len(KNN_PLAN_FIELDS)))
     return dict(zip(KNN_PLAN_FIELDS, (int(v) for v in w)))
@@ -1402,12 +1420,11 @@ def range_knn(xq, xb, radius, metric: str = "ip", max_total: int = 0, device: in
     """Exact brute-force range query on the device (`lmi_knn_range`): the `RangeResult` of, per query, every row of `xb` within
     distance `radius` (a number, or one per query) -- metric "ip": 1 - the inner product, "l2": the squared Euclidean distance, as
     `knn` computes them -- in ascending row order; `ids` are row numbers in `xb`.  A NaN or -inf radius admits nothing.  `xq`, `xb`:
-    float32 numpy arrays or contiguous float32 torch tensors on the device, both of one kind, as `knn` takes them; `radius` stays on
-    the host.  `max_total` > 0: the call fails (LmiError) once more results than that have been counted.  The same input gives the
+    float32 numpy arrays or contiguous float32 torch tensors on the device, both of one kind, as `knn` takes them -- or both float16,
+    which `lmi_knn_range_f16` takes as they are, with the result of the call on the widened arrays bit for bit; `radius` stays on the
+    host.  `max_total` > 0: the call fails (LmiError) once more results than that have been counted.  The same input gives the
     same result bit for bit.  Argument errors raise ValueError before the library is loaded."""
-    is_np = _array_arg("range_knn", "xq", xq, "float32", "2d"), _array_arg("range_knn", "xb", xb, "float32", "2d")
-    if is_np[0] != is_np[1]:
-        raise ValueError("range_knn: xq and xb must both be numpy arrays or both be torch tensors on the device")
+    is_np, f16 = _knn_inputs("range_knn", xq, xb)
     if metric not in KNN_METRICS:
         raise ValueError(f"range_knn: metric {metric!r} unknown ('ip' or 'l2')")
     nq, d, nb = int(xq.shape[0]), int(xq.shape[1]), int(xb.shape[0])
@@ -1423,15 +1440,15 @@ def range_knn(xq, xb, radius, metric: str = "ip", max_total: int = 0, device: in
     if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
         raise ValueError(f"range_knn: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
     r = np.ascontiguousarray(np.broadcast_to(r.astype(np.float32), (nq,)))
-    if is_np[0]:
+    if is_np:
         xq, xb, on_device = np.ascontiguousarray(xq), np.ascontiguousarray(xb), 0
     else:
         if not (xq.is_cuda and xb.is_cuda and xq.is_contiguous() and xb.is_contiguous()) or xq.device != xb.device:
             raise ValueError("range_knn: torch xq and xb must be contiguous tensors on one device")
         device, on_device = _sync_device(xq), 1
     res = _vp()
-    _check(lib().lmi_knn_range(int(device), _ptr(xq), nq, _ptr(xb), nb, d, KNN_METRICS[metric], _ptr(r), int(max_total), ctypes.byref(res),
-                               on_device))
+    call = lib().lmi_knn_range_f16 if f16 else lib().lmi_knn_range
+    _check(call(int(device), _ptr(xq), nq, _ptr(xb), nb, d, KNN_METRICS[metric], _ptr(r), int(max_total), ctypes.byref(res), on_device))
     return RangeResult(res, nq)
 
 

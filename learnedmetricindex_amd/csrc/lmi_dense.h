@@ -6,10 +6,17 @@
 // carry one link more than d: at link d a row of X holds a value the caller gives and a row of F another, so that their product adds
 // one term to the chain (L2: the 1 meets the -|.|^2/2); links past d are zeros.  The link order inside every accumulator is
 // 0, 1, 2, ..: an element of S is the canonical fmaf chain of oracle.knn_ip / knn_l2.
-// The loop that runs the product is written out in km_assign_kernel, again in knn_score_kernel and again in union_score_kernel
-// (lmi_union.h): the three must stay equal (DESIGN.md 5.11 says why it is not a function here).
+// The loop that runs the product is written out in km_assign_kernel, again in knn_score_kernel, again in knn_score16_kernel (lmi_knn.h:
+// the base as halves) and again in union_score_kernel (lmi_union.h): the four must stay equal (DESIGN.md 5.11 says why it is not a
+// function here).
+//
+// Half forms (lmi_knn_f16 / lmi_knn_range_f16: X and the rows F is packed from arrive as binary16 bit patterns): dense_load_b on an
+// unsigned short row, dense_pack16_kernel, dense_norm16_kernel.  Every half is widened by an exact conversion where it is loaded and
+// from there on the arithmetic is the float form's, so the results are those of the widened arrays bit for bit; no row is widened
+// into a buffer.  The float forms are left as they are, instruction for instruction.
 #pragma once
 #include "lmi_kernels.h"
+#include "lmi_prefilter.h"   // half8
 
 namespace lmi {
 
@@ -34,6 +41,19 @@ __global__ void dense_norm_kernel(const float* __restrict__ x, long long n, int 
     out[i] = neg_half ? -0.5f * acc : acc;
 }
 
+// dense_norm_kernel over rows of halves: the same chain over the widened values
+__global__ void dense_norm16_kernel(const unsigned short* __restrict__ x, long long n, int d, int neg_half, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned short* r = x + (size_t)i * d;
+    float acc = 0.0f;
+    for (int t = 0; t < d; ++t) {
+        const float v = (float)__builtin_bit_cast(_Float16, r[t]);
+        acc = __builtin_fmaf(v, v, acc);
+    }
+    out[i] = neg_half ? -0.5f * acc : acc;
+}
+
 // rows [n][d] -> fragment order [nct][KG][64] float4 (rows >= n and links > d: zeros; link d: tailv[row], or `tail` for every row
 // when tailv is null).  One thread per (row, group of 8 links); element loads: any 4-byte aligned src.
 __global__ void dense_pack_kernel(const float* __restrict__ src, const float* __restrict__ tailv, float tail, int n, int d, int nct,
@@ -47,6 +67,24 @@ __global__ void dense_pack_kernel(const float* __restrict__ src, const float* __
     for (int j = 0; j < 8; ++j) {
         const int t = g * 8 + j;
         v[j] = p >= n ? 0.0f : t < d ? src[(size_t)p * d + t] : t == d ? (tailv ? tailv[p] : tail) : 0.0f;
+    }
+    float4* f = dst + ((size_t)(p >> 5) * KG + g) * 64 + (p & 31);
+    f[0] = make_float4(v[0], v[2], v[4], v[6]);
+    f[32] = make_float4(v[1], v[3], v[5], v[7]);
+}
+
+// dense_pack_kernel from rows of halves (no tailv: the callers give one tail for every row).  Element loads: any 2-byte aligned src.
+__global__ void dense_pack16_kernel(const unsigned short* __restrict__ src, float tail, int n, int d, int nct, int KG,
+                                    float4* __restrict__ dst) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)nct * 32 * KG) return;
+    const int g = (int)(idx % KG);
+    const int p = (int)(idx / KG);
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int t = g * 8 + j;
+        v[j] = p >= n ? 0.0f : t < d ? (float)__builtin_bit_cast(_Float16, src[(size_t)p * d + t]) : t == d ? tail : 0.0f;
     }
     float4* f = dst + ((size_t)(p >> 5) * KG + g) * 64 + (p & 31);
     f[0] = make_float4(v[0], v[2], v[4], v[6]);
@@ -80,6 +118,37 @@ __device__ __forceinline__ void dense_load_b(const float* __restrict__ xr, int d
         for (int s = 0; s < 16; ++s) {
             const int t = 32 * ch + 2 * s + h;
             const float v = xr[t < d ? t : 0];
+            b[s] = t < d ? v : t == d ? tail : 0.0f;
+        }
+    }
+}
+
+// dense_load_b for a row of halves.  VEC (d % 8 == 0, x 16-byte aligned: every row then starts on a 16-byte boundary and every group
+// of 8 links that starts below d lies inside the row): the lane's 16 links 32*ch + 16*h .. + 15 are two 16-byte loads of 8 halves,
+// each widened exactly and traded as in the float form; a group that starts at or past d is read at offset 0 and replaced (link d:
+// `tail`), so nothing is read past the row's d halves.  Otherwise sixteen 2-byte loads.
+template <bool VEC>
+__device__ __forceinline__ void dense_load_b(const unsigned short* __restrict__ xr, int d, int ch, int h, float tail, float (&b)[16]) {
+    if constexpr (VEC) {
+        float r[16];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int k0 = 32 * ch + 16 * h + 8 * f;
+            const half8 hv = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(xr + (k0 < d ? k0 : 0)));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[8 * f + j] = k0 < d ? (float)hv[j] : j == 0 && k0 == d ? tail : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r[2 * i]), __float_as_uint(r[2 * i + 1]), false, false);
+            b[i] = __uint_as_float(sw[0]);
+            b[8 + i] = __uint_as_float(sw[1]);
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int t = 32 * ch + 2 * s + h;
+            const float v = (float)__builtin_bit_cast(_Float16, xr[t < d ? t : 0]);
             b[s] = t < d ? v : t == d ? tail : 0.0f;
         }
     }

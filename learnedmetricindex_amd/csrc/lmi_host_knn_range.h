@@ -5,6 +5,7 @@
 // (ONE synchronisation per piece); a chunk of exactly the piece's results is allocated, the offsets go up, emit.  Behind the last group
 // the final arrays are allocated once at lims[nq] and every (query, piece) run is gathered (one descriptor table, one synchronisation).
 // lmi_knn_range, lmi_debug_knn_range_plan.  The result is an lmi_range_result (lmi_host_range.h) with nb = 1.
+// lmi_knn_range_f16 is the same implementation (knn_range_run) on halves, through lmi_host_knn.h's source-type overloads.
 #pragma once
 #include "lmi_host_knn.h"
 #include "lmi_host_range.h"
@@ -25,6 +26,10 @@ lmi_range_result* knn_range_empty(int device, int64_t nq) {
     return r;
 }
 
+template <class T>
+int knn_range_run(const char* who, int device, const T* xq, int64_t nq, const T* xb, int64_t nb, int d, int metric, const float* radius,
+                  int64_t max_total, lmi_range_result** result, int on_device);
+
 }  // namespace
 
 extern "C" LMI_API int lmi_debug_knn_range_plan(int64_t* out, int n) {
@@ -35,34 +40,48 @@ extern "C" LMI_API int lmi_debug_knn_range_plan(int64_t* out, int n) {
 
 extern "C" LMI_API int lmi_knn_range(int device, const float* xq, int64_t nq, const float* xb, int64_t nb, int d, int metric,
                                      const float* radius, int64_t max_total, lmi_range_result** result, int on_device) {
+    return knn_range_run<float>("lmi_knn_range", device, xq, nq, xb, nb, d, metric, radius, max_total, result, on_device);
+}
+
+extern "C" LMI_API int lmi_knn_range_f16(int device, const uint16_t* xq, int64_t nq, const uint16_t* xb, int64_t nb, int d, int metric,
+                                         const float* radius, int64_t max_total, lmi_range_result** result, int on_device) {
+    return knn_range_run<uint16_t>("lmi_knn_range_f16", device, xq, nq, xb, nb, d, metric, radius, max_total, result, on_device);
+}
+
+namespace {
+
+template <class T>
+int knn_range_run(const char* who, int device, const T* xq, int64_t nq, const T* xb, int64_t nb, int d, int metric, const float* radius,
+                  int64_t max_total, lmi_range_result** result, int on_device) {
     namespace kp = lmi_knn_plan;
     namespace krp = lmi_knn_range_plan;
     for (int64_t& w : g_knn_range_last) w = 0;
     if (result) *result = nullptr;
-    if (d < 1 || d > 4096) return fail("lmi_knn_range: d %d outside [1,4096]", d);
-    if (nq < 0 || nq >= (1ll << 31)) return fail("lmi_knn_range: nq %lld outside [0, 2^31)", (long long)nq);
-    if (nb < 0 || nb >= (1ll << 31)) return fail("lmi_knn_range: nb %lld outside [0, 2^31)", (long long)nb);
-    if (metric != LMI_METRIC_IP && metric != LMI_METRIC_L2) return fail("lmi_knn_range: unknown metric %d", metric);
-    if (!result) return fail("lmi_knn_range: the result pointer is NULL");
-    if (nq > 0 && !radius) return fail("lmi_knn_range: radius is NULL");
-    if (nq > 0 && !xq) return fail("lmi_knn_range: xq must not be NULL");
-    if (nq > 0 && nb > 0 && !xb) return fail("lmi_knn_range: xb must not be NULL");
-    if (max_total < 0) return fail("lmi_knn_range: max_total %lld is negative", (long long)max_total);
+    if (d < 1 || d > 4096) return fail("%s: d %d outside [1,4096]", who, d);
+    if (nq < 0 || nq >= (1ll << 31)) return fail("%s: nq %lld outside [0, 2^31)", who, (long long)nq);
+    if (nb < 0 || nb >= (1ll << 31)) return fail("%s: nb %lld outside [0, 2^31)", who, (long long)nb);
+    if (metric != LMI_METRIC_IP && metric != LMI_METRIC_L2) return fail("%s: unknown metric %d", who, metric);
+    if (!result) return fail("%s: the result pointer is NULL", who);
+    if (nq > 0 && !radius) return fail("%s: radius is NULL", who);
+    if (nq > 0 && !xq) return fail("%s: xq must not be NULL", who);
+    if (nq > 0 && nb > 0 && !xb) return fail("%s: xb must not be NULL", who);
+    if (max_total < 0) return fail("%s: max_total %lld is negative", who, (long long)max_total);
     if (nq == 0) {
         *result = knn_range_empty(device, 0);
         return 0;
     }
     hipDeviceProp_t prop;
-    CHK(open_device("lmi_knn_range", device, &prop));
+    CHK(open_device(who, device, &prop));
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
 
     const bool l2 = metric == LMI_METRIC_L2;
-    const krp::Plan P = krp::make_plan(nq, nb, d, l2, on_device != 0, (int64_t)free_b, prop.multiProcessorCount, g_knn_forced);
+    const krp::Plan P = krp::make_plan(nq, nb, d, l2, on_device != 0, (int64_t)free_b, prop.multiProcessorCount, g_knn_forced, (int)sizeof(T));
     const kp::Plan& p = P.g;
     const int KG = p.kg;
-    CallScratch mem("lmi_knn_range"), chunks("lmi_knn_range");
-    float *d_S = nullptr, *d_qn = nullptr, *d_xnh = nullptr, *d_xq = nullptr, *d_xb = nullptr, *d_radius = nullptr;
+    CallScratch mem(who), chunks(who);
+    float *d_S = nullptr, *d_qn = nullptr, *d_xnh = nullptr, *d_radius = nullptr;
+    T *d_xq = nullptr, *d_xb = nullptr;
     float4* d_qf = nullptr;
     int* d_counts = nullptr;
     long long* d_off = nullptr;
@@ -79,7 +98,7 @@ extern "C" LMI_API int lmi_knn_range(int device, const float* xq, int64_t nq, co
     CHK(mem.alloc(&d_off, P.offset_bytes, "stretch offsets"));
     HIPCHK(hipMemcpy(d_radius, radius, (size_t)nq * 4, hipMemcpyHostToDevice));
     // 16-byte loads of the base: as in lmi_knn
-    const bool vec_xb = d % 4 == 0 && (reinterpret_cast<uintptr_t>(on_device ? xb : d_xb) & 15) == 0;
+    const bool vec_xb = knn_vec_xb(on_device ? xb : d_xb, d);
 
     // what a (group, piece) leaves behind for the gather: its chunk and its runs
     struct PieceOut {
@@ -97,28 +116,26 @@ extern "C" LMI_API int lmi_knn_range(int device, const float* xq, int64_t nq, co
         kp::group_range(p, g, &q0, &q1);
         const int gq = (int)(q1 - q0), nct = cdiv(gq, 32), ct = nct >= 3 ? 4 : nct;
         const size_t slots = (size_t)gq * p.splits;
-        const float* gxq = xq + (size_t)q0 * d;
+        const T* gxq = xq + (size_t)q0 * d;
         if (!on_device) {
-            CHK(upload_pieces(d_xq, gxq, (size_t)gq * d * 4));
+            CHK(upload_pieces(d_xq, gxq, (size_t)gq * d * sizeof(T)));
             gxq = d_xq;
         }
-        dense_pack_kernel<<<cdiv((long long)nct * 32 * KG, 256), 256>>>(gxq, nullptr, l2 ? 1.0f : 0.0f, gq, d, nct, KG, d_qf);
-        if (l2) dense_norm_kernel<<<cdiv(gq, 64), 64>>>(gxq, gq, d, 0, d_qn);
+        knn_pack_queries(gxq, l2 ? 1.0f : 0.0f, gq, d, nct, KG, d_qf);
+        if (l2) knn_norms(gxq, gq, d, 0, d_qn);
         HIPCHK(hipGetLastError());
         const float* qn = l2 ? d_qn : nullptr;
         for (int64_t i = 0; i < p.pieces; ++i) {
             int64_t r0, r1;
             kp::piece_range(p, i, &r0, &r1);
             const long long len = r1 - r0;
-            const float* px = xb + (size_t)r0 * d;
+            const T* px = xb + (size_t)r0 * d;
             if (!on_device) {
-                CHK(upload_pieces(d_xb, px, (size_t)len * d * 4));
+                CHK(upload_pieces(d_xb, px, (size_t)len * d * sizeof(T)));
                 px = d_xb;
             }
-            if (l2) dense_norm_kernel<<<cdiv(len, 64), 64>>>(px, len, d, 1, d_xnh);
-            const dim3 grid(cdiv(len, KNN_ROWS), cdiv(nct, ct));
-            if (vec_xb) CHK(knn_score_launch<true>(ct, grid, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));
-            else CHK(knn_score_launch<false>(ct, grid, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));
+            if (l2) knn_norms(px, len, d, 1, d_xnh);
+            CHK(knn_score_piece(vec_xb, ct, px, len, d, l2 ? d_xnh : nullptr, d_qf, KG, nct, gq, d_S, p.pitch));
             knn_range_count_kernel<<<dim3(gq, p.splits), 64>>>(d_S, p.pitch, len, qn, d_radius + q0, d_counts);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpy(counts.data(), d_counts, slots * 4, hipMemcpyDeviceToHost));   // the piece's one synchronisation
@@ -127,9 +144,9 @@ extern "C" LMI_API int lmi_knn_range(int device, const float* xq, int64_t nq, co
             const krp::PieceRuns& R = runs.back();
             counted += krp::add_piece(tot, R);
             if (krp::over_total(counted, max_total))
-                return fail("lmi_knn_range: more than max_total = %lld results: %lld had been counted when the call stopped (group %lld of "
+                return fail("%s: more than max_total = %lld results: %lld had been counted when the call stopped (group %lld of "
                             "%lld, piece %lld of %lld); nothing further was launched",
-                            (long long)max_total, (long long)counted, (long long)g + 1, (long long)p.query_groups, (long long)i + 1,
+                            who, (long long)max_total, (long long)counted, (long long)g + 1, (long long)p.query_groups, (long long)i + 1,
                             (long long)p.pieces);
             if (R.total == 0) continue;
             PieceOut& O = outs.back();
@@ -185,3 +202,5 @@ extern "C" LMI_API int lmi_knn_range(int device, const float* xq, int64_t nq, co
     *result = r;
     return 0;
 }
+
+}  // namespace

@@ -6,6 +6,8 @@
 // piece (dense_load_b; L2: -|x|^2/2 at link d, from dense_norm_kernel), the link order inside every accumulator 0, 1, 2, ..: a score is
 // the canonical chain of oracle.knn_ip / knn_l2.
 // A block writes its 256 rows x 32 CT queries to the slab S[query][row of the piece].
+// knn_score16_kernel is the same kernel for a piece of halves (lmi_knn_f16, lmi_knn_range_f16); everything behind
+// the slab is shared by both.
 // Selection (knn_select_kernel): one wave per (query, split) reads its stretch of the query's slab row, keeps what beats the k-th best
 // so far -- compared as the pair (score, row) -- in an LDS buffer by ballot compaction, and when the buffer is full sorts it and merges
 // it into the sorted list (bitonic, in LDS), which raises the threshold.  The list lives in global memory between launches: the next
@@ -44,6 +46,90 @@ __global__ __launch_bounds__(256) void knn_score_kernel(const float* __restrict_
     if (row0 >= n) return;
     const int ct0 = blockIdx.y * CT;
     const float* xr[KNN_XB];
+    float tl[KNN_XB];
+#pragma unroll
+    for (int b = 0; b < KNN_XB; ++b) {
+        const long long r = row0 + b * 32 + c;
+        const long long rc = r < n ? r : n - 1;   // clamp: duplicates are computed and not written
+        xr[b] = x + (size_t)rc * d;
+        tl[b] = xnh ? xnh[rc] : 0.0f;
+    }
+    const int nch = KG >> 2;
+    f32x16 acc[CT][KNN_XB];
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int b = 0; b < KNN_XB; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][b][r] = 0.0f;
+    const float4* ap[CT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) ap[t] = Qf + (size_t)(ct0 + t < nct ? ct0 + t : nct - 1) * KG * 64 + lane;
+    float bv[KNN_XB][16];
+#pragma unroll
+    for (int b = 0; b < KNN_XB; ++b) dense_load_b<VEC>(xr[b], d, 0, h, tl[b], bv[b]);
+    float4 a[CT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) a[t] = ap[t][0];
+    for (int ch = 0; ch < nch; ++ch) {
+        // the next chunk's rows are requested before this chunk's MFMAs (the last chunk reads itself again)
+        float bn[KNN_XB][16];
+        const int chn = ch + 1 < nch ? ch + 1 : ch;
+#pragma unroll
+        for (int b = 0; b < KNN_XB; ++b) dense_load_b<VEC>(xr[b], d, chn, h, tl[b], bn[b]);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int gn = ch * 4 + g + 1 < KG ? ch * 4 + g + 1 : ch * 4 + g;
+            float4 an[CT];
+#pragma unroll
+            for (int t = 0; t < CT; ++t) an[t] = ap[t][(size_t)gn * 64];
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int t = 0; t < CT; ++t) {
+                    const float av = s == 0 ? a[t].x : s == 1 ? a[t].y : s == 2 ? a[t].z : a[t].w;
+#pragma unroll
+                    for (int b = 0; b < KNN_XB; ++b)
+                        acc[t][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[b][4 * g + s], acc[t][b], 0, 0, 0);
+                }
+#pragma unroll
+            for (int t = 0; t < CT; ++t) a[t] = an[t];
+        }
+#pragma unroll
+        for (int b = 0; b < KNN_XB; ++b)
+#pragma unroll
+            for (int s = 0; s < 16; ++s) bv[b][s] = bn[b][s];
+    }
+    // a lane holds one row of the piece and 16 queries of every tile: 32 lanes write 128 consecutive bytes of a query's slab row
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+        if (ct0 + t >= nct) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int q = (ct0 + t) * 32 + acc_row(r, h);
+            if (q >= nq) continue;
+#pragma unroll
+            for (int b = 0; b < KNN_XB; ++b) {
+                const long long row = row0 + b * 32 + c;
+                if (row < n) S[(size_t)q * pitch + row] = acc[t][b][r];
+            }
+        }
+    }
+}
+
+// knn_score_kernel for a piece of halves (lmi_knn_f16, lmi_knn_range_f16): x [n][d] binary16 bit patterns, widened where they are
+// loaded (dense_load_b's half form; VEC: d % 8 == 0 and x 16-byte aligned).  Grid, block, Qf, xnh and S as there, and the product loop
+// word for word: a score is the chain of the widened row, bit for bit.  A kernel of its own so that the float kernel keeps its
+// instructions (the precedent: ingest16_half_kernel).
+template <int CT, bool VEC>
+__global__ __launch_bounds__(256) void knn_score16_kernel(const unsigned short* __restrict__ x, long long n, int d,
+                                                          const float* __restrict__ xnh, const float4* __restrict__ Qf, int KG, int nct,
+                                                          int nq, float* __restrict__ S, long long pitch) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c = lane & 31;
+    const long long row0 = ((long long)blockIdx.x * 4 + w) * (KNN_XB * 32);
+    if (row0 >= n) return;
+    const int ct0 = blockIdx.y * CT;
+    const unsigned short* xr[KNN_XB];
     float tl[KNN_XB];
 #pragma unroll
     for (int b = 0; b < KNN_XB; ++b) {

@@ -1,6 +1,7 @@
 // lmi_knn_plan.h -- the geometry of one lmi_knn call: how the base is cut into pieces (uploaded or scanned one at a time), a piece into
 // splits (scanned by different waves of one query, their lists merged afterwards), the queries into groups, and the device bytes the
-// call allocates for that.  Host only and pure: the standard library, no HIP call, no kernel header -- lmi_host_knn.h passes the
+// call allocates for that (elem: the bytes of an input element -- 2 for the _f16 forms, whose uploaded queries and piece are halves).
+// Host only and pure: the standard library, no HIP call, no kernel header -- lmi_host_knn.h passes the
 // sizes, the free memory and the forced values in and acts on what comes back; tests/host/knn_plan_selftest.cpp checks it on the CPU.
 //
 // Nothing here can change a result (include/lmi_hip.h, lmi_knn: every score is one unsplit chain and the order is total); the
@@ -26,6 +27,7 @@ struct Forced { int64_t piece_rows = 0; int splits = 0; int64_t query_rows = 0; 
 struct Plan {
     int64_t nq = 0, nb = 0;
     int d = 0, k = 0, l2 = 0, on_device = 0;
+    int elem = 4;             // bytes of an input element: 4 = binary32 (lmi_knn), 2 = binary16 (lmi_knn_f16); sizes xq_bytes and xb_bytes only
     int list_rows = 0;        // entries of a query's sorted list (a power of two >= max(k, MIN_LIST))
     int kg = 0;               // groups of 8 links of a chain: the d links (d + 1 for L2), padded to a multiple of 32
     int64_t piece_rows = 0, pieces = 0;
@@ -53,8 +55,8 @@ inline void size_buffers(Plan& p) {
     p.qfrag_bytes = qp / 32 * p.kg * 1024;
     p.qn_bytes = p.query_rows * 4;
     p.xnh_bytes = p.piece_rows * 4;
-    p.xq_bytes = p.on_device ? 0 : p.query_rows * p.d * 4;
-    p.xb_bytes = p.on_device ? 0 : p.piece_rows * p.d * 4;
+    p.xq_bytes = p.on_device ? 0 : p.query_rows * p.d * p.elem;
+    p.xb_bytes = p.on_device ? 0 : p.piece_rows * p.d * p.elem;
     p.d_bytes = p.on_device ? 0 : p.query_rows * p.k * 4;
     p.i_bytes = p.on_device ? 0 : p.query_rows * p.k * 8;
     p.workspace_bytes = p.slab_bytes + p.list_bytes + p.qfrag_bytes + p.qn_bytes + p.xnh_bytes + p.xq_bytes + p.xb_bytes + p.d_bytes + p.i_bytes;
@@ -62,7 +64,11 @@ inline void size_buffers(Plan& p) {
 
 // (nq, nb, d, k) as lmi_knn accepts them (nq >= 1; nb may be 0).  free_bytes: the device's free memory, 0 = unknown; cus: its compute
 // units.  With host pointers nothing that is allocated depends on nb: a piece is sized by the queries, d and the memory alone.
-inline Plan make_plan(int64_t nq, int64_t nb, int d, int k, bool l2, bool on_device, int64_t free_bytes, int cus, const Forced& f) {
+// elem (4 or 2): the geometry -- piece rows, pieces, splits, groups, pitch, lists -- is made for binary32 inputs whatever elem is, short
+// memory included, so that a call on halves is cut exactly as the call on the widened arrays; only xq_bytes, xb_bytes and with them
+// workspace_bytes follow elem.
+inline Plan make_plan(int64_t nq, int64_t nb, int d, int k, bool l2, bool on_device, int64_t free_bytes, int cus, const Forced& f,
+                      int elem = 4) {
     Plan p;
     p.nq = nq; p.nb = nb; p.d = d; p.k = k; p.l2 = l2; p.on_device = on_device;
     p.list_rows = list_rows_for(k);
@@ -96,6 +102,10 @@ inline Plan make_plan(int64_t nq, int64_t nb, int d, int k, bool l2, bool on_dev
     }
     p.pieces = cdiv(nb, p.piece_rows);
     p.query_groups = cdiv(nq, p.query_rows);
+    if (elem != p.elem) {
+        p.elem = elem;
+        size_buffers(p);
+    }
     return p;
 }
 

@@ -33,9 +33,11 @@ struct Plan {
 // (nq, nb, d) as lmi_knn_range accepts them (nq >= 1; nb may be 0); free_bytes, cus, f: as lmi_knn_plan::make_plan takes them.  The
 // geometry is lmi_knn's at k = 1 -- memory that is short shrinks pieces and groups exactly as there, judged with that call's lists
 // counted in, which errs on the safe side -- and the bytes are this call's own.
-inline Plan make_plan(int64_t nq, int64_t nb, int d, bool l2, bool on_device, int64_t free_bytes, int cus, const kp::Forced& f) {
+// elem: the bytes of an input element, as there (2: lmi_knn_range_f16).
+inline Plan make_plan(int64_t nq, int64_t nb, int d, bool l2, bool on_device, int64_t free_bytes, int cus, const kp::Forced& f,
+                      int elem = 4) {
     Plan p;
-    p.g = kp::make_plan(nq, nb, d, PLAN_K, l2, on_device, free_bytes, cus, f);
+    p.g = kp::make_plan(nq, nb, d, PLAN_K, l2, on_device, free_bytes, cus, f, elem);
     p.g.list_bytes = p.g.d_bytes = p.g.i_bytes = 0;
     p.radius_bytes = nq * 4;
     p.count_bytes = p.g.query_rows * p.g.splits * 4;

@@ -295,9 +295,14 @@ def range_recall(lims_found, ids_found, lims_true, ids_true) -> float:
 
 def range_truth(queries: np.ndarray, objects: pd.DataFrame, radius: float, sample: int = 1000):
     """(lims, object ids) of the exhaustive range query (`lmi_knn_range`) of the first `sample` queries over the scan vectors AS THE
-    INDEX HOLDS THEM -- not re-normalised: a radius is an absolute distance.  Rows map to ids through `objects.index`."""
+    INDEX HOLDS THEM -- not re-normalised: a radius is an absolute distance.  Rows map to ids through `objects.index`.
+    Where the frame and the queries are both held as float16 (`--storage f16` on files of 16-bit floats) they go to the call as
+    halves (`lmi_knn_range_f16`: the same result bit for bit, and no float32 copy of the data on the host); otherwise as float32.
+    (The top-k truth of `recall_against_bruteforce` cannot do the same: `li.Baseline` re-normalises its rows in float32.)"""
     m = min(sample, queries.shape[0])
-    with _capi.range_knn(np.ascontiguousarray(queries[:m], dtype=np.float32), objects.to_numpy(dtype=np.float32), radius, metric="ip") as res:
+    f16 = queries.dtype == np.float16 and bool((objects.dtypes == np.float16).all())
+    dtype = np.float16 if f16 else np.float32
+    with _capi.range_knn(np.ascontiguousarray(queries[:m], dtype=dtype), objects.to_numpy(dtype=dtype), radius, metric="ip") as res:
         _, rows = res.read()
         return res.lims, objects.index.to_numpy()[rows.astype(np.int64)]
 

@@ -13,7 +13,12 @@ call; median (min .. max) in ms, FLOP/s = 2 * nq * nb * d / median, and its shar
 The split between the score, selection and merge kernels comes from a kernel trace of `--trace-run` (this program started with
 that flag runs only the device legs, once each after a warm-up, for a profiler to watch).
 
-  python tools/knn_bench.py [--nb 1000000] [--d 768] [--nq 10000] [--ks 10 100 1024] [--reps 5] [--out profiles/knn.txt]
+--f16: the binary16 form (lmi_knn_f16) beside the binary32 one.  The rows are narrowed once (`astype(float16)` of the same draw); the
+"knn16" legs take the halves, the "knn" legs the same values widened, so both forms do the same arithmetic and return the same bits
+(checked on the warm-up); the legs of the two forms alternate, and the yardsticks (a) and (b) are left out.  Per pair of legs the
+table adds f16 / f32, and per form the host leg minus the device leg: the upload and the staging the host arrays cost.
+
+  python tools/knn_bench.py [--nb 1000000] [--d 768] [--nq 10000] [--ks 10 100 1024] [--reps 5] [--f16] [--out profiles/knn.txt]
 
 Prints a table and one JSON line; --out also writes both to a file.  No gate: the feature is the capability.  Not a yardstick:
 bench.py is.
@@ -54,6 +59,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=2023)
     ap.add_argument("--no-host", action="store_true", help="skip the legs that upload from host arrays")
+    ap.add_argument("--f16", action="store_true", help="lmi_knn_f16 on the rows narrowed once beside lmi_knn on the same values widened")
     ap.add_argument("--trace-run", action="store_true", help="only the device legs, once each (for a kernel trace)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -64,11 +70,16 @@ def main():
     db = torch.randn((a.nb, a.d), generator=gen, device="cuda", dtype=torch.float32)
     dq = torch.randn((a.nq, a.d), generator=gen, device="cuda", dtype=torch.float32)
     flop = 2.0 * a.nq * a.nb * a.d
+    if a.f16:
+        db16, dq16 = db.half(), dq.half()
+        db, dq = db16.float(), dq16.float()
 
     legs = {}
     for metric in ("ip", "l2"):
         for k in a.ks:
             legs[f"knn device {metric} k={k}"] = (lambda metric=metric, k=k: _capi.knn(dq, db, k, metric))
+            if a.f16:
+                legs[f"knn16 device {metric} k={k}"] = (lambda metric=metric, k=k: _capi.knn(dq16, db16, k, metric))
     if a.trace_run:
         for name, fn in legs.items():
             fn()
@@ -77,11 +88,18 @@ def main():
         return
 
     xb, xq = db.cpu().numpy(), dq.cpu().numpy()
+    if a.f16:
+        xb16, xq16 = xb.astype(np.float16), xq.astype(np.float16)
     if not a.no_host:
         for metric in ("ip", "l2"):
             for k in a.ks:
                 legs[f"knn host {metric} k={k}"] = (lambda metric=metric, k=k: _capi.knn(xq, xb, k, metric))
-        legs["(a) knn_ip host k=10"] = lambda: _capi.knn_ip(xq, xb, 10)
+                if a.f16:
+                    legs[f"knn16 host {metric} k={k}"] = (lambda metric=metric, k=k: _capi.knn(xq16, xb16, k, metric))
+        if not a.f16:
+            legs["(a) knn_ip host k=10"] = lambda: _capi.knn_ip(xq, xb, 10)
+    if a.f16:
+        return report_f16(a, legs, flop)
     # (b): the all-f32 scan of a resident one-bucket index
     idx = _capi.Index(0, prefilter=False)
     idx.set_buckets(xb, np.zeros(a.nb, dtype=np.int64), 1)
@@ -140,6 +158,55 @@ def main():
         with open(a.out, "w") as fh:
             fh.write(text + "\n")
     idx.close()
+
+
+def report_f16(a, legs, flop):
+    """The --f16 run: warm-up (the two forms must agree bit for bit), timed runs with the legs alternated, the table."""
+    import torch
+
+    plans, first = {}, {}
+    for name, fn in legs.items():
+        D, I = fn()
+        plans[name] = _capi.knn_last_plan()
+        first[name] = (np.asarray(D.cpu() if hasattr(D, "cpu") else D).view(np.uint32), np.asarray(I.cpu() if hasattr(I, "cpu") else I))
+    for name in legs:
+        if name.startswith("knn16 "):
+            ref = first["knn " + name[len("knn16 "):]]
+            assert np.array_equal(first[name][0], ref[0]) and np.array_equal(first[name][1], ref[1]), f"{name} differs from the binary32 leg"
+    del first
+    times = {name: [] for name in legs}
+    for _ in range(a.reps):
+        for name, fn in legs.items():
+            _, ms = wall(fn)
+            times[name].append(ms)
+    med = {n: statistics.median(v) for n, v in times.items()}
+    lines = [f"# tools/knn_bench.py --f16: base {a.nb} x {a.d}, {a.nq} queries, {a.reps} timed runs per leg after one warm-up, legs alternated",
+             "# knn16: lmi_knn_f16 on the rows narrowed once; knn: lmi_knn on the same values widened; the warm-up results agree bit for bit",
+             f"# library: {_capi.lib().lmi_build_info().decode()}",
+             f"# device: {torch.cuda.get_device_name(0)}; 2 * nq * nb * d = {flop:.3e} FLOP; f32 MFMA peak {PEAK_F32_MFMA / 1e12:.1f} TFLOP/s",
+             "# leg | ms median (min .. max) | TFLOP/s | share of peak"]
+    for n, v in times.items():
+        lines.append(f"{n:38s} | {med[n]:9.2f} ({min(v):.2f} .. {max(v):.2f}) | {flop / med[n] / 1e9:7.2f} | {flop / med[n] * 1e3 / PEAK_F32_MFMA:6.1%}")
+    result = {"nb": a.nb, "d": a.d, "nq": a.nq, "median_ms": med, "f16_over_f32": {}}
+    for n in legs:
+        if n.startswith("knn16 "):
+            n32 = "knn " + n[len("knn16 "):]
+            result["f16_over_f32"][n32] = med[n] / med[n32]
+            lines.append(f"# {n} / {n32}: {med[n] / med[n32]:.3f}   ({med[n]:.2f} ms against {med[n32]:.2f} ms, whose own max is {max(times[n32]):.2f})")
+    if not a.no_host:
+        for form in ("knn", "knn16"):
+            for metric in ("ip", "l2"):
+                for k in a.ks:
+                    h, dv = f"{form} host {metric} k={k}", f"{form} device {metric} k={k}"
+                    lines.append(f"# {form} {metric} k={k}: host - device = {med[h] - med[dv]:.2f} ms")
+    for n, p in plans.items():
+        lines.append(f"# plan of {n}: {p}")
+    lines.append(json.dumps(result))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
 
 
 if __name__ == "__main__":

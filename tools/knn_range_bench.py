@@ -14,7 +14,11 @@ synchronising call, result read-back not included (the result stays on the devic
 (min .. max) in ms.  The split between the score, count, emit and gather kernels comes from a kernel trace of `--trace-run` (this
 program started with that flag runs only the device legs, once each after a warm-up, for a profiler to watch).
 
-  python tools/knn_range_bench.py [--nb 1000000] [--d 768] [--nq 10000] [--targets 10 1000] [--reps 5] [--out FILE]
+--f16: the binary16 forms (lmi_knn_range_f16, lmi_knn_f16) beside the binary32 ones.  The rows are narrowed once; the "range16" /
+"knn16" legs take the halves, the others the same values widened (the radii are made on those), so both forms admit the same results;
+the legs of the two forms alternate.
+
+  python tools/knn_range_bench.py [--nb 1000000] [--d 768] [--nq 10000] [--targets 10 1000] [--reps 5] [--f16] [--out FILE]
 
 Prints a table and one JSON line; --out also writes both to a file.  No gate.  Not a yardstick: bench.py is.
 """
@@ -40,6 +44,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=2023)
     ap.add_argument("--no-host", action="store_true", help="skip the legs that upload from host arrays")
+    ap.add_argument("--f16", action="store_true", help="the _f16 forms on the rows narrowed once beside the binary32 forms on the same values widened")
     ap.add_argument("--trace-run", action="store_true", help="only the device legs, once each after a warm-up (for a kernel trace)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -50,12 +55,16 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     db = torch.randn((a.nb, a.d), generator=gen, device="cuda", dtype=torch.float32)
     dq = torch.randn((a.nq, a.d), generator=gen, device="cuda", dtype=torch.float32)
+    if a.f16:
+        db16, dq16 = db.half(), dq.half()
+        db, dq = db16.float(), dq16.float()
     D, _ = _capi.knn(dq, db, max(a.targets), "ip")
     radii = {t: (1.0 - D[:, t - 1]).cpu().numpy() for t in a.targets}
     del D
     if a.trace_run:
         a.no_host = True
     xb, xq = (None, None) if a.no_host else (db.cpu().numpy(), dq.cpu().numpy())
+    xb16, xq16 = (xb.astype("float16"), xq.astype("float16")) if a.f16 and not a.no_host else (None, None)
 
     plans, results = {}, {}
 
@@ -85,11 +94,16 @@ def main():
         return run
 
     legs = {}
-    for kind, q, x in (("device", dq, db),) + (() if a.no_host else (("host", xq, xb),)):
+    for kind, q, x, q16, x16 in (("device", dq, db, dq16 if a.f16 else None, db16 if a.f16 else None),) + (() if a.no_host else (("host", xq, xb, xq16, xb16),)):
         legs[f"knn {kind} k=10"] = timed(knn_leg(q, x))
+        if a.f16:
+            legs[f"knn16 {kind} k=10"] = timed(knn_leg(q16, x16))
         for t in a.targets:
             name = f"range {kind} ~{t}/query"
             legs[name] = range_leg(name, q, x, t)
+            if a.f16:
+                name = f"range16 {kind} ~{t}/query"
+                legs[name] = range_leg(name, q16, x16, t)
     if a.trace_run:
         for name, fn in legs.items():
             fn()
@@ -105,15 +119,28 @@ def main():
             times[name].append(fn())
 
     med = {n: statistics.median(v) for n, v in times.items()}
-    lines = [f"# tools/knn_range_bench.py: base {a.nb} x {a.d}, {a.nq} queries, inner product, {a.reps} timed runs per leg after one warm-up, legs alternated",
+    lines = [f"# tools/knn_range_bench.py{' --f16' if a.f16 else ''}: base {a.nb} x {a.d}, {a.nq} queries, inner product, {a.reps} timed runs per leg after one warm-up, legs alternated",
              f"# library: {_capi.lib().lmi_build_info().decode()}",
              f"# device: {torch.cuda.get_device_name(0)}",
              "# leg | ms median (min .. max) | results | ratio to knn k=10 of the same pointer kind"]
     result = {"nb": a.nb, "d": a.d, "nq": a.nq, "median_ms": med, "ratio": {}, "results": results}
     for n, v in times.items():
-        base = med[f"knn {n.split()[1]} k=10"]
+        base = med[f"knn{'16' if n.split()[0].endswith('16') else ''} {n.split()[1]} k=10"]   # the knn leg of the same form
         result["ratio"][n] = med[n] / base
         lines.append(f"{n:28s} | {med[n]:9.2f} ({min(v):.2f} .. {max(v):.2f}) | {results.get(n, a.nq * 10):11d} | {med[n] / base:6.3f}")
+    if a.f16:
+        result["f16_over_f32"] = {}
+        for n in legs:
+            if n.split()[0] in ("knn16", "range16"):
+                n32 = n.replace("16 ", " ", 1)
+                assert results.get(n) == results.get(n32), f"{n} admits {results.get(n)} results, {n32} {results.get(n32)}"
+                result["f16_over_f32"][n32] = med[n] / med[n32]
+                lines.append(f"# {n} / {n32}: {med[n] / med[n32]:.3f}   ({med[n]:.2f} ms against {med[n32]:.2f} ms, whose own max is {max(times[n32]):.2f})")
+        for form in ("", "16"):
+            for n in legs:
+                if n.split()[0] == "knn" + form or n.split()[0] == "range" + form:
+                    if " host " in n:
+                        lines.append(f"# {n}: host - device = {med[n] - med[n.replace(' host ', ' device ')]:.2f} ms")
     for n, p in plans.items():
         lines.append(f"# plan of {n}: {p}")
     lines.append(json.dumps(result))
