@@ -347,7 +347,9 @@ LMI_API int lmi_bucket_read(lmi_index *h, int bucket, float *rows, uint32_t *ids
  *        piece can only fail it by inf / NaN or by the scale).
  * lmi_buckets_insert_f16: as lmi_buckets_insert, its checks and refusals included (an LMI_STORAGE_F16 index is refused).
  * lmi_knn_f16 / lmi_knn_range_f16 (declared beside lmi_knn and lmi_knn_range below): the exact ground truths on queries AND base
- *        as halves; the same contract, and the base is never widened into a buffer. */
+ *        as halves; the same contract, and the base is never widened into a buffer.
+ * lmi_kmeans_f16 / lmi_train_f16 / lmi_mlp_topk_f16 (declared beside their namesakes below): the index build -- clustering, training
+ *        and the placement check -- on rows as halves; the same contract. */
 LMI_API int lmi_buckets_add_rows_f16(lmi_index *h, const uint16_t *rows, int64_t row0, int64_t nrows, int on_device);
 LMI_API int lmi_buckets_add_owned_rows_f16(lmi_index *h, const uint16_t *rows, const int64_t *index, int64_t nrows,
                                    int on_device);
@@ -402,6 +404,12 @@ LMI_API int lmi_search_f16(lmi_index *h, const uint16_t *queries_nav, const uint
                    int k, float *dists, uint32_t *ids, uint32_t *keys, int32_t *bucket_order, int on_device);
 LMI_API int lmi_search_tree_f16(lmi_index *h, const uint16_t *queries_nav, const uint16_t *queries_search, int nq, int nb, int k,
                         float *dists, uint32_t *ids, uint32_t *keys, int32_t *slab_ids, int32_t *entries, int on_device);
+/* lmi_mlp_topk with queries_nav as halves, by the same front as lmi_search_f16: host halves are uploaded as they are and widened on the
+ * device into the handle's buffer, device halves (2-byte aligned; only read) are widened from where they lie.  bucket_order and
+ * logits are those of lmi_mlp_topk on the widened queries, bit for bit; refusals as there, naming lmi_mlp_topk_f16.  The placement
+ * check of an index build on halves goes through this call.  There is no lmi_mlp_proba_f16. */
+LMI_API int lmi_mlp_topk_f16(lmi_index *h, const uint16_t *queries_nav, int nq, int nb, int32_t *bucket_order,
+                     float *logits, int on_device);
 
 /* Multi-GPU: gathered_{dists,ids,keys}[w] is rank w's lmi_scan_topk output [nq][kout], found
  * world_stride elements after rank w-1's (0 -> dense, nq*kout; a packed all-gather of
@@ -481,6 +489,23 @@ LMI_API int lmi_kmeans(int device, const float *x, int64_t n, int d, int k, int 
                        int64_t *counts /* [k] host, nullable */, int64_t *changed /* [niter+1] host, nullable */,
                        int on_device);
 
+/* lmi_kmeans with x [n][d] given as binary16 bit patterns (2-byte alignment is enough, host or device): the index build's clustering
+ * on data that is distributed as 16-bit floats, without a widened copy of it on the host or in device memory.  centroids stay binary32,
+ * in and out: means are not halves.  The contract is lmi_kmeans's, word for word, on the widened values -- the key, the tie rule, e,
+ * q(v), the int64 sums, the division, the schedule, the fixed-point stop: widening a half is exact, so centroids, labels, counts and
+ * changed are bit for bit what lmi_kmeans returns on the widened array.  e is that of the widened array too, also where every value
+ * is a binary16 subnormal (the maximal half is widened on the host; e comes from the same frexp).
+ * Host pointers: x goes up once, as halves, in pieces, and stays resident as halves.  Device pointers: x is read where it is; 16-byte
+ * loads are used only where d % 8 == 0 and x is 16-byte aligned, 2-byte loads otherwise.
+ * Bounds and refusals: lmi_kmeans's, naming lmi_kmeans_f16; a half that is inf or NaN (bits & 0x7fff >= 0x7c00) is the value that is
+ * not finite.  Nothing is written by a refused call.
+ * Peak device memory: lmi_kmeans's with 2nd in place of 4nd: 8n + k' * (8d + 4 * roundup(d+1, 32) + 12) with k' = roundup(k, 32)
+ * + 8 * (niter + 2); with host pointers 2nd + 4kd + 4n more for x, the centroids and the labels. */
+LMI_API int lmi_kmeans_f16(int device, const uint16_t *x, int64_t n, int d, int k, int niter,
+                           float *centroids /* [k][d] binary32, in: initial, out: final */, int32_t *labels /* [n] out */,
+                           int64_t *counts /* [k] host, nullable */, int64_t *changed /* [niter+1] host, nullable */,
+                           int on_device);
+
 /* Adam steps on a Linear/ReLU stack with the cross-entropy loss, on the device, deterministic (replaces the training stage of the
  * index build: NeuralNetwork.train_batch, li/model.py:185-211, whose epoch is ONE optimizer step on its last mini-batch).  The same
  * input gives the same parameters and moments bit for bit on any launch geometry; tests/train_ref.py restates the call in numpy on
@@ -524,6 +549,21 @@ LMI_API int lmi_train(int device, const float *x, int64_t n, const int32_t *labe
                       int64_t *t /* host; in: steps taken so far, out: += n_steps; NULL: 0 */,
                       const int64_t *batch_rows /* host, [n_steps][bsz] */, int n_steps, int bsz,
                       double lr, float *losses /* host [n_steps], nullable */, int on_device /* covers x and labels */);
+
+/* lmi_train with x [n][dims[0]] given as binary16 bit patterns (2-byte alignment is enough).  The named rows are widened, exactly,
+ * into the same binary32 batch buffer lmi_train fills; from there on nothing differs -- same kernels, same finite check, same results,
+ * losses included: everything the call returns is bit for bit what lmi_train returns on the widened array.
+ * Device pointers: the named rows are gathered and widened by one kernel, label check included.  Host pointers: the named rows are
+ * gathered as halves on the host in pieces of the same byte budget (64 MiB), uploaded as halves -- half the bytes -- and widened on
+ * the device.  An unnamed row may hold anything; a named row with a half that is inf or NaN is refused by the finite check.
+ * Refusals and limits: lmi_train's, naming lmi_train_f16.
+ * Peak device memory: lmi_train's; with host pointers + min(64 MiB, 2 * n_steps * bsz * dims[0]) for the piece of halves. */
+LMI_API int lmi_train_f16(int device, const uint16_t *x, int64_t n, const int32_t *labels /* [n][dims[0]], [n] */,
+                          int n_layers, const int *dims, float *const *W, float *const *b /* host; in: initial, out: trained */,
+                          float *const *adam /* host, [4*n_layers], in/out; NULL: zeros in, discarded */,
+                          int64_t *t /* host; in: steps taken so far, out: += n_steps; NULL: 0 */,
+                          const int64_t *batch_rows /* host, [n_steps][bsz] */, int n_steps, int bsz,
+                          double lr, float *losses /* host [n_steps], nullable */, int on_device /* covers x and labels */);
 
 /* Exact brute-force k-NN on the device for k up to LMI_KNN_MAX_K, deterministic (faiss.knn(xq, xb, k, metric) with any k: the
  * ground truth of the reference's Baseline, li/Baseline.py:7-21, and of recall@k).  Its k has nothing to do with the bucket scan's

@@ -170,6 +170,12 @@ SIGNATURES = {
                                   ctypes.c_int]),
     "lmi_train": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                  ctypes.POINTER(_vp), _i64p, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, ctypes.c_int]),
+    # the index build on binary16 rows (arguments as the namesakes')
+    "lmi_kmeans_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                      ctypes.c_int]),
+    "lmi_train_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                     ctypes.POINTER(_vp), _i64p, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, ctypes.c_int]),
+    "lmi_mlp_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_timings": (ctypes.c_int, [_vp, _vp]),
     "lmi_timings_reset": (ctypes.c_int, [_vp]),
     "lmi_set_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -701,10 +707,12 @@ class Index:
 
     # ---- query path, host arrays ------------------------------------------------------------
     def mlp_topk(self, queries_nav, nb: int, want_logits: bool = False):
-        q = _np(queries_nav, np.float32)
+        f16 = _is_f16(queries_nav)   # float16 queries are uploaded as halves (lmi_mlp_topk_f16) and widened on the device
+        q = _np(queries_nav, np.float16 if f16 else np.float32)
         order = np.empty((q.shape[0], nb), dtype=np.int32)
         logits = np.empty((q.shape[0], self.n_classes), dtype=np.float32) if want_logits else None
-        _check(lib().lmi_mlp_topk(self._h, _ptr(q), q.shape[0], int(nb), _ptr(order), _ptr(logits), 0))
+        fn = lib().lmi_mlp_topk_f16 if f16 else lib().lmi_mlp_topk
+        _check(fn(self._h, _ptr(q), q.shape[0], int(nb), _ptr(order), _ptr(logits), 0))
         return (order, logits) if want_logits else order
 
     def mlp_proba(self, queries_nav):
@@ -1067,7 +1075,9 @@ class Index:
                                 _ptr(i_t), _ptr(keys_t), _ptr(bo_t), 1))
 
     def mlp_topk_device(self, qn_t, nb: int, bo_t, logits_t=None) -> None:
-        _check(lib().lmi_mlp_topk(self._h, _ptr(qn_t), int(qn_t.shape[0]), int(nb), _ptr(bo_t), _ptr(logits_t), 1))
+        """A contiguous torch.float16 query tensor -> `lmi_mlp_topk_f16` (any 2-byte-aligned address)."""
+        fn = lib().lmi_mlp_topk_f16 if _device_f16(qn_t, qn_t) else lib().lmi_mlp_topk
+        _check(fn(self._h, _ptr(qn_t), int(qn_t.shape[0]), int(nb), _ptr(bo_t), _ptr(logits_t), 1))
 
     def scan_topk_device(self, qs_t, bo_t, nb: int, k: int, d_t, i_t, keys_t=None) -> None:
         fn = lib().lmi_scan_topk_f16 if _device_f16(qs_t, qs_t) else lib().lmi_scan_topk
@@ -1559,10 +1569,13 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
     """Lloyd's k-means on the device (`lmi_kmeans`): (centroids f32[k,d], labels i32[n], counts i64[k], changed i64[niter+1]).
     The same input gives the same result bit for bit (include/lmi_hip.h states the arithmetic; tests/kmeans_ref.py restates it).
     `x`: a float32 numpy array [n,d], or a contiguous float32 torch tensor on the device -- then `centroids` and `labels` come back
-    as tensors on that device and `x` is only read.  `init`: f32 [k,d] initial centroids; None: the rows
-    `np.random.RandomState(seed).choice(n, k, replace=False)` of `x`.  `changed[it]`: rows whose label moved in pass `it`
-    (zeros behind a fixed point).  Argument errors raise ValueError before the library is loaded."""
-    is_np = _array_arg("kmeans", "x", x, "float32", "nd")
+    as tensors on that device and `x` is only read.  A float16 `x` (numpy, or a contiguous torch.float16 tensor on the device) goes to
+    `lmi_kmeans_f16` as it is -- half the upload, resident as halves, no widened copy anywhere -- and the result is bit for bit that of
+    the call on `x` widened to float32; the centroids are float32 either way.  `init`: f32 [k,d] initial centroids; None: the rows
+    `np.random.RandomState(seed).choice(n, k, replace=False)` of `x`, widened to float32.  `changed[it]`: rows whose label moved in
+    pass `it` (zeros behind a fixed point).  Argument errors raise ValueError before the library is loaded."""
+    f16 = _is_f16(x)
+    is_np = _array_arg("kmeans", "x", x, "float16" if f16 else "float32", "nd")
     n, d = int(x.shape[0]), int(x.shape[1])
     k, niter = int(k), int(niter)
     if k < 1 or k > n:
@@ -1579,7 +1592,8 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
         x = np.ascontiguousarray(x)
         cent = np.array(x[np.random.RandomState(seed).choice(n, k, replace=False)] if init is None else init, dtype=np.float32, order="C")
         labels = np.empty(n, dtype=np.int32)
-        _check(lib().lmi_kmeans(int(device), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 0))
+        call = lib().lmi_kmeans_f16 if f16 else lib().lmi_kmeans
+        _check(call(int(device), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 0))
         return cent, labels, counts, changed
     if not x.is_cuda or not x.is_contiguous():
         raise ValueError("kmeans: a torch x must be a contiguous tensor on the device")
@@ -1587,11 +1601,12 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
 
     if init is None:
         rows = torch.from_numpy(np.random.RandomState(seed).choice(n, k, replace=False)).to(x.device)
-        cent = x[rows].clone()
+        cent = x[rows].to(torch.float32)   # a copy either way: indexing gathers
     else:
         cent = torch.from_numpy(np.array(init, dtype=np.float32, order="C")).to(x.device)
     labels = torch.empty(n, dtype=torch.int32, device=x.device)
-    _check(lib().lmi_kmeans(_sync_device(x), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
+    call = lib().lmi_kmeans_f16 if f16 else lib().lmi_kmeans
+    _check(call(_sync_device(x), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
     return cent, labels, counts, changed
 
 
@@ -1601,12 +1616,15 @@ def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0)
     `layers` = [(W [out,in], b [out]), ...] the initial parameters (copied, not changed); `batch_rows` int64 [n_steps, bsz]: the rows
     step s trains on; `state` = (adam, t) as returned by an earlier call -- adam = [m(W_0), v(W_0), m(b_0), v(b_0), m(W_1), ...], t the
     Adam steps taken so far -- or None: zeros.  `losses` f32 [n_steps].  The same input gives the same parameters and moments bit for bit
-    (include/lmi_hip.h states the arithmetic; tests/train_ref.py restates it).  Argument errors raise ValueError before the library is
-    loaded."""
+    (include/lmi_hip.h states the arithmetic; tests/train_ref.py restates it).  A float16 `x` (numpy, or a contiguous torch.float16
+    tensor on the device) goes to `lmi_train_f16` as it is -- the named rows are uploaded as halves and widened on the device -- and
+    everything returned, losses included, is bit for bit that of the call on `x` widened to float32.  Argument errors raise ValueError
+    before the library is loaded."""
     is_np = _array_arg("train", "x", x)
     if isinstance(labels, np.ndarray) != is_np:
         raise ValueError("train: x and labels must both be numpy arrays or both be tensors on the device")
-    _array_arg("train", "x", x, "float32")
+    f16 = _is_f16(x)
+    _array_arg("train", "x", x, "float16" if f16 else "float32")
     _array_arg("train", "labels", labels, "int32", kind=False)
     _array_arg("train", "x", x, rank="nd")
     n, d = int(x.shape[0]), int(x.shape[1])
@@ -1648,6 +1666,7 @@ def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0)
     Wp = (_vp * nl)(*[W.ctypes.data for W in Ws])
     bp = (_vp * nl)(*[b.ctypes.data for b in bs])
     ap = (_vp * (4 * nl))(*[a.ctypes.data for a in adam])
-    _check(lib().lmi_train(int(device), _ptr(x), n, _ptr(labels), nl, dims_c, Wp, bp, ap, ctypes.byref(t), _ptr(rows), n_steps, bsz,
-                           float(lr), _ptr(losses), on_device))
+    call = lib().lmi_train_f16 if f16 else lib().lmi_train
+    _check(call(int(device), _ptr(x), n, _ptr(labels), nl, dims_c, Wp, bp, ap, ctypes.byref(t), _ptr(rows), n_steps, bsz,
+                float(lr), _ptr(losses), on_device))
     return list(zip(Ws, bs)), (adam, int(t.value)), losses

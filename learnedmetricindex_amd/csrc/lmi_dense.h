@@ -6,12 +6,12 @@
 // carry one link more than d: at link d a row of X holds a value the caller gives and a row of F another, so that their product adds
 // one term to the chain (L2: the 1 meets the -|.|^2/2); links past d are zeros.  The link order inside every accumulator is
 // 0, 1, 2, ..: an element of S is the canonical fmaf chain of oracle.knn_ip / knn_l2.
-// The loop that runs the product is written out in km_assign_kernel, again in knn_score_kernel, again in knn_score16_kernel (lmi_knn.h:
-// the base as halves) and again in union_score_kernel (lmi_union.h): the four must stay equal (DESIGN.md 5.11 says why it is not a
-// function here).
+// The loop that runs the product is written out in km_assign_kernel, again in km_assign16_kernel (lmi_kmeans.h: the rows as halves),
+// again in knn_score_kernel, again in knn_score16_kernel (lmi_knn.h: the base as halves) and again in union_score_kernel (lmi_union.h):
+// the five must stay equal (DESIGN.md 5.11 says why it is not a function here).
 //
-// Half forms (lmi_knn_f16 / lmi_knn_range_f16: X and the rows F is packed from arrive as binary16 bit patterns): dense_load_b on an
-// unsigned short row, dense_pack16_kernel, dense_norm16_kernel.  Every half is widened by an exact conversion where it is loaded and
+// Half forms (lmi_knn_f16 / lmi_knn_range_f16: X and the rows F is packed from arrive as binary16 bit patterns; lmi_kmeans_f16: X
+// does): dense_load_b on an unsigned short row, dense_pack16_kernel, dense_norm16_kernel, dense_absmax16_kernel.  Every half is widened by an exact conversion where it is loaded and
 // from there on the arithmetic is the float form's, so the results are those of the widened arrays bit for bit; no row is widened
 // into a buffer.  The float forms are left as they are, instruction for instruction.
 #pragma once
@@ -26,6 +26,17 @@ __global__ void dense_absmax_kernel(const float* __restrict__ v, long long total
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride)
         m = max(m, __float_as_uint(v[i]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
+// dense_absmax_kernel over halves: max of bits & 0x7fff (monotone for binary16; >= 0x7c00: inf or NaN).  The widened maximum is the
+// maximum of the widened values -- subnormal halves included: widening is monotone and exact.
+__global__ void dense_absmax16_kernel(const unsigned short* __restrict__ v, long long total, unsigned* __restrict__ out) {
+    unsigned m = 0;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) m = max(m, (unsigned)v[i] & 0x7fffu);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);

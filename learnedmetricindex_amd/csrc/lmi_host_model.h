@@ -463,16 +463,19 @@ static int mlp_enqueue(lmi_index* h, const float* d_q, int nq, int nb, int* d_or
     return mlp_layers_enqueue(h, h->stream, d_q, nq, nb, d_order, d_logits_out, d_probs, stop);
 }
 
-extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int nq, int nb, int32_t* bucket_order,
-                            float* logits, int on_device) {
-    if (!h) return fail("lmi_mlp_topk: NULL handle");
-    if (nq < 0) return fail("lmi_mlp_topk: nq < 0");
+// lmi_mlp_topk and (q16) lmi_mlp_topk_f16: the halves take lmi_search_f16's front -- uploaded as they are, widened on the device into
+// q_nav (input_ptr16) -- and from there on the call is the binary32 call on the widened values
+static int mlp_topk_impl(lmi_index* h, const void* queries_nav, int q16, int nq, int nb, int32_t* bucket_order, float* logits, int on_device) {
+    const char* who = q16 ? "lmi_mlp_topk_f16" : "lmi_mlp_topk";
+    if (!h) return fail("%s: NULL handle", who);
+    if (nq < 0) return fail("%s: nq < 0", who);
     if (nq == 0) return 0;
     CHK(set_dev(h));
-    if (h->root().n_layers == 0) return fail("lmi_mlp_topk: no MLP set (lmi_set_mlp)");
+    if (h->root().n_layers == 0) return fail("%s: no MLP set (lmi_set_mlp)", who);
     const int L = h->root().dims.back();
     const void* d_q = nullptr;
-    CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_q));
+    if (q16) CHK(input_ptr16(h, queries_nav, nq, h->root().dims[0], on_device, h->q16_nav, h->q_nav, &d_q));
+    else CHK(input_ptr(h, queries_nav, (size_t)nq * h->root().dims[0] * 4, on_device, h->q_nav, &d_q));
     int* d_order = bucket_order;
     float* d_logits = logits;
     if (!on_device) {
@@ -487,6 +490,15 @@ extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int 
     CHK(stamp_end(h, ST_MLP1));
     if (!on_device) CHK(copy_back(h, {{bucket_order, d_order, (size_t)nq * nb * 4}, {logits, d_logits, (size_t)nq * L * 4}}));
     return 0;
+}
+
+extern "C" LMI_API int lmi_mlp_topk(lmi_index* h, const float* queries_nav, int nq, int nb, int32_t* bucket_order,
+                            float* logits, int on_device) {
+    return mlp_topk_impl(h, queries_nav, 0, nq, nb, bucket_order, logits, on_device);
+}
+extern "C" LMI_API int lmi_mlp_topk_f16(lmi_index* h, const uint16_t* queries_nav, int nq, int nb, int32_t* bucket_order,
+                                float* logits, int on_device) {
+    return mlp_topk_impl(h, queries_nav, 1, nq, nb, bucket_order, logits, on_device);
 }
 
 extern "C" LMI_API int lmi_mlp_proba(lmi_index* h, const float* queries_nav, int nq, float* probs, int32_t* classes,

@@ -1,4 +1,4 @@
-// lmi_host_train.h -- lmi_train: argument checks, the call's device buffers, the gather of the named rows (on the host in pieces, or by
+// lmi_host_train.h -- lmi_train and lmi_train_f16 (one body over the type of x): argument checks, the call's device buffers, the gather of the named rows (on the host in pieces, or by
 // a kernel), the finite check, and the step schedule (forward, softmax gradient, then per layer from the last: da, dW with Adam) on
 // the NULL stream of the device.
 #pragma once
@@ -16,43 +16,72 @@ int tr_launch(const TrGemm& P) {
     return 0;
 }
 
+// the named rows of a device array into the batch buffer, by the type of x
+void tr_gather(int grid, const float* x, const int* labels, const long long* rows, long long nb, int d, int classes, float* xb, int* yb, int* bad) {
+    tr_gather_kernel<<<grid, 256>>>(x, labels, rows, nb, d, classes, xb, yb, bad);
+}
+void tr_gather(int grid, const uint16_t* x, const int* labels, const long long* rows, long long nb, int d, int classes, float* xb, int* yb, int* bad) {
+    tr_gather16_kernel<<<grid, 256>>>(x, labels, rows, nb, d, classes, xb, yb, bad);
+}
+
+template <class T>
+int train_run(const char* who, int device, const T* x, int64_t n, const int32_t* labels, int n_layers, const int* dims, float* const* W,
+              float* const* b, float* const* adam, int64_t* t, const int64_t* batch_rows, int n_steps, int bsz, double lr, float* losses,
+              int on_device);
+
 }  // namespace
 
 extern "C" LMI_API int lmi_train(int device, const float* x, int64_t n, const int32_t* labels, int n_layers, const int* dims, float* const* W,
                                  float* const* b, float* const* adam, int64_t* t, const int64_t* batch_rows, int n_steps, int bsz, double lr,
                                  float* losses, int on_device) {
-    if (!x || !labels || !dims || !W || !b) return fail("lmi_train: x, labels, dims, W and b must not be NULL");
-    if (n < 1) return fail("lmi_train: n %lld < 1", (long long)n);
-    if (n_layers < 1 || n_layers > LMI_MAX_LAYERS) return fail("lmi_train: n_layers %d outside [1,%d]", n_layers, LMI_MAX_LAYERS);
+    return train_run<float>("lmi_train", device, x, n, labels, n_layers, dims, W, b, adam, t, batch_rows, n_steps, bsz, lr, losses, on_device);
+}
+
+extern "C" LMI_API int lmi_train_f16(int device, const uint16_t* x, int64_t n, const int32_t* labels, int n_layers, const int* dims,
+                                     float* const* W, float* const* b, float* const* adam, int64_t* t, const int64_t* batch_rows, int n_steps,
+                                     int bsz, double lr, float* losses, int on_device) {
+    return train_run<uint16_t>("lmi_train_f16", device, x, n, labels, n_layers, dims, W, b, adam, t, batch_rows, n_steps, bsz, lr, losses,
+                               on_device);
+}
+
+namespace {
+
+template <class T>
+int train_run(const char* who, int device, const T* x, int64_t n, const int32_t* labels, int n_layers, const int* dims, float* const* W,
+              float* const* b, float* const* adam, int64_t* t, const int64_t* batch_rows, int n_steps, int bsz, double lr, float* losses,
+              int on_device) {
+    if (!x || !labels || !dims || !W || !b) return fail("%s: x, labels, dims, W and b must not be NULL", who);
+    if (n < 1) return fail("%s: n %lld < 1", who, (long long)n);
+    if (n_layers < 1 || n_layers > LMI_MAX_LAYERS) return fail("%s: n_layers %d outside [1,%d]", who, n_layers, LMI_MAX_LAYERS);
     for (int i = 0; i < n_layers; ++i)
-        if (dims[i] < 1 || dims[i] > 4096) return fail("lmi_train: dims[%d] = %d outside [1,4096]", i, dims[i]);
+        if (dims[i] < 1 || dims[i] > 4096) return fail("%s: dims[%d] = %d outside [1,4096]", who, i, dims[i]);
     const int d = dims[0], classes = dims[n_layers];
-    if (classes < 1 || classes > 16384) return fail("lmi_train: %d classes outside [1,16384]", classes);
-    if (bsz < 1 || bsz > 256) return fail("lmi_train: bsz %d outside [1,256]", bsz);
-    if (n_steps < 0 || n_steps > 100000) return fail("lmi_train: n_steps %d outside [0,100000]", n_steps);
-    if (!std::isfinite(lr) || !(lr > 0.0)) return fail("lmi_train: lr %g is not a finite positive number", lr);
+    if (classes < 1 || classes > 16384) return fail("%s: %d classes outside [1,16384]", who, classes);
+    if (bsz < 1 || bsz > 256) return fail("%s: bsz %d outside [1,256]", who, bsz);
+    if (n_steps < 0 || n_steps > 100000) return fail("%s: n_steps %d outside [0,100000]", who, n_steps);
+    if (!std::isfinite(lr) || !(lr > 0.0)) return fail("%s: lr %g is not a finite positive number", who, lr);
     const int64_t t0 = t ? *t : 0;
-    if (t0 < 0) return fail("lmi_train: *t = %lld < 0", (long long)t0);
+    if (t0 < 0) return fail("%s: *t = %lld < 0", who, (long long)t0);
     for (int i = 0; i < n_layers; ++i)
-        if (!W[i] || !b[i]) return fail("lmi_train: NULL weight/bias for layer %d", i);
+        if (!W[i] || !b[i]) return fail("%s: NULL weight/bias for layer %d", who, i);
     if (adam)
         for (int i = 0; i < 4 * n_layers; ++i)
-            if (!adam[i]) return fail("lmi_train: adam[%d] is NULL", i);
-    if (n_steps > 0 && !batch_rows) return fail("lmi_train: batch_rows must not be NULL");
+            if (!adam[i]) return fail("%s: adam[%d] is NULL", who, i);
+    if (n_steps > 0 && !batch_rows) return fail("%s: batch_rows must not be NULL", who);
     const long long nb = (long long)n_steps * bsz;   // named rows
     for (long long j = 0; j < nb; ++j)
         if (batch_rows[j] < 0 || batch_rows[j] >= n)
-            return fail("lmi_train: batch_rows[%lld] = %lld outside [0,%lld)", j, (long long)batch_rows[j], (long long)n);
+            return fail("%s: batch_rows[%lld] = %lld outside [0,%lld)", who, j, (long long)batch_rows[j], (long long)n);
     if (!on_device)
         for (long long j = 0; j < nb; ++j) {
             const int lab = labels[batch_rows[j]];
-            if (lab < 0 || lab >= classes) return fail("lmi_train: the label %d of row %lld is outside [0,%d)", lab, (long long)batch_rows[j], classes);
+            if (lab < 0 || lab >= classes) return fail("%s: the label %d of row %lld is outside [0,%d)", who, lab, (long long)batch_rows[j], classes);
         }
     hipDeviceProp_t prop;
-    CHK(open_device("lmi_train", device, &prop));
+    CHK(open_device(who, device, &prop));
     if (n_steps == 0) return 0;   // nothing to train on: the parameters, the moments and *t stay as they are
 
-    CallScratch mem("lmi_train");
+    CallScratch mem(who);
     float* d_xb = nullptr;
     int* d_yb = nullptr;
     CHK(mem.alloc(&d_xb, (size_t)nb * d * 4, "the named rows"));
@@ -82,17 +111,24 @@ extern "C" LMI_API int lmi_train(int device, const float* x, int64_t n, const in
         long long* d_rows = nullptr;
         CHK(mem.alloc(&d_rows, (size_t)nb * 8, "batch_rows"));
         HIPCHK(hipMemcpyAsync(d_rows, batch_rows, (size_t)nb * 8, hipMemcpyHostToDevice, nullptr));
-        tr_gather_kernel<<<(int)std::min<long long>(gs, cdiv(nb * d, 256)), 256>>>(x, labels, d_rows, nb, d, classes, d_xb, d_yb,
-                                                                                 reinterpret_cast<int*>(d_max + 2));
+        tr_gather((int)std::min<long long>(gs, cdiv(nb * d, 256)), x, labels, d_rows, nb, d, classes, d_xb, d_yb, reinterpret_cast<int*>(d_max + 2));
         HIPCHK(hipGetLastError());
     } else {
-        const long long piece_rows = std::max<long long>(1, ((long long)16 << 20) / d);   // 64 MiB of rows at a time
-        std::vector<float> stage((size_t)std::min(piece_rows, nb) * d);
+        // 64 MiB of rows at a time, in the type they came in: halves go up as halves into a piece buffer and are widened from there
+        const long long piece_rows = std::max<long long>(1, ((long long)64 << 20) / ((long long)sizeof(T) * d));
+        std::vector<T> stage((size_t)std::min(piece_rows, nb) * d);
         std::vector<int> yb((size_t)nb);
+        uint16_t* d_x16 = nullptr;
+        if constexpr (sizeof(T) == 2) CHK(mem.alloc(&d_x16, stage.size() * 2, "a piece of the named rows as halves"));
         for (long long j0 = 0; j0 < nb; j0 += piece_rows) {
             const long long m = std::min(piece_rows, nb - j0);
-            for (long long j = 0; j < m; ++j) memcpy(&stage[(size_t)j * d], x + (size_t)batch_rows[j0 + j] * d, (size_t)d * 4);
-            HIPCHK(hipMemcpy(d_xb + (size_t)j0 * d, stage.data(), (size_t)m * d * 4, hipMemcpyHostToDevice));
+            for (long long j = 0; j < m; ++j) memcpy(&stage[(size_t)j * d], x + (size_t)batch_rows[j0 + j] * d, (size_t)d * sizeof(T));
+            if constexpr (sizeof(T) == 2) {
+                HIPCHK(hipMemcpy(d_x16, stage.data(), (size_t)m * d * 2, hipMemcpyHostToDevice));
+                CHK(widen16_enqueue(d_x16, m, d, d_xb + (size_t)j0 * d, nullptr));
+            } else {
+                HIPCHK(hipMemcpy(d_xb + (size_t)j0 * d, stage.data(), (size_t)m * d * 4, hipMemcpyHostToDevice));
+            }
         }
         for (long long j = 0; j < nb; ++j) yb[(size_t)j] = labels[batch_rows[j]];
         HIPCHK(hipMemcpy(d_yb, yb.data(), (size_t)nb * 4, hipMemcpyHostToDevice));
@@ -118,9 +154,9 @@ extern "C" LMI_API int lmi_train(int device, const float* x, int64_t n, const in
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(h_max, d_max, 12, hipMemcpyDeviceToHost));
-    if (h_max[2]) return fail("lmi_train: the label of a named row is outside [0,%d)", classes);
-    if (h_max[0] >= 0x7f800000u) return fail("lmi_train: a named row of x holds a value that is not finite (inf or NaN)");
-    if (h_max[1] >= 0x7f800000u) return fail("lmi_train: the initial weights hold a value that is not finite (inf or NaN)");
+    if (h_max[2]) return fail("%s: the label of a named row is outside [0,%d)", who, classes);
+    if (h_max[0] >= 0x7f800000u) return fail("%s: a named row of x holds a value that is not finite (inf or NaN)", who);
+    if (h_max[1] >= 0x7f800000u) return fail("%s: the initial weights hold a value that is not finite (inf or NaN)", who);
 
     // P1 = 0.9^t', P2 = 0.999^t' as running products in binary64 (once both are 0 they stay 0)
     double P1 = 1.0, P2 = 1.0;
@@ -190,3 +226,5 @@ extern "C" LMI_API int lmi_train(int device, const float* x, int64_t n, const in
     if (t) *t = t0 + n_steps;
     return 0;
 }
+
+}  // namespace

@@ -162,4 +162,22 @@ __global__ void tr_gather_kernel(const float* __restrict__ x, const int* __restr
     }
 }
 
+// tr_gather_kernel on rows of halves (lmi_train_f16): xb[j][:] = the named row widened exactly; the label check is the same
+__global__ void tr_gather16_kernel(const unsigned short* __restrict__ x, const int* __restrict__ labels, const long long* __restrict__ rows,
+                                   long long n_rows, int d, int classes, float* __restrict__ xb, int* __restrict__ yb,
+                                   int* __restrict__ bad) {
+    const long long total = n_rows * d, stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const long long j = i / d;
+        const int t = (int)(i - j * d);
+        const long long src = rows[j];
+        xb[i] = (float)__builtin_bit_cast(_Float16, x[(size_t)src * d + t]);
+        if (t == 0) {
+            const int lab = labels[src];
+            yb[j] = lab;
+            if (lab < 0 || lab >= classes) atomicOr(bad, 1);
+        }
+    }
+}
+
 }  // namespace lmi

@@ -72,7 +72,10 @@ class LearnedIndexBuilder(Logger):
         t0 = time.time()
         cfg = self.config
         depth = cfg.n_levels
-        vectors = np.ascontiguousarray(self.data.to_numpy(dtype=np.float32))
+        # trainer="hip" on a frame whose every column is float16: the vectors stay float16 -- hip_kmeans, the trainer and the
+        # placement check take halves (lmi_kmeans_f16, lmi_train_f16, lmi_mlp_topk_f16) and no float32 copy of the frame is made
+        half = self.trainer == "hip" and len(self.data.columns) > 0 and all(t == np.float16 for t in self.data.dtypes)
+        vectors = np.ascontiguousarray(self.data.to_numpy(dtype=np.float16 if half else np.float32))
         placement = np.full((vectors.shape[0], depth), EMPTY_VALUE, dtype=np.int64)
         self.internal_models, self.bucket_paths = {}, []
         clustering_seconds = 0.0
@@ -112,7 +115,11 @@ class LearnedIndexBuilder(Logger):
         else:
             # a node with fewer objects than categories asks for fewer clusters (:282-304)
             want = fan_out if x.shape[0] >= fan_out else max(x.shape[0] // 5, 2)
-            _, labels = cluster(x, want, None)
+            # halves go to hip_kmeans as they are; any other clusterer gets what it gets from a float32 frame, widened per node
+            # (the registry's entry is a function named hip_kmeans, the module's own is hip_kmeans.cluster)
+            as_is = x.dtype != np.float16 or "hip_kmeans" in (getattr(cluster, "__name__", ""),
+                                                              getattr(cluster, "__module__", "").rpartition(".")[2])
+            _, labels = cluster(x if as_is else x.astype(np.float32), want, None)
         secs = time.time() - t
         # the classes are the clusters that received rows, renumbered in ascending order (a no-op unless the clustering left one empty)
         used, labels = np.unique(labels, return_inverse=True)

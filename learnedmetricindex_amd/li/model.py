@@ -206,6 +206,7 @@ class NeuralNetwork(Logger):
         """train_batch's effective schedule on the device (`lmi_train`): per epoch ONE Adam step on r = n - 256*floor((n-1)/256)
         distinct random rows -- without the forward passes train_batch runs over the other mini-batches and throws away.
         `x` f32 [n,d] and `y` [n]: numpy arrays, or contiguous tensors on the device (then only the named rows are read there).
+        A float16 `x` (array or tensor) stays float16 (`lmi_train_f16`): the weights are those of the widened rows, bit for bit.
         The rows come from one `np.random.default_rng(seed)` per network, kept across calls like the Adam state; the weights start
         from the torch modules' and are written back to them.  The same calls give the same weights bit for bit."""
         self._engine = None
@@ -214,7 +215,8 @@ class NeuralNetwork(Logger):
             self._hip_rng, self._hip_state = np.random.default_rng(seed), None
         rows = self.hip_batch_rows(self._hip_rng, n, epochs)
         if isinstance(x, np.ndarray):
-            x, y = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(y, dtype=np.int32)
+            x = np.ascontiguousarray(x, dtype=np.float16 if x.dtype == np.float16 else np.float32)
+            y = np.ascontiguousarray(y, dtype=np.int32)
         else:
             y = y.to(device=x.device, dtype=torch.int32).contiguous()
         lr = self.optimizer.param_groups[0]["lr"]
@@ -247,17 +249,22 @@ class NeuralNetwork(Logger):
         return np.ascontiguousarray(data_X, dtype=np.float32)
 
     def predict(self, data_X):
-        """argmax class per row, int64 (model.py:213-224) -- used for object placement.  A contiguous float32 tensor on the
-        device is read where it is (`lmi_mlp_topk`, on_device)."""
+        """argmax class per row, int64 (model.py:213-224) -- used for object placement.  A contiguous float32 or float16 tensor
+        on the device is read where it is (`lmi_mlp_topk` / `lmi_mlp_topk_f16`, on_device); a float16 numpy array or host tensor
+        goes up as halves, chunk by chunk."""
         eng = self.engine()
-        if isinstance(data_X, torch.Tensor) and data_X.is_cuda and data_X.dtype == torch.float32 and data_X.is_contiguous():
+        if (isinstance(data_X, torch.Tensor) and data_X.is_cuda and data_X.dtype in (torch.float32, torch.float16)
+                and data_X.is_contiguous()):
             order = torch.empty((data_X.shape[0], 1), dtype=torch.int32, device=data_X.device)
             torch.cuda.synchronize(data_X.device)   # the engine's stream is not torch's
             for r0 in range(0, data_X.shape[0], self._CHUNK):
                 eng.mlp_topk_device(data_X[r0: r0 + self._CHUNK], 1, order[r0: r0 + self._CHUNK])
             torch.cuda.synchronize(data_X.device)
             return order[:, 0].cpu().numpy().astype(np.int64)
-        x = self._as_numpy(data_X)
+        if isinstance(data_X, torch.Tensor) and data_X.dtype == torch.float16:
+            data_X = data_X.detach().cpu().numpy()
+        half = isinstance(data_X, np.ndarray) and data_X.dtype == np.float16
+        x = np.ascontiguousarray(data_X) if half else self._as_numpy(data_X)
         out = np.empty(x.shape[0], dtype=np.int64)
         for r0 in range(0, x.shape[0], self._CHUNK):
             out[r0: r0 + self._CHUNK] = eng.mlp_topk(x[r0: r0 + self._CHUNK], 1)[:, 0]

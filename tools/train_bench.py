@@ -15,12 +15,18 @@ time of one step (the launches of a step run back to back on the NULL stream; th
 
   python tools/train_bench.py [--n 100000] [--d 768] [--classes 120] [--epochs 20] [--torch-epochs E] [--reps 3] [--out FILE]
   python tools/train_bench.py --quality [--seeds 3] [--epochs 20] [--out FILE]
+  python tools/train_bench.py --f16 [--n ..] [--d ..] [--classes ..] [--epochs ..] [--out profiles/kmeans_f16.txt]
 
 --quality: instead of the timings, what the two trainers' models are worth.  On the C1 mixture of bench.py (`synth.mixture`, 100 000 x
 768, 120 leaves, 1 000 queries, top-4 buckets) the index is built (hip_kmeans labels, MLP-4, --epochs epochs per round, lr 0.01) with
 --seeds torch seeds and as many hip seeds; per build: the training rounds the stopping rule needed, the build seconds and recall@10
 against exact brute force.  The hip schedule draws other rows than torch's shuffle, so the models differ; accepted when every hip build
 met the stopping rule and its recall lies within the torch builds' range widened by that range's own width on either side.
+
+--f16: instead of the timings above, `lmi_train_f16` beside `lmi_train` on the same values in one process (the mixture narrowed to
+float16 and widened again): --epochs steps from host arrays (the gather and the upload of the named rows are in the window) and from
+device tensors, five repeats each with the forms alternating, the spread of the float form's five beside the medians, and the peak
+device memory of the host-array call (polled from a second thread).  The results must be equal bit for bit, losses included.
 
 Prints a table and one JSON line; --out appends both to a file.  Not a yardstick: bench.py is.
 """
@@ -35,6 +41,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from learnedmetricindex_amd import _capi  # noqa: E402
 from learnedmetricindex_amd.li.LearnedIndexBuilder import MINI_BATCH, _PositionBatches  # noqa: E402
@@ -114,6 +121,63 @@ def quality(a):
     return 0 if ok else 1
 
 
+def f16_ab(a):
+    """lmi_train_f16 beside lmi_train on the same values"""
+    import torch
+
+    from kmeans_bench import PeakPoll
+
+    reps = 5
+    xt, yt = device_mixture(a.seed, a.n, a.d, a.classes)
+    x16t = xt.half()
+    del xt
+    x32t = x16t.float()
+    y = yt.cpu().numpy()
+    forms = {"f32": (x32t.cpu().numpy(), x32t), "f16": (x16t.cpu().numpy(), x16t)}
+    torch.manual_seed(a.seed)
+    layers = linear_layers(NeuralNetwork(input_dim=a.d, output_dim=a.classes, lr=0.01, model_type=a.model).model)
+    rows = NeuralNetwork.hip_batch_rows(np.random.default_rng(a.seed), a.n, a.epochs)
+    lines = [f"train_bench --f16: {a.n} x {a.d}, {a.model}, {a.classes} classes, {a.epochs} steps on {rows.shape[1]} rows each, {reps} repeats, "
+             f"the forms alternating; {torch.cuda.get_device_name(0)}; {_capi.lib().lmi_build_info().decode()}"]
+    out, t = {}, {f: dict(host=[], dev=[]) for f in forms}
+    for f, (xh, xd) in forms.items():   # warm-up, and the results
+        out[f] = _capi.train(xh, y, layers, rows, 0.01)
+        _capi.train(xd, yt, layers, rows, 0.01)
+    flat = lambda o: [v for W, b in o[0] for v in (W, b)] + list(o[1][0]) + [o[2]]  # noqa: E731
+    assert all(np.array_equal(u.view(np.uint32), v.view(np.uint32)) for u, v in zip(flat(out["f32"]), flat(out["f16"]))), \
+        "lmi_train_f16 and lmi_train differ on the same values"
+    for _ in range(reps):
+        for f, (xh, xd) in forms.items():
+            t[f]["host"].append(wall(lambda: _capi.train(xh, y, layers, rows, 0.01))[1] * 1e3)
+            t[f]["dev"].append(wall(lambda: _capi.train(xd, yt, layers, rows, 0.01))[1] * 1e3)
+    res = dict(n=a.n, d=a.d, classes=a.classes, model=a.model, steps=a.epochs, rows_per_step=int(rows.shape[1]), bitwise_equal=True,
+               build=_capi.lib().lmi_build_info().decode())
+    lines.append("form   host arrays ms: median  min  max     device tensors ms: median  min  max     peak device MiB (polled, host arrays)")
+    for f, (xh, xd) in forms.items():
+        with PeakPoll() as peak:
+            _capi.train(xh, y, layers, rows, 0.01)
+        h, d = t[f]["host"], t[f]["dev"]
+        lines.append(f"  {f}  {statistics.median(h):20.3f} {min(h):8.3f} {max(h):8.3f}   {statistics.median(d):22.3f} {min(d):8.3f} {max(d):8.3f}"
+                     f"   {peak.peak / 2 ** 20:12.1f}")
+        res[f] = dict(host_ms=h, device_ms=d, host_median_ms=statistics.median(h), device_median_ms=statistics.median(d),
+                      peak_polled_bytes=int(peak.peak))
+    for kind in ("host", "device"):
+        spread = max(res["f32"][kind + "_ms"]) - min(res["f32"][kind + "_ms"])
+        diff = res["f16"][kind + "_median_ms"] - res["f32"][kind + "_median_ms"]
+        lines.append(f"  {kind}: spread of the float form's {reps}: {spread:.3f} ms; f16 - f32 (medians): {diff:+.3f} ms: "
+                     + ("within the spread" if diff <= spread else "the half form is SLOWER by more than the spread"))
+        res.update({kind + "_f32_spread_ms": spread, kind + "_f16_minus_f32_ms": diff})
+    lines.append("  parameters, moments, t and losses of the two forms: equal bit for bit")
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n" + json.dumps(res) + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--n", type=int, default=100_000)
@@ -127,7 +191,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--quality", action="store_true", help="model quality of the two trainers instead of the timings")
     ap.add_argument("--seeds", type=int, default=3)
+    ap.add_argument("--f16", action="store_true", help="lmi_train_f16 beside lmi_train on the same values")
     a = ap.parse_args()
+    if a.f16:
+        _capi.lib()
+        return f16_ab(a)
     if a.quality:
         _capi.lib()
         return quality(a)
