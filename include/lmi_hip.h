@@ -327,6 +327,54 @@ enum {
 /* What the last lmi_regroup on this thread did (all zero after a refused call): out[0..n) <- the first
  * min(n, LMI_REGROUP_PLAN_COUNT) words. */
 LMI_API int lmi_debug_regroup_plan(int64_t *out, int n);
+/* Several built indexes over the same partition as ONE new index, derived on the device (no reference counterpart: the reference
+ * concatenates its DataFrames and rebuilds).  lmi_subset is "same labels, fewer objects", lmi_regroup "same objects, new labels"; this
+ * is "same labels, the objects of parts[0..n_parts)".  It is how an LMI_STORAGE_F16 index, which lmi_buckets_insert refuses, grows
+ * (build the delta as a small index, fold it in), how an index is assembled from parts built separately, and how several mutated
+ * handles are compacted in one pass.  *n_total (nullable) <- the objects the new index stores.
+ * THE ORDER RULE: *out holds exactly what lmi_create + parts[0]'s settings + lmi_buckets_begin / add_rows / end would hold for the
+ * object list "parts[0]'s objects in the order it holds them -- bucket ascending, then row within the bucket --, then parts[1]'s, and
+ * so on, each with its bucket as its label".  So bucket b of the result is parts[0]'s bucket b, followed by parts[1]'s bucket b, and
+ * so on: every search (lmi_search, lmi_scan_topk, the tree walk and, where the stored form allows them, the union and range calls)
+ * returns the same dists, ids and keys bit for bit, lmi_bucket_sizes / lmi_bucket_read / lmi_bucket_read_f16 / lmi_index_bytes
+ * return the same, and lmi_debug_layout shows a fresh build's layout with all four counters zero.  A single part is therefore that
+ * part's compaction, equal to lmi_subset(h, NULL, 0, LMI_SUBSET_DROP, ..).  No position depends on the arrival order of an atomic or
+ * on a grid.
+ * *out is a NEW, INDEPENDENT handle on the parts' device, as lmi_subset's: no clone view, every part may be destroyed first, any may
+ * be mutated without the others noticing.  It carries copies of parts[0]'s models and tree tables -- valid, because L and the
+ * buckets' meaning are the same --, parts[0]'s settings and chunk rule (lmi_subset's list) and a layout stamp of its own: a filter
+ * made on a part is refused on it.  The other parts' models are ignored.  A part may be listed twice; its objects then appear twice.
+ * Ids are the caller's and are not compared across parts, as with lmi_buckets_insert.
+ * All three stored forms: row-major f32 (both metrics; rows are moved as stored, the -|x|^2/2 column of L2 travels with its row; the
+ * fp16 fragments, absmax, scale, norms and bounds are derived from the new handle's own rows), f32 fragments (lmi_set_prefilter(0))
+ * and LMI_STORAGE_F16, whose halves are moved out of the fragments -- no binary32 image exists at any point.  Every F16 part stores
+ * x * s_t under its own scale; the result's scale s_out is that of the largest of the parts' maxima (each handle keeps its own: no
+ * pass over the rows) and part t's halves are multiplied by the power of two s_out / s_t <= 1 on the way.  Going down in exponent
+ * can lose bits: if a half changes when it is rounded back the call is refused with the words lmi_buckets_end has for such data --
+ * the verdict a fresh build of the concatenated rows reaches, for which x * s_out must be a half too.
+ * Sharded ranks: either every part carries an `owned` mask and the masks are equal, or none does; the result carries the mask, a
+ * bucket holds rows on some rank if it does so in any part, and N is the sum of the parts' N.
+ * The call synchronises every part's stream first, then only READS the parts -- allowed on clone views and while clone views of a
+ * part live -- and returns when the new index is complete.  Peak device memory: the parts' images + the new index's + 8 bytes per
+ * slab row of the new index (the source map, freed before the call returns).
+ * Refused before any launch, with *out left NULL and every part untouched, each by name: NULL parts or out, a NULL part; n_parts
+ * outside [1, LMI_CONCAT_MAX_PARTS]; a part that is not built or is being built; parts on different devices; a part that differs
+ * from parts[0] in d, L, the metric, the storage, the prefilter (on / off) or the `owned` mask (the message names the part and the
+ * property); a bucket or a layout past the 32-bit slab positions.  Refused after launches: the F16 scale loss above, and a failed
+ * allocation (the message says how many bytes it wanted).  Then no index is made and everything the call allocated is freed. */
+#define LMI_CONCAT_MAX_PARTS 64
+LMI_API int lmi_concat(lmi_index *const *parts, int n_parts, lmi_index **out, int64_t *n_total /* nullable */);
+enum {
+    LMI_CONCAT_PLAN_PARTS = 0,       /* n_parts                                                           */
+    LMI_CONCAT_PLAN_ROWS,            /* objects the new index stores = *n_total                           */
+    LMI_CONCAT_PLAN_SLAB_ROWS,       /* rows of the new slab: 32 per row-block of the fresh layout        */
+    LMI_CONCAT_PLAN_MAP_BYTES,       /* device bytes of the call's maps                                   */
+    LMI_CONCAT_PLAN_RESCALED_PARTS,  /* LMI_STORAGE_F16: parts whose halves were multiplied (ratio < 1)   */
+    LMI_CONCAT_PLAN_COUNT
+};
+/* What the last lmi_concat on this thread did (all zero after a refused call): out[0..n) <- the first
+ * min(n, LMI_CONCAT_PLAN_COUNT) words. */
+LMI_API int lmi_debug_concat_plan(int64_t *out, int n);
 /* sizes[L] <- number of objects per bucket (0 for buckets not owned). */
 LMI_API int lmi_bucket_sizes(lmi_index *h, int64_t *sizes);
 /* Reads one bucket back to the host in bucket order (what `data_search.loc[g.index].to_numpy()`

@@ -52,6 +52,9 @@ RANGE_SORT_MIN_TILE_ROWS, RANGE_SORT_MAX_TILE_ROWS = 64, 8192   # what lmi_range
 REGROUP_PLAN_FIELDS = ("ROWS", "TILE_ROWS", "TILES", "MERGE_ROWS", "PASSES", "MAP_BYTES", "NAMED")
 REGROUP_MIN_TILE_ROWS, REGROUP_MAX_TILE_ROWS = 64, 8192   # what lmi_regroup_set_geometry takes (a power of two)
 REGROUP_MAX_LABELS = 1 << 20                              # lmi_regroup: L_new stays below it
+CONCAT_MAX_PARTS = 64   # LMI_CONCAT_MAX_PARTS: parts of one `Index.concat`, the receiver included
+#: the LMI_CONCAT_PLAN_* words, in their order (lmi_debug_concat_plan)
+CONCAT_PLAN_FIELDS = ("PARTS", "ROWS", "SLAB_ROWS", "MAP_BYTES", "RESCALED_PARTS")
 
 _lib = None
 
@@ -92,6 +95,8 @@ SIGNATURES = {
     "lmi_regroup": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int, ctypes.POINTER(_vp), _i64p]),
     "lmi_regroup_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
     "lmi_debug_regroup_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    "lmi_concat": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.POINTER(_vp), _i64p]),
+    "lmi_debug_concat_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_bucket_sizes": (ctypes.c_int, [_vp, _vp]),
     "lmi_mlp_topk": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_mlp_proba": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -698,6 +703,26 @@ class Index:
         _check(lib().lmi_regroup(self._h, _ptr(ids_a), _ptr(lab_a), int(ids_a.shape[0]), _ptr(map_a), L_new, ctypes.byref(v._h),
                                  ctypes.byref(named)))
         v.L, v.N, v.bytes_in, v.n_named = L_new, getattr(self, "N", None), 0, named.value
+        return v
+
+    def concat(self, *others: "Index") -> "Index":
+        """A new, independent `Index` that holds this one's objects and then every one of `others`', derived on the device
+        (`lmi_concat`).  All parts are built indexes over the same partition (same d, L, metric, storage, prefilter and `owned`
+        mask, on one device; the library refuses anything else by name).  Bucket b of the result is this index's bucket b followed
+        by `others[0]`'s bucket b and so on -- exactly what a fresh build of "this index's objects in the order held here, then
+        `others[0]`'s, ..." would hold: same search results bit for bit, same layout.  It owns its images and copies of THIS
+        index's models and tree (the others' models are ignored) and carries this one's settings.  How a `storage="f16"` index,
+        which `insert` refuses, grows: build the new objects as a small index, concatenate, close the small one; the library
+        refuses (`LmiError`) if the larger scale of the result would push a stored half below the binary16 subnormals, as a fresh
+        build of the same rows would.  Without `others` the result is this index's compaction (`subset([], drop=True)`).  A part
+        may be passed twice.  The parts are only read: works while clone views live, and on them.  `N` is the stored objects.
+        Arguments that are no open `Index`, or more than `CONCAT_MAX_PARTS` parts, raise ValueError before the library is called."""
+        parts = concat_args(self, others)
+        v = self._derived()
+        total = ctypes.c_int64(0)
+        handles = (_vp * len(parts))(*[p._h.value if isinstance(p._h, _vp) else p._h for p in parts])
+        _check(lib().lmi_concat(handles, len(parts), ctypes.byref(v._h), ctypes.byref(total)))
+        v.N, v.bytes_in = total.value, 0
         return v
 
     def bucket_sizes(self) -> np.ndarray:
@@ -1550,6 +1575,28 @@ def regroup_last_plan() -> dict:
     w = (ctypes.c_int64 * len(REGROUP_PLAN_FIELDS))()
     _check(lib().lmi_debug_regroup_plan(w, len(REGROUP_PLAN_FIELDS)))
     return dict(zip((n.lower() for n in REGROUP_PLAN_FIELDS), (int(v) for v in w)))
+
+
+def concat_args(first, others):
+    """`Index.concat`'s parts as the library takes them -- the list [first, *others] of open `Index` objects -- or ValueError,
+    before the library is touched.  What the parts must agree in (d, L, metric, storage, prefilter, `owned` mask, device) is the
+    library's to check: it knows all of it, this module only part."""
+    parts = [first] + list(others)
+    if len(parts) > CONCAT_MAX_PARTS:
+        raise ValueError(f"concat: {len(parts)} parts (this index and {len(others)} others), at most {CONCAT_MAX_PARTS}")
+    for t, p in enumerate(parts):
+        if not isinstance(p, Index):
+            raise ValueError(f"concat: part {t} must be an Index, not {type(p).__name__}")
+        if getattr(p, "_h", None) is None or not p._h:
+            raise ValueError(f"concat: part {t} is closed")
+    return parts
+
+
+def concat_last_plan() -> dict:
+    """What the last `Index.concat` on this thread did (`lmi_debug_concat_plan`): `CONCAT_PLAN_FIELDS` (lower case) -> int."""
+    w = (ctypes.c_int64 * len(CONCAT_PLAN_FIELDS))()
+    _check(lib().lmi_debug_concat_plan(w, len(CONCAT_PLAN_FIELDS)))
+    return dict(zip((n.lower() for n in CONCAT_PLAN_FIELDS), (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

@@ -32,6 +32,8 @@
 #include "lmi_host_range_sort.h"   // lmi_range_result_sort / lmi_range_result_sorted, lmi_range_sort_set_geometry, lmi_debug_range_sort_plan
 #include "lmi_regroup.h"        // the kernels of lmi_regroup (its sort merges with lmi_range_sort.h's kernel)
 #include "lmi_host_regroup.h"   // lmi_regroup, lmi_regroup_set_geometry, lmi_debug_regroup_plan
+#include "lmi_concat.h"         // the kernels of lmi_concat
+#include "lmi_host_concat.h"    // lmi_concat, lmi_debug_concat_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

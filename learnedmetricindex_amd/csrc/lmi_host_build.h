@@ -289,6 +289,17 @@ static int storage16_images(lmi_index* h, const DevBuf& factor, MakeScale make_s
     return 0;
 }
 
+// what S16_SCALE_LOSS means, in words (lmi_buckets_end; lmi_concat, whose verdict is a fresh build's): scale = the index scale,
+// maxbits = the bits of max |x|
+static std::string scale_loss_reason(float scale, unsigned maxbits) {
+    float mx;
+    memcpy(&mx, &maxbits, 4);
+    char buf[320];
+    snprintf(buf, sizeof(buf), "LMI_STORAGE_F16 refused: every value is binary16-exact, but not once multiplied by the index scale %g "
+                               "(max|x| = %g; a small value falls below the binary16 subnormals)", (double)scale, (double)mx);
+    return buf;
+}
+
 // LMI_STORAGE_F16: the fragments were filled unscaled by lmi_buckets_add_*rows; the scale from their absmax, the slab times the scale
 // in place, the buckets' norms from the stored halves -- and the verdict: the flags are read after the synchronisation, a refused
 // build launches nothing more and leaves the handle without an index.
@@ -306,12 +317,7 @@ static int storage16_finish(lmi_index* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (st[1] & S16_NONFINITE) return fail("lmi_buckets_end: LMI_STORAGE_F16 refused: a stored value is not finite (inf or NaN)");
     if (st[1] & S16_INEXACT) return fail("lmi_buckets_end: LMI_STORAGE_F16 refused: a stored value is not exactly representable in binary16");
-    if (st[1] & S16_SCALE_LOSS) {
-        float mx;
-        memcpy(&mx, &st[0], 4);
-        return fail("lmi_buckets_end: LMI_STORAGE_F16 refused: every value is binary16-exact, but not once multiplied by the index scale %g "
-                    "(max|x| = %g; a small value falls below the binary16 subnormals)", (double)sc[0], (double)mx);
-    }
+    if (st[1] & S16_SCALE_LOSS) return fail("lmi_buckets_end: %s", scale_loss_reason(sc[0], st[0]).c_str());
     h->have16 = true;
     return 0;
 }

@@ -27,13 +27,7 @@ static int regroup_fill(lmi_index* h, lmi_index* c, const lmi_regroup_plan::List
     const int L = h->L;
     hipStream_t st = c->stream;
     // ---- h's settings and copies of all its models; not the tree, whose child_bucket entries name h's buckets ----
-    static_cast<Settings&>(*c) = *h;
-    c->storage_req = h->storage;
-    if (!h->chunk_rows_auto) c->chunk_rows = h->chunk_rows_set;
-    c->models.resize(h->models.size());
-    for (size_t m = 0; m < h->models.size(); ++m) CHK(copy_model(st, h->models[m], c->models[m]));
-    c->tree_set = false;
-    c->desc_dirty = true;
+    CHK(inherit_handle(h, c, false));
     // ---- 1: every row's new label, its word and its slab row at its ordinal; the counts come back to the host ----
     const std::vector<int64_t> base64 = rp::ordinal_bases(h->h_nb_rows);
     const int64_t n = base64[L];

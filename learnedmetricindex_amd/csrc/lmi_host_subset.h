@@ -30,22 +30,18 @@ int copy_table(hipStream_t st, const DevBuf& src, size_t bytes, DevBuf& dst) {
     HIPCHK(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, st));
     return 0;
 }
-// blocks of a grid-stride gather over `pieces` 16-byte pieces: enough waves to keep every CU's memory pipe busy, no more than the work
-int gather_blocks(const lmi_index* h, long long pieces) { return (int)std::max<long long>(1, std::min<long long>((pieces + 255) / 256, (long long)h->num_cus * 32)); }
-}  // namespace
-
-// everything of lmi_subset behind the argument checks: fills the fresh handle c from h (h->stream is idle; c runs on the NULL stream)
-static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t n, int mode, int64_t* n_kept) {
-    const int L = h->L;
+// What a derived index (lmi_subset, lmi_regroup, lmi_concat) takes over from the built index h it is derived from, on c's stream: h's
+// settings (lmi_create read the environment's again) and chunk rule, copies of all its models and -- with_tree -- of the tree tables
+// (the device descriptors point at the weights: rebuilt at the first use).
+int inherit_handle(const lmi_index* h, lmi_index* c, bool with_tree) {
     hipStream_t st = c->stream;
-    // ---- h's settings (lmi_create read the environment's again) ----
     static_cast<Settings&>(*c) = *h;
     c->storage_req = h->storage;
     if (!h->chunk_rows_auto) c->chunk_rows = h->chunk_rows_set;
-    // ---- the models and the tree: copies of its own (the device descriptors point at the weights: rebuilt at the first use) ----
     c->models.resize(h->models.size());
     for (size_t m = 0; m < h->models.size(); ++m) CHK(copy_model(st, h->models[m], c->models[m]));
-    if (h->tree_set) {
+    c->tree_set = false;
+    if (with_tree && h->tree_set) {
         c->h_child_offset = h->h_child_offset; c->h_child_model = h->h_child_model; c->h_child_bucket = h->h_child_bucket;
         const size_t total = h->h_child_model.size();
         CHK(copy_table(st, h->d_child_offset, h->h_child_offset.size() * 4, c->d_child_offset));
@@ -54,6 +50,18 @@ static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t 
         c->tree_set = true;
     }
     c->desc_dirty = true;
+    return 0;
+}
+// blocks of a grid-stride gather over `pieces` 16-byte pieces: enough waves to keep every CU's memory pipe busy, no more than the work
+int gather_blocks(const lmi_index* h, long long pieces) { return (int)std::max<long long>(1, std::min<long long>((pieces + 255) / 256, (long long)h->num_cus * 32)); }
+}  // namespace
+
+// everything of lmi_subset behind the argument checks: fills the fresh handle c from h (h->stream is idle; c runs on the NULL stream)
+static int subset_fill(lmi_index* h, lmi_index* c, const uint32_t* ids, int64_t n, int mode, int64_t* n_kept) {
+    const int L = h->L;
+    hipStream_t st = c->stream;
+    // ---- h's settings, the models and the tree: copies of its own ----
+    CHK(inherit_handle(h, c, true));
     // ---- 1: mark the rows that stay and count them per bucket; the counts come back to the host (16 zeroed bytes behind them: the
     //         fp16 gather's maximum) ----
     std::vector<int> cnt, iota(L);   // (iota: compact_map_kernel's bucket list; alive until the stream has taken it)

@@ -322,7 +322,8 @@ class LearnedIndex(Logger):
         """Adds objects to the HBM-resident index (an extension: the reference rebuilds).  Each object is placed the way
         `LearnedIndexBuilder.build` places it -- argmax of the root model, then argmax of each internal node's model down the
         tree, through the HIP MLP -- and goes after the last object of its bucket (`lmi_buckets_insert`; refused by the library,
-        `_capi.LmiError`, on a `storage="f16"` index, which cannot be changed in place yet).  `data_search_new`
+        `_capi.LmiError`, on a `storage="f16"` index, which cannot be changed in place yet: `extended` returns a new index
+        instead).  `data_search_new`
         (default: `data_navigation_new`) holds the scan vectors, `ids` (default: `data_navigation_new.index`) the labels.
         Returns the objects' `data_prediction` rows (int64 [n, n_levels]) for the caller to append to their own frames.
         A multi-level placement onto a leaf path that holds no bucket would need a new bucket: the whole call is refused
@@ -331,6 +332,17 @@ class LearnedIndex(Logger):
         the paths join `bucket_paths`) and the insert goes on as usual.  Afterwards `search_resident` answers from the mutated
         index; `search` keeps answering from the frames it is given (they no longer match the resident copy, which it rebuilds)."""
         eng = self._resident("insert")
+        dp, bucket_of, rows, labels = self._place(data_navigation_new, data_search_new, ids, create_buckets)
+        eng = self._engine   # (create_buckets may have replaced it)
+        eng.insert(rows, bucket_of, labels)
+        self._engine_key = self._mutated_key()
+        return dp
+
+    def _place(self, data_navigation_new, data_search_new, ids, create_buckets: bool = False):
+        """What `insert` and `extended` share: the new objects' `data_prediction` rows (int64 [n, n_levels]; argmax of the root
+        model, then of each internal node's model down the tree), their bucket ids in the resident engine, their scan vectors
+        (float16 frames stay halves) and their ids (uint32).  A placement onto a leaf path that holds no bucket raises ValueError
+        before anything changes -- unless `create_buckets`, which opens the missing paths first (`_open_buckets`)."""
         nav = data_navigation_new
         srch = nav if data_search_new is None else data_search_new
         labels = nav.index.to_numpy() if ids is None else np.asarray(ids).reshape(-1)
@@ -355,7 +367,7 @@ class LearnedIndex(Logger):
             bucket_of = np.asarray([self._path_ids.get(tuple(int(v) for v in p), -1) for p in dp], dtype=np.int64)
             missing = int((bucket_of < 0).sum())
             if missing and create_buckets:
-                eng = self._open_buckets(np.unique(dp[bucket_of < 0], axis=0))
+                self._open_buckets(np.unique(dp[bucket_of < 0], axis=0))
                 bucket_of = np.asarray([self._path_ids[tuple(int(v) for v in p)] for p in dp], dtype=np.int64)
             elif missing:
                 raise ValueError(f"{missing} of {dp.shape[0]} object(s) fall on a leaf path that holds no bucket; creating buckets "
@@ -363,9 +375,56 @@ class LearnedIndex(Logger):
         cols = _feature_columns(srch)
         frame = srch if srch.index.equals(nav.index) else srch.loc[nav.index]
         rows = np.ascontiguousarray(frame[cols].to_numpy(dtype=_scan_dtype(frame, cols)))
-        eng.insert(rows, bucket_of, labels.astype(np.uint32))
-        self._engine_key = self._mutated_key()
-        return dp
+        return dp, bucket_of, rows, labels.astype(np.uint32)
+
+    def _derived_like(self, engine) -> "LearnedIndex":
+        """A new `LearnedIndex` over this object's models and bucket paths that answers from `engine` (an index derived from the
+        resident one without a change of partition: `subset`, `concat`)."""
+        other = LearnedIndex(self.root_model, self.internal_models, self.bucket_paths)
+        other._engine, other._engine_key = engine, self._mutated_key()
+        other._path_ids, other._entry_paths, other._nav_cap = self._path_ids, self._entry_paths, self._nav_cap
+        return other
+
+    def concat(self, *others: "LearnedIndex") -> "LearnedIndex":
+        """A new `LearnedIndex` over this object's models and bucket paths whose HBM-resident index holds this one's resident
+        objects followed by every one of `others`' (an extension; `lmi_concat`): bucket by bucket this index's objects, then
+        `others[0]`'s, and so on -- laid out like a fresh build of that list.  Every other must be resident and have this object's
+        `bucket_paths` (a bucket id must mean the same path in every part): anything else is refused with ValueError before any
+        device work.  The copy is derived on the device, is independent of every part, is answered by `search_resident` /
+        `range_search_resident` and saves and loads through `index_io` like any derived index.  Works on `storage="f16"`.  The
+        parts are unchanged."""
+        eng = self._resident("concat")
+        mine = [tuple(int(v) for v in p) for p in self.bucket_paths]
+        engines = []
+        for t, o in enumerate(others):
+            if not isinstance(o, LearnedIndex):
+                raise ValueError(f"concat: argument {t} must be a LearnedIndex, not {type(o).__name__}")
+            if o._engine is None:
+                raise ValueError(f"concat: argument {t} has no resident index: call prepare()/search() or index_io.load_index()")
+            if [tuple(int(v) for v in p) for p in o.bucket_paths] != mine or o._path_ids != self._path_ids:
+                raise ValueError(f"concat: argument {t} has other bucket_paths than this index: its bucket ids do not mean the same "
+                                 "paths (parts with different partitions are not concatenated; regroup one of them first)")
+            engines.append(o._engine)
+        return self._derived_like(eng.concat(*engines))
+
+    def extended(self, data_navigation_new: pd.DataFrame, data_search_new: Optional[pd.DataFrame] = None, ids=None):
+        """`insert`'s counterpart that returns a NEW index and works on `storage="f16"` (an extension; `lmi_concat`): the objects
+        are placed exactly as `insert` places them, built into a small index in the resident engine's storage and metric (a
+        `float16` frame goes up as halves), and the result is the resident index followed, bucket by bucket, by the new objects --
+        what `insert` leaves behind where `insert` works.  Returns `(new LearnedIndex, data_prediction)`; this object is
+        unchanged and the small index is closed, also when the concatenation is refused (`_capi.LmiError`: on `storage="f16"`, new
+        values so large that the result's scale pushes a stored half below the binary16 subnormals -- as a fresh build of all the
+        rows would be refused).  A placement onto a leaf path that holds no bucket is refused with ValueError, as in `insert`
+        without `create_buckets`."""
+        eng = self._resident("extended")
+        dp, bucket_of, rows, labels = self._place(data_navigation_new, data_search_new, ids)
+        small = _capi.Index(eng.device, metric=eng.metric, storage=eng.storage)
+        try:
+            small.set_buckets(rows, bucket_of, eng.L, ids=labels)
+            new = eng.concat(small)
+        finally:
+            small.close()
+        return self._derived_like(new), dp
 
     def delete(self, ids) -> int:
         """Removes every object whose id (DataFrame index label) is in `ids` from the HBM-resident index (an extension;
@@ -384,11 +443,7 @@ class LearnedIndex(Logger):
         out like a fresh build of the kept objects; it is answered by `search_resident`.  Unlike `delete` it works on a
         `storage="f16"` index.  Ids not present are ignored; this object is unchanged."""
         eng = self._resident("subset")
-        other = LearnedIndex(self.root_model, self.internal_models, self.bucket_paths)
-        other._engine = eng.subset(np.asarray(ids).reshape(-1), drop=drop)
-        other._engine_key = self._mutated_key()
-        other._path_ids, other._entry_paths, other._nav_cap = self._path_ids, self._entry_paths, self._nav_cap
-        return other
+        return self._derived_like(eng.subset(np.asarray(ids).reshape(-1), drop=drop))
 
     def regroup(self, ids, data_prediction, root_model: Optional[NeuralNetwork] = None,
                 internal_models: Optional[Dict[Tuple, NeuralNetwork]] = None,
