@@ -410,6 +410,59 @@ LMI_API int lmi_buckets_insert_f16(lmi_index *h, const uint16_t *rows, const int
  * not returned. */
 LMI_API int lmi_bucket_read_f16(lmi_index *h, int bucket, uint16_t *rows, uint32_t *ids);
 
+/* Stored objects by id (the resident counterpart of `data_search.loc[ids]`, LearnedIndex.py:357; lmi_bucket_read needs the bucket
+ * number, this call finds it).  For request i:
+ *   bucket[i], row[i]   the location of the FIRST live stored row whose id equals ids[i], first in lexicographic order: bucket
+ *                       ascending, then row within the bucket ascending -- not slab position (after lmi_buckets_insert / _delete a
+ *                       bucket may lie anywhere in the slab).  (-1, -1): no live row carries the id.  Stored ids are the caller's and
+ *                       may repeat; the rule holds bit for bit on any grid (the minimum of a set does not depend on the order it is
+ *                       taken in).
+ *   rows[i][0..d)       exactly what lmi_bucket_read(bucket[i]) (lmi_rows_fetch_f16: lmi_bucket_read_f16) returns at index row[i]:
+ *                       the row-major values (LMI_STORAGE_F32, prefilter on), the f32 fragments unpacked (lmi_set_prefilter(0)), the
+ *                       halves widened and unscaled, both exact (LMI_STORAGE_F16).  The L2 norm column is not returned.  An absent id
+ *                       gets a row of zeros.
+ * Request ids need not be sorted and may repeat; every occurrence gets the same answer.  rows, bucket and row are each nullable, at
+ * least one must be given; rows == NULL makes the call a pure locate.  on_device covers all four pointers: ids on the device are
+ * copied to the host (4n bytes, the one internal synchronisation -- the list is sorted there), and with rows on the device the
+ * vectors never leave it.
+ * lmi_rows_fetch_f16: the rows as halves.  LMI_STORAGE_F16: the halves that were ingested.  The two f32 forms are narrowed on the
+ * device, as by lmi_bucket_read_f16: if any fetched value is not finite or not exactly representable in binary16 the call fails and
+ * says so; host outputs (rows, bucket, row) then receive nothing, a device `rows` buffer has unspecified content.  The zero rows of
+ * absent ids do not count.
+ * How: the ids are sorted and de-duplicated on the host; every live row of the index searches its id in that list (one pass over the
+ * ids, 4N bytes) and lowers the id's word of a location table with one 64-bit atomicMin; one gather per piece of requests reads the
+ * located rows out of the stored image.  No id table is kept between calls, so a mutation can never make one stale.  Device memory
+ * of the call: at most 16n bytes of tables, freed before it returns, and -- for host outputs -- the handle's staging buffer, one
+ * piece of requests at a time (what 64 MiB hold; device outputs are written in place, 2^24 requests per launch).  Besides the
+ * outputs one more transfer reaches the host, with device pointers too: the location table, 8 bytes per distinct id, ahead of the
+ * closing synchronisation -- lmi_debug_fetch_plan's FOUND is counted from it.
+ * The call only reads: clone views, lmi_subset / lmi_regroup / lmi_concat results and sharded ranks are served alike (a rank reports
+ * the ids of buckets it does not own as absent: those buckets hold no live rows there).  It synchronises the handle's stream before it
+ * returns, like lmi_bucket_read.
+ * Refused before any launch: a NULL handle; an index that is not built; n < 0 or n >= 2^31; NULL ids with n > 0; rows, bucket and row
+ * all NULL.  n == 0 succeeds and writes nothing. */
+LMI_API int lmi_rows_fetch(lmi_index *h, const uint32_t *ids, int64_t n, float *rows /* nullable */, int32_t *bucket /* nullable */,
+                           int32_t *row /* nullable */, int on_device);
+LMI_API int lmi_rows_fetch_f16(lmi_index *h, const uint32_t *ids, int64_t n, uint16_t *rows /* nullable */,
+                               int32_t *bucket /* nullable */, int32_t *row /* nullable */, int on_device);
+/* Test hook: requests per piece (one gather launch and, for host outputs, one round through the staging buffer) of the fetch calls
+ * on this thread, host and device outputs alike; 0 = the default (host outputs: what a 64-MiB stage holds; device outputs: 2^24).
+ * Refused outside [0, 2^24].  Never changes a result. */
+LMI_API int lmi_fetch_set_geometry(int64_t piece_rows);
+enum {
+    LMI_FETCH_PLAN_REQUESTS = 0,     /* n                                                                 */
+    LMI_FETCH_PLAN_UNIQUE,           /* distinct requested ids                                            */
+    LMI_FETCH_PLAN_PIECES,           /* pieces the requests were cut into                                 */
+    LMI_FETCH_PLAN_PIECE_ROWS,       /* requests per piece (the last may hold fewer)                      */
+    LMI_FETCH_PLAN_FOUND,            /* requests whose id a live row carries (every occurrence counts)    */
+    LMI_FETCH_PLAN_FORM,             /* the stored form read: 0 f32 fragments, 1 row-major f32, 2 fp16 fragments */
+    LMI_FETCH_PLAN_WORKSPACE_BYTES,  /* device bytes of the call's tables + the stage it asked for        */
+    LMI_FETCH_PLAN_COUNT
+};
+/* What the last lmi_rows_fetch / lmi_rows_fetch_f16 on this thread did (all zero after a refused or failed call; n == 0 reports
+ * the form only): out[0..n) <- the first min(n, LMI_FETCH_PLAN_COUNT) words. */
+LMI_API int lmi_debug_fetch_plan(int64_t *out, int n);
+
 /* Navigation: bucket_order[nq][nb] <- the nb most probable classes per query, most probable first.
  * logits (nullable) [nq][L] <- raw outputs of the last Linear layer.
  * With on_device, queries_nav (here and in every call that takes it) must be 16-byte aligned -- any whole device allocation is:

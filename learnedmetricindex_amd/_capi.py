@@ -55,6 +55,9 @@ REGROUP_MAX_LABELS = 1 << 20                              # lmi_regroup: L_new s
 CONCAT_MAX_PARTS = 64   # LMI_CONCAT_MAX_PARTS: parts of one `Index.concat`, the receiver included
 #: the LMI_CONCAT_PLAN_* words, in their order (lmi_debug_concat_plan)
 CONCAT_PLAN_FIELDS = ("PARTS", "ROWS", "SLAB_ROWS", "MAP_BYTES", "RESCALED_PARTS")
+#: the LMI_FETCH_PLAN_* words, in their order (lmi_debug_fetch_plan)
+FETCH_PLAN_FIELDS = ("REQUESTS", "UNIQUE", "PIECES", "PIECE_ROWS", "FOUND", "FORM", "WORKSPACE_BYTES")
+FETCH_MAX_PIECE_ROWS = 1 << 24   # what lmi_fetch_set_geometry takes at most
 
 _lib = None
 
@@ -205,6 +208,11 @@ SIGNATURES = {
     "lmi_buckets_add_owned_rows_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
     "lmi_buckets_insert_f16": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _i64p]),
     "lmi_bucket_read_f16": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    # stored objects by id: (handle, ids, n, rows, bucket, row, on_device)
+    "lmi_rows_fetch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_rows_fetch_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_fetch_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
+    "lmi_debug_fetch_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_scan_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
                                          ctypes.c_int]),
     "lmi_search_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
@@ -1179,6 +1187,44 @@ class Index:
         _check(fn(self._h, int(b), _ptr(rows), _ptr(ids)))
         return rows, ids
 
+    def fetch(self, ids, dtype=np.float32, rows_out=None, where: bool = False):
+        """The stored vectors of the objects with these ids (`lmi_rows_fetch`; np.float16: `lmi_rows_fetch_f16`): rows [n, d], exactly
+        what `read_bucket` returns for them, in the order asked for.  `ids`: any integer array-like with values in [0, 2^32), in any
+        order, repeats allowed (ValueError otherwise, before the library is called).  An id no stored object carries gets a row of
+        zeros; `where=True` returns (rows, bucket int32 [n], row int32 [n]) -- the object's bucket and its row in `read_bucket`'s
+        order, (-1, -1) for an absent id, and for an id several objects carry the first one by (bucket, row).  `rows_out`: a
+        C-contiguous array [n, d] of `dtype` to fill.  np.float16 on an f32 index narrows on the device and raises `LmiError` when
+        a fetched value is not exactly representable in binary16 (`rows_out` is then untouched)."""
+        ids_a, dtype = fetch_args("fetch", self, ids, dtype)
+        n = int(ids_a.shape[0])
+        rows = np.empty((n, self.d), dtype=dtype) if rows_out is None else rows_out
+        if not (isinstance(rows, np.ndarray) and rows.shape == (n, self.d) and rows.dtype == dtype and rows.flags.c_contiguous):
+            raise ValueError(f"fetch: rows_out must be a C-contiguous {dtype} array of shape {(n, self.d)}")
+        bucket = np.empty(n, np.int32) if where else None
+        row = np.empty(n, np.int32) if where else None
+        fn = lib().lmi_rows_fetch_f16 if dtype == np.float16 else lib().lmi_rows_fetch
+        _check(fn(self._h, _ptr(ids_a), n, _ptr(rows), _ptr(bucket), _ptr(row), 0))
+        return (rows, bucket, row) if where else rows
+
+    def locate(self, ids):
+        """(bucket int32 [n], row int32 [n]) of the objects with these ids, as `fetch(.., where=True)` reports them, without reading
+        a vector (`lmi_rows_fetch` with no rows)."""
+        ids_a, _ = fetch_args("locate", self, ids, np.float32)
+        n = int(ids_a.shape[0])
+        bucket, row = np.empty(n, np.int32), np.empty(n, np.int32)
+        _check(lib().lmi_rows_fetch(self._h, _ptr(ids_a), n, None, _ptr(bucket), _ptr(row), 0))
+        return bucket, row
+
+    def fetch_device(self, ids_t, rows_t=None, bucket_t=None, row_t=None) -> None:
+        """`fetch` on contiguous device tensors: ids_t [n] holding uint32 bit patterns (torch.uint32 or torch.int32) -> rows_t [n, d]
+        (torch.float32: `lmi_rows_fetch`; torch.float16: `lmi_rows_fetch_f16`), bucket_t / row_t int32 [n]; each output may be
+        None, not all.  The vectors never leave the device (the ids are copied to the host to be sorted: 4n bytes)."""
+        n = fetch_device_args(self, ids_t, rows_t, bucket_t, row_t)
+        if n == 0:   # (an empty tensor has no address: nothing to ask the library for)
+            return
+        fn = lib().lmi_rows_fetch_f16 if rows_t is not None and _is_f16(rows_t) else lib().lmi_rows_fetch
+        _check(fn(self._h, _ptr(ids_t), n, _ptr(rows_t), _ptr(bucket_t), _ptr(row_t), 1))
+
     def workspace_bytes(self, nq: int, nb: int) -> int:
         """Device bytes the per-call workspaces of a search of nq queries x nb buckets need (lmi_workspace_bytes)."""
         out = ctypes.c_int64(0)
@@ -1597,6 +1643,67 @@ def concat_last_plan() -> dict:
     w = (ctypes.c_int64 * len(CONCAT_PLAN_FIELDS))()
     _check(lib().lmi_debug_concat_plan(w, len(CONCAT_PLAN_FIELDS)))
     return dict(zip((n.lower() for n in CONCAT_PLAN_FIELDS), (int(v) for v in w)))
+
+
+def fetch_args(who: str, index, ids, dtype):
+    """(ids uint32 [n], dtype) of `Index.fetch` / `Index.locate`, or ValueError; needs no library."""
+    if getattr(index, "_h", None) is None or not index._h:
+        raise ValueError(f"{who}: the index is closed")
+    try:
+        dtype = np.dtype(dtype)
+    except TypeError:
+        raise ValueError(f"{who}: dtype must be np.float32 or np.float16, not {dtype!r}") from None
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError(f"{who}: dtype must be np.float32 or np.float16, not {dtype}")
+    a = np.asarray(ids).reshape(-1)
+    if a.size and a.dtype.kind not in "iu":   # (an empty list is float64 and has nothing to truncate)
+        raise ValueError(f"{who}: ids must be integers, not {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+        raise ValueError(f"{who}: ids must lie in [0, 2^32)")
+    if a.size >= 2 ** 31:
+        raise ValueError(f"{who}: {a.size} ids, at most 2^31 - 1")
+    return _np(a, np.uint32), dtype
+
+
+def fetch_device_args(index, ids_t, rows_t, bucket_t, row_t) -> int:
+    """n of `Index.fetch_device`, or ValueError; needs no library."""
+    who = "fetch_device"
+    if getattr(index, "_h", None) is None or not index._h:
+        raise ValueError(f"{who}: the index is closed")
+    def dev(name, t, dtypes, shape):
+        if not (hasattr(t, "data_ptr") and getattr(t, "is_cuda", False) and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous torch tensor on the device")
+        if str(t.dtype).replace("torch.", "") not in dtypes:
+            raise ValueError(f"{who}: {name} must be {' or '.join(dtypes)}, not {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{who}: {name} must have shape {shape}, not {tuple(t.shape)}")
+    if not hasattr(ids_t, "shape") or len(ids_t.shape) != 1:
+        raise ValueError(f"{who}: ids_t must be one-dimensional")
+    n = int(ids_t.shape[0])
+    dev("ids_t", ids_t, ("uint32", "int32"), (n,))
+    if rows_t is None and bucket_t is None and row_t is None:
+        raise ValueError(f"{who}: rows_t, bucket_t and row_t are all None: nothing was asked for")
+    if rows_t is not None:
+        dev("rows_t", rows_t, ("float32", "float16"), (n, index.d))
+    for name, t in (("bucket_t", bucket_t), ("row_t", row_t)):
+        if t is not None:
+            dev(name, t, ("int32",), (n,))
+    return n
+
+
+def fetch_set_geometry(piece_rows: int = 0) -> None:
+    """Test hook (`lmi_fetch_set_geometry`): requests per piece of `Index.fetch` / `locate` / `fetch_device` on this thread, an integer
+    in [0, 2^24]; 0 = the default (host outputs: what a 64-MiB stage holds; device outputs: 2^24).  Never changes a result."""
+    if isinstance(piece_rows, bool) or not isinstance(piece_rows, (int, np.integer)) or not 0 <= piece_rows <= FETCH_MAX_PIECE_ROWS:
+        raise ValueError(f"fetch_set_geometry: piece_rows {piece_rows!r} must be an integer in [0, {FETCH_MAX_PIECE_ROWS}] (0: the default)")
+    _check(lib().lmi_fetch_set_geometry(int(piece_rows)))
+
+
+def fetch_last_plan() -> dict:
+    """What the last fetch on this thread did (`lmi_debug_fetch_plan`): `FETCH_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(FETCH_PLAN_FIELDS))()
+    _check(lib().lmi_debug_fetch_plan(w, len(FETCH_PLAN_FIELDS)))
+    return dict(zip(FETCH_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def union_set_geometry(query_rows: int = 0, slab_bytes: int = 0) -> None:

@@ -34,6 +34,8 @@
 #include "lmi_host_regroup.h"   // lmi_regroup, lmi_regroup_set_geometry, lmi_debug_regroup_plan
 #include "lmi_concat.h"         // the kernels of lmi_concat
 #include "lmi_host_concat.h"    // lmi_concat, lmi_debug_concat_plan
+#include "lmi_fetch.h"          // the kernels of lmi_rows_fetch
+#include "lmi_host_fetch.h"     // lmi_rows_fetch / lmi_rows_fetch_f16, lmi_fetch_set_geometry, lmi_debug_fetch_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

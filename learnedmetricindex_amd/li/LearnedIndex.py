@@ -285,6 +285,78 @@ class LearnedIndex(Logger):
         return self._search_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, k,
                                  time.time(), stop_mass, path_mass, stop_rows, merge, filter, filter_of)
 
+    # ---- stored objects by id (an extension; the resident counterpart of the reference's `data_search.loc[ids]`, :357) ----
+    @staticmethod
+    def _missing(who: str, ids, found) -> KeyError:
+        """What `DataFrame.loc` would raise for labels it does not hold: the absent ids, ten at most."""
+        gone = np.unique(np.asarray(ids).reshape(-1)[~found])
+        more = f" and {gone.size - 10} more" if gone.size > 10 else ""
+        return KeyError(f"{who}: {[int(v) for v in gone[:10]]}{more} not in the index")
+
+    def reconstruct(self, ids, dtype=np.float32, missing: str = "raise"):
+        """The scan vectors of the objects with these ids (DataFrame index labels), [n, d], read back from the index resident in HBM
+        (after `prepare`, a `search` or `index_io.load_index`; `Index.fetch`): no DataFrame needed, and exactly the stored values
+        also for `storage="f16"`.  `ids` in any order, repeats allowed.  `dtype`: np.float32 or np.float16 (an f32 index whose
+        values are not binary16-exact raises `_capi.LmiError`).  `missing`: "raise" (default) raises KeyError naming up to ten ids
+        no object carries, as `DataFrame.loc` would; "zero" returns (rows, found bool [n]) with zero rows for them."""
+        if missing not in ("raise", "zero"):
+            raise ValueError(f"missing {missing!r} unknown: 'raise' or 'zero'")
+        eng = self._resident("reconstruct")
+        rows, bucket, _ = eng.fetch(ids, dtype=dtype, where=True)
+        found = bucket >= 0
+        if missing == "zero":
+            return rows, found
+        if not found.all():
+            raise self._missing("reconstruct", ids, found)
+        return rows
+
+    @staticmethod
+    def _torch_device(eng):
+        import torch
+
+        return torch.device("cuda", eng.device)
+
+    def search_like(self, ids, n_categories: List[int], n_buckets: int = 1, k: int = 10, queries_navigation=None, **kw):
+        """Query by stored object: `search_resident` with the scan vectors of the objects `ids` as queries -- "more like this".  The
+        vectors are fetched into a device tensor (`Index.fetch_device`) and handed to the engine's device calls as they lie: no
+        host copy of them exists.  Returns what `search_resident(V, V, ..)` with V = `reconstruct(ids)` returns, bit for bit; `**kw`
+        (`stop_mass`, `path_mass`, `stop_rows`, `merge`, `filter`, `filter_of`) as there.  The index holds scan vectors only: where
+        the root model's input width differs from the scan width `queries_navigation` [n, d_nav] is required (ValueError
+        otherwise); where it is the same the fetched vectors navigate too unless `queries_navigation` is given.  KeyError for an
+        id no object carries."""
+        import torch
+
+        eng = self._resident("search_like")
+        ids_a, _ = _capi.fetch_args("search_like", eng, ids, np.float32)
+        n = int(ids_a.shape[0])
+        if queries_navigation is None and eng.d_nav != eng.d:
+            raise ValueError(f"search_like: the root model takes {eng.d_nav} inputs, the index stores vectors of {eng.d}: it holds no "
+                             "navigation vectors, pass queries_navigation")
+        unknown = sorted(set(kw) - {"stop_mass", "path_mass", "stop_rows", "merge", "filter", "filter_of"})
+        if unknown:
+            raise TypeError(f"search_like: unexpected keyword {unknown[0]!r}")
+        merge = kw.get("merge", "ranks")
+        self._check_merge(merge)
+        self._check_filter(kw.get("filter"), kw.get("filter_of"), merge)
+        self._check_stop_mass(kw.get("stop_mass"), n_categories)
+        self._check_path_mass(kw.get("path_mass"), n_categories)
+        qn = None
+        if queries_navigation is not None:
+            qn = np.ascontiguousarray(_query_array(queries_navigation), dtype=np.float32)
+            if qn.ndim != 2 or qn.shape[0] != n:
+                raise ValueError(f"search_like: queries_navigation must be [{n}, d_nav], not {tuple(qn.shape)}")
+        dev = self._torch_device(eng)
+        ids_t = torch.from_numpy(ids_a.view(np.int32)).to(dev)
+        rows_t = torch.empty((n, eng.d), dtype=torch.float32, device=dev)
+        bucket_t = torch.empty((n,), dtype=torch.int32, device=dev)
+        eng.fetch_device(ids_t, rows_t, bucket_t)
+        found = bucket_t.cpu().numpy() >= 0 if n else np.ones(0, dtype=bool)
+        if not found.all():
+            raise self._missing("search_like", ids_a, found)
+        qn_t = rows_t if qn is None else torch.from_numpy(qn).to(dev)
+        return self._search_with(eng, qn_t, rows_t, n_categories, n_buckets, k, time.time(), kw.get("stop_mass"), kw.get("path_mass"),
+                                 kw.get("stop_rows"), merge, kw.get("filter"), kw.get("filter_of"), on_device=True)
+
     MERGES = ("ranks", "union")
 
     @classmethod
@@ -596,17 +668,21 @@ class LearnedIndex(Logger):
                                  filter, filter_of)
 
     def _search_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass=None, path_mass=None,
-                     stop_rows=None, merge="ranks", filter=None, filter_of=None):
+                     stop_rows=None, merge="ranks", filter=None, filter_of=None, on_device=False):
+        """`on_device` (`search_like`): the queries are device tensors and go to the `_device` forms of the same engine calls."""
         if filter is not None and not isinstance(filter, _capi.Filter):   # an id list: one keep filter, made for this call
             made = _capi.Filter(eng, [np.asarray(filter).reshape(-1)])
             try:
                 return self._search_with(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, stop_mass, path_mass,
-                                         stop_rows, merge, made, filter_of)
+                                         stop_rows, merge, made, filter_of, on_device)
             finally:
                 made.close()
-        run = self._search_union if merge == "union" else self._search_chunks
+        union, chunks = self._search_union, self._search_chunks
+        if on_device:
+            union, chunks = functools.partial(union, on_device=True), functools.partial(chunks, on_device=True)
+        run = union if merge == "union" else chunks
         if filter is not None:
-            run = functools.partial(self._search_union, filter=filter, filter_of=filter_of)
+            run = functools.partial(union, filter=filter, filter_of=filter_of)
         if stop_mass is None and path_mass is None and stop_rows is None:
             return run(eng, queries_navigation, queries_search, n_categories, n_buckets, k, s)
         # the engine's own settings come back afterwards: a later call without the arguments is as before
@@ -624,13 +700,20 @@ class LearnedIndex(Logger):
             eng.set_path_mass(before[1])
             eng.set_stop_rows(before[2])
 
-    def _search_union(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, filter=None, filter_of=None):
+    def _search_union(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, filter=None, filter_of=None,
+                      on_device=False):
         """merge="union": the batch goes to the library whole (it groups the queries itself); a multi-level index is walked in
-        pieces of `_nav_chunk()` queries, the walk's queue limit.  `filter` (a `_capi.Filter`) and `filter_of` go with the calls."""
+        pieces of `_nav_chunk()` queries, the walk's queue limit.  `filter` (a `_capi.Filter`) and `filter_of` go with the calls.
+        `on_device` (`search_like`): the queries are float32 device tensors and go to the `_device` forms, in the same pieces."""
         fo = None if filter_of is None else np.asarray(filter_of).reshape(-1)
         measured_time = defaultdict(float)
-        qn = np.ascontiguousarray(_query_array(queries_navigation), dtype=np.float32)   # the union calls take binary32 queries
-        qs = qn if queries_search is queries_navigation else np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
+        if on_device:
+            qn, qs = queries_navigation, queries_search
+            search_union, search_tree_union = self._device_form(eng.search_union_device, k), self._device_form(eng.search_tree_union_device, k)
+        else:
+            qn = np.ascontiguousarray(_query_array(queries_navigation), dtype=np.float32)   # the union calls take binary32 queries
+            qs = qn if queries_search is queries_navigation else np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
+            search_union, search_tree_union = eng.search_union, eng.search_tree_union
         assert qn.shape[0] == qs.shape[0]
         nq = qs.shape[0]
         if len(n_categories) == 1:
@@ -639,10 +722,10 @@ class LearnedIndex(Logger):
             return np.empty((0, k)), np.empty((0, k), dtype=np.uint32), measured_time
         t0 = time.time()
         if len(n_categories) == 1:
-            d32, nns = eng.search_union(qn, qs, n_buckets, k, filter=filter, filter_of=fo)[:2]
+            d32, nns = search_union(qn, qs, n_buckets, k, filter=filter, filter_of=fo)[:2]
         else:
             step = self._nav_chunk()
-            parts = [eng.search_tree_union(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets, k,
+            parts = [search_tree_union(qn[lo: lo + step], qn[lo: lo + step] if qs is qn else qs[lo: lo + step], n_buckets, k,
                                            filter=filter, filter_of=None if fo is None else fo[lo: lo + step])[:2]
                      for lo in range(0, nq, step)]
             d32 = parts[0][0] if len(parts) == 1 else np.concatenate([p[0] for p in parts])
@@ -793,10 +876,17 @@ class LearnedIndex(Logger):
         measured_time["search"] = time.time() - s
         return lims, d32.astype(np.float64), nns, measured_time
 
-    def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s):
+    def _search_chunks(self, eng, queries_navigation, queries_search, n_categories, n_buckets, k, s, on_device=False):
+        """`on_device` (`search_like`): the queries are float32 device tensors and go to the `_device` forms, in the same chunks."""
         measured_time = defaultdict(float)
-        qn = _query_array(queries_navigation)   # float16 arrays stay halves: the engine uploads them as they are
-        qs = qn if queries_search is queries_navigation else _query_array(queries_search)
+        if on_device:
+            qn, qs = queries_navigation, queries_search
+            kout = _capi.Index.kout(n_buckets, k)
+            search, search_tree = self._device_form(eng.search_device, kout), self._device_form(eng.search_tree_device, kout)
+        else:
+            qn = _query_array(queries_navigation)   # float16 arrays stay halves: the engine uploads them as they are
+            qs = qn if queries_search is queries_navigation else _query_array(queries_search)
+            search, search_tree = eng.search, eng.search_tree
         assert qn.shape[0] == qs.shape[0]
         nq = qs.shape[0]
         if n_buckets >= 2:
@@ -821,13 +911,13 @@ class LearnedIndex(Logger):
             qn_c = qn if whole else qn[lo:hi]
             qs_c = qs if whole else (qn_c if qs is qn else qs[lo:hi])
             if len(n_categories) == 1:
-                d32, nn, _ = eng.search(qn_c, qs_c, n_buckets, k)
+                d32, nn = search(qn_c, qs_c, n_buckets, k)[:2]
                 t = eng.timings() * 1e-3
                 measured_time["inference"] += float(t[_capi.T_INFERENCE])
             else:
                 # the priority-queue walk on the device, then the scan of its buckets: one call (lmi_search_tree), the scan vectors
                 # uploaded while the walk runs
-                d32, nn = eng.search_tree(qn_c, qs_c, n_buckets, k)
+                d32, nn = search_tree(qn_c, qs_c, n_buckets, k)
                 t = eng.timings() * 1e-3
                 measured_time["inference"] += float(t[_capi.T_INFERENCE])
             measured_time["search_within_buckets"] += float(t[_capi.T_ROUTE] + t[_capi.T_SCAN] + t[_capi.T_MERGE])
@@ -841,6 +931,22 @@ class LearnedIndex(Logger):
         assert dists.shape == nns.shape
         measured_time["search"] = time.time() - s
         return dists, nns, measured_time
+
+    @staticmethod
+    def _device_form(call, kout: int):
+        """The `_device` form of an engine's search call (`search_like`: the queries are float32 device tensors) as the host form is
+        called: (qn_t, qs_t, n_buckets, k, **kw) -> (dists f32 [n, kout], ids u32 [n, kout]) as numpy, the outputs made beside the
+        queries and read back once the call has run."""
+        def run(qn_t, qs_t, n_buckets, k, **kw):
+            import torch
+
+            d_t = torch.empty((int(qs_t.shape[0]), kout), dtype=torch.float32, device=qs_t.device)
+            i_t = torch.empty((int(qs_t.shape[0]), kout), dtype=torch.int32, device=qs_t.device)
+            call(qn_t, qs_t, n_buckets, k, d_t, i_t, **kw)
+            if d_t.is_cuda:
+                torch.cuda.synchronize(d_t.device)
+            return d_t.cpu().numpy(), i_t.cpu().numpy().view(np.uint32)
+        return run
 
     # ------------------------------------------------------------------------------------------
     def _upload_tree(self, eng, n_levels: int) -> None:

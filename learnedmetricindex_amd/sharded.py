@@ -292,6 +292,44 @@ class ShardedSearcher:
             self.index.set_stop_rows(self._rows_before)
             self._rows_before = None
 
+    # ---- stored objects by id across the ranks: every rank fetches what it owns, the join is a host-side pick.  `reconstruct` is the
+    #      call; `fetch_part` and `join_fetch_parts` are its two halves, public as helpers for ranks that live in separate processes
+    #      (the library makes no collective here: INTEGRATION.md section 3 has the recipe) ----
+    def fetch_part(self, ids, dtype=np.float32):
+        """This rank's part of a fetch: (rows [n, d], bucket i32 [n], row i32 [n]) of `Index.fetch(ids, where=True)` on the rank's
+        handle.  An id whose bucket another rank owns is absent here (zero row, bucket -1): the bucket holds no rows on this rank."""
+        return self.index.fetch(ids, dtype=dtype, where=True)
+
+    @staticmethod
+    def join_fetch_parts(ids, parts):
+        """The ranks' `fetch_part` results for the same `ids`, in rank order -> rows [n, d]: per request the row of the rank that
+        holds it (`bucket >= 0`); where objects on several ranks carry the id, the first by (bucket, row), as on one handle.  Host
+        arrays, no collective.  KeyError naming up to ten ids no rank holds."""
+        absent = np.iinfo(np.int64).max
+        where = np.stack([np.where(b >= 0, (b.astype(np.int64) << 32) | r.astype(np.int64), absent) for _, b, r in parts])   # [world, n]
+        best = where.argmin(axis=0)
+        found = where.min(axis=0) != absent
+        rows = np.zeros_like(parts[0][0])
+        for rank, (part_rows, _, _) in enumerate(parts):
+            take = found & (best == rank)
+            rows[take] = part_rows[take]
+        if not found.all():
+            gone = np.unique(np.asarray(ids).reshape(-1)[~found])
+            more = f" and {gone.size - 10} more" if gone.size > 10 else ""
+            raise KeyError(f"reconstruct: {[int(v) for v in gone[:10]]}{more} not in the index")
+        return rows
+
+    def reconstruct(self, ids, dtype=np.float32, peers=()):
+        """The scan vectors of the objects with these ids, [n, d], from a bucket-sharded index: what `Index.fetch` returns on one
+        handle that holds everything.  `peers`: the other ranks' searchers where one process drives several ranks (one per
+        card); their parts are joined on the host.  No collective is made: ranks that live in other processes exchange their
+        `fetch_part` results by whatever carries host arrays and call `join_fetch_parts`.  KeyError for an id no rank holds."""
+        if self.world > 1 and len(peers) != self.world - 1:
+            raise ValueError(f"reconstruct: a world of {self.world} ranks needs the {self.world - 1} other ranks' searchers as peers "
+                             f"(got {len(peers)}); across processes exchange fetch_part() results and call join_fetch_parts()")
+        parts = [s.fetch_part(ids, dtype) for s in sorted([self, *peers], key=lambda s: s.rank)]
+        return self.join_fetch_parts(ids, parts)
+
     def _timed(self, name, fn, on_cuda: bool):
         if not self.time_collectives or self.world == 1:
             return fn()
