@@ -1152,6 +1152,94 @@ enum {
  * min(n, LMI_RANGE_SORT_PLAN_COUNT) words. */
 LMI_API int lmi_debug_range_sort_plan(int64_t *out, int n);
 
+/* The exact range search through the index (no reference counterpart): every range call above answers "the objects within radius[q]
+ * among the buckets that were visited"; this one answers it for EVERYTHING the handle stores, and still skips the buckets that cannot
+ * hold an answer.  It discards them by the geometry of the partition: a COVER holds per bucket a centre, a covering radius and a row
+ * count, and a PRUNING PASS turns (queries, radii) into the list of buckets whose ball the query's ball may meet.
+ * The cover (lmi_cover_create): an opaque object like lmi_filter, made from a built handle; it owns its device arrays and may outlive
+ * the handle.  For every bucket b of the index (L buckets; d = the caller's columns -- for LMI_METRIC_L2 the stored -|x|^2/2 column is
+ * not part of it):
+ *   n_b      the live rows (lmi_bucket_sizes; 0 for a bucket this handle does not own).
+ *   c_b [d]  binary32: the mean of the live rows by lmi_kmeans's update rule: e = the smallest integer with max|x| < 2^e over the
+ *            finite live values of the whole index (0 for all-zero data; the call takes this maximum itself, in a pass of its own),
+ *            q(v) = rint(v * 2^(36-e)), S = the int64 sum of q over the bucket's rows per column, c = (float)((double)S / (double)n_b
+ *            * 2^(e-36)).  Integer sums are associative: the centres are the same bits on any grid.  An empty bucket gets zeros.
+ *   R_b      binary32: per live row the binary64 chain acc = fma(delta, delta, acc), delta = (double)x[t] - (double)c_b[t], t
+ *            ascending from acc = 0, one unsplit chain per row; R2_b = the maximum of the chains; R_b = 0 if R2_b == 0, else
+ *            nextafterf((float)sqrt(R2_b), +inf).  A one-row bucket and a bucket of equal rows have R_b = 0 where q loses nothing of
+ *            the row (no value below 2^(e-36) steps), since the mean is then the row itself.
+ *            A bucket that holds a value that is not finite gets R_b = +inf and is always visited (its centre is unspecified).
+ *   cn_b     binary64: sqrt(sum c_b[t]^2), a chain in ascending t.
+ * The rows are read where they lie (through the per-bucket tables, as lmi_bucket_read does), in three passes: maximum, sums, radii.
+ * lmi_cover_create synchronises the handle's stream and only READS the handle: it is allowed on clone views and while clone views
+ * live; it returns when the cover is complete.  A cover holds 4 L d + 16 L bytes of device memory; the call allocates 8 L d + 8 L + 4
+ * bytes more while it runs.  A failed allocation names the bytes it wanted and frees everything the call allocated.
+ * Refused: a NULL handle or out; an index that is not built; an index that is not stored row-major (lmi_set_prefilter(0),
+ * LMI_STORAGE_F16), in lmi_scan_range's words; an index of more than 65535 buckets; a bucket of more than 2^26 rows (the bound of the
+ * integer sums, as in lmi_kmeans), by name.
+ * lmi_cover_read: HOST pointers, each nullable: centres [L][d], radius [L], counts [L].
+ * Validity is lmi_filter's rule: a cover fits the handle it was made from and that handle's clone views, keyed by the layout stamp and
+ * the device.  After lmi_buckets_insert / lmi_buckets_delete, on the output of lmi_subset / lmi_regroup / lmi_concat and on any other
+ * index it is refused -- the message says "stale" -- and must be made again.
+ * The admission rule, one binary64 function with explicit fma (csrc/lmi_cover_plan.h; the kernel and a stand-alone CPU self-test run
+ * the same text).  For query q, bucket b, r = (double)radius[q], qn = sqrt(sum q[t]^2) (a chain in ascending t) and
+ * u = (d + 8) * 2^-23:
+ *   IP   ub = (sum q[t] c_b[t]) + qn R_b, the sum one unsplit chain in ascending t;  m = u (1 + |r| + qn (cn_b + R_b));
+ *        b is PRUNED iff ub < 1 - r - m.
+ *   L2   dc = sqrt(sum (q[t] - c_b[t])^2), an unsplit chain;  lo = max(0, dc - R_b);  m = u (qn + cn_b + R_b)^2;
+ *        b is PRUNED iff lo lo > r + m.
+ * b is ADMITTED iff n_b > 0, radius[q] is neither NaN nor -inf, and b is not pruned; a NaN anywhere in the test admits (a NaN query
+ * admits every non-empty bucket); a radius of +inf admits every non-empty bucket.  The margin m makes the rule hold against the
+ * distance the scan COMPUTES in binary32, not the real one: whenever some live row of b has a computed distance <= radius[q], b is
+ * admitted (DESIGN.md 5.14.6 proves it).  Every (query, bucket) verdict is one thread's unsplit chain in a fixed order: the admitted
+ * set does not depend on groups, waves or grids.
+ * lmi_cover_order: row q of bucket_order [nq][nb] <- the admitted bucket ids in ASCENDING bucket id, then -1 up to nb; counts [nq] <-
+ * the number admitted.  Both nullable; with bucket_order == NULL the call only counts (nb is not looked at).  If some query admits
+ * more than nb buckets the call is refused -- the message names the first such query, its count and nb -- and NOTHING is written.
+ * radius is a HOST float [nq], also with on_device; queries_search, bucket_order and counts are all device pointers or all host
+ * pointers.  Refused before any launch: a NULL handle; an index that is not built or not stored row-major; a NULL, stale or foreign
+ * cover; nq < 0; with an order, nb < 1 or nq * nb >= 2^31; a NULL queries_search or radius where nq > 0.  nq == 0 succeeds.
+ * lmi_search_range_exact: the pruning pass, nb = max(1, max_q counts[q]), then lmi_scan_range's own schedule on that order, unchanged.
+ *   result     bit for bit that of lmi_scan_range(h, queries, the order of lmi_cover_order, nb, radius, f, filter_of, max_total):
+ *              (bucket, row) order; filters, max_total, lmi_range_result_*, lmi_range_result_sort and the pair counts as there.
+ *   complete   every live row of the handle whose scan distance is <= radius[q] (and which query q's filter allows) is in it: as sets
+ *              the result is lmi_knn_range over everything the handle stores, with equal distance bits per object.  On a sharded
+ *              rank: complete over the buckets the rank owns (lmi_join_range_parts joins the ranks' parts, all made at one nb).
+ *   nb_used    (nullable, a HOST int32) <- nb; counts (nullable, [nq]; host or device as on_device says) <- the buckets admitted.
+ * Refused, all before any launch or with no result made (*result = NULL): everything lmi_scan_range refuses; a NULL, stale or foreign
+ * cover; a query that needs more than 1024 buckets, the scan's limit on nb -- the message names the query and its count.
+ * nq == 0 succeeds with an empty result.  The call synchronises the stream once for the counts and then as lmi_scan_range does.
+ * Device memory of the pruning pass: 12 nq + 4 min(nq, query_rows) * 2 ceil(L / 64) bytes, and the [nq][nb] order.
+ * Not offered: _f16 query forms, lmi_pipeline_submit, a query split over several scans, a norm-interval bound beside the ball, exact
+ * k-NN by the same bound, the stored forms that are not row-major. */
+typedef struct lmi_cover lmi_cover;
+LMI_API int lmi_cover_create(lmi_index *h, lmi_cover **out);
+LMI_API int lmi_cover_destroy(lmi_cover *c);
+LMI_API int lmi_cover_read(const lmi_cover *c, float *centres /* [L][d], nullable */, float *radius /* [L], nullable */,
+                           int64_t *counts /* [L], nullable */);
+LMI_API int lmi_cover_order(lmi_index *h, const lmi_cover *c, const float *queries_search, int nq, const float *radius /* host [nq] */,
+                            int nb, int32_t *bucket_order /* [nq][nb], nullable */, int32_t *counts /* [nq], nullable */, int on_device);
+LMI_API int lmi_search_range_exact(lmi_index *h, const lmi_cover *c, const float *queries_search, int nq,
+                                   const float *radius /* host [nq] */, const lmi_filter *f /* nullable */,
+                                   const int32_t *filter_of /* host [nq], nullable */, int64_t max_total, lmi_range_result **result,
+                                   int32_t *nb_used /* host, nullable */, int32_t *counts /* [nq], nullable */, int on_device);
+/* Test hook, per thread: the queries of one group of the pruning pass (0 = the default: 16 384, fewer where a group's bitmap would pass
+ * 64 MiB).  Never changes a bit of an order or a result.  Refused: a value outside [0, 2^20]; nothing is set then. */
+LMI_API int lmi_cover_set_geometry(int64_t query_rows);
+enum {
+    LMI_COVER_PLAN_GROUPS = 0,        /* groups the queries were taken in                                                     */
+    LMI_COVER_PLAN_QUERY_ROWS,        /* queries per group (the last may be smaller)                                          */
+    LMI_COVER_PLAN_BUCKETS,           /* L of the cover                                                                       */
+    LMI_COVER_PLAN_ADMITTED,          /* admitted (query, bucket) pairs of the call                                           */
+    LMI_COVER_PLAN_MAX_PER_QUERY,     /* the most buckets any query admitted                                                  */
+    LMI_COVER_PLAN_NB_USED,           /* nb of the order that was written (0: the call only counted)                          */
+    LMI_COVER_PLAN_WORKSPACE_BYTES,   /* device bytes the pruning pass allocated (the order not included)                     */
+    LMI_COVER_PLAN_COUNT
+};
+/* What the last lmi_cover_order / lmi_search_range_exact on this thread did (all zero before the first, after a refused or failed call
+ * and after one with nq == 0); writes min(n, LMI_COVER_PLAN_COUNT) words.  lmi_debug_range_plan reports the scan of an exact call. */
+LMI_API int lmi_debug_cover_plan(int64_t *out, int n);
+
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);
 /* Mean of the timing slots over the calls made since lmi_timings_reset (the newest 128 at most), read

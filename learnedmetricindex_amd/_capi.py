@@ -58,6 +58,9 @@ CONCAT_PLAN_FIELDS = ("PARTS", "ROWS", "SLAB_ROWS", "MAP_BYTES", "RESCALED_PARTS
 #: the LMI_FETCH_PLAN_* words, in their order (lmi_debug_fetch_plan)
 FETCH_PLAN_FIELDS = ("REQUESTS", "UNIQUE", "PIECES", "PIECE_ROWS", "FOUND", "FORM", "WORKSPACE_BYTES")
 FETCH_MAX_PIECE_ROWS = 1 << 24   # what lmi_fetch_set_geometry takes at most
+#: the words of `cover_last_plan` (LMI_COVER_PLAN_* of include/lmi_hip.h, in the enum's order)
+COVER_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "BUCKETS", "ADMITTED", "MAX_PER_QUERY", "NB_USED", "WORKSPACE_BYTES")
+COVER_MAX_QUERY_ROWS = 1 << 20   # what lmi_cover_set_geometry takes at most
 
 _lib = None
 
@@ -213,6 +216,15 @@ SIGNATURES = {
     "lmi_rows_fetch_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int]),
     "lmi_fetch_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
     "lmi_debug_fetch_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    # the bucket cover and the exact range search: (handle, cover, queries, nq, radius on the host, ..)
+    "lmi_cover_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "lmi_cover_destroy": (ctypes.c_int, [_vp]),
+    "lmi_cover_read": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "lmi_cover_order": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "lmi_search_range_exact": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, ctypes.POINTER(_vp), _i32p, _vp,
+                                              ctypes.c_int]),
+    "lmi_cover_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
+    "lmi_debug_cover_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_scan_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
                                          ctypes.c_int]),
     "lmi_search_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
@@ -968,6 +980,104 @@ class Index:
                                  max_total: int = 0, sort: bool = False) -> "RangeResult":
         return self._range("search_tree", qn_t, qs_t, nb, radius, filter, filter_of, max_total, sort, (slab_t, ent_t))
 
+    # ---- the exact range search: buckets pruned by covering balls (include/lmi_hip.h, lmi_cover_create / lmi_search_range_exact) ----
+    def _cover_args(self, who: str, queries, radius, cover, device: bool) -> np.ndarray:
+        """radius f32[nq] of a call that takes a cover; argument errors are raised before the library loads."""
+        if getattr(self, "_h", None) is None or not self._h:
+            raise ValueError(f"{who}: the index is closed")
+        if not isinstance(cover, Cover):
+            raise ValueError(f"{who}: cover must be a _capi.Cover, not {type(cover).__name__}")
+        if getattr(cover, "_c", None) is None:
+            raise ValueError(f"{who}: the cover is closed")
+        if queries is None or not hasattr(queries, "shape") or len(queries.shape) != 2:
+            raise ValueError(f"{who}: queries_search must be a two-dimensional array")
+        if device:
+            if not (hasattr(queries, "is_cuda") and queries.is_cuda and queries.is_contiguous() and str(queries.dtype) == "torch.float32"):
+                raise ValueError(f"{who}: queries_search must be a contiguous float32 tensor on the device")
+        elif hasattr(queries, "is_cuda"):
+            raise ValueError(f"{who}: queries_search must be a numpy array (device tensors go to {who}_device)")
+        if self.d is not None and int(queries.shape[1]) != int(self.d):
+            raise ValueError(f"{who}: queries_search has {int(queries.shape[1])} columns, the index {int(self.d)}")
+        return self._range_args(who, 1, radius, 0, queries_search=queries)
+
+    @staticmethod
+    def _cover_nb(who: str, nb):
+        if nb is None:
+            return None
+        if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or nb < 1:
+            raise ValueError(f"{who}: nb {nb!r} must be an integer >= 1, or None to size the order by the counts")
+        return int(nb)
+
+    def cover_order(self, queries_search, radius, cover: "Cover", nb: Optional[int] = None):
+        """(order i32[nq, nb], counts i32[nq]) of `lmi_cover_order`: per query the buckets that may hold an object within `radius` (a
+        number, or one per query), in ascending bucket id, then -1.  `nb=None` counts first and sizes the order by the largest count
+        (at least 1); a given `nb` that some query exceeds is refused (LmiError) and nothing is returned."""
+        nb = self._cover_nb("cover_order", nb)
+        r = self._cover_args("cover_order", queries_search, radius, cover, False)
+        q = _np(queries_search, np.float32)
+        nq = int(q.shape[0])
+        counts = np.zeros(nq, dtype=np.int32)
+        if nb is None:
+            _check(lib().lmi_cover_order(self._h, cover._c, _ptr(q), nq, _ptr(r), 0, None, _ptr(counts), 0))
+            nb = max(1, int(counts.max()) if nq else 1)
+        order = np.full((nq, nb), -1, dtype=np.int32)
+        _check(lib().lmi_cover_order(self._h, cover._c, _ptr(q), nq, _ptr(r), nb, _ptr(order), _ptr(counts), 0))
+        return order, counts
+
+    def cover_order_device(self, qs_t, radius, cover: "Cover", nb: int, order_t=None, counts_t=None) -> None:
+        """Device tensors: float32 queries, `order_t` int32 [nq, nb] and `counts_t` int32 [nq] (each may be None); `radius` stays on the
+        host.  Returns when they have landed."""
+        nb = self._cover_nb("cover_order_device", nb if order_t is not None else (nb or 1))
+        r = self._cover_args("cover_order_device", qs_t, radius, cover, True)
+        nq = int(qs_t.shape[0])
+        for name, t, shape in (("order_t", order_t, (nq, nb)), ("counts_t", counts_t, (nq,))):
+            if t is not None and not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.int32"
+                                      and tuple(t.shape) == shape):
+                raise ValueError(f"cover_order_device: {name} must be a contiguous int32 device tensor of shape {shape}")
+        _check(lib().lmi_cover_order(self._h, cover._c, _ptr(qs_t), nq, _ptr(r), nb, _ptr(order_t), _ptr(counts_t), 1))
+
+    def _range_exact(self, who: str, queries, radius, cover, filter, filter_of, max_total, sort, counts, on_device: int) -> "RangeResult":
+        r = self._cover_args(who, queries, radius, cover, bool(on_device))
+        if isinstance(max_total, bool) or not isinstance(max_total, (int, np.integer)) or max_total < 0:
+            raise ValueError(f"{who}: max_total {max_total!r} must be an integer >= 0 (0: no limit)")
+        nq = int(queries.shape[0])
+        f, fo = self._filter_args(who, filter, filter_of, nq)
+        res, nb_used = _vp(), ctypes.c_int32(0)
+        _check(lib().lmi_search_range_exact(self._h, cover._c, _ptr(queries), nq, _ptr(r), f, _ptr(fo), int(max_total), ctypes.byref(res),
+                                            ctypes.byref(nb_used), _ptr(counts), on_device))
+        out = RangeResult(res, nq)
+        out.nb_used = int(nb_used.value)
+        if sort:
+            try:
+                out.sort(self)
+            except Exception:
+                out.close()
+                raise
+        return out
+
+    def search_range_exact(self, queries_search, radius, cover: "Cover", filter=None, filter_of=None, max_total: int = 0,
+                           sort: bool = False):
+        """(lims i64[nq + 1], dists f32[total], ids u32[total]) of `lmi_search_range_exact`: per query EVERY object this handle stores
+        whose distance is <= `radius` (a number, or one per query), in (bucket, row) order -- as sets what `range_knn` gives over all
+        stored objects -- while only the buckets whose covering ball the query's ball may meet are scanned.  `cover`: a `Cover` made on
+        this index (or on the index this one is a clone view of).  `filter`, `filter_of`, `max_total`, `sort`: as in `scan_range`."""
+        q = queries_search
+        self._cover_args("search_range_exact", q, radius, cover, False)
+        q = _np(q, np.float32)
+        with self._range_exact("search_range_exact", q, radius, cover, filter, filter_of, max_total, sort, None, 0) as res:
+            return (res.lims,) + res.read()
+
+    def search_range_exact_device(self, qs_t, radius, cover: "Cover", filter=None, filter_of=None, max_total: int = 0, sort: bool = False,
+                                  counts_t=None) -> "RangeResult":
+        """Device tensors (float32 queries; `counts_t` int32 [nq] or None <- the buckets admitted per query); `radius` and `filter_of`
+        stay on the host.  Returns the `RangeResult` (its `nb_used`: the buckets per query of the scan), whose arrays stay on the device
+        until `read()` / `read_into()`."""
+        if counts_t is not None and not (hasattr(counts_t, "is_cuda") and counts_t.is_cuda and counts_t.is_contiguous()
+                                         and str(counts_t.dtype) == "torch.int32" and hasattr(qs_t, "shape")
+                                         and tuple(counts_t.shape) == (int(qs_t.shape[0]),)):
+            raise ValueError("search_range_exact_device: counts_t must be a contiguous int32 device tensor of shape (nq,)")
+        return self._range_exact("search_range_exact_device", qs_t, radius, cover, filter, filter_of, max_total, sort, counts_t, 1)
+
     # ---- the range search across ranks: the join of the ranks' parts (include/lmi_hip.h, lmi_join_range_parts) ----
     @staticmethod
     def _range_join_args(who: str, counts, dists, ids, max_total):
@@ -1405,6 +1515,65 @@ class Filter:
             self.close()
         except Exception:
             pass
+
+
+class Cover:
+    """The covering balls of a built `Index` (`lmi_cover_create`): per bucket a centre, a covering radius and the live row count,
+    computed on the device from the stored rows.  Passed as `cover=` to `Index.cover_order`, `Index.search_range_exact` and their
+    `_device` forms, on the index it was made on or a clone view of it; after `insert` / `delete`, and on a `subset`, `regroup` or
+    `concat` result, the library refuses it as stale and it has to be made again.  It does not refer to the `Index` and may outlive
+    it.  A context manager: leaving the block closes it."""
+
+    def __init__(self, index: "Index"):
+        self._c = None   # (closed until the library has made it)
+        if not isinstance(index, Index) or getattr(index, "_h", None) is None or not index._h:
+            raise ValueError("Cover: index must be an open Index")
+        c = _vp()
+        _check(lib().lmi_cover_create(index._h, ctypes.byref(c)))
+        self._c = c
+        self.L, self.d = int(index.L), int(index.d)
+
+    def read(self):
+        """(centres f32[L, d], radius f32[L], counts i64[L]) on the host (`lmi_cover_read`)."""
+        if getattr(self, "_c", None) is None:
+            raise ValueError("Cover: the cover is closed")
+        centres = np.zeros((self.L, self.d), dtype=np.float32)
+        radius = np.zeros(self.L, dtype=np.float32)
+        counts = np.zeros(self.L, dtype=np.int64)
+        _check(lib().lmi_cover_read(self._c, _ptr(centres), _ptr(radius), _ptr(counts)))
+        return centres, radius, counts
+
+    def close(self) -> None:
+        if getattr(self, "_c", None) is not None:
+            c, self._c = self._c, None
+            lib().lmi_cover_destroy(c)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cover_set_geometry(query_rows: int = 0) -> None:
+    """Test hook (`lmi_cover_set_geometry`): queries per group of the pruning pass on this thread, an integer in [0, 2^20]; 0 = the
+    default.  Never changes a result."""
+    if isinstance(query_rows, bool) or not isinstance(query_rows, (int, np.integer)) or not 0 <= query_rows <= COVER_MAX_QUERY_ROWS:
+        raise ValueError(f"cover_set_geometry: query_rows {query_rows!r} must be an integer in [0, {COVER_MAX_QUERY_ROWS}] (0: the default)")
+    _check(lib().lmi_cover_set_geometry(int(query_rows)))
+
+
+def cover_last_plan() -> dict:
+    """What the last `cover_order` / `search_range_exact` on this thread did (`lmi_debug_cover_plan`): `COVER_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(COVER_PLAN_FIELDS))()
+    _check(lib().lmi_debug_cover_plan(w, len(COVER_PLAN_FIELDS)))
+    return dict(zip(COVER_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def filter_last_plan() -> dict:

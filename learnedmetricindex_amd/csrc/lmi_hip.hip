@@ -36,6 +36,8 @@
 #include "lmi_host_concat.h"    // lmi_concat, lmi_debug_concat_plan
 #include "lmi_fetch.h"          // the kernels of lmi_rows_fetch
 #include "lmi_host_fetch.h"     // lmi_rows_fetch / lmi_rows_fetch_f16, lmi_fetch_set_geometry, lmi_debug_fetch_plan
+#include "lmi_cover.h"          // the kernels of the bucket cover and of the pruning pass
+#include "lmi_host_cover.h"     // lmi_cover_create / _destroy / _read, lmi_cover_order, lmi_search_range_exact, lmi_cover_set_geometry, lmi_debug_cover_plan
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

@@ -20,6 +20,14 @@ namespace {
 
 thread_local int64_t g_union_last[LMI_UNION_PLAN_COUNT] = {};
 
+// the stored form the union scan, the range search and the bucket cover read
+int rowmajor_check(const lmi_index* h, const char* who) {
+    if (stored_form(h) != FORM_ROWMAJOR)
+        return fail("%s: the index is not stored row-major (%s): the union scan reads its candidates from the row-major f32 image only", who,
+                    h->storage == LMI_STORAGE_F16 ? "LMI_STORAGE_F16" : "lmi_set_prefilter(0)");
+    return 0;
+}
+
 // what every form refuses before any launch
 int union_check(lmi_index* h, const char* who, int nq, int nb, int k) {
     if (!h->built) return fail("%s: the bucket index is not built (lmi_buckets_begin/add_rows/end)", who);
@@ -27,9 +35,7 @@ int union_check(lmi_index* h, const char* who, int nq, int nb, int k) {
     if (nq < 0 || nb < 1) return fail("%s: bad nq/n_buckets", who);
     if (nb > 1024) return fail("%s: n_buckets %d exceeds 1024", who, nb);
     if ((long long)nq * nb >= (1ll << 31)) return fail("%s: nq*n_buckets too large", who);
-    if (stored_form(h) != FORM_ROWMAJOR)
-        return fail("%s: the index is not stored row-major (%s): the union scan reads its candidates from the row-major f32 image only", who,
-                    h->storage == LMI_STORAGE_F16 ? "LMI_STORAGE_F16" : "lmi_set_prefilter(0)");
+    CHK(rowmajor_check(h, who));
     int64_t largest = 0;
     for (int n : h->h_nb_rows) largest = std::max<int64_t>(largest, n);
     if ((int64_t)nb * largest >= (1ll << 32) - 1)

@@ -268,6 +268,12 @@ __global__ void km_scatter_kernel(const int* __restrict__ labels, long long n, i
     }
 }
 
+// The update rule's two pieces of arithmetic, shared with the bucket cover (lmi_cover.h), whose centres are this rule's means:
+// q(v) = rint(v * 2^(36-e)) -- the product is exact in binary64, rint rounds to nearest even -- and the mean of a cluster of m rows
+// from its int64 sum S, c = (float)((double)S / (double)m * 2^(e-36)).
+__device__ __forceinline__ long long km_quant(float v, double scale) { return (long long)__builtin_rint((double)v * scale); }
+__device__ __forceinline__ float km_mean(long long S, long long m, double unscale) { return (float)((double)S / (double)m * unscale); }
+
 // grid (cdiv(n, KM_ACC_ROWS), cdiv(d, 256)), block 256: thread -> dimension blockIdx.y * 256 + threadIdx.x, sorted rows
 // [blockIdx.x * KM_ACC_ROWS, +KM_ACC_ROWS).  scale = 2^(36-e): the product is exact in binary64, rint rounds to nearest even.
 __global__ __launch_bounds__(256) void km_accum_kernel(const float* __restrict__ x, int d, const int* __restrict__ perm,
@@ -296,7 +302,7 @@ __global__ __launch_bounds__(256) void km_accum_kernel(const float* __restrict__
                 cur = l[u];
                 acc = 0;
             }
-            acc += (long long)__builtin_rint((double)v[u] * scale);
+            acc += km_quant(v[u], scale);
         }
     }
     if (cur >= 0 && acc) atomicAdd(&S[(size_t)cur * d + t], (unsigned long long)acc);
@@ -329,7 +335,7 @@ __global__ __launch_bounds__(256) void km_accum16_kernel(const unsigned short* _
                 cur = l[u];
                 acc = 0;
             }
-            acc += (long long)__builtin_rint((double)v[u] * scale);
+            acc += km_quant(v[u], scale);
         }
     }
     if (cur >= 0 && acc) atomicAdd(&S[(size_t)cur * d + t], (unsigned long long)acc);
@@ -341,7 +347,7 @@ __global__ void km_finish_kernel(const long long* __restrict__ S, const int* __r
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)k * d) return;
     const int m = cnt[idx / d];
-    if (m > 0) c[idx] = (float)((double)S[idx] / (double)m * unscale);
+    if (m > 0) c[idx] = km_mean(S[idx], m, unscale);
 }
 
 }  // namespace lmi

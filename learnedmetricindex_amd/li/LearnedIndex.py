@@ -170,6 +170,9 @@ class LearnedIndex(Logger):
     def close(self) -> None:
         """Frees the HBM-resident index."""
         if self._engine is not None:
+            cover = getattr(self._engine, "_li_cover", None)   # the cover range_search_exact keeps with the engine
+            if cover is not None:
+                cover.close()
             self._engine.close()
         self._engine = None
         self._engine_key = None
@@ -795,6 +798,89 @@ class LearnedIndex(Logger):
         self._check_path_mass(path_mass, n_categories)
         return self._range_with(self._engine, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total,
                                 time.time(), stop_mass, path_mass, stop_rows, filter, filter_of)
+
+    # ---- exact range search (an extension; no reference counterpart): every stored object within a radius, buckets pruned by balls ----
+    def range_search_exact(
+        self,
+        data_navigation: pd.DataFrame,
+        queries_navigation: npt.NDArray[np.float32],
+        data_search: pd.DataFrame,
+        queries_search: npt.NDArray[np.float32],
+        data_prediction: npt.NDArray[np.int64],
+        n_categories: List[int],
+        radius,
+        metric: str = "ip",
+        sort: bool = False,
+        max_total: int = 0,
+        assume_unchanged: bool = False,
+        filter=None,
+        filter_of=None,
+    ):
+        """EVERY object of the index whose distance to the query is <= `radius` (a number, or one per query): `lmi_search_range_exact`.
+        No model is consulted and there is no `n_buckets`: the buckets a query visits are those whose covering ball (centre, radius:
+        `_capi.Cover`, over the leaf buckets of 1-level and multi-level indexes alike) its own ball may meet, and the answer is the one a
+        brute force over all stored objects gives.  `queries_navigation` is accepted for symmetry with `range_search` and not read.
+        Return values, `sort`, `max_total`, `filter` and `filter_of` as in `range_search`; the results of a query come in (bucket, row)
+        order unless sorted.  The cover is made on first use, kept with the resident index and made again when the library calls it
+        stale (after `insert` / `delete`).  It needs the default storage."""
+        self._check_range(radius, max_total, "f32")
+        self._check_filter(filter, filter_of, "union")
+        s = time.time()
+        eng = self.prepare(data_navigation, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged)
+        return self._range_exact_with(eng, queries_search, radius, sort, max_total, s, filter, filter_of)
+
+    def range_search_exact_resident(self, queries_navigation, queries_search, n_categories: List[int], radius, sort: bool = False,
+                                    max_total: int = 0, filter=None, filter_of=None):
+        """`range_search_exact` against the index already resident in HBM: no DataFrames needed.  Same return values."""
+        eng = self._resident("range_search_exact_resident")
+        self._check_range(radius, max_total, getattr(eng, "storage", "f32"))
+        self._check_filter(filter, filter_of, "union")
+        return self._range_exact_with(eng, queries_search, radius, sort, max_total, time.time(), filter, filter_of)
+
+    @staticmethod
+    def _cover_of(eng, remake: bool = False):
+        """The engine's cover: made on first use and kept with the engine."""
+        cover = getattr(eng, "_li_cover", None)
+        if remake and cover is not None:
+            cover.close()
+            cover = None
+        if cover is None or getattr(cover, "_c", None) is None:
+            cover = _capi.Cover(eng)
+            eng._li_cover = cover
+        return cover
+
+    def _range_exact_with(self, eng, queries_search, radius, sort, max_total, s, filter, filter_of):
+        if filter is not None and not isinstance(filter, _capi.Filter):   # an id list: one keep filter, made for this call
+            made = _capi.Filter(eng, [np.asarray(filter).reshape(-1)])
+            try:
+                return self._range_exact_with(eng, queries_search, radius, sort, max_total, s, made, filter_of)
+            finally:
+                made.close()
+        fo = None if filter_of is None else np.asarray(filter_of).reshape(-1)
+        measured_time = defaultdict(float)
+        qs = np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
+        nq = qs.shape[0]
+        r = np.asarray(radius, dtype=np.float32)
+        if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != nq):
+            raise ValueError(f"range_search_exact: radius must be a number or one number per query ([{nq}]), not {tuple(r.shape)}")
+        r = np.ascontiguousarray(np.broadcast_to(r, (nq,)))
+        if nq == 0:
+            return np.zeros(1, dtype=np.int64), np.empty(0), np.empty(0, dtype=np.uint32), measured_time
+        t0 = time.time()
+        cover = self._cover_of(eng)
+        measured_time["cover"] = time.time() - t0
+        t0 = time.time()
+        try:
+            lims, d32, nns = eng.search_range_exact(qs, r, cover, filter=filter, filter_of=fo, max_total=max_total, sort=bool(sort))
+        except _capi.LmiError as e:
+            if "stale" not in str(e) or "cover" not in str(e):
+                raise
+            cover = self._cover_of(eng, remake=True)   # the index was mutated since the cover was made
+            lims, d32, nns = eng.search_range_exact(qs, r, cover, filter=filter, filter_of=fo, max_total=max_total, sort=bool(sort))
+        measured_time["search_within_buckets"] = time.time() - t0   # wall time of the call: the library times no phase of it
+        measured_time["search"] = time.time() - s
+        measured_time["buckets_visited"] = float(_capi.cover_last_plan()["ADMITTED"]) / nq
+        return lims, d32.astype(np.float64), nns, measured_time
 
     def _range_with(self, eng, queries_navigation, queries_search, n_categories, n_buckets, radius, sort, max_total, s, stop_mass,
                     path_mass, stop_rows, filter, filter_of):

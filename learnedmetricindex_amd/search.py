@@ -82,6 +82,7 @@ class Experiment:
     merge: str = "ranks"
     range_radius: Optional[float] = None
     range_sort: bool = False
+    range_exact: bool = False
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -128,6 +129,10 @@ class Experiment:
                             "exhaustive range query over all objects (GPU brute force)")
         p.add_argument("--range-sort", action="store_true",
                        help="with --range-radius: every query's range results nearest first, sorted on the device")
+        p.add_argument("--range-exact", action="store_true",
+                       help="with --range-radius: also answer the range query EXACTLY through the index -- every object within the "
+                            "radius, visiting only the buckets whose covering ball the query's ball may meet; the visited fraction of "
+                            "the buckets and the time are reported -- with --eval also range_recall_exact, which must print 1.0")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -151,6 +156,10 @@ class Experiment:
             p.error("--range-radius must be a number")
         if a["range_sort"] and a["range_radius"] is None:
             p.error("--range-sort needs --range-radius")
+        if a["range_exact"] and a["range_radius"] is None:
+            p.error("--range-exact needs --range-radius")
+        if a["range_exact"] and a["storage"] != "f32":
+            p.error("--range-exact needs --storage f32 (the bucket cover reads the row-major f32 image)")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -368,6 +377,20 @@ def run(exp: Experiment) -> Dict:
                 out[f"range_recall_{budget}"] = range_recall(lims, found, *truth)
                 LOG.info("%d buckets: range recall within %g = %.5f (%d true results over %d queries)", budget, exp.range_radius,
                          out[f"range_recall_{budget}"], int(truth[0][-1]), len(truth[0]) - 1)
+    if exp.range_exact:   # once, not per budget: the exact call has no budget
+        lims, _, found, xclock = index.range_search_exact_resident(nav_q, scan_q, exp.n_categories, exp.range_radius, sort=exp.range_sort)
+        out["range_exact_visited"] = xclock["buckets_visited"] / n_buckets_in_index
+        out["range_exact_seconds"] = xclock["search"]
+        per_query = np.diff(lims)
+        LOG.info("exact range search within %g: %.4fs (cover %.4fs), %.4f of the %d buckets visited per query, results per query mean %.2f, "
+                 "max %d", exp.range_radius, xclock["search"], xclock["cover"], out["range_exact_visited"], n_buckets_in_index,
+                 float(per_query.mean()) if per_query.size else 0.0, int(per_query.max(initial=0)))
+        if exp.evaluate:
+            if truth is None:
+                truth = range_truth(scan_q, scan, exp.range_radius)
+            out["range_recall_exact"] = range_recall(lims, found, *truth)
+            LOG.info("exact range search: range_recall_exact = %s (%d true results over %d queries)", out["range_recall_exact"],
+                     int(truth[0][-1]), len(truth[0]) - 1)
     index.close()
     return out
 
