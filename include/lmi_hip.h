@@ -484,7 +484,15 @@ LMI_API int lmi_mlp_proba(lmi_index *h, const float *queries_nav, int nq, float 
  * dist = 1 - ip (binary32), merged over the ranks to k results (k <= LMI_MAX_K).
  * dists[nq][kout], ids[nq][kout] with kout = (nb == 1 ? LMI_K_PER_BUCKET : k).
  * Unvisited slots: dist = +inf, id = 0.  keys (nullable) [nq][kout] <- rank*16 + position, the
- * tie-break key needed by lmi_merge_gathered. */
+ * tie-break key needed by lmi_merge_gathered.
+ * Non-finite and extreme values: for every input the all-f32 scan accepts, the fp16 prefilter returns the all-f32 scan's ids and
+ * distance bits, which are the oracle's -- NaN, +-inf and subnormal values and values whose products overflow included, in stored
+ * rows and in queries.  A score that is NaN, -inf or -FLT_MAX is never returned (the oracle's insertion test is `s > worst`, from
+ * -FLT_MAX); a +inf score is returned, under the inner product with dist = -inf.  A slot left with fewer than LMI_K_PER_BUCKET
+ * admissible rows is padded as a short bucket is (the worst distance of the metric, the bucket's last id), and a special value in
+ * one query changes no other query's answer.  (The prefilter serves such a slot from its exact fallback: a bound that is not
+ * finite, or under L2 a |q|^2 that is not, sends the slot's whole bucket through the canonical chain.)  Left unspecified: under
+ * LMI_METRIC_L2 a query with an infinite component -- its distances are fmaf(-2, +-inf, +inf) = NaN, and no order of NaNs is defined. */
 LMI_API int lmi_scan_topk(lmi_index *h, const float *queries_search, int nq, const int32_t *bucket_order,
                   int nb, int k, float *dists, uint32_t *ids, uint32_t *keys, int on_device);
 

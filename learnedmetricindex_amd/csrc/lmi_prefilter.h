@@ -67,12 +67,15 @@ __global__ void absmax_kernel(const float* __restrict__ x, long long n, unsigned
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
 
-// scale[0] <- power of two s with max*s in [0.5, 1) (1 if max == 0); scale[1] <- 1/s
+// scale[0] <- power of two s with max*s in [0.5, 1) (1 if max == 0 or not finite); scale[1] <- 1/s.  The exponent is kept within
+// +-126 so that s and 1/s are both finite, normal binary32 numbers: a maximum below 2^-127 (a query of subnormals) is scaled by 2^126
+// and stays below 0.5, one from 2^126 on is scaled by 2^-126 and lies in [1, 4).  The bound (header) is built from MEASURED norms
+// and needs no more of the scale than a power of two under which the fp16 images do not overflow.
 __device__ __forceinline__ float scale_of_max(unsigned maxbits) {
     const float m = __uint_as_float(maxbits);
     int e = 0;
     float s = 1.0f;
-    if (m > 0.0f && m < INFINITY) { (void)frexpf(m, &e); s = ldexpf(1.0f, -e); }
+    if (m > 0.0f && m < INFINITY) { (void)frexpf(m, &e); s = ldexpf(1.0f, -min(max(e, -126), 126)); }
     return s;
 }
 __global__ void make_scale_kernel(const unsigned* __restrict__ maxbits, float* __restrict__ scale) {
@@ -476,6 +479,14 @@ __device__ __forceinline__ void pf_x_scatter(const RescoreParams& P, unsigned fi
     }
 }
 
+// A slot the fp16 scores cannot serve, whatever they are: its bound is not finite (an infinite or NaN norm of the query or of a row of
+// the bucket, stored values whose fp16 images overflow) or -- L2 -- |q|^2 is not finite, so that every distance of the query is +inf
+// or NaN and the ranks merge in rank order, not by score (the query-level bound of query_bound_kernel assumes the latter).  The
+// selection flags such a slot and fallback_kernel scans its whole bucket with the canonical chain: what its candidates are is irrelevant.
+__device__ __forceinline__ bool slot_exact_only(const RescoreParams& P, float e2, int q) {
+    return !(fabsf(e2) < INFINITY) || (P.qn2 != nullptr && !(fabsf(P.qn2[q]) < INFINITY));
+}
+
 // flags slot p for fallback_kernel (called by one lane)
 __device__ __forceinline__ void flag_fallback(const RescoreParams& P, int p) {
     P.fallback[p] = 1;
@@ -573,7 +584,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(L
         return;
     }
     const unsigned cnt = P.cand_cnt[col];
-    if (cnt > (unsigned)PF_CAP) {
+    if (cnt > (unsigned)PF_CAP || slot_exact_only(P, P.eps2[col], p / P.nb)) {
         if (lane == 0) flag_fallback(P, p);
         return;
     }
@@ -866,7 +877,8 @@ __global__ __launch_bounds__(256) void fallback_kernel(RescoreParams P, FR... fr
             if (better(s, row, v[0], id[0])) { v[0] = s; id[0] = row; }
         }
     };
-    if (ccnt <= (unsigned)PF_CAP || in_table || in_log) {
+    const bool whole = ccol >= 0 && slot_exact_only(P, P.eps2[ccol], p / P.nb);   // the candidates prove nothing: the whole bucket
+    if (!whole && (ccnt <= (unsigned)PF_CAP || in_table || in_log)) {
         const unsigned* cr = P.cand_row + (size_t)ccol * PF_CAP;
         for (unsigned it = tid; it < min(ccnt, (unsigned)PF_CAP); it += 256) consider(cr[it]);
         if (in_table) {

@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void select_kernel(RescoreParams P, SelectOut 
 #pragma unroll
     for (int i = 0; i < SPEC; ++i) { s_spec[i] = cs[lane + 64 * i]; r_spec[i] = cr[lane + 64 * i]; }
     const unsigned cnt = P.cand_cnt[col];
-    if (cnt > (unsigned)PF_CAP) {
+    if (cnt > (unsigned)PF_CAP || slot_exact_only(P, P.eps2[col], p / P.nb)) {
         if (lane == 0) flag_fallback(P, p);
         return;
     }

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(64 * RC_WAVES, 3) void tail_kernel(RescoreParams P,
                 rl_d[sl * KPB + lane] = dv;
                 rl_i[sl * KPB + lane] = iv;
             }
-        } else if (cnt[sl] > (unsigned)PF_CAP) {
+        } else if (cnt[sl] > (unsigned)PF_CAP || slot_exact_only(P, e2[sl], q)) {
             fbv[sl] = 1;
         } else {
             const float* cs = P.cand_s + (size_t)colv[sl] * PF_CAP;

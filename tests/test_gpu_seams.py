@@ -214,6 +214,16 @@ SEAMS = [
     ("lowd_ip_d129", (59, 20_000, 129, 16, 300, MESSY), 4, 10, dict(low_d=0, KG16=10, tile_cb=12)),
     ("lowd_l2_d127", (60, 20_000, 127, 16, 300, CLEAN), 4, 10, dict(low_d=1, KG16=8, dp=128), dict(metric="l2")),
     ("lowd_l2_d128", (60, 20_000, 128, 16, 300, CLEAN), 4, 10, dict(low_d=0, KG16=10, dp=132), dict(metric="l2")),
+    # ... and every width seam above: the plan decides on the STORED width rup(d + 1, 4), so under L2 each threshold falls one user
+    # column earlier (the expectations are the rules of this file's docstring applied to that width)
+    ("front_l2_d2047", WIDE + (2047, 4, 96, CLEAN), 2, 10, dict(use_front=1, dp=2048), dict(metric="l2")),
+    ("front_l2_d2048", WIDE + (2048, 4, 96, CLEAN), 2, 10, dict(use_front=0, dp=2052), dict(metric="l2")),
+    ("tail_l2_d1823_nb4", WIDE + (1823, 4, 96, MESSY), 4, 10, dict(use_tail=1, G=4, dp=1824), dict(metric="l2")),
+    ("tail_l2_d1824_nb4", WIDE + (1824, 4, 96, MESSY), 4, 10, dict(use_tail=0, G=4, dp=1828), dict(metric="l2")),
+    ("tail_l2_d1943_nb1", WIDE + (1943, 4, 96, CLEAN), 1, 10, dict(use_tail=1, G=1, dp=1944), dict(metric="l2")),
+    ("tail_l2_d1944_nb1", WIDE + (1944, 4, 96, CLEAN), 1, 10, dict(use_tail=0, G=1, dp=1948), dict(metric="l2")),
+    ("waves_l2_d1983", WIDE + (1983, 4, 96, MESSY), 4, 10, dict(streamed=1, use_tail=0, rescore_small_waves=4, dp=1984), dict(metric="l2")),
+    ("waves_l2_d1984", WIDE + (1984, 4, 96, MESSY), 4, 10, dict(streamed=1, use_tail=0, rescore_small_waves=1, dp=1988), dict(metric="l2")),
 ]
 
 
