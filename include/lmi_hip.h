@@ -1218,8 +1218,8 @@ LMI_API int lmi_debug_range_sort_plan(int64_t *out, int n);
  * cover; a query that needs more than 1024 buckets, the scan's limit on nb -- the message names the query and its count.
  * nq == 0 succeeds with an empty result.  The call synchronises the stream once for the counts and then as lmi_scan_range does.
  * Device memory of the pruning pass: 12 nq + 4 min(nq, query_rows) * 2 ceil(L / 64) bytes, and the [nq][nb] order.
- * Not offered: _f16 query forms, lmi_pipeline_submit, a query split over several scans, a norm-interval bound beside the ball, exact
- * k-NN by the same bound, the stored forms that are not row-major. */
+ * Not offered: _f16 query forms, lmi_pipeline_submit, a query split over several scans, a norm-interval bound beside the ball, the
+ * stored forms that are not row-major. */
 typedef struct lmi_cover lmi_cover;
 LMI_API int lmi_cover_create(lmi_index *h, lmi_cover **out);
 LMI_API int lmi_cover_destroy(lmi_cover *c);
@@ -1247,6 +1247,57 @@ enum {
 /* What the last lmi_cover_order / lmi_search_range_exact on this thread did (all zero before the first, after a refused or failed call
  * and after one with nq == 0); writes min(n, LMI_COVER_PLAN_COUNT) words.  lmi_debug_range_plan reports the scan of an exact call. */
 LMI_API int lmi_debug_cover_plan(int64_t *out, int n);
+
+/* The exact k-NN through the index (no reference counterpart): the k nearest objects among EVERYTHING the handle stores, found while
+ * skipping the buckets whose covering ball (the cover above) cannot hold one of them.
+ *   result     with L the number of buckets: bit for bit what lmi_scan_union(h, queries, nq, order, L, k, ..) returns for
+ *              order[q] = 0, 1, .., L-1 -- the first k live rows of the whole handle in the order (score descending with -0 == +0,
+ *              bucket id ascending, row ascending) among the scores > -FLT_MAX; dist, id, the padding (+inf, 0) and counts as there.
+ *              This also holds for L > 1024, where lmi_scan_union itself refuses that order.  As sets with equal distance bits it is
+ *              lmi_knn over everything the handle stores.  On a sharded rank: complete over the buckets the rank owns.
+ *   visited    (nullable, [nq]; host or device as on_device says) <- the distinct buckets scored for query q.  The result does not
+ *              depend on it.
+ * How: (1) a BOUND PASS computes for every (query, bucket with rows) the admission rule's optimistic bound -- IP: <q, c_b> + qn R_b,
+ * L2: max(0, |q - c_b| - R_b), the rule's own unsplit binary64 chains -- and keeps it as one 64-bit word (the order-preserving image of
+ * the bound in binary32 above the bucket id; a NaN takes the best image).  (2) Per query the buckets of the smallest words are taken
+ * as SEEDS until their live rows reach k, LMI_KNN_EXACT_MAX_SEEDS at most, and scanned as one part of a union scan
+ * (lmi_scan_union_part's schedule).  tau[q] = the k-th distance of that part, +inf if it holds fewer than k results.  (3) The
+ * pruning pass of lmi_cover_order runs with radius = tau.  (4) The admitted buckets that are no seeds are scanned as a second part;
+ * the seed part's ranks are renumbered to positions in the admitted order, which the second part's ranks are by construction.
+ * (5) lmi_merge_union_parts's kernel merges the two parts.  No bucket is scored twice.
+ * Exact, because tau[q] is the k-th smallest computed distance over a SUBSET of the rows, so every row of the true first k has a
+ * computed distance <= tau[q] (dist is a non-increasing function of the score in binary32), and the rule admits every bucket that
+ * holds such a row; with tau = +inf every bucket with rows is admitted; a bucket with a value that is not finite has R_b = +inf and is
+ * always admitted.
+ * Deterministic: the result cannot depend on the seed choice, the query groups, waves or grids -- each part is a union scan, whose
+ * result does not depend on its geometry, each bucket lies in exactly one part, and the merge is over a TOTAL order (score, rank, row)
+ * in which the two parts' ranks share one numbering: any division of the admitted buckets between the parts merges to the same bits.
+ * queries_search, dists, ids, counts and visited are all device pointers or all host pointers (staged as lmi_scan_union stages them).
+ * Refused before any launch, with nothing written: everything lmi_scan_union refuses (the stored forms that are not row-major
+ * included), in its words, with n_buckets = LMI_KNN_EXACT_MAX_SEEDS; a NULL, stale or foreign cover, in lmi_cover_order's words; k
+ * outside 1..LMI_UNION_MAX_K; 10 nq k >= 2^31.  Refused after the pruning pass, with nothing written: a query that admits more than
+ * 1024 buckets, the scan's limit on nb -- the message names the query and its count.  nq == 0 succeeds.
+ * Device memory beside the two union scans' own: 8 min(nq, query_rows) L bytes of words (query_rows: lmi_cover_set_geometry's, fewer
+ * where the words would pass 256 MiB), 40 nq k bytes of parts, 148 nq bytes, the pruning pass's buffers and the [nq][nb] order.
+ * Not offered: an _f16 query form, a filter argument, a lmi_pipeline_submit form, a ShardedSearcher method. */
+#define LMI_KNN_EXACT_MAX_SEEDS 32
+LMI_API int lmi_search_knn_exact(lmi_index *h, const lmi_cover *c, const float *queries_search, int nq, int k, float *dists,
+                                 uint32_t *ids, int32_t *counts /* nullable */, int32_t *visited /* [nq], nullable */, int on_device);
+enum {
+    LMI_KNN_EXACT_PLAN_GROUPS = 0,        /* groups the bound pass took the queries in                                        */
+    LMI_KNN_EXACT_PLAN_QUERY_ROWS,        /* queries per group (the last may be smaller)                                      */
+    LMI_KNN_EXACT_PLAN_SEED_BUCKETS,      /* seed buckets of all queries                                                      */
+    LMI_KNN_EXACT_PLAN_TAU_INF,           /* queries whose tau stayed +inf                                                    */
+    LMI_KNN_EXACT_PLAN_ADMITTED,          /* admitted (query, bucket) pairs, the seeds among them                             */
+    LMI_KNN_EXACT_PLAN_MAX_PER_QUERY,     /* the most buckets any query admitted                                              */
+    LMI_KNN_EXACT_PLAN_NB_REST,           /* nb of the second scan                                                            */
+    LMI_KNN_EXACT_PLAN_WORKSPACE_BYTES,   /* device bytes the call allocated beside the two union scans' own                  */
+    LMI_KNN_EXACT_PLAN_COUNT
+};
+/* What the last lmi_search_knn_exact on this thread did (all zero before the first, after a refused or failed call and after one with
+ * nq == 0); writes min(n, LMI_KNN_EXACT_PLAN_COUNT) words.  lmi_debug_union_plan reports the second scan, lmi_debug_cover_plan the
+ * pruning pass. */
+LMI_API int lmi_debug_knn_exact_plan(int64_t *out, int n);
 
 /* Timings of the last lmi_mlp_topk / lmi_scan_topk / lmi_search call (synchronises the stream). */
 LMI_API int lmi_timings(lmi_index *h, float *ms /* [LMI_T_COUNT] */);

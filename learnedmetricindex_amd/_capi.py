@@ -61,6 +61,9 @@ FETCH_MAX_PIECE_ROWS = 1 << 24   # what lmi_fetch_set_geometry takes at most
 #: the words of `cover_last_plan` (LMI_COVER_PLAN_* of include/lmi_hip.h, in the enum's order)
 COVER_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "BUCKETS", "ADMITTED", "MAX_PER_QUERY", "NB_USED", "WORKSPACE_BYTES")
 COVER_MAX_QUERY_ROWS = 1 << 20   # what lmi_cover_set_geometry takes at most
+#: the words of `knn_exact_last_plan` (LMI_KNN_EXACT_PLAN_* of include/lmi_hip.h, in the enum's order)
+KNN_EXACT_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "SEED_BUCKETS", "TAU_INF", "ADMITTED", "MAX_PER_QUERY", "NB_REST", "WORKSPACE_BYTES")
+KNN_EXACT_MAX_SEEDS = 32         # LMI_KNN_EXACT_MAX_SEEDS
 
 _lib = None
 
@@ -225,6 +228,9 @@ SIGNATURES = {
                                               ctypes.c_int]),
     "lmi_cover_set_geometry": (ctypes.c_int, [ctypes.c_int64]),
     "lmi_debug_cover_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    # the exact k-NN through the index: (handle, cover, queries, nq, k, dists, ids, counts, visited, on_device)
+    "lmi_search_knn_exact": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_debug_knn_exact_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_scan_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
                                          ctypes.c_int]),
     "lmi_search_f16": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
@@ -1078,6 +1084,34 @@ class Index:
             raise ValueError("search_range_exact_device: counts_t must be a contiguous int32 device tensor of shape (nq,)")
         return self._range_exact("search_range_exact_device", qs_t, radius, cover, filter, filter_of, max_total, sort, counts_t, 1)
 
+    # ---- the exact k-NN through the index: seed, bound, prune by covering balls (include/lmi_hip.h, lmi_search_knn_exact) ----
+    def search_knn_exact(self, queries_search, k: int, cover: "Cover"):
+        """(dists f32[nq,k], ids u32[nq,k], counts i32[nq], visited i32[nq]) of `lmi_search_knn_exact`: per query the k nearest of
+        EVERYTHING this handle stores -- bit for bit `scan_union` with every bucket listed -- while only the buckets whose covering
+        ball may hold one of them are scanned; `visited[q]`: the buckets scored for query q.  `cover`: a `Cover` made on this index (or
+        on the index this one is a clone view of).  numpy queries give numpy arrays; a contiguous float32 device tensor gives device
+        tensors (ids as int32 bit patterns) and the call returns when they have landed."""
+        who = "search_knn_exact"
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > UNION_MAX_K:
+            raise ValueError(f"{who}: k {k!r} outside [1, {UNION_MAX_K}]")
+        device = hasattr(queries_search, "is_cuda")
+        self._cover_args(who, queries_search, 0.0, cover, device)
+        k = int(k)
+        if device:
+            import torch
+
+            nq, dev = int(queries_search.shape[0]), queries_search.device
+            q = queries_search
+            outs = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int32, device=dev),
+                    torch.empty((nq,), dtype=torch.int32, device=dev), torch.empty((nq,), dtype=torch.int32, device=dev))
+        else:
+            q = _np(queries_search, np.float32)
+            nq = int(q.shape[0])
+            outs = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.uint32), np.zeros(nq, dtype=np.int32),
+                    np.zeros(nq, dtype=np.int32))
+        _check(lib().lmi_search_knn_exact(self._h, cover._c, _ptr(q), nq, k, *(_ptr(x) for x in outs), 1 if device else 0))
+        return outs
+
     # ---- the range search across ranks: the join of the ranks' parts (include/lmi_hip.h, lmi_join_range_parts) ----
     @staticmethod
     def _range_join_args(who: str, counts, dists, ids, max_total):
@@ -1574,6 +1608,13 @@ def cover_last_plan() -> dict:
     w = (ctypes.c_int64 * len(COVER_PLAN_FIELDS))()
     _check(lib().lmi_debug_cover_plan(w, len(COVER_PLAN_FIELDS)))
     return dict(zip(COVER_PLAN_FIELDS, (int(v) for v in w)))
+
+
+def knn_exact_last_plan() -> dict:
+    """What the last `search_knn_exact` on this thread did (`lmi_debug_knn_exact_plan`): `KNN_EXACT_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(KNN_EXACT_PLAN_FIELDS))()
+    _check(lib().lmi_debug_knn_exact_plan(w, len(KNN_EXACT_PLAN_FIELDS)))
+    return dict(zip(KNN_EXACT_PLAN_FIELDS, (int(v) for v in w)))
 
 
 def filter_last_plan() -> dict:

@@ -4,6 +4,7 @@
 //   link / tail    the admission rule of one (query, bucket) pair: the chain over the columns, one link at a time in ascending
 //                  order, and what is decided from the finished chain.  cover_admit_kernel runs the links with the chain in a
 //                  register and then the tail; admit() below runs the same two over whole rows.
+//   bound_ip / _l2 the optimistic bound inside the tail, on its own: the exact k-NN (lmi_knn_exact.h) ranks the buckets by it.
 //   words, groups  the geometry of the admission bitmap and the cut of the queries into groups
 // Everything that decides is binary64 with explicit fma() calls and no product that feeds a sum otherwise, so that no compiler
 // contracts anything and the host and the device decide alike.  Pure: <cmath> only, no HIP call, no handle;
@@ -61,6 +62,12 @@ LMI_COVER_HD inline double link(int metric, double acc, float q, float c) {
     return fma(delta, delta, acc);
 }
 
+// The rule's optimistic bound of one (query, bucket) pair from the finished chain: the largest similarity (IP) / the smallest
+// distance before squaring (L2) that a row inside the bucket's ball could have.  tail() below decides from it; the bound pass of the
+// exact k-NN (lmi_knn_exact.h) ranks the buckets by it.
+LMI_COVER_HD inline double bound_ip(double chain, double qn, double Rb) { return fma(qn, Rb, chain); }
+LMI_COVER_HD inline double bound_l2(double chain, double Rb) { return fmax(0.0, sqrt(chain) - Rb); }   // (fmax drops a NaN: 0 admits)
+
 // The verdict from the finished chain.  qn = |q|, cn = |c_b| (norm_of), R = R_b, n_b the bucket's live rows, u = margin_unit(d).
 // IP: pruned iff  chain + qn R  <  1 - r - u (1 + |r| + qn (cn + R)).
 // L2: pruned iff  max(0, sqrt(chain) - R)^2  >  r + u (qn + cn + R)^2.
@@ -71,13 +78,12 @@ LMI_COVER_HD inline bool tail(int metric, double chain, double qn, double cn, fl
     if (radius != radius || radius == -INFINITY) return false;
     const double r = (double)radius, Rb = (double)R;
     if (metric == METRIC_IP) {
-        const double ub = fma(qn, Rb, chain);
+        const double ub = bound_ip(chain, qn, Rb);
         const double scale = fma(qn, cn + Rb, 1.0 + fabs(r));
         const double thr = fma(-u, scale, 1.0 - r);
         return !(ub < thr);
     }
-    const double dc = sqrt(chain);
-    const double lo = fmax(0.0, dc - Rb);   // (fmax drops a NaN: lo = 0 admits)
+    const double lo = bound_l2(chain, Rb);
     const double s = qn + cn + Rb;
     const double s2 = s * s;
     const double thr = fma(u, s2, r);

@@ -139,7 +139,8 @@ struct CoverPass {
 
     CoverPass(lmi_index* h_, const lmi_cover* c_, const char* who) : h(h_), c(c_), mem(who) {}
 
-    int open(const float* d_qs_, int nq_, const float* radius) {
+    // qn_have: |q| per query where the caller has computed it already (cover_qnorm_kernel's values, enqueued on h->stream)
+    int open(const float* d_qs_, int nq_, const float* radius, double* qn_have = nullptr) {
         namespace cp = lmi_cover_plan;
         d_qs = d_qs_;
         nq = nq_;
@@ -147,10 +148,12 @@ struct CoverPass {
         Q = cp::query_rows_for(g_cover_query_rows, nq, c->L);
         groups = cp::groups_for(nq, Q);
         CHK(mem.alloc(&d_radius, (size_t)nq * 4, "radius"));
-        CHK(mem.alloc(&d_qn, (size_t)nq * 8, "query norms"));
+        if (qn_have) d_qn = qn_have;
+        else CHK(mem.alloc(&d_qn, (size_t)nq * 8, "query norms"));
         CHK(mem.alloc(&d_bitmap, (size_t)Q * W * 4, "admission bitmap"));
         CHK(mem.alloc(&d_counts, (size_t)nq * 4, "counts"));
         HIPCHK(hipMemcpyAsync(d_radius, radius, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
+        if (qn_have) return 0;
         cover_qnorm_kernel<<<cdiv(nq, 256), 256, 0, h->stream>>>(d_qs, nq, c->d, d_qn);
         HIPCHK(hipGetLastError());
         return 0;

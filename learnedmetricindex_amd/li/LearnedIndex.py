@@ -837,6 +837,45 @@ class LearnedIndex(Logger):
         self._check_filter(filter, filter_of, "union")
         return self._range_exact_with(eng, queries_search, radius, sort, max_total, time.time(), filter, filter_of)
 
+    # ---- exact k-NN (an extension; no reference counterpart): the k nearest of every stored object, buckets pruned by balls ----
+    def search_exact(self, data_search: pd.DataFrame, queries_search: npt.NDArray[np.float32], data_prediction: npt.NDArray[np.int64],
+                     n_categories: List[int], k: int = 10, metric: str = "ip", assume_unchanged: bool = False):
+        """The `k` nearest objects of the WHOLE index per query: `lmi_search_knn_exact`.  No model is consulted and there is no
+        `n_buckets`: a few buckets whose covering ball lies nearest are scanned first, their k-th distance becomes the query's radius,
+        and only the buckets whose ball that radius may meet are scanned after them -- the answer is the one a brute force over all
+        stored objects gives (`Baseline.search`).  Returns (dists f64[nq, k], nns u32[nq, k], measured_time); `measured_time
+        ["buckets_visited"]` is the mean number of buckets scored per query.  The resident index and its cover are `search`'s and
+        `range_search_exact`'s: made on first use, kept, the cover made again when the library calls it stale."""
+        s = time.time()
+        eng = self.prepare(data_search, data_search, data_prediction, n_categories, metric=metric, assume_unchanged=assume_unchanged)
+        return self._exact_with(eng, queries_search, k, s)
+
+    def search_exact_resident(self, queries_search, k: int = 10):
+        """`search_exact` against the index already resident in HBM: no DataFrames needed.  Same return values."""
+        return self._exact_with(self._resident("search_exact_resident"), queries_search, k, time.time())
+
+    def _exact_with(self, eng, queries_search, k, s):
+        measured_time = defaultdict(float)
+        qs = np.ascontiguousarray(_query_array(queries_search), dtype=np.float32)
+        nq = qs.shape[0]
+        if nq == 0:
+            return np.empty((0, k)), np.empty((0, k), dtype=np.uint32), measured_time
+        t0 = time.time()
+        cover = self._cover_of(eng)
+        measured_time["cover"] = time.time() - t0
+        t0 = time.time()
+        try:
+            d32, nns, _, visited = eng.search_knn_exact(qs, k, cover)
+        except _capi.LmiError as e:
+            if "stale" not in str(e) or "cover" not in str(e):
+                raise
+            cover = self._cover_of(eng, remake=True)   # the index was mutated since the cover was made
+            d32, nns, _, visited = eng.search_knn_exact(qs, k, cover)
+        measured_time["search_within_buckets"] = time.time() - t0   # wall time of the call: the library times no phase of it
+        measured_time["search"] = time.time() - s
+        measured_time["buckets_visited"] = float(visited.mean())
+        return d32.astype(np.float64), nns, measured_time
+
     @staticmethod
     def _cover_of(eng, remake: bool = False):
         """The engine's cover: made on first use and kept with the engine."""

@@ -83,6 +83,7 @@ class Experiment:
     range_radius: Optional[float] = None
     range_sort: bool = False
     range_exact: bool = False
+    knn_exact: bool = False
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -133,6 +134,10 @@ class Experiment:
                        help="with --range-radius: also answer the range query EXACTLY through the index -- every object within the "
                             "radius, visiting only the buckets whose covering ball the query's ball may meet; the visited fraction of "
                             "the buckets and the time are reported -- with --eval also range_recall_exact, which must print 1.0")
+        p.add_argument("--knn-exact", action="store_true",
+                       help="also answer the k-NN query EXACTLY through the index -- the k nearest of all stored objects, visiting only "
+                            "the buckets whose covering ball may hold one; knn_exact_visited (mean buckets per query) and the time are "
+                            "reported -- with --eval also recall_exact@k, which must print 1.0 on unit-norm scan vectors (the truth re-normalises)")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         levels = len(a["n_categories"])
@@ -160,6 +165,8 @@ class Experiment:
             p.error("--range-exact needs --range-radius")
         if a["range_exact"] and a["storage"] != "f32":
             p.error("--range-exact needs --storage f32 (the bucket cover reads the row-major f32 image)")
+        if a["knn_exact"] and a["storage"] != "f32":
+            p.error("--knn-exact needs --storage f32 (the bucket cover reads the row-major f32 image)")
         for name in PER_LEVEL:  # one value for all levels, or one per level
             if len(a[name]) == 1:
                 a[name] = a[name] * levels
@@ -391,6 +398,15 @@ def run(exp: Experiment) -> Dict:
             out["range_recall_exact"] = range_recall(lims, found, *truth)
             LOG.info("exact range search: range_recall_exact = %s (%d true results over %d queries)", out["range_recall_exact"],
                      int(truth[0][-1]), len(truth[0]) - 1)
+    if exp.knn_exact:   # once, not per budget: the exact call has no budget
+        _, xnns, xclock = index.search_exact_resident(scan_q, exp.k)
+        out["knn_exact_visited"] = xclock["buckets_visited"]
+        out["knn_exact_seconds"] = xclock["search"]
+        LOG.info("exact k-NN: %.4fs (cover %.4fs), knn_exact_visited = %.2f of the %d buckets per query", xclock["search"], xclock["cover"],
+                 out["knn_exact_visited"], n_buckets_in_index)
+        if exp.evaluate:
+            out["recall_exact"] = recall_against_bruteforce(scan_q, scan, xnns, exp.k)
+            LOG.info("exact k-NN: recall_exact@%d = %s", exp.k, out["recall_exact"])
     index.close()
     return out
 
