@@ -615,6 +615,81 @@ LMI_API int lmi_kmeans_f16(int device, const uint16_t *x, int64_t n, int d, int 
                            int64_t *counts /* [k] host, nullable */, int64_t *changed /* [niter+1] host, nullable */,
                            int on_device);
 
+/* The mean and the centred scatter matrix of x [n][d] on the device, deterministic: the two inputs of a PCA fit (the navigation
+ * vectors the reference downloads ready-made as pca32 / pca96 -- a user with embeddings of their own derives them with this and
+ * lmi_project below; the eigen-solve of the d x d matrix is the caller's, on the host).  The same input gives the same mean and gram
+ * bit for bit on any launch geometry; tests/pca_ref.py restates the call in numpy on top of oracle.dot.
+ * No handle (like lmi_kmeans): the work runs on the NULL stream of `device` and the call returns when the outputs have landed.
+ * on_device covers x, mean [d] and gram [d][d]: device pointers, x is only read where it lies; otherwise host pointers -- x is uploaded
+ * once, in pieces, and stays resident for both passes.
+ * Arithmetic contract
+ *   e            the smallest integer with max|x| < 2^e (0 for all-zero data), found on the device.
+ *   mean         lmi_kmeans's update with one cluster: S_t = the sum over the rows of q(x[i][t]) in int64, q(v) = rint(v * 2^(36-e));
+ *                m_t = (float)((double)S_t / (double)n * 2^(e-36)).
+ *   centred      c[i][t] = x[i][t] - m_t in binary32, one rounding, taken in the register that feeds the MFMA: no centred copy of x
+ *                exists.
+ *   piece chains the rows are cut into pieces of LMI_GRAM_PIECE_ROWS = 4096 rows (the last may be shorter); the constant is part of
+ *                this contract, not a tuning knob.  For piece p, g_p[a][b] = the chain acc = fmaf(c[i][a], c[i][b], acc) from +0 over
+ *                the piece's rows, i ascending, in binary32.  A chain is never split.  Only a <= b is computed: fmaf's product
+ *                commutes, so the mirror has the same bits.  (The chains run in v_mfma_f32_32x32x2_f32 and are padded by
+ *                fmaf(+0, +0, acc); a g_p of -0 becomes +0, which the fold cannot see.)
+ *   fold         Q_p = llrint((double)g_p * 2^(32-2e)), to nearest even; T[a][b] = the sum of Q_p over the pieces in int64.
+ *                |c| <= 2^(e+1) and a piece has at most 4096 rows, so |g_p| < 2^(2e+15) and |Q_p| < 2^47; n <= 2^26 gives at most
+ *                2^14 pieces, so |T| < 2^61.  Integer addition is associative: any grid, any split of the pieces over blocks and any
+ *                atomic order give the same T.
+ *   result       gram[a][b] = (double)T[a][b] * 2^(2e-32): one int64 -> binary64 conversion and an exact scaling.  gram is the
+ *                scatter matrix; the covariance is gram / (n - 1).
+ * Refused, with nothing written: n < 1, d < 1, d > 4096, n > 2^26, NULL x / mean / gram; and, found on the device in the pass that
+ * takes max|x|, a value that is not finite, and max|x| >= 2^56 (a piece's chain could overflow binary32).  A failed allocation names
+ * the bytes it wanted; the call frees all it allocated.
+ * Peak device memory: 8 d^2 (T) + 12 d + 4 * tiles; with host pointers 4nd + 8 d^2 more for x and gram. */
+#define LMI_GRAM_PIECE_ROWS 4096
+LMI_API int lmi_gram(int device, const float *x, int64_t n, int d, float *mean /* [d] out */, double *gram /* [d][d] out */,
+                     int on_device);
+/* lmi_gram with x [n][d] given as binary16 bit patterns (2-byte alignment is enough, host or device).  Host pointers: x goes up once,
+ * as halves, and stays resident as halves.  Every half is widened exactly where it is loaded (16-byte loads of 8 halves where
+ * d % 8 == 0 and the base is 16-byte aligned, 2-byte loads otherwise), so mean and gram are bit for bit what lmi_gram returns on the
+ * widened array.  Refusals: lmi_gram's, naming lmi_gram_f16 (max|x| >= 2^56 cannot occur).  Memory: 2nd in place of 4nd. */
+LMI_API int lmi_gram_f16(int device, const uint16_t *x, int64_t n, int d, float *mean /* [d] out */, double *gram /* [d][d] out */,
+                         int on_device);
+/* Tuning / test hook: the width of a block's tile of the scatter matrix (64 or 128) and the consecutive pieces a block folds in its
+ * registers (<= 2^14).  0 = chosen by the library.  Thread-local, like lmi_last_error; never changes a result. */
+LMI_API int lmi_gram_set_geometry(int tile_cols, int64_t pieces_per_block);
+enum {
+    LMI_GRAM_PLAN_TILE_COLS = 0,     /* width of a block's tile of the scatter matrix                                          */
+    LMI_GRAM_PLAN_TILES,             /* tiles of the upper triangle, the diagonal included                                     */
+    LMI_GRAM_PLAN_PIECES,            /* pieces of LMI_GRAM_PIECE_ROWS rows (the last may be shorter)                           */
+    LMI_GRAM_PLAN_PIECES_PER_BLOCK,  /* consecutive pieces a block folds before its atomics                                    */
+    LMI_GRAM_PLAN_RUNS,              /* runs of pieces: the grid is TILES x RUNS                                               */
+    LMI_GRAM_PLAN_VEC,               /* 16-byte loads of x (binary32: d % 4 == 0, halves: d % 8 == 0; an aligned base)         */
+    LMI_GRAM_PLAN_EXPONENT,          /* e                                                                                      */
+    LMI_GRAM_PLAN_WORKSPACE_BYTES,   /* device bytes the call allocated                                                        */
+    LMI_GRAM_PLAN_COUNT
+};
+/* What the last lmi_gram or lmi_gram_f16 on this thread did (all zero before the first and after a refused call); writes
+ * min(n, LMI_GRAM_PLAN_COUNT) words. */
+LMI_API int lmi_debug_gram_plan(int64_t *out, int n);
+
+/* y = (x - mean) . basis^T on the device, deterministic: applies a fitted projection to data, queries or inserted rows.
+ * y[i][j] = the chain acc = fmaf(c[i][t], basis[j][t], acc) from +0, t = 0..d-1, with c[i][t] = x[i][t] - mean[t] in binary32 (one
+ * rounding, as in lmi_gram); a NULL mean gives c = x.  No chain is split; the result does not depend on the grid or the pieces.  (The
+ * chains run in v_mfma_f32_32x32x2_f32 and are padded to a multiple of 32 links by fmaf(+0, +0, acc): a y of -0 becomes +0 where d is
+ * no multiple of 32.)  tests/pca_ref.py restates the call.  Non-finite inputs are not refused; they do what the chain does with them.
+ * No handle; the NULL stream of `device`.  on_device covers x [n][d], mean [d], basis [m][d] and y [n][m]: device pointers, the inputs
+ * are only read (x with 16-byte loads where d % 4 == 0 and its base is 16-byte aligned; y with 16-byte stores where m % 4 == 0 and
+ * its base is); otherwise host pointers -- x goes up in pieces of at most 64 MiB and is never resident as a whole, y comes back piece
+ * by piece: the device memory of the call does not depend on n.
+ * Refused, with nothing written: n < 1 or >= 2^31, d outside 1..4096, m outside 1..LMI_PROJECT_MAX_M, NULL x / basis / y.
+ * Peak device memory: 4 * roundup(m, 32) * roundup(d, 32) + 4 * roundup(d, 32); with host pointers 4md + 4d + P (4d + 4m) more, P the
+ * rows of a piece. */
+#define LMI_PROJECT_MAX_M 1024
+LMI_API int lmi_project(int device, const float *x, int64_t n, int d, const float *mean /* [d], nullable */,
+                        const float *basis /* [m][d] */, int m, float *y /* [n][m] out */, int on_device);
+/* lmi_project with x given as binary16 bit patterns (2-byte alignment is enough; 16-byte loads where d % 8 == 0 and the base is
+ * 16-byte aligned); mean, basis and y stay binary32.  y is bit for bit what lmi_project returns on the widened array. */
+LMI_API int lmi_project_f16(int device, const uint16_t *x, int64_t n, int d, const float *mean /* [d], nullable */,
+                            const float *basis /* [m][d] */, int m, float *y /* [n][m] out */, int on_device);
+
 /* Adam steps on a Linear/ReLU stack with the cross-entropy loss, on the device, deterministic (replaces the training stage of the
  * index build: NeuralNetwork.train_batch, li/model.py:185-211, whose epoch is ONE optimizer step on its last mini-batch).  The same
  * input gives the same parameters and moments bit for bit on any launch geometry; tests/train_ref.py restates the call in numpy on

@@ -64,6 +64,11 @@ COVER_MAX_QUERY_ROWS = 1 << 20   # what lmi_cover_set_geometry takes at most
 #: the words of `knn_exact_last_plan` (LMI_KNN_EXACT_PLAN_* of include/lmi_hip.h, in the enum's order)
 KNN_EXACT_PLAN_FIELDS = ("GROUPS", "QUERY_ROWS", "SEED_BUCKETS", "TAU_INF", "ADMITTED", "MAX_PER_QUERY", "NB_REST", "WORKSPACE_BYTES")
 KNN_EXACT_MAX_SEEDS = 32         # LMI_KNN_EXACT_MAX_SEEDS
+#: the LMI_GRAM_PLAN_* words, in their order (lmi_debug_gram_plan)
+GRAM_PLAN_FIELDS = ("TILE_COLS", "TILES", "PIECES", "PIECES_PER_BLOCK", "RUNS", "VEC", "EXPONENT", "WORKSPACE_BYTES")
+GRAM_PIECE_ROWS = 4096           # LMI_GRAM_PIECE_ROWS: part of `gram`'s arithmetic contract
+GRAM_MAX_ROWS = 1 << 26          # `gram`: the bound of its int64 sums
+PROJECT_MAX_M = 1024             # LMI_PROJECT_MAX_M: the most basis rows of `project`
 
 _lib = None
 
@@ -190,6 +195,13 @@ SIGNATURES = {
     "lmi_train_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                      ctypes.POINTER(_vp), _i64p, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, ctypes.c_int]),
     "lmi_mlp_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    # the PCA pair: (device, x, n, d, mean, gram, on_device) and (device, x, n, d, mean, basis, m, y, on_device)
+    "lmi_gram": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "lmi_gram_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "lmi_gram_set_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64]),
+    "lmi_debug_gram_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    "lmi_project": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
+    "lmi_project_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "lmi_timings": (ctypes.c_int, [_vp, _vp]),
     "lmi_timings_reset": (ctypes.c_int, [_vp]),
     "lmi_set_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -1972,6 +1984,94 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
     call = lib().lmi_kmeans_f16 if f16 else lib().lmi_kmeans
     _check(call(_sync_device(x), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
     return cent, labels, counts, changed
+
+
+def _pca_rows(who: str, x):
+    """(is numpy, is float16, n, d) of the rows of `gram` / `project`: float32 or float16 by dtype, [n, d] with n, d >= 1, d <= 4096;
+    a torch x contiguous and on the device."""
+    f16 = _is_f16(x)
+    is_np = _array_arg(who, "x", x, "float16" if f16 else "float32", "nd")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if d > 4096:
+        raise ValueError(f"{who}: d {d} outside [1, 4096]")
+    if not is_np and not (x.is_cuda and x.is_contiguous()):
+        raise ValueError(f"{who}: a torch x must be a contiguous tensor on the device")
+    return is_np, f16, n, d
+
+
+def gram(x, device: int = 0):
+    """The mean and the centred scatter matrix of the rows of `x` on the device (`lmi_gram`): (mean f32[d], gram f64[d,d]) -- the two
+    inputs of a PCA fit; the covariance is gram / (n - 1).  The same input gives the same result bit for bit on any launch geometry
+    (include/lmi_hip.h states the arithmetic; tests/pca_ref.py restates it).  `x`: a float32 numpy array [n,d] -- uploaded once, in
+    pieces, resident for both passes -- or a contiguous float32 torch tensor on the device, read where it lies; mean and gram then
+    come back as tensors on that device.  A float16 `x` of either kind goes to `lmi_gram_f16` as it is and gives bit for bit the
+    result of the call on `x` widened to float32.  Argument errors raise ValueError before the library is loaded."""
+    is_np, f16, n, d = _pca_rows("gram", x)
+    if n > GRAM_MAX_ROWS:
+        raise ValueError(f"gram: n {n} exceeds 2^26")
+    if is_np:
+        x = np.ascontiguousarray(x)
+        mean, g = np.empty(d, dtype=np.float32), np.empty((d, d), dtype=np.float64)
+        call = lib().lmi_gram_f16 if f16 else lib().lmi_gram
+        _check(call(int(device), _ptr(x), n, d, _ptr(mean), _ptr(g), 0))
+        return mean, g
+    import torch
+
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    g = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    call = lib().lmi_gram_f16 if f16 else lib().lmi_gram
+    _check(call(_sync_device(x), _ptr(x), n, d, _ptr(mean), _ptr(g), 1))
+    return mean, g
+
+
+def gram_set_geometry(tile_cols: int = 0, pieces_per_block: int = 0) -> None:
+    """Tuning / test hook (`lmi_gram_set_geometry`): the tile width (64 or 128) and the pieces a block folds of the `gram` calls of
+    this thread; 0 = chosen by the library.  Never changes a result."""
+    _check(lib().lmi_gram_set_geometry(int(tile_cols), int(pieces_per_block)))
+
+
+def gram_last_plan() -> dict:
+    """What the last `gram` on this thread did (`lmi_debug_gram_plan`): `GRAM_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(GRAM_PLAN_FIELDS))()
+    _check(lib().lmi_debug_gram_plan(w, len(GRAM_PLAN_FIELDS)))
+    return dict(zip(GRAM_PLAN_FIELDS, (int(v) for v in w)))
+
+
+def project(x, basis, mean=None, device: int = 0):
+    """y = (x - mean) . basis^T on the device (`lmi_project`): f32 [n,m], every element one fmaf chain over the d columns
+    (include/lmi_hip.h; tests/pca_ref.py restates it).  `x`: float32 or float16 [n,d], a numpy array -- uploaded in pieces, never
+    resident as a whole, y comes back piece by piece -- or a contiguous torch tensor on the device; y is then a tensor there.
+    `basis` f32 [m,d], m <= PROJECT_MAX_M, and `mean` f32 [d] or None (then x is not centred) are numpy arrays or tensors; they are
+    brought to where x is.  A float16 `x` goes to `lmi_project_f16` as it is: bit for bit the result of the widened array.
+    Argument errors raise ValueError before the library is loaded."""
+    is_np, f16, n, d = _pca_rows("project", x)
+
+    def host(name, a, shape):
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        if a.dtype != np.float32 or a.ndim != len(shape) or any(s is not None and s != t for s, t in zip(shape, a.shape)):
+            want = ",".join("m" if s is None else str(s) for s in shape)
+            raise ValueError(f"project: {name} must be float32 [{want}], not {a.dtype} {tuple(a.shape)}")
+        return np.ascontiguousarray(a)
+
+    basis = host("basis", basis, (None, d))
+    m = int(basis.shape[0])
+    if m < 1 or m > PROJECT_MAX_M:
+        raise ValueError(f"project: m {m} outside [1, {PROJECT_MAX_M}]")
+    mean = None if mean is None else host("mean", mean, (d,))
+    if is_np:
+        x = np.ascontiguousarray(x)
+        y = np.empty((n, m), dtype=np.float32)
+        call = lib().lmi_project_f16 if f16 else lib().lmi_project
+        _check(call(int(device), _ptr(x), n, d, _ptr(mean), _ptr(basis), m, _ptr(y), 0))
+        return y
+    import torch
+
+    bt = torch.from_numpy(basis).to(x.device)
+    mt = None if mean is None else torch.from_numpy(mean).to(x.device)
+    y = torch.empty((n, m), dtype=torch.float32, device=x.device)
+    call = lib().lmi_project_f16 if f16 else lib().lmi_project
+    _check(call(_sync_device(x), _ptr(x), n, d, _ptr(mt), _ptr(bt), m, _ptr(y), 1))
+    return y
 
 
 def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0):

@@ -40,6 +40,10 @@
 #include "lmi_host_cover.h"     // lmi_cover_create / _destroy / _read, lmi_cover_order, lmi_search_range_exact, lmi_cover_set_geometry, lmi_debug_cover_plan
 #include "lmi_knn_exact.h"      // the kernels of the exact k-NN through the index: bound, seeds, tau, split
 #include "lmi_host_knn_exact.h" // lmi_search_knn_exact, lmi_debug_knn_exact_plan
+#include "lmi_gram.h"           // the kernels of lmi_gram
+#include "lmi_host_gram.h"      // lmi_gram / lmi_gram_f16, lmi_gram_set_geometry, lmi_debug_gram_plan
+#include "lmi_project.h"        // the kernel of lmi_project
+#include "lmi_host_project.h"   // lmi_project / lmi_project_f16
 #include <mutex>
 
 extern "C" LMI_API int lmi_abi_version(void) { return LMI_ABI_VERSION; }

@@ -1,0 +1,69 @@
+"""A PCA projection fitted and applied on the device: navigation vectors for data that comes without a `pca32` / `pca96` kind.
+
+`PcaProjection.fit(x, m)` takes the mean and the centred scatter matrix from `_capi.gram` (bit for bit reproducible: include/lmi_hip.h)
+and solves the d x d eigenproblem on the host; `.transform(x)` is `_capi.project`.  There is no CPU fallback for either call."""
+from __future__ import annotations
+
+import numpy as np
+
+try:
+    from . import _capi   # the package
+except ImportError:
+    import _capi          # next to _capi.py on sys.path (search.py's layout)
+
+
+class PcaProjection:
+    """`mean` f32 [d], `basis` f32 [m, d] (rows: principal directions, by descending eigenvalue, each with its largest-magnitude
+    entry positive), `explained_variance` f64 [m] (the eigenvalues of gram / (n - 1)).
+
+    The eigen-solve is LAPACK's (`np.linalg.eigh` in float64) and NOT part of the bit-for-bit contract: `mean` and the scatter
+    matrix are reproducible to the bit, the basis only as far as LAPACK is on the machine at hand.  `transform` is reproducible
+    to the bit for a given (mean, basis): keep a fitted projection with `save` rather than fitting it again elsewhere."""
+
+    def __init__(self, mean, basis, explained_variance):
+        self.mean = np.ascontiguousarray(mean, dtype=np.float32)
+        self.basis = np.ascontiguousarray(basis, dtype=np.float32)
+        self.explained_variance = np.ascontiguousarray(explained_variance, dtype=np.float64)
+        if self.basis.ndim != 2 or self.mean.shape != (self.basis.shape[1],) or self.explained_variance.shape != (self.basis.shape[0],):
+            raise ValueError(f"PcaProjection: mean {self.mean.shape}, basis {self.basis.shape} and explained_variance "
+                             f"{self.explained_variance.shape} do not fit [d], [m,d], [m]")
+
+    @property
+    def m(self) -> int:
+        return int(self.basis.shape[0])
+
+    @property
+    def d(self) -> int:
+        return int(self.basis.shape[1])
+
+    @classmethod
+    def fit(cls, x, m: int, device: int = 0) -> "PcaProjection":
+        """`x`: what `_capi.gram` takes (float32 or float16 [n,d], numpy or a device tensor), n >= 2; 1 <= m <= min(d, 1024)."""
+        if getattr(x, "ndim", 0) != 2:
+            raise ValueError("PcaProjection.fit: x must be [n,d]")
+        n, d, m = int(x.shape[0]), int(x.shape[1]), int(m)
+        if n < 2:
+            raise ValueError(f"PcaProjection.fit: n {n} < 2")
+        if m < 1 or m > min(d, _capi.PROJECT_MAX_M):
+            raise ValueError(f"PcaProjection.fit: m {m} outside [1, min(d = {d}, {_capi.PROJECT_MAX_M})]")
+        mean, g = _capi.gram(x, device=device)
+        if not isinstance(mean, np.ndarray):
+            mean, g = mean.cpu().numpy(), g.cpu().numpy()
+        w, v = np.linalg.eigh(g / float(n - 1))   # ascending
+        order = np.argsort(w, kind="stable")[::-1][:m]
+        basis = v[:, order].T
+        lead = basis[np.arange(m), np.abs(basis).argmax(axis=1)]
+        basis = basis * np.where(lead < 0, -1.0, 1.0)[:, None]
+        return cls(mean, basis.astype(np.float32), w[order])
+
+    def transform(self, x, device: int = 0):
+        """f32 [n, m]: numpy for a numpy `x`, a tensor on x's device for a device tensor (`_capi.project`)."""
+        return _capi.project(x, self.basis, mean=self.mean, device=device)
+
+    def save(self, path) -> None:
+        np.savez(path, mean=self.mean, basis=self.basis, explained_variance=self.explained_variance)
+
+    @classmethod
+    def load(cls, path) -> "PcaProjection":
+        with np.load(path) as z:
+            return cls(z["mean"], z["basis"], z["explained_variance"])

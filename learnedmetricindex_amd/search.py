@@ -46,6 +46,7 @@ from li.BuildConfiguration import BuildConfiguration  # noqa: E402
 from li.clustering import algorithms  # noqa: E402
 from li.LearnedIndexBuilder import LearnedIndexBuilder  # noqa: E402
 from li.utils import save_as_pickle, serialize  # noqa: E402
+from projection import PcaProjection  # noqa: E402
 
 LOG = logging.getLogger("lmi.driver")
 
@@ -84,6 +85,7 @@ class Experiment:
     range_sort: bool = False
     range_exact: bool = False
     knn_exact: bool = False
+    nav_pca: Optional[int] = None
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -138,8 +140,14 @@ class Experiment:
                        help="also answer the k-NN query EXACTLY through the index -- the k nearest of all stored objects, visiting only "
                             "the buckets whose covering ball may hold one; knn_exact_visited (mean buckets per query) and the time are "
                             "reported -- with --eval also recall_exact@k, which must print 1.0 on unit-norm scan vectors (the truth re-normalises)")
+        p.add_argument("--nav-pca", type=int, default=None, metavar="M",
+                       help="derive the navigation vectors of the data and of the queries from the scan vectors by an M-dimensional PCA "
+                            "fitted on the data on the device (PcaProjection), instead of loading --dataset / --emb: for embeddings that "
+                            "come without a pca32 / pca96 kind; with --synthetic it replaces the stand-in's fixed random projection")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
+        if a["nav_pca"] is not None and not 1 <= a["nav_pca"] <= min(WIDTH[SCAN_KIND], 1024):
+            p.error(f"--nav-pca takes M from 1 to {min(WIDTH[SCAN_KIND], 1024)}")
         levels = len(a["n_categories"])
         if a["stop_mass"] is not None and levels > 1:
             p.error("--stop-mass needs a 1-level index (one value for --n-categories)")
@@ -326,7 +334,15 @@ def range_truth(queries: np.ndarray, objects: pd.DataFrame, radius: float, sampl
 def run(exp: Experiment) -> Dict:
     LOG.info("experiment: %s", dataclasses.asdict(exp))
     src = VectorSource(exp.size, exp.synthetic)
-    nav_x, nav_q = src.load(exp.dataset, exp.emb)
+    keep_f16 = exp.storage == "f16"
+    sx = None
+    if exp.nav_pca is not None:   # the navigation vectors are the scan vectors' leading principal components, fitted on the data
+        sx, scan_q = src.load(SCAN_KIND, SCAN_KEY, keep_f16=keep_f16)
+        pca = PcaProjection.fit(sx, exp.nav_pca)
+        nav_x, nav_q = pca.transform(sx), pca.transform(scan_q.astype(sx.dtype, copy=False))
+        LOG.info("navigation by a %d-d PCA of %s: variance kept %.6g", exp.nav_pca, SCAN_KIND, float(pca.explained_variance.sum()))
+    else:
+        nav_x, nav_q = src.load(exp.dataset, exp.emb)
     if exp.preprocess:
         nav_x, nav_q = unit_rows(nav_x), unit_rows(nav_q)
     LOG.info("navigation vectors %s, queries %s", nav_x.shape, nav_q.shape)
@@ -336,8 +352,10 @@ def run(exp: Experiment) -> Dict:
     # vectors are a dataset of their own: when one dataset serves navigation and scan, the builder needs it as float32 anyway and a
     # second, float16 copy would cost host memory instead of saving it.  The scan queries stay halves too, but beside float32
     # navigation queries they are widened on the host (`_capi._queries`): the driver saves on the ingest, not on the query upload.
-    keep_f16 = exp.storage == "f16"
-    if exp.dataset == SCAN_KIND:
+    if sx is not None:   # --nav-pca: the scan vectors are loaded already
+        scan = pd.DataFrame(sx)
+        scan.index += 1
+    elif exp.dataset == SCAN_KIND:
         scan, scan_q = nav, nav_q
     else:  # navigate in the narrow embedding, scan in clip768v2 (not normalised by the driver, as upstream)
         sx, scan_q = src.load(SCAN_KIND, SCAN_KEY, keep_f16=keep_f16)

@@ -9,6 +9,7 @@ For `pass2_kernel<true>` and `pass2_kernel<false>` of the gfx950 code object ins
   (b) every instruction that names v232..v255 is a `global_load_dwordx4` whose destination is a reserved set, or a
       `v_mfma_f32_16x16x32_f16` whose A operand is a reserved pair of registers (and whose other operands are not);
   (c) no `scratch_` instruction sits inside a tile body (a run of MFMAs less than 400 instructions apart).
+And (d), for the kernels of lmi_gram / lmi_project (PCA_KERNELS): no packed binary32 add, multiply or fma.
 
   python3 tools/isa_guard.py [path/to/liblmi_hip.so]     exit code 0 = all checks pass
 """
@@ -129,13 +130,34 @@ def check_kernel(name: str, body, notes: dict) -> list:
     return errs, {"reserved_loads": n_load, "reserved_mfmas": n_mfma, "mfma": len(mfma_at), "scratch": len(scratch_at), "tile_bodies": len(runs)}
 
 
+#: (d) the kernels of lmi_gram / lmi_project hold no packed binary32 arithmetic: the library is one translation unit built with
+#: packed-fp32-ops on, and these kernels' bit-for-bit contracts want every subtract and every fused multiply-add on its own
+PCA_KERNELS = ("_ZN3lmi11gram_kernel", "_ZN3lmi15gram_sum_kernel", "_ZN3lmi16gram_mean_kernel", "_ZN3lmi18gram_finish_kernel",
+               "_ZN3lmi14project_kernel", "_ZN3lmi19project_mean_kernel")
+_PACKED_F32 = re.compile(r"\bv_pk_(add|mul|fma)_f32\b")
+
+
+def check_unpacked(disasm_lines) -> list:
+    errs, cur, seen = [], None, set()
+    for l in disasm_lines:
+        m = re.match(r"^[0-9a-f]+ <(.*)>:$", l)
+        if m:
+            cur = m.group(1) if m.group(1).startswith(PCA_KERNELS) else None
+            seen.add(cur)
+        elif cur and _PACKED_F32.search(l):
+            errs.append(f"{cur}: packed binary32 arithmetic: `{l.split('//')[0].strip()}`")
+    if len(seen) < 2:   # (None is always there)
+        errs.append("no lmi_gram / lmi_project kernel found in the disassembly")
+    return errs[:20]
+
+
 def check(so_path: str = DEFAULT_SO):
     """-> (errors, per-kernel summary)"""
     with tempfile.TemporaryDirectory() as wd:
         co = extract_code_object(so_path, wd)
         notes = kernel_notes(co)
         dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout.splitlines()
-    errors, summary = [], {}
+    errors, summary = check_unpacked(dis), {}
     for name, mangled in KERNELS.items():
         if mangled not in notes:
             errors.append(f"{name}: no kernel descriptor for {mangled}")
