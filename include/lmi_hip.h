@@ -617,7 +617,7 @@ LMI_API int lmi_kmeans_f16(int device, const uint16_t *x, int64_t n, int d, int 
 
 /* The mean and the centred scatter matrix of x [n][d] on the device, deterministic: the two inputs of a PCA fit (the navigation
  * vectors the reference downloads ready-made as pca32 / pca96 -- a user with embeddings of their own derives them with this and
- * lmi_project below; the eigen-solve of the d x d matrix is the caller's, on the host).  The same input gives the same mean and gram
+ * lmi_project below; the eigen-solve of the d x d matrix between them is lmi_eigh, or the caller's).  The same input gives the same mean and gram
  * bit for bit on any launch geometry; tests/pca_ref.py restates the call in numpy on top of oracle.dot.
  * No handle (like lmi_kmeans): the work runs on the NULL stream of `device` and the call returns when the outputs have landed.
  * on_device covers x, mean [d] and gram [d][d]: device pointers, x is only read where it lies; otherwise host pointers -- x is uploaded
@@ -689,6 +689,68 @@ LMI_API int lmi_project(int device, const float *x, int64_t n, int d, const floa
  * 16-byte aligned); mean, basis and y stay binary32.  y is bit for bit what lmi_project returns on the widened array. */
 LMI_API int lmi_project_f16(int device, const uint16_t *x, int64_t n, int d, const float *mean /* [d], nullable */,
                             const float *basis /* [m][d] */, int m, float *y /* [n][m] out */, int on_device);
+
+/* The m leading eigenpairs of a symmetric binary64 matrix on the device, deterministic: the step between lmi_gram and lmi_project, so
+ * that a PCA basis is the same to the bit wherever it is fitted.  A cyclic Jacobi method on a fixed round-robin schedule; the same
+ * input gives the same w, v and *sweeps bit for bit in either form and on any tile; tests/eigh_ref.py restates the call in numpy.
+ * No handle (like lmi_gram): the work runs on the NULL stream of `device` and the call returns when the outputs have landed.
+ * on_device covers a [d][d], w [m] and v [m][d]: device pointers, a is only read where it lies; otherwise host pointers.  Only the
+ * entries a[i][j] with i <= j are read.  sweeps is a host pointer, nullable.
+ * Arithmetic contract -- all binary64, every operation rounded once, nothing contracted into an fma
+ *   scale        e = the smallest integer with max|a_ij| < 2^e over i <= j (0 for the zero matrix), found on the device.
+ *                A = a * 2^(-e) (ldexp: exact, but for an entry that lands below 2^-1022, which is rounded once), the lower triangle
+ *                the mirror of the upper; V = I.  w is scaled back by 2^e (ldexp) at the end.
+ *   schedule     D = d rounded up to even.  A sweep is the rounds r = 0 .. D-2; round r holds the pairs {D-1, r} and
+ *                {(r+i) mod (D-1), (r-i) mod (D-1)}, i = 1 .. D/2-1, each written p < q.  A pair with q >= d sits out (the bye of an
+ *                odd d): its p takes part in no arithmetic that round.  The schedule is a function of d alone; the pairs of a round are
+ *                disjoint and the rounds of a sweep hold every pair once.
+ *   rotation     of a pair, from A as it stands at the start of the round.  The pair is SKIPPED -- c = 1, s = 0, t = 0 -- when
+ *                |a_pp| + |a_pq| == |a_pp| and |a_qq| + |a_pq| == |a_qq| (a_pq == 0 included).  Otherwise it is ROTATED:
+ *                theta = (a_qq - a_pp) / (2 * a_pq); t = sg / (|theta| + sqrt(theta * theta + 1)) with sg = -1 for theta < 0 and
+ *                +1 otherwise (theta == -0 included); where |theta| >= 2^512 (theta * theta would overflow), t = 1 / (2 * theta)
+ *                instead.  c = 1 / sqrt(t * t + 1), s = t * c.
+ *   round        B = J^T A J over all pairs of the round at once, for i <= j, then mirrored.  Column step: for j the p of a pair
+ *                u_ij = a_ip * c - a_iq * s, for j its q u_ij = a_ip * s + a_iq * c -- two rounded products, one rounded sum, with a
+ *                skipped pair's c = 1, s = 0 like any other --, for a j that sits out u_ij = a_ij.  Row step: the same rule on u
+ *                over i with the rotation of i's pair.  Overrides for a ROTATED pair: b_pq = +0, b_pp = a_pp - t * a_pq,
+ *                b_qq = a_qq + t * a_pq (one product, one sum).  V takes the column step alone.  An output depends on the round's
+ *                input only: no grid, tile or form can show in a bit.
+ *   stop         a sweep in which every pair was skipped ends the call; *sweeps counts it too.  More than LMI_EIGH_SWEEP_CAP = 64
+ *                sweeps is a refusal, not a result.
+ *   output       the eigenvalues are A's diagonal, in descending order, ties by ascending index.  v[r] = the column order[r] of V,
+ *                negated when its largest-magnitude entry (the lowest index on a tie) is negative.
+ * Two forms with the same bits: d <= 100 runs resident -- one block holds A and V in 16 d^2 + 18 D + 16 bytes of LDS for all sweeps,
+ * one launch --, larger d streams A and V through double buffers in device memory, one launch per round and one 4-byte read per
+ * sweep.  No matrix instruction is used: a round is plane rotations, there is no product to feed one.
+ * Refused, with nothing written: d outside 1..LMI_EIGH_MAX_D, m outside 1..d, NULL a / w / v; found on the device: an a_ij, i <= j,
+ * that is not finite; no convergence within the sweep cap.  A failed allocation names the bytes it wanted; the call frees all it
+ * allocated.
+ * Peak device memory: resident 8 d^2 + 12 d; streamed 32 d^2 + 4 d; with host pointers 8 d^2 + 8 m (d + 1) more for a, w and v. */
+#define LMI_EIGH_MAX_D 4096
+#define LMI_EIGH_SWEEP_CAP 64
+#define LMI_EIGH_FORM_RESIDENT 1
+#define LMI_EIGH_FORM_STREAMED 2
+LMI_API int lmi_eigh(int device, const double *a /* [d][d], only i <= j is read */, int d, int m,
+                     double *w /* [m] out, descending */, double *v /* [m][d] out: row r = eigenvector of w[r] */,
+                     int *sweeps /* host, nullable */, int on_device);
+/* Tuning / test hook: the form (LMI_EIGH_FORM_*; forcing the resident form on a d it does not hold makes lmi_eigh refuse) and the
+ * streamed form's tile, 8 or 16 pairs a side.  0, 0 = the library's choice.  Thread-local; never changes a bit. */
+LMI_API int lmi_eigh_set_geometry(int form, int tile);
+enum {
+    LMI_EIGH_PLAN_FORM = 0,          /* LMI_EIGH_FORM_RESIDENT or LMI_EIGH_FORM_STREAMED                                        */
+    LMI_EIGH_PLAN_TILE,              /* streamed: pairs per side of a block's tile (0 when resident)                           */
+    LMI_EIGH_PLAN_LDS_BYTES,         /* LDS of a block: resident A, V and the rotations; streamed the tile's rotations         */
+    LMI_EIGH_PLAN_RESIDENT_MAX_D,    /* the largest d the resident form holds                                                  */
+    LMI_EIGH_PLAN_GRID,              /* blocks of a launch                                                                     */
+    LMI_EIGH_PLAN_SWEEPS,            /* sweeps run, the one that rotated nothing included                                      */
+    LMI_EIGH_PLAN_LAUNCHES,          /* solver launches: 1 resident, (D - 1) * sweeps streamed                                 */
+    LMI_EIGH_PLAN_EXPONENT,          /* e                                                                                      */
+    LMI_EIGH_PLAN_WORKSPACE_BYTES,   /* device bytes the call allocated                                                        */
+    LMI_EIGH_PLAN_COUNT
+};
+/* What the last lmi_eigh on this thread did (all zero before the first and after a refused call); writes
+ * min(n, LMI_EIGH_PLAN_COUNT) words. */
+LMI_API int lmi_debug_eigh_plan(int64_t *out, int n);
 
 /* Adam steps on a Linear/ReLU stack with the cross-entropy loss, on the device, deterministic (replaces the training stage of the
  * index build: NeuralNetwork.train_batch, li/model.py:185-211, whose epoch is ONE optimizer step on its last mini-batch).  The same

@@ -68,6 +68,10 @@ KNN_EXACT_MAX_SEEDS = 32         # LMI_KNN_EXACT_MAX_SEEDS
 GRAM_PLAN_FIELDS = ("TILE_COLS", "TILES", "PIECES", "PIECES_PER_BLOCK", "RUNS", "VEC", "EXPONENT", "WORKSPACE_BYTES")
 GRAM_PIECE_ROWS = 4096           # LMI_GRAM_PIECE_ROWS: part of `gram`'s arithmetic contract
 GRAM_MAX_ROWS = 1 << 26          # `gram`: the bound of its int64 sums
+#: the LMI_EIGH_PLAN_* words, in their order (lmi_debug_eigh_plan)
+EIGH_PLAN_FIELDS = ("FORM", "TILE", "LDS_BYTES", "RESIDENT_MAX_D", "GRID", "SWEEPS", "LAUNCHES", "EXPONENT", "WORKSPACE_BYTES")
+EIGH_MAX_D = 4096                # LMI_EIGH_MAX_D
+EIGH_FORM_RESIDENT, EIGH_FORM_STREAMED = 1, 2   # LMI_EIGH_FORM_*
 PROJECT_MAX_M = 1024             # LMI_PROJECT_MAX_M: the most basis rows of `project`
 
 _lib = None
@@ -200,6 +204,10 @@ SIGNATURES = {
     "lmi_gram_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_gram_set_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64]),
     "lmi_debug_gram_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
+    # (device, a, d, m, w, v, sweeps, on_device)
+    "lmi_eigh": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
+    "lmi_eigh_set_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "lmi_debug_eigh_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_project": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "lmi_project_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "lmi_timings": (ctypes.c_int, [_vp, _vp]),
@@ -2035,6 +2043,51 @@ def gram_last_plan() -> dict:
     w = (ctypes.c_int64 * len(GRAM_PLAN_FIELDS))()
     _check(lib().lmi_debug_gram_plan(w, len(GRAM_PLAN_FIELDS)))
     return dict(zip(GRAM_PLAN_FIELDS, (int(v) for v in w)))
+
+
+def eigh(a, m=None, device: int = 0):
+    """The `m` leading eigenpairs (default: all d) of the symmetric matrix `a` on the device (`lmi_eigh`): (w f64[m] descending,
+    v f64[m,d] with row r the eigenvector of w[r], sweeps).  A cyclic Jacobi method whose every operation is written down: the same
+    input gives the same bits in either form and on any tile (include/lmi_hip.h states the arithmetic; tests/eigh_ref.py restates
+    it).  Only the upper triangle of `a` is read.  `a`: a float64 numpy array [d,d], or a contiguous float64 torch tensor on the
+    device, used where it lies; w and v then come back as tensors on that device.  Argument errors raise ValueError before the
+    library is loaded."""
+    is_np = _array_arg("eigh", "a", a, "float64", "nd")
+    d = int(a.shape[0])
+    if int(a.shape[1]) != d:
+        raise ValueError(f"eigh: a must be square, not {tuple(a.shape)}")
+    if d > EIGH_MAX_D:
+        raise ValueError(f"eigh: d {d} outside [1, {EIGH_MAX_D}]")
+    m = d if m is None else int(m)
+    if m < 1 or m > d:
+        raise ValueError(f"eigh: m {m} outside [1, d = {d}]")
+    sweeps = ctypes.c_int(0)
+    if is_np:
+        a = np.ascontiguousarray(a)
+        w, v = np.empty(m, dtype=np.float64), np.empty((m, d), dtype=np.float64)
+        _check(lib().lmi_eigh(int(device), _ptr(a), d, m, _ptr(w), _ptr(v), ctypes.byref(sweeps), 0))
+        return w, v, int(sweeps.value)
+    if not (a.is_cuda and a.is_contiguous()):
+        raise ValueError("eigh: a torch a must be a contiguous tensor on the device")
+    import torch
+
+    w = torch.empty(m, dtype=torch.float64, device=a.device)
+    v = torch.empty((m, d), dtype=torch.float64, device=a.device)
+    _check(lib().lmi_eigh(_sync_device(a), _ptr(a), d, m, _ptr(w), _ptr(v), ctypes.byref(sweeps), 1))
+    return w, v, int(sweeps.value)
+
+
+def eigh_set_geometry(form: int = 0, tile: int = 0) -> None:
+    """Tuning / test hook (`lmi_eigh_set_geometry`): the form (EIGH_FORM_RESIDENT, EIGH_FORM_STREAMED) and the streamed form's tile
+    (8 or 16 pairs a side) of the `eigh` calls of this thread; 0 = chosen by the library.  Never changes a bit."""
+    _check(lib().lmi_eigh_set_geometry(int(form), int(tile)))
+
+
+def eigh_plan() -> dict:
+    """What the last `eigh` on this thread did (`lmi_debug_eigh_plan`): `EIGH_PLAN_FIELDS` -> int."""
+    w = (ctypes.c_int64 * len(EIGH_PLAN_FIELDS))()
+    _check(lib().lmi_debug_eigh_plan(w, len(EIGH_PLAN_FIELDS)))
+    return dict(zip(EIGH_PLAN_FIELDS, (int(x) for x in w)))
 
 
 def project(x, basis, mean=None, device: int = 0):

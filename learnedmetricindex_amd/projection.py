@@ -1,7 +1,8 @@
 """A PCA projection fitted and applied on the device: navigation vectors for data that comes without a `pca32` / `pca96` kind.
 
 `PcaProjection.fit(x, m)` takes the mean and the centred scatter matrix from `_capi.gram` (bit for bit reproducible: include/lmi_hip.h)
-and solves the d x d eigenproblem on the host; `.transform(x)` is `_capi.project`.  There is no CPU fallback for either call."""
+and solves the d x d eigenproblem on the host -- or, with `solver="hip"`, on the device by `_capi.eigh`; `.transform(x)` is
+`_capi.project`.  There is no CPU fallback for any of these calls."""
 from __future__ import annotations
 
 import numpy as np
@@ -18,7 +19,8 @@ class PcaProjection:
 
     The eigen-solve is LAPACK's (`np.linalg.eigh` in float64) and NOT part of the bit-for-bit contract: `mean` and the scatter
     matrix are reproducible to the bit, the basis only as far as LAPACK is on the machine at hand.  `transform` is reproducible
-    to the bit for a given (mean, basis): keep a fitted projection with `save` rather than fitting it again elsewhere."""
+    to the bit for a given (mean, basis): keep a fitted projection with `save` rather than fitting it again elsewhere.
+    With `solver="hip"` the eigen-solve is `lmi_eigh` and the basis is part of the bit-for-bit contract too."""
 
     def __init__(self, mean, basis, explained_variance):
         self.mean = np.ascontiguousarray(mean, dtype=np.float32)
@@ -37,8 +39,10 @@ class PcaProjection:
         return int(self.basis.shape[1])
 
     @classmethod
-    def fit(cls, x, m: int, device: int = 0) -> "PcaProjection":
-        """`x`: what `_capi.gram` takes (float32 or float16 [n,d], numpy or a device tensor), n >= 2; 1 <= m <= min(d, 1024)."""
+    def fit(cls, x, m: int, device: int = 0, solver: str = "lapack") -> "PcaProjection":
+        """`x`: what `_capi.gram` takes (float32 or float16 [n,d], numpy or a device tensor), n >= 2; 1 <= m <= min(d, 1024).
+        `solver`: "lapack" (`np.linalg.eigh` of gram / (n - 1) on the host) or "hip" (`_capi.eigh` of gram itself, where it lies;
+        the eigenvalues are divided by n - 1 afterwards, so the matrix solved is the integer-exact scatter matrix)."""
         if getattr(x, "ndim", 0) != 2:
             raise ValueError("PcaProjection.fit: x must be [n,d]")
         n, d, m = int(x.shape[0]), int(x.shape[1]), int(m)
@@ -46,7 +50,14 @@ class PcaProjection:
             raise ValueError(f"PcaProjection.fit: n {n} < 2")
         if m < 1 or m > min(d, _capi.PROJECT_MAX_M):
             raise ValueError(f"PcaProjection.fit: m {m} outside [1, min(d = {d}, {_capi.PROJECT_MAX_M})]")
+        if solver not in ("lapack", "hip"):
+            raise ValueError(f"PcaProjection.fit: solver {solver!r} is neither 'lapack' nor 'hip'")
         mean, g = _capi.gram(x, device=device)
+        if solver == "hip":
+            w, v, _ = _capi.eigh(g, m, device=device)
+            if not isinstance(mean, np.ndarray):
+                mean, w, v = mean.cpu().numpy(), w.cpu().numpy(), v.cpu().numpy()
+            return cls(mean, v.astype(np.float32), w / float(n - 1))
         if not isinstance(mean, np.ndarray):
             mean, g = mean.cpu().numpy(), g.cpu().numpy()
         w, v = np.linalg.eigh(g / float(n - 1))   # ascending

@@ -86,6 +86,7 @@ class Experiment:
     range_exact: bool = False
     knn_exact: bool = False
     nav_pca: Optional[int] = None
+    nav_pca_solver: str = "lapack"
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -144,6 +145,9 @@ class Experiment:
                        help="derive the navigation vectors of the data and of the queries from the scan vectors by an M-dimensional PCA "
                             "fitted on the data on the device (PcaProjection), instead of loading --dataset / --emb: for embeddings that "
                             "come without a pca32 / pca96 kind; with --synthetic it replaces the stand-in's fixed random projection")
+        p.add_argument("--nav-pca-solver", choices=("lapack", "hip"), default="lapack",
+                       help="with --nav-pca: lapack = the eigen-solve on the host (np.linalg.eigh); hip = on the device (lmi_eigh): "
+                            "the fitted basis, and with it the navigation vectors, is then repeatable bit for bit on any host")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
         if a["nav_pca"] is not None and not 1 <= a["nav_pca"] <= min(WIDTH[SCAN_KIND], 1024):
@@ -338,7 +342,7 @@ def run(exp: Experiment) -> Dict:
     sx = None
     if exp.nav_pca is not None:   # the navigation vectors are the scan vectors' leading principal components, fitted on the data
         sx, scan_q = src.load(SCAN_KIND, SCAN_KEY, keep_f16=keep_f16)
-        pca = PcaProjection.fit(sx, exp.nav_pca)
+        pca = PcaProjection.fit(sx, exp.nav_pca, solver=exp.nav_pca_solver)
         nav_x, nav_q = pca.transform(sx), pca.transform(scan_q.astype(sx.dtype, copy=False))
         LOG.info("navigation by a %d-d PCA of %s: variance kept %.6g", exp.nav_pca, SCAN_KIND, float(pca.explained_variance.sum()))
     else:
