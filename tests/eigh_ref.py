@@ -87,6 +87,66 @@ INPUTS.update(rank20_d70=functools.partial(scatter, 20, 70, 1), degenerate=funct
               indefinite=lambda: np.pad(np.array([[0.0, 1.0], [1.0, 0.0]]), ((1, 2), (1, 2))), zero=functools.partial(np.zeros, (6, 6)))
 
 
+ORDINARY_SCALE = sorted(INPUTS)   # what test_eigh_host.py holds against LAPACK; the inputs of ordinary scale below join it
+
+
+def exponent(a):
+    """e of the contract's scale step: the smallest integer with max|a_ij| < 2^e over i <= j, 0 for the zero matrix."""
+    amax = np.abs(np.triu(a)).max()
+    return int(np.frexp(amax)[1]) if amax else 0
+
+
+def base():
+    return INPUTS["degenerate"]()
+
+
+def symmetric(d, entries):
+    """The d x d matrix with a[i, j] = a[j, i] = v for (i, j, v) in entries, zero elsewhere."""
+    a = np.zeros((d, d))
+    for i, j, v in entries:
+        a[i, j] = a[j, i] = v
+    return a
+
+
+def mixed_sub():
+    """base * 2^600 with one entry that lands below 2^-1022 when the matrix is scaled by 2^-e: the one rounding ldexp may make."""
+    a = np.ldexp(base(), 600)
+    a[0, 11] = a[11, 0] = (1.0 + 2.0 ** -52) * 2.0 ** -470
+    return a
+
+
+MIXED_SUB_SEEN = (1.0 + 2.0 ** -51 + 2.0 ** -52) * 2.0 ** -418
+
+
+def mixed_sub_seen(entry=MIXED_SUB_SEEN):
+    """mixed_sub's rounding where it shows in v: the entry (2^-1024 (1 + 3 * 2^-52) after scaling, between two subnormals and past
+    their midpoint) couples the zero row 3 -- a_33 == 0, so the pair is rotated, with t = 1 / (2 theta) -- to row 11."""
+    a = np.ldexp(base(), 600)
+    assert not a[3].any()
+    a[3, 11] = a[11, 3] = entry
+    return a
+
+
+# Extreme scales: the scaling step far from e = 0, subnormal inputs, an entry that ldexp rounds.
+INPUTS.update(scaled_up=lambda: np.ldexp(base(), 900), scaled_down=lambda: np.ldexp(base(), -900),
+              subnormal=lambda: np.ldexp(base(), -1040), mixed_sub=mixed_sub, mixed_sub_seen=mixed_sub_seen)
+# The branches of the rotation (test_eigh_host.py counts that each is reached): |theta| >= 2^512 once and twice, an infinite theta,
+# theta == -0 (a_pp == a_qq against a negative a_pq).
+BRANCHES = dict(
+    big_theta_d2=lambda: symmetric(2, [(0, 1, 2.0 ** -600), (1, 1, 0.75)]),
+    big_theta_d5=lambda: symmetric(5, [(4, 4, 0.75), (0, 4, 2.0 ** -600), (3, 3, 2.0 ** -700), (3, 4, -2.0 ** -620),
+                                       (1, 1, 2.0), (2, 2, 1.0), (1, 2, 0.5)]),
+    inf_theta=lambda: symmetric(2, [(0, 1, 2.0 ** -1060), (1, 1, 0.75)]),
+    neg_zero_theta=lambda: np.array([[1.0, -0.5, 0.25], [-0.5, 1.0, 0.125], [0.25, 0.125, 1.0]]))
+INPUTS.update(BRANCHES)
+# Spectra: all negative; repeated and unsorted on a diagonal (ties by index, nothing to rotate); the odd sizes with a bye at the
+# resident bound (99) and where the pair count does not (127: 64 pairs) and does (129: 65 pairs) run past the streamed tile.
+SPECTRA = dict(negative_definite=lambda: -base(), diag_unsorted=lambda: np.diag([3.0, -1.0, 3.0, 0.0, 7.0, -1.0, 3.0]),
+               identity9=functools.partial(np.eye, 9), **{f"d{d}": functools.partial(scatter, 3 * d + 5, d, d) for d in (99, 127, 129)})
+INPUTS.update(SPECTRA)
+ORDINARY_SCALE = sorted(ORDINARY_SCALE + list(BRANCHES) + list(SPECTRA))
+
+
 @functools.lru_cache(maxsize=None)
 def case(name: str):
     """(a, w, v, sweeps) of a named input: computed once, shared, read-only."""

@@ -54,7 +54,56 @@ def test_argument_errors_raise_before_the_library_loads(monkeypatch, name):
         call(_capi)
 
 
-@pytest.mark.parametrize("name", sorted(eigh_ref.INPUTS))
+def test_the_branch_inputs_reach_their_branches(monkeypatch):
+    """big_theta_*: rotated pairs with a finite |theta| >= 2^512 (d5: two of them); inf_theta: an infinite theta; neg_zero_theta:
+    theta == -0.  Counted on the restatement, which the device equals bit for bit (tests/test_gpu_eigh.py)."""
+    seen = {}
+    plain = eigh_ref.rotations
+
+    def spy(A, p, q):
+        out = plain(A, p, q)
+        with np.errstate(all="ignore"):
+            theta = ((A[q, q] - A[p, p]) / (2.0 * A[p, q]))[out[3]]
+        seen["big"] += int((np.isfinite(theta) & (np.abs(theta) >= 2.0 ** 512)).sum())
+        seen["inf"] += int(np.isinf(theta).sum())
+        seen["neg_zero"] += int(((theta == 0) & np.signbit(theta)).sum())
+        return out
+
+    monkeypatch.setattr(eigh_ref, "rotations", spy)
+    for name, branch, at_least in [("big_theta_d2", "big", 1), ("big_theta_d5", "big", 2), ("inf_theta", "inf", 1),
+                                   ("neg_zero_theta", "neg_zero", 1), ("mixed_sub_seen", "big", 1), ("d33", "big", 0)]:
+        seen.update(big=0, inf=0, neg_zero=0)
+        eigh_ref.eigh_ref(eigh_ref.INPUTS[name]())
+        print(name, seen)
+        assert seen[branch] >= at_least and (name != "d33" or not any(seen.values()))
+
+
+@pytest.mark.parametrize("k", [900, -900])
+def test_the_restatement_is_scale_invariant(k):
+    """eigh_ref(a 2^k) = (w 2^k, v, sweeps) bit for bit: the first step normalises, ldexp is exact on both ends.  This, not LAPACK,
+    is the statement for scaled_up and scaled_down."""
+    a, w, v, sweeps = eigh_ref.case("degenerate")
+    scaled = eigh_ref.case("scaled_up" if k > 0 else "scaled_down")
+    assert np.array_equal(scaled[0], np.ldexp(a, k)) and eigh_ref.exponent(scaled[0]) == eigh_ref.exponent(a) + k
+    assert np.array_equal(scaled[1].view(np.uint64), np.ldexp(w, k).view(np.uint64))
+    assert np.array_equal(scaled[2].view(np.uint64), v.view(np.uint64)) and scaled[3] == sweeps
+
+
+def test_the_rounded_entry_of_mixed_sub_seen_shows_in_v():
+    """The entry lies past the midpoint of two subnormals after scaling: ldexp rounds it up.  An entry cut off instead (or flushed to
+    zero) is a different matrix with a different v, so a device that scaled otherwise could not pass the parity test.  mixed_sub's own
+    entry vanishes: it underflows to zero against a pair that is skipped."""
+    a, w, v, sweeps = eigh_ref.case("mixed_sub_seen")
+    e = eigh_ref.exponent(a)
+    kept = np.ldexp(a[3, 11], -e)
+    assert 0 < kept < 2.0 ** -1022 and kept == 2.0 ** -1024 + 2.0 ** -1074 and np.ldexp(kept, e) != a[3, 11]
+    for entry in (2.0 ** -418, 0.0):   # the entry rounded toward zero, flushed
+        other = eigh_ref.eigh_ref(eigh_ref.mixed_sub_seen(entry))
+        assert not np.array_equal(other[1].view(np.uint64), v.view(np.uint64))
+    assert np.ldexp(eigh_ref.INPUTS["mixed_sub"]()[0, 11], -eigh_ref.exponent(eigh_ref.INPUTS["mixed_sub"]())) == 0.0
+
+
+@pytest.mark.parametrize("name", eigh_ref.ORDINARY_SCALE)
 def test_the_restatement_against_lapack(name):
     """Residual ||GV - V L||_F / ||G||_F and orthogonality ||V^T V - I||_F within K = 3 * sweeps times LAPACK's own on the same
     matrix (DESIGN.md 5.16 derives K: an entry of V takes sweeps * (D - 1) plane rotations of three roundings each where LAPACK's

@@ -1,6 +1,7 @@
 """GPU (`-m gpu`): `lmi_eigh` against its numpy restatement (tests/eigh_ref.py).  Parity is exact -- w and v as uint64 bit patterns,
 sweeps as an integer -- on every form the size admits and both streamed tiles.  d covers 1, 2, the bye of an odd d, one and several
-tiles, both sides of the resident bound; the matrices full rank, rank-deficient, with zero and repeated eigenvalues, indefinite, zero."""
+tiles, both sides of the resident bound; the matrices full rank, rank-deficient, with zero and repeated eigenvalues, indefinite, zero;
+scaled by 2^+-900, subnormal, with an entry the scaling rounds; every branch of the rotation (eigh_ref.BRANCHES)."""
 import numpy as np
 import pytest
 import torch
@@ -43,7 +44,54 @@ def test_parity_on_every_form_and_tile(capi, name):
         assert plan["RESIDENT_MAX_D"] == eigh_ref.RESIDENT_MAX_D and plan["SWEEPS"] == sweeps
         assert plan["FORM"] == (form or (RES if resident else STR)) and plan["TILE"] == (tile or (0 if plan["FORM"] == RES else 16))
         assert plan["LAUNCHES"] == (1 if plan["FORM"] == RES else (d + d % 2 - 1) * sweeps)
+        assert plan["EXPONENT"] == eigh_ref.exponent(a)
+        assert (plan["LDS_BYTES"], plan["GRID"]) == lds_and_grid(d, plan["TILE"])
     capi.eigh_set_geometry(0, 0)
+
+
+def lds_and_grid(d, tile):
+    """lmi_eigh_plan.h restated.  Resident (tile 0): A, V and the rotations of D / 2 pairs in one block.  Streamed: a tile's row and
+    column rotations; one block per tile (ti <= tj) of pairs x pairs for A, one per (strip of 2 * tile rows, tile of pairs) for V."""
+    D = d + d % 2
+    if tile == 0:
+        return 16 * d * d + 18 * D + 16, 1
+    side = -(-(D // 2) // tile)
+    return 64 * tile, side * (side + 1) // 2 + -(-d // (2 * tile)) * side
+
+
+def test_a_tie_cut_by_index_inside_the_leading_rows(capi):
+    """diag(3, -1, 3, 0, 7, -1, 3), m = 3: the rows of 7, of the 3 at index 0 and of the 3 at index 2 -- not the one at index 6."""
+    a, w, v, sweeps = eigh_ref.case("diag_unsorted")
+    assert w[:3].tolist() == [7.0, 3.0, 3.0] and v[:3].argmax(axis=1).tolist() == [4, 0, 2] and sweeps == 1
+    for form, tile in [(0, 0), (capi.EIGH_FORM_STREAMED, 8), (capi.EIGH_FORM_STREAMED, 16), (capi.EIGH_FORM_RESIDENT, 0)]:
+        capi.eigh_set_geometry(form, tile)
+        assert_eigh(capi.eigh(a, 3), w[:3], v[:3], sweeps)
+        wt, vt, st = capi.eigh(torch.from_numpy(np.array(a)).cuda(), 3)
+        assert_eigh((wt.cpu().numpy(), vt.cpu().numpy(), st), w[:3], v[:3], sweeps)
+    capi.eigh_set_geometry(0, 0)
+
+
+@pytest.mark.parametrize("name", ["full_mantissa", "up40"])
+def test_fit_and_transform_end_to_end_by_bits(capi, name):
+    """PcaProjection.fit(solver="hip") and transform against gram_ref -> eigh_ref -> project_ref: mean, basis, explained variance
+    and y, on rows with full binary32 mantissas and on rows of order 2^40."""
+    from learnedmetricindex_amd.projection import PcaProjection
+
+    n, d, m = 500, 44, 8
+    x, mean, g, e = pca_ref.gram_values_case(name, n, d)
+    w, v, _ = eigh_ref.eigh_ref(g, m)
+    basis = v.astype(np.float32)
+    from oracle import lmi_oracle
+
+    y = pca_ref.project_ref(lmi_oracle, x, basis, mean)
+    for xs in (x, torch.from_numpy(np.array(x)).cuda()):
+        p = PcaProjection.fit(xs, m, solver="hip")
+        assert capi.gram_last_plan()["EXPONENT"] == e and capi.eigh_plan()["EXPONENT"] == eigh_ref.exponent(g)
+        assert np.array_equal(p.mean.view(np.uint32), mean.view(np.uint32)) and np.array_equal(p.basis.view(np.uint32), basis.view(np.uint32))
+        assert np.array_equal(b64(p.explained_variance), b64(w / float(n - 1)))
+        got = p.transform(xs)
+        got = got if isinstance(got, np.ndarray) else got.cpu().numpy()
+        assert np.array_equal(got.view(np.uint32), y.view(np.uint32)), int((got.view(np.uint32) != y.view(np.uint32)).sum())
 
 
 @pytest.mark.parametrize("name", ["d33", "d101"])

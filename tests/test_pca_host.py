@@ -55,6 +55,74 @@ def test_argument_errors_raise_before_the_library_loads(monkeypatch, name):
         call(_capi)
 
 
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def u64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+@pytest.mark.parametrize("n,d", pca_ref.GRAM_VALUE_SHAPES)
+def test_the_value_cases_are_what_their_names_say(n, d):
+    """The exponent of every case, and what the restatement makes of the degenerate ones (tests/test_gpu_pca.py holds the device to
+    the restatement bit for bit, so these are statements about the device too)."""
+    for name in pca_ref.GRAM_VALUE_NAMES:
+        x, mean, g, e = pca_ref.gram_values_case(name, n, d)
+        assert e == pca_ref.VALUES[name][1], (name, e)
+        assert np.isfinite(g).all() and np.array_equal(g, g.T)
+    x, mean, g, _ = pca_ref.gram_values_case("down70", n, d)
+    c = x - mean
+    assert float(np.abs(c[:, 0] * c[:, 1]).max()) < 2.0 ** -126 and g.all()   # subnormal products, and none of them lost
+    x, mean, g, _ = pca_ref.gram_values_case("last_exponent", n, d)
+    assert float(np.abs(x).max()) == 2.0 ** 56 - 2.0 ** 32 == float(np.nextafter(np.float32(2.0 ** 56), np.float32(0)))
+    x, mean, g, _ = pca_ref.gram_values_case("full_mantissa", n, d)
+    assert not np.array_equal(x.astype(np.float16).astype(np.float32), x) and (u32(x) & 0xfff).any()
+    x, mean, g, _ = pca_ref.gram_values_case("zero", n, d)
+    assert not u32(mean).any() and not u64(g).any()   # +0 everywhere
+    x, mean, g, _ = pca_ref.gram_values_case("const_and_equal", n, d)
+    assert mean[3] == 2.5 and not u64(g[3]).any() and not u64(g[:, 3]).any()
+    assert np.array_equal(u64(g[5]), u64(g[8])) and g[5, 5] == g[8, 8] == g[5, 8] > 0
+    x, mean, g, _ = pca_ref.gram_values_case("halves_only", n, d)
+    x16 = x.astype(np.float16)
+    assert np.array_equal(u32(x16.astype(np.float32)), u32(x)) and np.signbit(x[3]).all() and not x[3].any()
+    assert (np.abs(x[:2]) == 65504).all() and ((x16[2].view(np.uint16) & 0x7c00) == 0).all() and x[2].all()
+
+
+@pytest.mark.parametrize("n,d", pca_ref.GRAM_VALUE_SHAPES)
+def test_the_gram_restatement_under_a_change_of_scale(n, d):
+    """x 2^40 is exact all the way: mean 2^40 and gram 2^80 of the plain case, bit for bit.  x 2^-70 is not -- the products of a chain
+    are binary32 subnormals -- and is held against the float64 product instead: test_gram_against_float64's entrywise bound
+    (tests/test_gpu_pca.py) and one quantum of the smallest subnormal, 2^-149, for every link of every piece's chain."""
+    x, mean, g, e = pca_ref.gram_values_case("plain", n, d)
+    xu, meanu, gu, eu = pca_ref.gram_values_case("up40", n, d)
+    assert np.array_equal(u32(xu), u32(np.ldexp(x, 40))) and eu == e + 40
+    assert np.array_equal(u32(meanu), u32(np.ldexp(mean, 40))) and np.array_equal(u64(gu), u64(np.ldexp(g, 80)))
+    xd, meand, gd, ed = pca_ref.gram_values_case("down70", n, d)
+    assert np.array_equal(u32(xd), u32(np.ldexp(x, -70))) and ed == e - 70 and np.array_equal(u32(meand), u32(np.ldexp(mean, -70)))
+    c = (xd - meand).astype(np.float64)
+    bound = (4096 + 2) * 2.0 ** -24 * (np.abs(c).T @ np.abs(c)) + -(-n // 4096) * 2.0 ** (2 * ed - 33) + n * 2.0 ** -149
+    err = np.abs(gd - c.T @ c)
+    print("down70", (n, d), "max err / bound", float((err / bound).max()), "gram changed by the subnormal products:",
+          int((u64(gd) != u64(np.ldexp(g, -140))).sum()), "of", d * d)
+    assert (err <= bound).all()
+
+
+def test_the_project_value_cases(oracle):
+    """What the restatement makes of the special rows: the non-finite rows alone differ from the clean case; a row of -0.0 and an
+    all-zero basis row give +0 (the chain starts from +0) where nothing is centred."""
+    for centred in (False, True):
+        clean = pca_ref.project_values_case("clean", centred)[3]
+        x, basis, mean, y = pca_ref.project_values_case("nonfinite", centred)
+        others = np.setdiff1d(np.arange(x.shape[0]), pca_ref.NONFINITE_ROWS)
+        assert np.array_equal(u32(y[others]), u32(clean[others])) and np.isfinite(y[others]).all()
+        assert np.isnan(y[7]).all() and not np.isfinite(y[9]).any() and np.isinf(y[9]).any()
+        assert not u32(pca_ref.project_values_case("zero_basis_row", centred)[3][:, 2]).any()
+        y = pca_ref.project_values_case("down70", centred)[3]
+        assert y.all() and float(np.abs(y).max()) < 2.0 ** -60
+    assert not u32(pca_ref.project_values_case("neg_zero_row", False)[3][5]).any()
+
+
 def test_the_restatement_is_a_scatter_matrix_and_a_projection(oracle, tmp_path):
     from learnedmetricindex_amd.projection import PcaProjection
 
