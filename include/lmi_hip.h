@@ -615,6 +615,53 @@ LMI_API int lmi_kmeans_f16(int device, const uint16_t *x, int64_t n, int d, int 
                            int64_t *counts /* [k] host, nullable */, int64_t *changed /* [niter+1] host, nullable */,
                            int on_device);
 
+/* Greedy k-means++ seeding on the device, deterministic: the initial centroids lmi_kmeans takes from its caller, chosen the way
+ * scikit-learn's KMeans chooses them (li/clustering/scikit_kmeans.py: the reference's other label provider) -- each new centre the
+ * best of L candidates drawn with probability proportional to the squared distance to the nearest centre so far.  The same input
+ * and seed give the same rows, potentials and centroids bit for bit on any launch geometry; tests/kmeanspp_ref.py restates the call
+ * in numpy on top of oracle.knn_l2.
+ * No handle (like lmi_kmeans): the work runs on the NULL stream of `device` and the call returns when the outputs have landed.
+ * on_device covers x [n][d] and centroids [k][d]: device pointers, x is only read; otherwise host pointers -- x is uploaded once, in
+ * pieces, and stays resident for all rounds.  rows [k] and potential [k] are host pointers, nullable.
+ * Arithmetic contract
+ *   exponents    e = the smallest integer with max|x| < 2^e (0 for all-zero data), as in lmi_kmeans; E = 2e + 3 + ceil(log2(d)).
+ *                xn_i = the chain acc = fmaf(x[t], x[t], acc) from 0, t = 0..d-1.
+ *   distance     of row i to a centre c -- always a row of x: cn_c = xn of that row, s = the chain acc = fmaf(x_i[t], c[t], acc) from
+ *                0, key = fmaf(1.0f, -0.5f * cn_c, s), dist = fmaxf(fmaf(-2.0f, key, xn_i), 0.0f): the LMI_METRIC_L2 distance the
+ *                scan writes with row i as the query.
+ *   weight       w(dist) = (uint64) rint((double)dist * 2^(36-E)): the product is exact in binary64, the rounding is to nearest
+ *                even.  The true distance is at most 4 d 2^(2e) <= 2^(E-1), so w <= 2^36 with room for the chain's rounding, and
+ *                with n <= 2^26 every sum of weights is below 2^62.  w is monotone, so w(min(a, b)) = min(w(a), w(b)): the running
+ *                state of a row is one integer W_i, no float minimum is kept, and every sum is an integer sum -- any reduction
+ *                tree, grid or atomic order gives the same value.
+ *   draws        z(t, j) = splitmix64_finalise(seed + 0x9E3779B97F4A7C15 * (1 + 32 t + j)) for round t and trial j, all mod 2^64;
+ *                the finaliser is z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *                A draw below a bound B is mulhi64(z, B) = floor(z * B / 2^64).
+ *   round 0      rows[0] = mulhi64(z(0,0), n); W_i = w(dist(i, rows[0])); potential[0] = the sum of W.
+ *   round t      (1 .. k-1) T = the sum of W.  L = n_trials, or 2 + floor(ln k) when n_trials == 0.  Candidate j = 0..L-1 is the
+ *                first row whose inclusive prefix sum of W (rows ascending) exceeds mulhi64(z(t,j), T).  If T == 0 every row
+ *                coincides with a centre (scikit-learn divides by zero here): candidate j is then mulhi64(z(t,j), n).
+ *                pot_j = the sum over i of min(W_i, w(dist(i, cand_j))); the winner is the lowest pot_j, ties to the lowest j.
+ *                rows[t] = that candidate, W_i = min(W_i, w(dist(i, winner))), potential[t] = pot_winner.
+ *   output       centroids[t] = row rows[t] of x.  A chosen row has weight 0 and is not drawn again while T > 0.
+ * Refused, with nothing written: n < 1, d < 1, d > 4096, k < 1, k > n, k > 16384, n > 2^26 (the bound of the integer sums),
+ * n_trials outside [0, 32], NULL x / centroids; found on the device in the pass that takes max|x|: any value of x that is not
+ * finite; and E > 127 (max|x| of about 2^58 and more), at which a distance could overflow binary32 -- by name, with E.
+ * A failed allocation names the bytes it wanted; the call frees all it allocated.
+ * Peak device memory: 8n (W) + 4nL (the candidates' distances, [L][n]) + 4n (xn) + 16 * ceil(n / 1024) (block sums and their
+ * prefix) + 272k (rows, potentials, 32 trial potentials a round) + 32 * (4d + 12) + 128 * roundup(d+1, 32) (the candidates' rows
+ * and their tile); with host pointers 4nd + 4kd more for x and the centroids. */
+LMI_API int lmi_kmeans_seed(int device, const float *x, int64_t n, int d, int k, int n_trials, uint64_t seed,
+                            float *centroids /* [k][d] out */, int64_t *rows /* [k] host, nullable */,
+                            int64_t *potential /* [k] host, nullable */, int on_device);
+
+/* lmi_kmeans_seed with x [n][d] given as binary16 bit patterns (2-byte alignment is enough, host or device; resident as halves,
+ * 2nd in place of 4nd).  Every half is widened exactly where it is loaded: rows, potential and centroids (binary32) are bit for bit
+ * what lmi_kmeans_seed returns on the widened array.  Bounds and refusals: lmi_kmeans_seed's, naming lmi_kmeans_seed_f16. */
+LMI_API int lmi_kmeans_seed_f16(int device, const uint16_t *x, int64_t n, int d, int k, int n_trials, uint64_t seed,
+                                float *centroids /* [k][d] binary32 out */, int64_t *rows /* [k] host, nullable */,
+                                int64_t *potential /* [k] host, nullable */, int on_device);
+
 /* The mean and the centred scatter matrix of x [n][d] on the device, deterministic: the two inputs of a PCA fit (the navigation
  * vectors the reference downloads ready-made as pca32 / pca96 -- a user with embeddings of their own derives them with this and
  * lmi_project below; the eigen-solve of the d x d matrix between them is lmi_eigh, or the caller's).  The same input gives the same mean and gram

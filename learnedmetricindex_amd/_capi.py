@@ -199,6 +199,11 @@ SIGNATURES = {
     "lmi_train_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                      ctypes.POINTER(_vp), _i64p, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, ctypes.c_int]),
     "lmi_mlp_topk_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    # k-means++ seeding: (device, x, n, d, k, n_trials, seed, centroids, rows, potential, on_device)
+    "lmi_kmeans_seed": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                       _vp, _vp, _vp, ctypes.c_int]),
+    "lmi_kmeans_seed_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                           _vp, _vp, _vp, ctypes.c_int]),
     # the PCA pair: (device, x, n, d, mean, gram, on_device) and (device, x, n, d, mean, basis, m, y, on_device)
     "lmi_gram": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_gram_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -1949,7 +1954,44 @@ def union_last_plan() -> dict:
     return dict(zip(UNION_PLAN_FIELDS, (int(v) for v in w)))
 
 
-def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int = 0):
+KMEANS_SEED_MAX_TRIALS = 32
+
+
+def kmeans_seed(x, k: int, n_trials: int = 0, seed: int = 2023, device: int = 0):
+    """Greedy k-means++ seeding on the device (`lmi_kmeans_seed`): (centroids f32[k,d], rows i64[k], potential i64[k]) -- the rows of
+    `x` chosen as initial centroids, in the order chosen, and the integer potential (the sum of the weights W) after each choice.
+    The same input and seed give the same result bit for bit (include/lmi_hip.h states the arithmetic; tests/kmeanspp_ref.py restates
+    it).  `x` as for `kmeans`: a float32 or float16 numpy array [n,d], or such a contiguous torch tensor on the device -- then
+    `centroids` is a tensor on that device and `x` is only read where it lies; a float16 `x` goes to `lmi_kmeans_seed_f16` as it is
+    and gives the result of the widened array.  `n_trials`: candidates per round, 0 = 2 + floor(ln k) (scikit-learn's).  Argument
+    errors raise ValueError before the library is loaded."""
+    f16 = _is_f16(x)
+    is_np = _array_arg("kmeans_seed", "x", x, "float16" if f16 else "float32", "nd")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    k, n_trials = int(k), int(n_trials)
+    if k < 1 or k > n:
+        raise ValueError(f"kmeans_seed: k {k} outside [1, n = {n}]")
+    if not 0 <= n_trials <= KMEANS_SEED_MAX_TRIALS:
+        raise ValueError(f"kmeans_seed: n_trials {n_trials} outside [0, {KMEANS_SEED_MAX_TRIALS}]")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    rows, potential = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
+    if is_np:
+        x = np.ascontiguousarray(x)
+        cent = np.empty((k, d), dtype=np.float32)
+        call = lib().lmi_kmeans_seed_f16 if f16 else lib().lmi_kmeans_seed
+        _check(call(int(device), _ptr(x), n, d, k, n_trials, seed, _ptr(cent), _ptr(rows), _ptr(potential), 0))
+        return cent, rows, potential
+    if not x.is_cuda or not x.is_contiguous():
+        raise ValueError("kmeans_seed: a torch x must be a contiguous tensor on the device")
+    import torch
+
+    cent = torch.empty((k, d), dtype=torch.float32, device=x.device)
+    call = lib().lmi_kmeans_seed_f16 if f16 else lib().lmi_kmeans_seed
+    _check(call(_sync_device(x), _ptr(x), n, d, k, n_trials, seed, _ptr(cent), _ptr(rows), _ptr(potential), 1))
+    return cent, rows, potential
+
+
+def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int = 0, n_trials: int = 0):
     """Lloyd's k-means on the device (`lmi_kmeans`): (centroids f32[k,d], labels i32[n], counts i64[k], changed i64[niter+1]).
     The same input gives the same result bit for bit (include/lmi_hip.h states the arithmetic; tests/kmeans_ref.py restates it).
     `x`: a float32 numpy array [n,d], or a contiguous float32 torch tensor on the device -- then `centroids` and `labels` come back
@@ -1957,7 +1999,8 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
     `lmi_kmeans_f16` as it is -- half the upload, resident as halves, no widened copy anywhere -- and the result is bit for bit that of
     the call on `x` widened to float32; the centroids are float32 either way.  `init`: f32 [k,d] initial centroids; None: the rows
     `np.random.RandomState(seed).choice(n, k, replace=False)` of `x`, widened to float32.  `changed[it]`: rows whose label moved in
-    pass `it` (zeros behind a fixed point).  Argument errors raise ValueError before the library is loaded."""
+    pass `it` (zeros behind a fixed point).  `init="k-means++"`: the centroids of `kmeans_seed(x, k, n_trials, seed, device)`
+    (`lmi_kmeans_seed`), which stay on the device when `x` is there.  Argument errors raise ValueError before the library is loaded."""
     f16 = _is_f16(x)
     is_np = _array_arg("kmeans", "x", x, "float16" if f16 else "float32", "nd")
     n, d = int(x.shape[0]), int(x.shape[1])
@@ -1966,6 +2009,20 @@ def kmeans(x, k: int, niter: int = 20, init=None, seed: int = 2023, device: int 
         raise ValueError(f"kmeans: k {k} outside [1, n = {n}]")
     if niter < 0:
         raise ValueError(f"kmeans: niter {niter} < 0")
+    if isinstance(init, str):
+        if init != "k-means++":
+            raise ValueError(f"kmeans: init {init!r} unknown (None, \"k-means++\" or float32 [{k},{d}])")
+        cent = kmeans_seed(x, k, n_trials=n_trials, seed=seed, device=device)[0]
+        if is_np:
+            init = cent
+        else:
+            counts, changed = np.zeros(k, dtype=np.int64), np.zeros(niter + 1, dtype=np.int64)
+            import torch
+
+            labels = torch.empty(n, dtype=torch.int32, device=x.device)
+            call = lib().lmi_kmeans_f16 if f16 else lib().lmi_kmeans
+            _check(call(_sync_device(x), _ptr(x), n, d, k, niter, _ptr(cent), _ptr(labels), _ptr(counts), _ptr(changed), 1))
+            return cent, labels, counts, changed
     if init is not None:
         init = np.asarray(init.detach().cpu().numpy() if hasattr(init, "detach") else init)
         if init.dtype != np.float32 or init.shape != (k, d):

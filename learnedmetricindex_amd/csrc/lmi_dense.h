@@ -8,8 +8,9 @@
 // 0, 1, 2, ..: an element of S is the canonical fmaf chain of oracle.knn_ip / knn_l2.
 // The loop that runs the product is written out in km_assign_kernel, again in km_assign16_kernel (lmi_kmeans.h: the rows as halves),
 // again in knn_score_kernel, again in knn_score16_kernel (lmi_knn.h: the base as halves), again in union_score_kernel (lmi_union.h)
-// and again in project_kernel (lmi_project.h: one template over the type of x; it subtracts a mean from bv before the MFMAs):
-// the six must stay equal (DESIGN.md 5.11 says why it is not a function here).
+// again in project_kernel (lmi_project.h: one template over the type of x; it subtracts a mean from bv before the MFMAs) and again
+// in kpp_round_kernel (lmi_kmeans_seed.h: one template over the type of x, one tile of candidates, the wave walks its row blocks):
+// the seven must stay equal (DESIGN.md 5.11 says why it is not a function here).
 //
 // Half forms (lmi_knn_f16 / lmi_knn_range_f16: X and the rows F is packed from arrive as binary16 bit patterns; lmi_kmeans_f16: X
 // does): dense_load_b on an unsigned short row, dense_pack16_kernel, dense_norm16_kernel, dense_absmax16_kernel.  Every half is widened by an exact conversion where it is loaded and

@@ -14,6 +14,8 @@
 #include "lmi_host_debug.h"   // timings, statistics, test hooks
 #include "lmi_kmeans.h"       // the kernels of lmi_kmeans
 #include "lmi_host_kmeans.h"  // lmi_kmeans
+#include "lmi_kmeans_seed.h"       // the kernels of lmi_kmeans_seed
+#include "lmi_host_kmeans_seed.h"  // lmi_kmeans_seed / lmi_kmeans_seed_f16
 #include "lmi_train.h"        // the kernels of lmi_train
 #include "lmi_host_train.h"   // lmi_train
 #include "lmi_knn.h"          // the kernels of lmi_knn

@@ -1,8 +1,9 @@
 """k-means on the MI355X (`lmi_kmeans`): Lloyd's algorithm in HIP, deterministic -- the same data, seed and iteration count give
 the same centroids and labels bit for bit (include/lmi_hip.h states the arithmetic).  faiss's defaults: 20 iterations, random initial
 centroids from the data, seed 2023 (reference: li/clustering/faiss_kmeans.py:8-24).  A float16 array stays float16
-(`lmi_kmeans_f16`): half the upload, the result that of the widened array.  There is no fallback: without the library or the device
-the call raises."""
+(`lmi_kmeans_f16`): half the upload, the result that of the widened array.  `init="k-means++"` (with `n_trials`, 0 = 2 + floor(ln k))
+seeds the way scikit-learn's KMeans does, on the device and repeatably (`lmi_kmeans_seed`).  There is no fallback: without the library
+or the device the call raises."""
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -19,9 +20,12 @@ class HipKmeans:
 def cluster(data, n_clusters: int, parameters: Optional[Dict[str, Any]]):
     params = {} if parameters is None else dict(parameters)
     seed, niter = int(params.pop("seed", 2023)), int(params.pop("niter", 20))
+    init, n_trials = params.pop("init", "random"), int(params.pop("n_trials", 0))
     params.pop("verbose", None)
     if params:
-        raise ValueError(f"hip_kmeans: unknown parameters {sorted(params)} (seed, niter)")
+        raise ValueError(f"hip_kmeans: unknown parameters {sorted(params)} (seed, niter, init, n_trials)")
+    if init not in ("random", "k-means++"):
+        raise ValueError(f"hip_kmeans: init {init!r} must be \"random\" or \"k-means++\"")
     try:
         from ... import _capi   # the package
     except ImportError:
@@ -30,5 +34,7 @@ def cluster(data, n_clusters: int, parameters: Optional[Dict[str, Any]]):
         data = np.asarray(data)
     # a float16 array is passed on as it is (lmi_kmeans_f16: resident as halves, the result that of the widened array)
     data = np.ascontiguousarray(data, dtype=np.float16 if data.dtype == np.float16 else np.float32)
-    centroids, labels, counts, changed = _capi.kmeans(data, n_clusters, niter=niter, seed=seed)
+    # "k-means++": the seeding runs on the device too (lmi_kmeans_seed); "random" is the call as it always was
+    seeding = {} if init == "random" else {"init": init, "n_trials": n_trials}
+    centroids, labels, counts, changed = _capi.kmeans(data, n_clusters, niter=niter, seed=seed, **seeding)
     return HipKmeans(centroids, counts, changed), labels

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import functools
 import logging
 import os
 import sys
@@ -87,6 +88,7 @@ class Experiment:
     knn_exact: bool = False
     nav_pca: Optional[int] = None
     nav_pca_solver: str = "lapack"
+    kmeans_init: str = "random"
 
     @classmethod
     def from_argv(cls, argv: Optional[Sequence[str]] = None) -> "Experiment":
@@ -148,8 +150,13 @@ class Experiment:
         p.add_argument("--nav-pca-solver", choices=("lapack", "hip"), default="lapack",
                        help="with --nav-pca: lapack = the eigen-solve on the host (np.linalg.eigh); hip = on the device (lmi_eigh): "
                             "the fitted basis, and with it the navigation vectors, is then repeatable bit for bit on any host")
+        p.add_argument("--kmeans-init", choices=("random", "k-means++"), default="random",
+                       help="with --clustering-algorithm hip_kmeans: random = k rows drawn by the seed (faiss's); k-means++ = greedy "
+                            "k-means++ seeding on the device (lmi_kmeans_seed), scikit-learn's choice, repeatable bit for bit")
         a = vars(p.parse_args(argv))
         a.pop("n_buckets")
+        if a["kmeans_init"] != "random" and set(a["clustering_algorithm"]) != {"hip_kmeans"}:
+            p.error("--kmeans-init k-means++ needs --clustering-algorithm hip_kmeans")
         if a["nav_pca"] is not None and not 1 <= a["nav_pca"] <= min(WIDTH[SCAN_KIND], 1024):
             p.error(f"--nav-pca takes M from 1 to {min(WIDTH[SCAN_KIND], 1024)}")
         levels = len(a["n_categories"])
@@ -187,8 +194,21 @@ class Experiment:
         return cls(job=os.environ.get("PBS_JOBID", "unknown"), **a)
 
     def build_configuration(self) -> BuildConfiguration:
-        return BuildConfiguration([algorithms[c] for c in self.clustering_algorithm], self.epochs, self.model_type,
+        return BuildConfiguration([self._clusterer(c) for c in self.clustering_algorithm], self.epochs, self.model_type,
                                   self.lr, self.n_categories)
+
+    def _clusterer(self, name: str):
+        """The registry's entry; with --kmeans-init k-means++ the same entry with `init` among its clustering parameters (the
+        builder passes none of its own)."""
+        cluster = algorithms[name]
+        if self.kmeans_init == "random":
+            return cluster
+
+        @functools.wraps(cluster)   # the builder tells hip_kmeans by its name
+        def seeded(data, n_clusters, parameters):
+            return cluster(data, n_clusters, {**(parameters or {}), "init": self.kmeans_init})
+
+        return seeded
 
     def tag(self, prefix: str, **extra) -> str:
         """File-name stem in the upstream format: <prefix>-ep=..-lr=..-cat=..-model=..[-k=v..]-<job>."""

@@ -28,6 +28,14 @@ the peak device memory of the host-pointer call -- polled from a second thread w
 header's formula.  Five repeats each, alternating the forms; the spread (max - min) of the float form's five pass times is what a
 difference between the forms is held against.  The results of the two forms must be equal bit for bit, or the run stops.
 
+  python tools/kmeans_bench.py --init k-means++ [--n ..] [--d ..] [--k ..] [--niter ..] [--out profiles/kmeanspp.txt]
+
+--init k-means++: instead of the above, `lmi_kmeans_seed` beside `lmi_kmeans` on the same device tensor in one process, the calls
+alternating: the seed call at k = 1 and at --k, whose difference over k - 1 is one round; lmi_kmeans at niter = 0 and at --niter,
+whose difference over niter is one pass.  Gate: the median round is not above the median pass by more than the spread (max - min) of
+the pass times; exit status 1 otherwise.  For information: inertia, largest-to-mean bucket size and empty clusters after --niter
+passes from `random` and from `k-means++`.  With --trace-run only one seed call and a 3-pass lmi_kmeans, for a profiler to watch.
+
 Prints a table and one JSON line; --out also writes both to a file.  Not a yardstick: bench.py is.
 """
 import argparse
@@ -153,6 +161,60 @@ def f16_ab(a):
     return 0
 
 
+def seed_ab(a):
+    """lmi_kmeans_seed beside lmi_kmeans on device tensors: a round against a pass, and what the seeding buys after --niter passes"""
+    import torch
+    import synth
+
+    x, _ = synth.mixture(a.seed, a.n, a.d, a.k, 1)
+    xt = torch.from_numpy(x).cuda()
+    if a.trace_run:
+        _capi.kmeans_seed(xt, a.k, seed=a.seed)
+        _capi.kmeans(xt, a.k, niter=3, seed=a.seed)
+        torch.cuda.synchronize()
+        return 0
+    L = 2 + int(np.floor(np.log(a.k)))
+    lines = [f"kmeans_bench --init k-means++: {a.n} x {a.d}, k = {a.k}, L = {L} candidates a round, niter = {a.niter}, {a.reps} timed runs "
+             f"after one warm-up each, the calls alternating; {torch.cuda.get_device_name(0)}; {_capi.lib().lmi_build_info().decode()}"]
+    calls = dict(seed1=lambda: _capi.kmeans_seed(xt, 1, seed=a.seed), seedk=lambda: _capi.kmeans_seed(xt, a.k, seed=a.seed),
+                 km0=lambda: _capi.kmeans(xt, a.k, niter=0, seed=a.seed), kmn=lambda: _capi.kmeans(xt, a.k, niter=a.niter, seed=a.seed))
+    t = {name: [] for name in calls}
+    for fn in calls.values():
+        fn()
+    for _ in range(a.reps):
+        for name, fn in calls.items():
+            t[name].append(wall(fn)[1])
+    rounds = [(sk - s1) / max(a.k - 1, 1) for sk, s1 in zip(t["seedk"], t["seed1"])]
+    passes = [(kn - k0) / max(a.niter, 1) for kn, k0 in zip(t["kmn"], t["km0"])]
+    spread = max(passes) - min(passes)
+    med_r, med_p = statistics.median(rounds), statistics.median(passes)
+    ok = med_r <= med_p + spread
+    lines += ["device tensor in (ms)                              median       min       max",
+              f"  kmeans_seed, k = 1 (set-up + round 0)          {statistics.median(t['seed1']):10.3f} {min(t['seed1']):9.3f} {max(t['seed1']):9.3f}",
+              f"  kmeans_seed, k = {a.k:<5d} (the whole call)        {statistics.median(t['seedk']):10.3f} {min(t['seedk']):9.3f} {max(t['seedk']):9.3f}",
+              f"  one round (the difference over k - 1)          {med_r:10.3f} {min(rounds):9.3f} {max(rounds):9.3f}",
+              f"  one lmi_kmeans pass (niter {a.niter} less niter 0)     {med_p:10.3f} {min(passes):9.3f} {max(passes):9.3f}",
+              f"  round <= pass + the passes' spread ({spread:.3f} ms): {'met' if ok else 'MISSED'}; round / pass = {med_r / med_p:.2f}"]
+    res = dict(n=a.n, d=a.d, k=a.k, L=L, niter=a.niter, seed1_ms=t["seed1"], seedk_ms=t["seedk"], km0_ms=t["km0"], kmn_ms=t["kmn"],
+               round_ms=rounds, pass_ms=passes, round_median_ms=med_r, pass_median_ms=med_p, pass_spread_ms=spread, round_within_pass=bool(ok),
+               build=_capi.lib().lmi_build_info().decode())
+    lines.append(f"after {a.niter} Lloyd passes (for information)        inertia   largest / mean bucket   empty clusters")
+    for init in ("random", "k-means++"):
+        c, labels, counts, _ = _capi.kmeans(xt, a.k, niter=a.niter, seed=a.seed, init=None if init == "random" else init)
+        inertia = sum(float(((xt[i:i + 65536] - c[labels[i:i + 65536].long()]).double() ** 2).sum()) for i in range(0, a.n, 65536))
+        ratio = float(counts.max()) / (a.n / a.k)
+        lines.append(f"  init = {init:<10s}                      {inertia:16.2f} {ratio:14.3f} {int((counts == 0).sum()):18d}")
+        res[init] = dict(inertia=inertia, largest_over_mean=ratio, empty=int((counts == 0).sum()))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n" + json.dumps(res) + "\n")
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -164,6 +226,8 @@ def main():
     ap.add_argument("--kernel-ms", default="", help='traced kernel times per pass, e.g. "assign=3.1,update=1.2"')
     ap.add_argument("--trace-run", action="store_true", help="only the device-resident call (for a kernel trace)")
     ap.add_argument("--f16", action="store_true", help="lmi_kmeans_f16 beside lmi_kmeans on the same values")
+    ap.add_argument("--init", choices=("random", "k-means++"), default="random",
+                    help="k-means++: lmi_kmeans_seed beside lmi_kmeans on device tensors (a round against a pass)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -174,6 +238,8 @@ def main():
     _capi.lib()
     if a.f16:
         return f16_ab(a)
+    if a.init == "k-means++":
+        return seed_ab(a)
     x, _ = synth.mixture(a.seed, a.n, a.d, a.k, 1)
     xt = torch.from_numpy(x).cuda()
     if a.trace_run:
