@@ -908,6 +908,32 @@ LMI_API int lmi_knn(int device, const float *xq, int64_t nq, const float *xb, in
  * Not offered: one half array beside a binary32 one; halves in lmi_kmeans / lmi_train. */
 LMI_API int lmi_knn_f16(int device, const uint16_t *xq, int64_t nq, const uint16_t *xb, int64_t nb, int d, int k, int metric,
                         float *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
+/* Exact brute-force Hamming k-NN on bit-packed codes, deterministic: the ground truth of binary sketches and one-bit embeddings as
+ * they are distributed (the `hammingv2` kind of the SISAP LAION data: 1024-bit sketches), without unpacking them into floats.
+ * No handle (like lmi_knn): the work runs on the NULL stream of `device` and the call returns when D and I have landed.
+ *   codes        xq [nq][code_bytes] and xb [nb][code_bytes], rows contiguous; code_bytes a multiple of 4 in 4..512 (32 to 4096 bits).
+ *                Other lengths: pad every row, on both sides, with zero bytes -- equal bits add nothing to a distance.
+ *                on_device covers xq, xb, D [nq][k] and I [nq][k]: device pointers, xq and xb are only read; otherwise host pointers --
+ *                xb is uploaded in pieces and each piece is scanned against a group of queries, so the base is never resident as a
+ *                whole and the device memory of the call does not depend on nb, exactly as in lmi_knn.  xq and xb need 4-byte
+ *                alignment only (xb is read with 16-byte loads where code_bytes % 16 == 0 and the scanned base -- the call's piece
+ *                buffer with host pointers, the caller's pointer with on_device -- is 16-byte aligned, four bytes at a time otherwise).
+ *   distance     dist(q, x) = the number of bits in which the two codes differ, an integer in 0..8 * code_bytes.  Nothing is
+ *                rounded anywhere, so there is no chain order to state.
+ *   selection    the first k rows in the total order (distance ascending, row number ascending).  D holds the distances as int32,
+ *                ascending; I the row numbers.
+ *   padding      fewer than k rows pad with I = -1 and D = INT32_MAX; nb == 0 is all padding; nq == 0 writes nothing and succeeds.
+ *   geometry     the result does not depend on the pieces, the splits of a piece, the query groups, the tiles or the grid.
+ *                lmi_knn_set_geometry applies to this call too, and lmi_debug_knn_plan reports it as the last call on the thread:
+ *                the plan is the one lmi_knn makes for rows of code_bytes / 4 floats; VEC_XB reports whether the 16-byte loads ran.
+ * Refused, with nothing written: code_bytes outside 4..512 or not a multiple of 4; k outside 1..LMI_KNN_MAX_K; nq or nb < 0 or
+ * >= 2^31; a NULL pointer that is needed (xq, D, I when nq > 0; xb when nq > 0 and nb > 0); xq or xb not 4-byte aligned.  A failed
+ * allocation names the bytes it wanted; the call frees all it allocated.
+ * Peak device memory, with Q, Q', P, LR and splits as in lmi_knn and W = code_bytes / 4:  4 Q' roundup(P, 64) (scores: the negated
+ * distances as binary32, exact) + 8 Q splits LR (lists); with host pointers 4 Q W + 4 P W + 12 Q k more for the queries, the piece
+ * and the results.  There are no query fragments and no norms.  lmi_debug_knn_plan reports the sum. */
+LMI_API int lmi_knn_hamming(int device, const uint8_t *xq, int64_t nq, const uint8_t *xb, int64_t nb, int code_bytes, int k,
+                            int32_t *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
 /* Tuning / test hook: rows of xb per uploaded or scanned piece (< 2^31), base splits per piece (<= 1024; their partial lists are
  * merged afterwards), queries per group (<= 2^20).  0 = chosen by the library.  Thread-local, like lmi_last_error; never changes a
  * result. */
@@ -924,7 +950,7 @@ enum {
     LMI_KNN_PLAN_LIST_ROWS,        /* entries of a query's sorted list (LR above)                                            */
     LMI_KNN_PLAN_COUNT
 };
-/* What the last lmi_knn or lmi_knn_f16 on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
+/* What the last lmi_knn, lmi_knn_f16 or lmi_knn_hamming on this thread did (all zero before the first, after a refused call and after one with nq == 0); writes
  * min(n, LMI_KNN_PLAN_COUNT) words. */
 LMI_API int lmi_debug_knn_plan(int64_t *out, int n);
 

@@ -139,6 +139,8 @@ SIGNATURES = {
                                _vp, _vp, ctypes.c_int]),
     "lmi_knn_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    _vp, _vp, ctypes.c_int]),
+    "lmi_knn_hamming": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                       _vp, _vp, ctypes.c_int]),
     "lmi_knn_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "lmi_debug_knn_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_knn_range": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
@@ -1487,6 +1489,44 @@ def knn(xq, xb, k: int = 10, metric: str = "ip", device: int = 0):
     I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
     call = lib().lmi_knn_f16 if f16 else lib().lmi_knn
     _check(call(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, d, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
+    return D, I
+
+
+HAMMING_MAX_BYTES = 512   # the widest code of `knn_hamming` (lmi_knn_hamming): 4096 bits
+
+
+def knn_hamming(xq, xb, k: int = 10, device: int = 0):
+    """Exact brute-force Hamming k-NN on bit-packed codes (`lmi_knn_hamming`): (D int32[nq,k], I int64[nq,k]) -- per query the k rows
+    of `xb` that differ from it in the fewest bits, distance ascending, ties to the lower row; fewer than k rows pad with I = -1 and
+    D = the largest int32.  `xq` [nq, code_bytes], `xb` [nb, code_bytes]: uint8 numpy arrays -- `xb` is uploaded in pieces and never
+    resident as a whole -- or contiguous torch.uint8 tensors on one device, both of one kind; D and I then come back as tensors on
+    that device and the inputs are only read.  code_bytes: a multiple of 4 in [4, HAMMING_MAX_BYTES]; pad other lengths with zero
+    bytes on both sides.  `knn_set_geometry` and `knn_last_plan` serve this call too.  Argument errors raise ValueError before the
+    library is loaded."""
+    is_np = _array_arg("knn_hamming", "xq", xq, "uint8", "2d"), _array_arg("knn_hamming", "xb", xb, "uint8", "2d")
+    if is_np[0] != is_np[1]:
+        raise ValueError("knn_hamming: xq and xb must both be numpy arrays or both be torch tensors on the device")
+    nq, cb, nb, k = int(xq.shape[0]), int(xq.shape[1]), int(xb.shape[0]), int(k)
+    if int(xb.shape[1]) != cb:
+        raise ValueError(f"knn_hamming: xq has {cb} bytes per code, xb {int(xb.shape[1])}")
+    if cb < 4 or cb > HAMMING_MAX_BYTES or cb % 4:
+        raise ValueError(f"knn_hamming: code_bytes {cb} is not a multiple of 4 in [4, {HAMMING_MAX_BYTES}]")
+    if k < 1 or k > KNN_MAX_K:
+        raise ValueError(f"knn_hamming: k {k} outside [1, {KNN_MAX_K}]")
+    if is_np[0]:
+        # (a view that starts inside a word is copied: the library takes 4-byte aligned codes)
+        xq, xb = (a if a.ctypes.data % 4 == 0 else a.copy() for a in (np.ascontiguousarray(xq), np.ascontiguousarray(xb)))
+        D = np.empty((nq, k), dtype=np.int32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _check(lib().lmi_knn_hamming(int(device), _ptr(xq), nq, _ptr(xb), nb, cb, k, _ptr(D), _ptr(I), 0))
+        return D, I
+    if not (xq.is_cuda and xb.is_cuda and xq.is_contiguous() and xb.is_contiguous()) or xq.device != xb.device:
+        raise ValueError("knn_hamming: torch xq and xb must be contiguous tensors on one device")
+    import torch
+
+    D = torch.empty((nq, k), dtype=torch.int32, device=xq.device)
+    I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+    _check(lib().lmi_knn_hamming(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, cb, k, _ptr(D), _ptr(I), 1))
     return D, I
 
 

@@ -10,3 +10,7 @@ S=lmi_hip-hip-amdgcn-amd-amdhsa-gfx950.s
 awk '/^_ZN3lmi11scan_kernelENS_10ScanParamsE:/,/s_endpgm/' $S > scan.s
 grep -A12 "Function Name: _ZN3lmi11scan_kernel" usage.txt | grep -E "VGPRs:|Spill|Occupancy|LDS Size|SGPRs:" | sed 's/remark: [^ ]* //'
 echo "mfma $(grep -c v_mfma scan.s)  glds $(grep -c global_load_lds scan.s)  scratch $(grep -c scratch_ scan.s)  lines $(wc -l < scan.s)"
+# lmi_knn_hamming's score kernel (16-byte form): its inner loop is 256 xor + 256 bcnt per chunk of 8 words x 32 queries
+awk '/^_ZN3lmi20hamming_score_kernelILb1EEEvPKjxiS2_iiiPfx:/,/s_endpgm/' $S > hamming.s
+grep -A12 "Function Name: _ZN3lmi20hamming_score_kernelILb1" usage.txt | grep -E "VGPRs:|Spill|Occupancy|ScratchSize|SGPRs:" | sed 's/remark: [^ ]* //'
+echo "hamming: xor $(grep -c v_xor_b32 hamming.s)  bcnt $(grep -c v_bcnt_u32_b32 hamming.s)  s_load $(grep -c s_load_dword hamming.s)  scratch $(grep -c scratch_ hamming.s)  lines $(wc -l < hamming.s)"

@@ -46,6 +46,22 @@ class Baseline(Logger):
         dists = np.where(found, np.float32(1) - sims, np.float32(np.inf))
         return dists, np.where(found, rows + 1, 0), time.time() - t0
 
+    def search_hamming(self, queries, data, k: int = 10, device: int = 0):
+        """`search` on bit-packed codes under the Hamming distance (`lmi_knn_hamming`): (dists int32[nq,k], ids 1-based, seconds).
+        `queries`, `data`: uint8 arrays [n, code_bytes], or uint64 word arrays [n, words] as the challenge's `hammingv2` files hold
+        them -- viewed as bytes without a copy.  Fewer than k objects pad with ids = 0 and dists = the largest int32."""
+        if not 1 <= k <= self.MAX_K:
+            raise ValueError(f"Baseline.search_hamming: k must be in [1, {self.MAX_K}]")
+        codes = []
+        for name, a in (("queries", queries), ("data", data)):
+            a = np.asarray(a)
+            if a.dtype not in (np.uint8, np.uint64) or a.ndim != 2:
+                raise ValueError(f"Baseline.search_hamming: {name} must be a two-dimensional uint8 or uint64 array, not {a.dtype}{tuple(a.shape)}")
+            codes.append(np.ascontiguousarray(a).view(np.uint8))
+        t0 = time.time()
+        dists, rows = _capi.knn_hamming(codes[0], codes[1], k=k, device=device)
+        return dists, np.where(rows >= 0, rows + 1, 0), time.time() - t0
+
     def range_search(self, queries, data, radius, sort: bool = False, max_total: int = 0, device: int = 0):
         """Every object within cosine distance `radius` (a number, or one per query) of each query, by brute force (`lmi_knn_range`
         on unit rows, like `search`): (lims i64[nq + 1], dists f32[total], ids 1-based [total], seconds); query q owns

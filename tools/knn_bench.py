@@ -18,6 +18,19 @@ that flag runs only the device legs, once each after a warm-up, for a profiler t
 (checked on the warm-up); the legs of the two forms alternate, and the yardsticks (a) and (b) are left out.  Per pair of legs the
 table adds f16 / f32, and per form the host leg minus the device leg: the upload and the staging the host arrays cost.
 
+--hamming [--bits 1024]: the Hamming form (lmi_knn_hamming) on random codes generated on the device, --nb x --bits against --nq
+queries at k = --ks[0], device tensors, against the ways a user had before it, alternated in the same run:
+  (a) a torch expression on the device, chunked over the base to fit memory: the codes unpacked to +-1 halves and one half matmul per
+      chunk (dot = bits - 2 dist, exact: integers up to 4096 in a binary32 accumulator), or XOR and a SWAR bit count on int32 words
+      (a byte popcount table wants an int64 index per byte); both run on the warm-up and the faster is the leg; topk per chunk, merged
+  (b) `_capi.knn` with "l2" on the codes unpacked to float32 0/1, whose squared distance is the Hamming distance
+All legs' distances are compared exactly before a time is printed, and the row numbers of lmi_knn_hamming and (b), which share
+the tie rule (torch.topk has none).  Reported: median (min .. max), pairs/s, the call's device bytes (its plan) and, as a lower
+bound taken from the whole call, the rate against the vector ALU: the score kernel issues 2 operations per pair of 32-bit words, so
+2 * W * pairs / (CUs * 64 lanes * clock).  `--hamming --trace-run` runs only the HIP leg for `rocprofv3 --kernel-trace --stats`;
+`--hamming --kernel-stats FILE` reads that run's kernel_stats.csv and prints the score / select split and the same fraction from the
+score kernel's own time.
+
   python tools/knn_bench.py [--nb 1000000] [--d 768] [--nq 10000] [--ks 10 100 1024] [--reps 5] [--f16] [--out profiles/knn.txt]
 
 Prints a table and one JSON line; --out also writes both to a file.  No gate: the feature is the capability.  Not a yardstick:
@@ -61,8 +74,15 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the legs that upload from host arrays")
     ap.add_argument("--f16", action="store_true", help="lmi_knn_f16 on the rows narrowed once beside lmi_knn on the same values widened")
     ap.add_argument("--trace-run", action="store_true", help="only the device legs, once each (for a kernel trace)")
+    ap.add_argument("--hamming", action="store_true", help="lmi_knn_hamming on random codes against a torch expression and the unpacked lmi_knn")
+    ap.add_argument("--bits", type=int, default=1024, help="--hamming: bits per code (a multiple of 32)")
+    ap.add_argument("--torch-form", choices=["both", "matmul", "SWAR"], default="both",
+                    help="--hamming: the forms of leg (a) to run (the SWAR form takes seconds at 1M rows)")
+    ap.add_argument("--kernel-stats", default=None, help="--hamming: the kernel_stats.csv of a traced --trace-run, to print the split")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.hamming:
+        return main_hamming(a)
 
     import torch
 
@@ -206,6 +226,170 @@ def report_f16(a, legs, flop):
     print(text)
     if a.out:
         with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+TRACE_CALLS = 2   # what `--trace-run` runs of a leg: one warm-up and one timed call
+
+
+def valu_lanes_per_second():
+    """(lane operations per second of the vector ALUs, CUs, MHz): 4 SIMDs of 16 lanes per compute unit, at the peak engine clock the
+    runtime reports for the device (hipDeviceAttributeClockRate)."""
+    import ctypes
+
+    import torch
+
+    khz = ctypes.c_int(0)
+    err = ctypes.CDLL("libamdhip64.so").hipDeviceGetAttribute(ctypes.byref(khz), 5, 0)   # 5: hipDeviceAttributeClockRate, kHz
+    assert err == 0 and khz.value > 0, "hipDeviceGetAttribute(hipDeviceAttributeClockRate) failed"
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return cus * 64 * khz.value * 1e3, cus, khz.value / 1e3
+
+
+def hamming_torch_forms(dq, db, k, bits, chunk):
+    """Leg (a): {name: closure -> (D int32 [nq,k], I int64 [nq,k])}.  What a closure keeps resident beside the codes (the +-1 halves of
+    the base) is made here, outside every timed window."""
+    import torch
+
+    nq, nb, W = dq.shape[0], db.shape[0], bits // 32
+    shifts = torch.arange(8, device="cuda", dtype=torch.uint8)
+
+    def merged(parts, largest):
+        v, i = torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1)
+        tv, ti = torch.topk(v, min(k, v.shape[1]), dim=1, largest=largest)
+        return tv, torch.gather(i, 1, ti)
+
+    pm_b = torch.empty((nb, bits), device="cuda", dtype=torch.float16)
+    for c0 in range(0, nb, chunk):
+        pm_b[c0:c0 + chunk] = 1 - 2 * ((db[c0:c0 + chunk, :, None] >> shifts) & 1).reshape(-1, bits).to(torch.float16)
+
+    def matmul():
+        pm_q = 1 - 2 * ((dq[:, :, None] >> shifts) & 1).reshape(nq, bits).to(torch.float16)
+        parts = []
+        for c0 in range(0, nb, chunk):
+            v, i = torch.topk(pm_q @ pm_b[c0:c0 + chunk].T, min(k, nb - c0, chunk), dim=1, largest=True)
+            parts.append((v, i + c0))
+        v, i = merged(parts, True)
+        return ((bits - v.float()) / 2).to(torch.int32), i
+
+    q32, b32 = dq.view(torch.int32), db.view(torch.int32)
+
+    def swar():
+        rows = []
+        for q0 in range(0, nq, 256):
+            parts = []
+            for c0 in range(0, nb, chunk // 8):
+                v = q32[q0:q0 + 256, None, :] ^ b32[None, c0:c0 + chunk // 8, :]
+                v = v - ((v >> 1) & 0x55555555)
+                v = (v & 0x33333333) + ((v >> 2) & 0x33333333)
+                v = (((v + (v >> 4)) & 0x0F0F0F0F) * 0x01010101) >> 24
+                tv, ti = torch.topk(v.sum(-1, dtype=torch.int32), min(k, nb - c0, chunk // 8), dim=1, largest=False)
+                parts.append((tv, ti + c0))
+            rows.append(merged(parts, False))
+        return torch.cat([r[0] for r in rows]), torch.cat([r[1] for r in rows])
+
+    return {"(a) torch: +-1 halves, matmul, topk": matmul, "(a) torch: xor, SWAR bit count, topk": swar}
+
+
+def hamming_split(a):
+    """--kernel-stats: the score / select split of a traced `--hamming --trace-run`, and the score kernel's rate against the vector ALU."""
+    import csv
+
+    W, pairs = a.bits // 32, float(a.nq) * a.nb
+    with open(a.kernel_stats) as fh:
+        rows = [r for r in csv.DictReader(fh)]
+    ns = {}
+    for key in ("hamming_score_kernel", "knn_select_kernel", "knn_merge_hamming_kernel", "knn_fill_kernel"):
+        ns[key] = sum(float(r["TotalDurationNs"]) for r in rows if key in r["Name"]) / TRACE_CALLS
+    total = sum(ns.values())
+    lanes, cus, mhz = valu_lanes_per_second()
+    lines = [f"# tools/knn_bench.py --hamming --kernel-stats: base {a.nb} x {a.bits} bits, {a.nq} queries, k = {a.ks[0]}; kernel time per call, from {TRACE_CALLS} traced calls"]
+    for key, v in ns.items():
+        lines.append(f"{key:28s} | {v / 1e6:9.2f} ms | {v / total:6.1%}")
+    score_s = ns["hamming_score_kernel"] / 1e9
+    lines.append(f"# score kernel: {pairs / score_s:.3e} pairs/s; 2 * W * pairs = {2 * W * pairs:.3e} lane operations over {score_s * 1e3:.2f} ms = "
+                 f"{2 * W * pairs / score_s / lanes:.1%} of {cus} CUs x 64 lanes x {mhz:.0f} MHz (derived, not measured: 2 operations per word pair)")
+    lines.append(f"# slab traffic: {8 * pairs:.3e} bytes written by the score and read by the selection")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+
+
+def main_hamming(a):
+    import torch
+
+    if a.kernel_stats:
+        return hamming_split(a)
+    assert a.bits % 32 == 0 and 32 <= a.bits <= 4096
+    cb, W, k, pairs = a.bits // 8, a.bits // 32, a.ks[0], float(a.nq) * a.nb
+    gen = torch.Generator(device="cuda").manual_seed(a.seed)
+    db = torch.randint(0, 256, (a.nb, cb), generator=gen, device="cuda", dtype=torch.uint8)
+    dq = torch.randint(0, 256, (a.nq, cb), generator=gen, device="cuda", dtype=torch.uint8)
+    hip = "knn_hamming device"
+    legs = {hip: lambda: _capi.knn_hamming(dq, db, k)}
+    if a.trace_run:
+        legs[hip]()
+        _, ms = wall(legs[hip])
+        print(f"{hip}: {ms:.1f} ms   plan {_capi.knn_last_plan()}", flush=True)
+        return
+    chunk = 131072
+    forms = hamming_torch_forms(dq, db, k, a.bits, chunk)
+    if a.torch_form != "both":
+        forms = {n: f for n, f in forms.items() if a.torch_form in n}
+    shifts = torch.arange(8, device="cuda", dtype=torch.uint8)
+    fb = torch.empty((a.nb, a.bits), device="cuda", dtype=torch.float32)
+    for c0 in range(0, a.nb, chunk):
+        fb[c0:c0 + chunk] = ((db[c0:c0 + chunk, :, None] >> shifts) & 1).reshape(-1, a.bits).to(torch.float32)
+    fq = ((dq[:, :, None] >> shifts) & 1).reshape(a.nq, a.bits).to(torch.float32)
+    b = "(b) knn l2 on the codes unpacked to float32"
+
+    def knn_l2():
+        D, I = _capi.knn(fq, fb, k, "l2")
+        return D.to(torch.int32), I
+
+    # warm-up: every leg once; the results must agree before any time is printed; the faster form of (a) is its leg
+    first, warm = {}, {}
+    for name, fn in {**legs, **forms, b: knn_l2}.items():
+        first[name], warm[name] = wall(fn)
+        if name in forms:   # (the first call of a form also loads its kernels; the second one is what picks the leg)
+            warm[name] = wall(fn)[1]
+    legs[hip]()   # (the last knn call was (b)'s)
+    plan = _capi.knn_last_plan()
+    D0, I0 = first[hip]
+    for name, (D, I) in first.items():
+        assert torch.equal(D, D0), f"{name}: distances differ from {hip}"
+    assert torch.equal(first[b][1], I0), f"{b}: row numbers differ from {hip}"
+    ta = min(forms, key=lambda n: warm[n])
+    legs[ta], legs[b] = forms[ta], knn_l2
+    del first
+    times = {name: [] for name in legs}
+    for _ in range(a.reps):
+        for name, fn in legs.items():
+            _, ms = wall(fn)
+            times[name].append(ms)
+    med = {n: statistics.median(v) for n, v in times.items()}
+    lanes, cus, mhz = valu_lanes_per_second()
+    lines = [f"# tools/knn_bench.py --hamming: base {a.nb} x {a.bits} bits, {a.nq} queries, k = {k}, device tensors; {a.reps} timed runs per leg after one warm-up, legs alternated",
+             f"# library: {_capi.lib().lmi_build_info().decode()}",
+             f"# device: {torch.cuda.get_device_name(0)}; pairs = nq * nb = {pairs:.3e}",
+             "# the distances of all legs are equal, and the row numbers of knn_hamming and (b) (torch.topk has no tie order)",
+             "# second warm-up call of (a)'s forms: " + ", ".join(f"{n}: {warm[n]:.1f} ms" for n in forms) + "; what (a) and (b) keep unpacked is made outside the windows",
+             "# leg | ms median (min .. max) | pairs/s"]
+    for n, v in times.items():
+        lines.append(f"{n:44s} | {med[n]:9.2f} ({min(v):.2f} .. {max(v):.2f}) | {pairs / med[n] * 1e3:.3e}")
+    lines.append(f"# {hip} / {ta}: {med[hip] / med[ta]:.3f};  / {b}: {med[hip] / med[b]:.3f}")
+    lines.append(f"# vector ALU, whole call (a lower bound of the score kernel's share): 2 * W * pairs = {2 * W * pairs:.3e} lane operations / "
+                 f"{med[hip]:.2f} ms = {2 * W * pairs / med[hip] * 1e3 / lanes:.1%} of {cus} CUs x 64 lanes x {mhz:.0f} MHz")
+    lines.append(f"# device bytes of the call beside the codes ({(a.nb + a.nq) * cb} bytes): {plan['WORKSPACE_BYTES']}; plan {plan}")
+    result = {"hamming": True, "nb": a.nb, "bits": a.bits, "nq": a.nq, "k": k, "median_ms": med, "hip_over_torch": med[hip] / med[ta],
+              "hip_over_knn_l2": med[hip] / med[b], "workspace_bytes": plan["WORKSPACE_BYTES"]}
+    lines.append(json.dumps(result))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
             fh.write(text + "\n")
 
 
