@@ -934,6 +934,42 @@ LMI_API int lmi_knn_f16(int device, const uint16_t *xq, int64_t nq, const uint16
  * and the results.  There are no query fragments and no norms.  lmi_debug_knn_plan reports the sum. */
 LMI_API int lmi_knn_hamming(int device, const uint8_t *xq, int64_t nq, const uint8_t *xb, int64_t nb, int code_bytes, int k,
                             int32_t *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
+/* Exact re-ranking of candidate lists: for query q the exact top k among the rows cand[q][0 .. c) of xb -- the second half of a
+ * filter (lmi_knn_hamming on sketches, lmi_knn on projected vectors, any outside generator): the rows the filter lets through are
+ * scored on the real vectors and cut down to the true k, in lmi_knn's arithmetic and order.
+ * No handle (like lmi_knn): the work runs on the NULL stream of `device` and the call returns when D and I have landed.
+ *   pointers     on_device covers xq [nq][d], xb [nb][d], cand [nq][c], D [nq][k] and I [nq][k]: device pointers, the inputs are only
+ *                read, and only the candidate rows of xb are touched.  Otherwise host pointers: xb goes up in pieces and is never
+ *                resident, as in lmi_knn, and each piece scores the candidates whose rows it holds -- the WHOLE base is uploaded to
+ *                score a few rows of it; that is the price of host pointers.  xq and xb need 4-byte alignment, cand 8-byte (rows are
+ *                read with 16-byte loads where d % 4 == 0 and the scanned base -- the call's piece buffer with host pointers, the
+ *                caller's pointer with on_device -- is 16-byte aligned, element by element otherwise).
+ *   candidates   cand[q][j] is a row number of xb, or -1 for "no candidate": the padding lmi_knn and lmi_knn_hamming write, so their I
+ *                can be handed over as it is.  c in 1..LMI_KNN_MAX_K, k in 1..c.  A list need not be sorted.  A row that occurs twice
+ *                in a list is two entries of the result: nothing is de-duplicated.
+ *   arithmetic   lmi_knn's, word for word: s = the chain acc = fmaf(q[t], x[t], acc) from +0, t = 0..d-1, never split; L2: xn and qn
+ *                by the same chain, key = fmaf(1.0f, -0.5f * xn, s), D = fmaf(-2.0f, key, qn).  Where d (L2: d + 1) is no multiple of
+ *                32 the chain is closed by one link fmaf(+0, +0, acc), which is what lmi_knn's padding does to a score of -0.
+ *   selection    the first k entries in the total order (score descending, row number ascending; -0 == +0) among the entries whose
+ *                score is > -FLT_MAX.  D is descending for IP and ascending for L2.
+ *   padding      fewer than k admissible entries pad with I = -1 and D = -FLT_MAX (L2: FLT_MAX); nb == 0 or a list of only -1 is all
+ *                padding; nq == 0 writes nothing and succeeds.
+ *   property     if the set {cand[q][*]} holds the true top k of lmi_knn(xq, xb, k, metric), D and I equal that call's bit for bit;
+ *                in general they equal lmi_knn on the base restricted to the candidate rows, row numbers mapped back.  The result
+ *                does not depend on the pieces, the query groups, the tiles or the grid; nothing is added atomically.
+ *   geometry     lmi_knn_set_geometry's piece_rows and query_rows apply (splits is ignored); with device pointers the base is one
+ *                piece unless piece_rows is forced.  lmi_debug_knn_plan reports the call as the last on the thread: SPLITS = 1,
+ *                VEC_XQ = 0, VEC_XB = whether the 16-byte row loads ran, LIST_ROWS = LR below.
+ * Refused, with nothing written: d outside 1..4096; c outside 1..LMI_KNN_MAX_K; k outside 1..c; nq or nb < 0 or >= 2^31; an unknown
+ * metric; a NULL pointer that is needed (xq, cand, D, I when nq > 0; xb when nq > 0 and nb > 0); xq or xb not 4-byte aligned; cand
+ * not 8-byte aligned; any candidate outside [-1, nb) -- one pass over cand before anything is scored counts them and the message
+ * names the count.  A failed allocation names the bytes it wanted; the call frees all it allocated.
+ * Peak device memory, with Q = queries per group and P = rows per piece as in lmi_knn and LR = max(128, c rounded up to a power of
+ * two):  8 Q LR (lists) + 4 Q (qn); with device pointers 8 more (the candidate check's counter), with host pointers 4 Q d + 4 P d +
+ * 8 Q c + 12 Q k more for the queries, the piece, the candidates and the results.  lmi_debug_knn_plan reports the sum. */
+LMI_API int lmi_knn_rerank(int device, const float *xq, int64_t nq, const float *xb, int64_t nb, int d,
+                           const int64_t *cand /* [nq][c] */, int c, int k, int metric,
+                           float *D /* [nq][k] */, int64_t *I /* [nq][k] */, int on_device);
 /* Tuning / test hook: rows of xb per uploaded or scanned piece (< 2^31), base splits per piece (<= 1024; their partial lists are
  * merged afterwards), queries per group (<= 2^20).  0 = chosen by the library.  Thread-local, like lmi_last_error; never changes a
  * result. */

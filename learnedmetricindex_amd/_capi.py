@@ -141,6 +141,8 @@ SIGNATURES = {
                                    _vp, _vp, ctypes.c_int]),
     "lmi_knn_hamming": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                        _vp, _vp, ctypes.c_int]),
+    "lmi_knn_rerank": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_knn_set_geometry": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "lmi_debug_knn_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_knn_range": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
@@ -1527,6 +1529,48 @@ def knn_hamming(xq, xb, k: int = 10, device: int = 0):
     D = torch.empty((nq, k), dtype=torch.int32, device=xq.device)
     I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
     _check(lib().lmi_knn_hamming(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, cb, k, _ptr(D), _ptr(I), 1))
+    return D, I
+
+
+def knn_rerank(xq, xb, cand, k: int, metric: str = "ip", device: int = 0):
+    """Exact re-ranking of candidate lists (`lmi_knn_rerank`): (D f32[nq,k], I i64[nq,k]) -- per query the exact top k among the rows
+    `cand[q]` of `xb`, in `knn`'s arithmetic and order: where the candidates hold the true top k, the result is `knn`'s bit for bit.
+    `cand`: int64 [nq, c], c <= KNN_MAX_K, row numbers of `xb` or -1 for "no candidate" -- the `I` of `knn` or `knn_hamming` as it is;
+    unsorted lists are fine, a row listed twice comes back twice; k <= c.  `xq`, `xb` float32: all three numpy arrays (then ALL of
+    `xb` is uploaded, in pieces) or all contiguous torch tensors on one device, where only the candidate rows are read and D and I
+    come back as tensors.  Fewer than k admissible candidates pad with I = -1 and D = -FLT_MAX (l2: FLT_MAX).  `knn_set_geometry`
+    and `knn_last_plan` serve this call too.  Argument errors raise ValueError before the library is loaded."""
+    who = "knn_rerank"
+    is_np = (_array_arg(who, "xq", xq, "float32", "2d"), _array_arg(who, "xb", xb, "float32", "2d"),
+             _array_arg(who, "cand", cand, "int64", "2d"))
+    if len(set(is_np)) != 1:
+        raise ValueError(f"{who}: xq, xb and cand must all be numpy arrays or all be torch tensors on the device")
+    if metric not in KNN_METRICS:
+        raise ValueError(f"{who}: metric {metric!r} unknown ('ip' or 'l2')")
+    nq, d, nb, c, k = int(xq.shape[0]), int(xq.shape[1]), int(xb.shape[0]), int(cand.shape[1]), int(k)
+    if int(xb.shape[1]) != d:
+        raise ValueError(f"{who}: xq has {d} columns, xb {int(xb.shape[1])}")
+    if d < 1 or d > 4096:
+        raise ValueError(f"{who}: d {d} outside [1, 4096]")
+    if int(cand.shape[0]) != nq:
+        raise ValueError(f"{who}: cand has {int(cand.shape[0])} lists for {nq} queries")
+    if c < 1 or c > KNN_MAX_K:
+        raise ValueError(f"{who}: c {c} candidates per query outside [1, {KNN_MAX_K}]")
+    if k < 1 or k > c:
+        raise ValueError(f"{who}: k {k} outside [1, c = {c}]")
+    if is_np[0]:
+        xq, xb, cand = np.ascontiguousarray(xq), np.ascontiguousarray(xb), np.ascontiguousarray(cand)
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _check(lib().lmi_knn_rerank(int(device), _ptr(xq), nq, _ptr(xb), nb, d, _ptr(cand), c, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 0))
+        return D, I
+    if not all(t.is_cuda and t.is_contiguous() and t.device == xq.device for t in (xq, xb, cand)):
+        raise ValueError(f"{who}: torch xq, xb and cand must be contiguous tensors on one device")
+    import torch
+
+    D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
+    I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+    _check(lib().lmi_knn_rerank(_sync_device(xq), _ptr(xq), nq, _ptr(xb), nb, d, _ptr(cand), c, k, KNN_METRICS[metric], _ptr(D), _ptr(I), 1))
     return D, I
 
 

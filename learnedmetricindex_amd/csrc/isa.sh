@@ -14,3 +14,11 @@ echo "mfma $(grep -c v_mfma scan.s)  glds $(grep -c global_load_lds scan.s)  scr
 awk '/^_ZN3lmi20hamming_score_kernelILb1EEEvPKjxiS2_iiiPfx:/,/s_endpgm/' $S > hamming.s
 grep -A12 "Function Name: _ZN3lmi20hamming_score_kernelILb1" usage.txt | grep -E "VGPRs:|Spill|Occupancy|ScratchSize|SGPRs:" | sed 's/remark: [^ ]* //'
 echo "hamming: xor $(grep -c v_xor_b32 hamming.s)  bcnt $(grep -c v_bcnt_u32_b32 hamming.s)  s_load $(grep -c s_load_dword hamming.s)  scratch $(grep -c scratch_ hamming.s)  lines $(wc -l < hamming.s)"
+# lmi_knn_rerank's score kernel (16-byte form; IP, then L2): per chunk of 32 words the 32 links in ascending order -- IP: one v_fma_f32
+# and 31 v_fmac_f32 (+ 1 in the loop of the last, partial chunk), the query operand of each an SGPR; L2: 32 v_pk_fma_f32, the links of
+# s and xn of one element side by side; the 8 global_load_dwordx4 of the next chunk before them; no scratch
+for m in 0 1; do
+  awk "/^_ZN3lmi19rerank_score_kernelILb1ELb${m}EEE[^:]*:/,/s_endpgm/" $S > rerank$m.s
+  grep -A12 "Function Name: _ZN3lmi19rerank_score_kernelILb1ELb${m}EEE" usage.txt | grep -E "VGPRs:|Spill|Occupancy|ScratchSize|LDS Size|SGPRs:" | sed 's/remark: [^ ]* //'
+  echo "rerank L2=$m: fmac $(grep -c v_fmac_f32 rerank$m.s)  of them with an SGPR $(grep -cE 'v_fmac_f32(_e32)? v[0-9]+, s[0-9]+' rerank$m.s)  pk_fma $(grep -c v_pk_fma_f32 rerank$m.s)  v_fma/mul/add_f32 $(grep -cE 'v_(fma|mul|add)_f32' rerank$m.s)  dwordx4 $(grep -c global_load_dwordx4 rerank$m.s)  s_load $(grep -c s_load_dword rerank$m.s)  scratch $(grep -c scratch_ rerank$m.s)  lines $(wc -l < rerank$m.s)"
+done

@@ -22,6 +22,8 @@
 #include "lmi_host_knn.h"     // lmi_knn, lmi_knn_set_geometry, lmi_debug_knn_plan
 #include "lmi_knn_hamming.h"       // the kernels of lmi_knn_hamming: XOR / bit-count scores, the integer merge
 #include "lmi_host_knn_hamming.h"  // lmi_knn_hamming
+#include "lmi_knn_rerank.h"        // the kernels of lmi_knn_rerank: the gathered chain scores, the list sort
+#include "lmi_host_knn_rerank.h"   // lmi_knn_rerank
 #include "lmi_union.h"        // the kernels of the union scan
 #include "lmi_filter.h"       // the kernels of the filter sets and the masked select of the filtered union scan
 #include "lmi_host_candidates.h"   // the candidate stage of the union scan and the range search: plan, tables, buffers, pack and score

@@ -62,6 +62,37 @@ class Baseline(Logger):
         dists, rows = _capi.knn_hamming(codes[0], codes[1], k=k, device=device)
         return dists, np.where(rows >= 0, rows + 1, 0), time.time() - t0
 
+    def rerank(self, queries, data, candidates, k: int = 10, device: int = 0):
+        """`search` restricted to per-query candidate lists (`lmi_knn_rerank` on the unit rows): (dists, ids 1-based, seconds).
+        `candidates`: integer ids [nq, c], 1-based with 0 for "none", as `search` and `search_hamming` return them; c <= MAX_K,
+        k <= c.  Where a list holds the true k nearest objects the result is `search`'s."""
+        cand = np.asarray(candidates)
+        if cand.ndim != 2 or cand.dtype.kind not in "iu":
+            raise ValueError(f"Baseline.rerank: candidates must be a two-dimensional integer array, not {cand.dtype}{tuple(cand.shape)}")
+        if not 1 <= cand.shape[1] <= self.MAX_K or not 1 <= k <= cand.shape[1]:
+            raise ValueError(f"Baseline.rerank: c = {cand.shape[1]} must be in [1, {self.MAX_K}] and k = {k} in [1, c]")
+        if np.ndim(queries) != 2 or np.ndim(data) != 2 or np.shape(queries)[0] != cand.shape[0] or np.shape(queries)[1] != np.shape(data)[1]:
+            raise ValueError(f"Baseline.rerank: queries {np.shape(queries)}, data {np.shape(data)} and candidates {cand.shape} do not fit")
+        t0 = time.time()
+        sims, rows = _capi.knn_rerank(_unit(queries), _unit(data), cand.astype(np.int64) - 1, k, metric="ip", device=device)
+        found = rows >= 0
+        dists = np.where(found, np.float32(1) - sims, np.float32(np.inf))
+        return dists, np.where(found, rows + 1, 0), time.time() - t0
+
+    def search_sketch(self, queries, data, query_codes, data_codes, k: int = 10, n_candidates: int = 1024, device: int = 0):
+        """The sketch-filter baseline, two stages on the device: `search_hamming(query_codes, data_codes, k=n_candidates)`, then
+        `rerank` of those candidates on the vectors: (dists, ids 1-based, seconds) in `search`'s shape.  There is no CPU path."""
+        if not 1 <= n_candidates <= self.MAX_K or not 1 <= k <= n_candidates:
+            raise ValueError(f"Baseline.search_sketch: n_candidates = {n_candidates} must be in [1, {self.MAX_K}] and k = {k} in [1, n_candidates]")
+        if np.ndim(queries) != 2 or np.ndim(data) != 2 or np.shape(queries)[1] != np.shape(data)[1]:
+            raise ValueError(f"Baseline.search_sketch: queries {np.shape(queries)} and data {np.shape(data)} do not fit")
+        if len(query_codes) != len(queries) or len(data_codes) != len(data):
+            raise ValueError("Baseline.search_sketch: one code per query and one per object")
+        t0 = time.time()
+        _, cand, _ = self.search_hamming(query_codes, data_codes, k=n_candidates, device=device)
+        dists, ids, _ = self.rerank(queries, data, cand, k=k, device=device)
+        return dists, ids, time.time() - t0
+
     def range_search(self, queries, data, radius, sort: bool = False, max_total: int = 0, device: int = 0):
         """Every object within cosine distance `radius` (a number, or one per query) of each query, by brute force (`lmi_knn_range`
         on unit rows, like `search`): (lims i64[nq + 1], dists f32[total], ids 1-based [total], seconds); query q owns

@@ -31,6 +31,10 @@ bound taken from the whole call, the rate against the vector ALU: the score kern
 `--hamming --kernel-stats FILE` reads that run's kernel_stats.csv and prints the score / select split and the same fraction from the
 score kernel's own time.
 
+--rerank [--cands 1024] [--bits 1024]: the re-ranking call (lmi_knn_rerank) as the second stage of a sketch filter; main_rerank states
+the legs and the checks.  `--rerank --trace-run` and `--rerank --kernel-stats FILE` work as for --hamming and print the kernels' split
+and the score kernel's gather rate, nq * c * d * 4 bytes over its own time.
+
   python tools/knn_bench.py [--nb 1000000] [--d 768] [--nq 10000] [--ks 10 100 1024] [--reps 5] [--f16] [--out profiles/knn.txt]
 
 Prints a table and one JSON line; --out also writes both to a file.  No gate: the feature is the capability.  Not a yardstick:
@@ -79,10 +83,14 @@ def main():
     ap.add_argument("--torch-form", choices=["both", "matmul", "SWAR"], default="both",
                     help="--hamming: the forms of leg (a) to run (the SWAR form takes seconds at 1M rows)")
     ap.add_argument("--kernel-stats", default=None, help="--hamming: the kernel_stats.csv of a traced --trace-run, to print the split")
+    ap.add_argument("--rerank", action="store_true", help="lmi_knn_rerank behind a sketch filter against a torch gather + bmm and the whole-base lmi_knn")
+    ap.add_argument("--cands", type=int, default=1024, help="--rerank: candidates per query")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.hamming:
         return main_hamming(a)
+    if a.rerank:
+        return main_rerank(a)
 
     import torch
 
@@ -385,6 +393,115 @@ def main_hamming(a):
     lines.append(f"# device bytes of the call beside the codes ({(a.nb + a.nq) * cb} bytes): {plan['WORKSPACE_BYTES']}; plan {plan}")
     result = {"hamming": True, "nb": a.nb, "bits": a.bits, "nq": a.nq, "k": k, "median_ms": med, "hip_over_torch": med[hip] / med[ta],
               "hip_over_knn_l2": med[hip] / med[b], "workspace_bytes": plan["WORKSPACE_BYTES"]}
+    lines.append(json.dumps(result))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+
+
+RERANK_KERNELS = ("rerank_score_kernel", "rerank_sort_kernel", "rerank_qnorm_kernel", "rerank_check_kernel", "knn_fill_kernel")
+
+
+def rerank_split(a):
+    """--rerank --kernel-stats: the kernels' split of a traced `--rerank --trace-run`, and the score kernel's gather rate."""
+    import csv
+
+    with open(a.kernel_stats) as fh:
+        rows = [r for r in csv.DictReader(fh)]
+    ns = {key: sum(float(r["TotalDurationNs"]) for r in rows if key in r["Name"]) / TRACE_CALLS for key in RERANK_KERNELS}
+    total, gathered = sum(ns.values()), 4.0 * a.nq * a.cands * a.d
+    lines = [f"# tools/knn_bench.py --rerank --kernel-stats: base {a.nb} x {a.d}, {a.nq} queries, c = {a.cands}, k = {a.ks[0]}; kernel time per call, from {TRACE_CALLS} traced calls"]
+    lines += [f"{key:28s} | {v / 1e6:9.2f} ms | {v / total:6.1%}" for key, v in ns.items()]
+    lines.append("# knn_fill_kernel also holds the fills of the one knn_hamming call that makes the candidates in the traced process")
+    lines.append(f"# score kernel: nq * c * d * 4 = {gathered:.3e} bytes gathered in {ns['rerank_score_kernel'] / 1e6:.2f} ms = "
+                 f"{gathered / ns['rerank_score_kernel']:.1f} GB/s")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+
+
+def main_rerank(a):
+    """--rerank: lmi_knn_rerank behind a sketch filter.  Codes: the sign bits of a random projection to --bits, packed; stage 1 is
+    knn_hamming's top c = --cands; stage 2 the legs (a) knn_rerank, (b) a torch gather + bmm + topk in chunks of queries, (c) knn over
+    the whole base.  Before any time is printed: (a) on knn's own shuffled top c equals knn bit for bit; (b) sums in another order, so
+    bit equality with (a) cannot be asked of it: its scores must agree to 1e-4 and at least 99.9 % of its row numbers must be equal
+    (a rounding difference of about d * 2^-24 * |s| swaps two neighbours only where their scores are that close: far rarer)."""
+    import torch
+
+    if a.kernel_stats:
+        return rerank_split(a)
+    k, c, metric = a.ks[0], a.cands, "ip"
+    gen = torch.Generator(device="cuda").manual_seed(a.seed)
+    db = torch.randn((a.nb, a.d), generator=gen, device="cuda", dtype=torch.float32)
+    dq = torch.randn((a.nq, a.d), generator=gen, device="cuda", dtype=torch.float32)
+    proj = torch.randn((a.d, a.bits), generator=gen, device="cuda", dtype=torch.float32)
+    weights = (1 << torch.arange(8, device="cuda")).to(torch.uint8)
+
+    def codes(x):
+        out = torch.empty((x.shape[0], a.bits // 8), device="cuda", dtype=torch.uint8)
+        for r0 in range(0, x.shape[0], 131072):
+            bits = (x[r0:r0 + 131072] @ proj > 0).reshape(-1, a.bits // 8, 8).to(torch.uint8)
+            out[r0:r0 + 131072] = (bits * weights).sum(2, dtype=torch.uint8)
+        return out
+
+    cb, cq = codes(db), codes(dq)
+    stage1 = "stage 1: knn_hamming top c"
+    hip, tb, full = "(a) knn_rerank device", "(b) torch gather + bmm + topk", "(c) knn over the whole base"
+    cand = _capi.knn_hamming(cq, cb, c)[1]
+    chunk = max(1, (1 << 30) // (4 * c * a.d))   # 1 GiB of gathered rows at a time
+
+    def torch_leg():
+        D, I = torch.empty((a.nq, k), device="cuda"), torch.empty((a.nq, k), device="cuda", dtype=torch.int64)
+        for q0 in range(0, a.nq, chunk):
+            cd = cand[q0:q0 + chunk].clamp_min(0)
+            s = torch.bmm(db[cd], dq[q0:q0 + chunk, :, None]).squeeze(2)
+            D[q0:q0 + chunk], pos = s.topk(k, dim=1)
+            I[q0:q0 + chunk] = cd.gather(1, pos)
+        return D, I
+
+    legs = {stage1: lambda: _capi.knn_hamming(cq, cb, c), hip: lambda: _capi.knn_rerank(dq, db, cand, k, metric)}
+    if a.trace_run:
+        legs[hip]()
+        _, ms = wall(legs[hip])
+        print(f"{hip}: {ms:.1f} ms   plan {_capi.knn_last_plan()}", flush=True)
+        return
+    legs.update({tb: torch_leg, full: lambda: _capi.knn(dq, db, k, metric)})
+    first = {name: wall(fn)[0] for name, fn in legs.items()}
+    top = _capi.knn(dq, db, c, metric)[1]
+    top = top.gather(1, torch.rand(top.shape, generator=gen, device="cuda").argsort(1))
+    D, I = _capi.knn_rerank(dq, db, top, k, metric)
+    assert torch.equal(D.view(torch.int32), first[full][0].view(torch.int32)) and torch.equal(I, first[full][1]), \
+        "knn_rerank on knn's shuffled top c differs from knn"
+    assert torch.allclose(first[tb][0], first[hip][0], rtol=1e-4, atol=1e-4), f"{tb}: scores differ from {hip}"
+    same_ids = (first[tb][1] == first[hip][1]).float().mean().item()
+    assert same_ids >= 0.999, f"{tb}: only {same_ids:.4%} of the row numbers equal {hip}'s"
+    recall = (first[hip][1][:, :, None] == first[full][1][:, None, :]).any(2).float().mean().item()
+    legs[hip]()
+    plan = _capi.knn_last_plan()
+    del first, top
+    times = {name: [] for name in legs}
+    for _ in range(a.reps):
+        for name, fn in legs.items():
+            times[name].append(wall(fn)[1])
+    med = {n: statistics.median(v) for n, v in times.items()}
+    gathered = 4.0 * a.nq * c * a.d
+    lines = [f"# tools/knn_bench.py --rerank: base {a.nb} x {a.d}, {a.nq} queries, sketches of {a.bits} bits (sign bits of a random projection), "
+             f"c = {c}, k = {k}, {metric}, device tensors; {a.reps} timed runs per leg after one warm-up, legs alternated",
+             f"# library: {_capi.lib().lmi_build_info().decode()}",
+             f"# device: {torch.cuda.get_device_name(0)}",
+             f"# checked first: knn_rerank on knn's shuffled top {c} == knn bit for bit; (b)'s scores within 1e-4 of (a)'s, {same_ids:.4%} of its row numbers equal",
+             "# leg | ms median (min .. max)"]
+    lines += [f"{n:36s} | {med[n]:9.2f} ({min(v):.2f} .. {max(v):.2f})" for n, v in times.items()]
+    lines.append(f"# (a) / (b): {med[hip] / med[tb]:.3f};  two stages / (c): {(med[stage1] + med[hip]) / med[full]:.3f};  "
+                 f"stage 1 : stage 2 = {med[stage1]:.2f} : {med[hip]:.2f} ms;  recall@{k} of the two stages against (c): {recall:.4f}")
+    lines.append(f"# gather, whole call (a lower bound of the score kernel's rate): nq * c * d * 4 = {gathered:.3e} bytes / {med[hip]:.2f} ms = "
+                 f"{gathered / med[hip] / 1e6:.1f} GB/s;  device bytes of the call: {plan['WORKSPACE_BYTES']}; plan {plan}")
+    result = {"rerank": True, "nb": a.nb, "d": a.d, "nq": a.nq, "c": c, "k": k, "bits": a.bits, "median_ms": med, "recall": recall,
+              "hip_over_torch": med[hip] / med[tb], "gather_GBps_whole_call": gathered / med[hip] / 1e6}
     lines.append(json.dumps(result))
     text = "\n".join(lines)
     print(text)
