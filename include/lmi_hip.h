@@ -737,6 +737,31 @@ LMI_API int lmi_project(int device, const float *x, int64_t n, int d, const floa
 LMI_API int lmi_project_f16(int device, const uint16_t *x, int64_t n, int d, const float *mean /* [d], nullable */,
                             const float *basis /* [m][d] */, int m, float *y /* [n][m] out */, int on_device);
 
+/* Hamming sketches on the device, deterministic: the signs of a projection against per-bit thresholds, bit-packed -- the first stage of
+ * the sketch filter (lmi_knn_hamming on the codes, lmi_knn_rerank on the vectors).
+ * Bit j of row i is 1 exactly when y[i][j] > thresh[j] in binary32, where y[i][j] is the value lmi_project writes for the same x, mean
+ * and basis: one unsplit chain acc = fmaf(c[i][t], basis[j][t], acc) from +0, t = 0..d-1, c = x - mean with one rounding (a NULL mean
+ * gives c = x).  A NULL thresh is +0 for every bit.  The comparison is the ordered one: a NaN on either side gives 0, and -0 > +0 is 0.
+ * Bit j lies in byte j >> 3 at bit j & 7 (np.packbits(.., bitorder="little")): the bytes lmi_knn_hamming reads, and a hammingv2 uint64
+ * word viewed as bytes on a little-endian host.  y itself is never stored: the comparison happens on the accumulators.
+ * The result does not depend on the grid, the tile grouping, the pieces or the kind of pointer.
+ * No handle; the NULL stream of `device`.  on_device covers x [n][d], mean [d], basis [m][d], thresh [m] and codes [n][m / 8]: device
+ * pointers, the inputs are only read (x with 16-byte loads where d % 4 == 0 and its base is 16-byte aligned), codes 4-byte aligned
+ * (16-byte stores where m % 128 == 0 and its base is 16-byte aligned); otherwise host pointers -- x goes up in pieces of at most
+ * 64 MiB and is never resident as a whole, the codes come back piece by piece: the device memory of the call does not depend on n.
+ * Refused, with nothing written: n < 1 or >= 2^31, d outside 1..4096, m not a multiple of 32 in 32..4096 (lmi_knn_hamming's range, not
+ * LMI_PROJECT_MAX_M), NULL x / basis / codes, device codes that are not 4-byte aligned.
+ * Peak device memory: 4 m roundup(d, 32) + 4 roundup(d, 32) + 4 m; with host pointers 4md + 4d + 4m + P (4d + m / 8) more, P the rows
+ * of a piece. */
+LMI_API int lmi_sketch(int device, const float *x, int64_t n, int d, const float *mean /* [d], nullable */,
+                       const float *basis /* [m][d] */, int m, const float *thresh /* [m], nullable */,
+                       uint8_t *codes /* [n][m / 8] out */, int on_device);
+/* lmi_sketch with x given as binary16 bit patterns (as lmi_project_f16 takes them); mean, basis and thresh stay binary32.  The codes
+ * are bit for bit those of lmi_sketch on the widened array. */
+LMI_API int lmi_sketch_f16(int device, const uint16_t *x, int64_t n, int d, const float *mean /* [d], nullable */,
+                           const float *basis /* [m][d] */, int m, const float *thresh /* [m], nullable */,
+                           uint8_t *codes /* [n][m / 8] out */, int on_device);
+
 /* The m leading eigenpairs of a symmetric binary64 matrix on the device, deterministic: the step between lmi_gram and lmi_project, so
  * that a PCA basis is the same to the bit wherever it is fitted.  A cyclic Jacobi method on a fixed round-robin schedule; the same
  * input gives the same w, v and *sweeps bit for bit in either form and on any tile; tests/eigh_ref.py restates the call in numpy.

@@ -73,6 +73,7 @@ EIGH_PLAN_FIELDS = ("FORM", "TILE", "LDS_BYTES", "RESIDENT_MAX_D", "GRID", "SWEE
 EIGH_MAX_D = 4096                # LMI_EIGH_MAX_D
 EIGH_FORM_RESIDENT, EIGH_FORM_STREAMED = 1, 2   # LMI_EIGH_FORM_*
 PROJECT_MAX_M = 1024             # LMI_PROJECT_MAX_M: the most basis rows of `project`
+SKETCH_MAX_BITS = 4096           # the widest code of `sketch`: HAMMING_MAX_BYTES * 8, not PROJECT_MAX_M
 
 _lib = None
 
@@ -219,6 +220,9 @@ SIGNATURES = {
     "lmi_debug_eigh_plan": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "lmi_project": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "lmi_project_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
+    # (device, x, n, d, mean, basis, m, thresh, codes, on_device)
+    "lmi_sketch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "lmi_sketch_f16": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
     "lmi_timings": (ctypes.c_int, [_vp, _vp]),
     "lmi_timings_reset": (ctypes.c_int, [_vp]),
     "lmi_set_timing": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -2266,6 +2270,46 @@ def project(x, basis, mean=None, device: int = 0):
     call = lib().lmi_project_f16 if f16 else lib().lmi_project
     _check(call(_sync_device(x), _ptr(x), n, d, _ptr(mt), _ptr(bt), m, _ptr(y), 1))
     return y
+
+
+def sketch(x, basis, mean=None, thresh=None, device: int = 0):
+    """Hamming sketches on the device (`lmi_sketch`): uint8 [n, m // 8], bit j of row i = `project(x, basis, mean)[i, j] > thresh[j]`
+    in binary32 with the value `project` would write, bit for bit, laid out as `np.packbits(..., bitorder="little")` -- the codes
+    `knn_hamming` reads.  The projection is never stored.  A NaN on either side of a comparison gives bit 0.  `x`: float32 or
+    float16 [n,d], a numpy array -- uploaded in pieces, the codes come back piece by piece -- or a contiguous torch tensor on the
+    device; the codes are then a tensor there.  `basis` f32 [m,d], m a multiple of 32 in [32, SKETCH_MAX_BITS]; `mean` f32 [d] or
+    None (x is not centred); `thresh` f32 [m] or None (+0): numpy arrays or tensors, brought to where x is.  A float16 `x` goes to
+    `lmi_sketch_f16` as it is.  Argument errors raise ValueError before the library is loaded."""
+    is_np, f16, n, d = _pca_rows("sketch", x)
+
+    def host(name, a, shape):
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        if a.dtype != np.float32 or a.ndim != len(shape) or any(s is not None and s != t for s, t in zip(shape, a.shape)):
+            want = ",".join("m" if s is None else str(s) for s in shape)
+            raise ValueError(f"sketch: {name} must be float32 [{want}], not {a.dtype} {tuple(a.shape)}")
+        return np.ascontiguousarray(a)
+
+    basis = host("basis", basis, (None, d))
+    m = int(basis.shape[0])
+    if m < 32 or m > SKETCH_MAX_BITS or m % 32:
+        raise ValueError(f"sketch: m {m} is not a multiple of 32 in [32, {SKETCH_MAX_BITS}]")
+    mean = None if mean is None else host("mean", mean, (d,))
+    thresh = None if thresh is None else host("thresh", thresh, (m,))
+    if is_np:
+        x = np.ascontiguousarray(x)
+        codes = np.empty((n, m // 8), dtype=np.uint8)
+        call = lib().lmi_sketch_f16 if f16 else lib().lmi_sketch
+        _check(call(int(device), _ptr(x), n, d, _ptr(mean), _ptr(basis), m, _ptr(thresh), _ptr(codes), 0))
+        return codes
+    import torch
+
+    bt = torch.from_numpy(basis).to(x.device)
+    mt = None if mean is None else torch.from_numpy(mean).to(x.device)
+    tt = None if thresh is None else torch.from_numpy(thresh).to(x.device)
+    codes = torch.empty((n, m // 8), dtype=torch.uint8, device=x.device)
+    call = lib().lmi_sketch_f16 if f16 else lib().lmi_sketch
+    _check(call(_sync_device(x), _ptr(x), n, d, _ptr(mt), _ptr(bt), m, _ptr(tt), _ptr(codes), 1))
+    return codes
 
 
 def train(x, labels, layers, batch_rows, lr: float, state=None, device: int = 0):

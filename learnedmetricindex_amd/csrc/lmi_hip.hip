@@ -50,6 +50,8 @@
 #include "lmi_host_gram.h"      // lmi_gram / lmi_gram_f16, lmi_gram_set_geometry, lmi_debug_gram_plan
 #include "lmi_project.h"        // the kernel of lmi_project
 #include "lmi_host_project.h"   // lmi_project / lmi_project_f16
+#include "lmi_sketch.h"         // the kernels of lmi_sketch: project_kernel's product, compared and packed in the registers
+#include "lmi_host_sketch.h"    // lmi_sketch / lmi_sketch_f16
 #include "lmi_eigh.h"           // the kernels of lmi_eigh
 #include "lmi_host_eigh.h"      // lmi_eigh, lmi_eigh_set_geometry, lmi_debug_eigh_plan
 #include <mutex>

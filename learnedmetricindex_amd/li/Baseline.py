@@ -93,6 +93,21 @@ class Baseline(Logger):
         dists, ids, _ = self.rerank(queries, data, cand, k=k, device=device)
         return dists, ids, time.time() - t0
 
+    def search_sketched(self, queries, data, sketcher, k: int = 10, n_candidates: int = 1024, device: int = 0):
+        """`search_sketch` from the vectors alone: `sketcher` (a `projection.SketchProjection`) encodes the unit rows of `queries`
+        and `data` on the device (`lmi_sketch`), then the Hamming filter and the exact re-rank run as in `search_sketch`."""
+        if not (hasattr(sketcher, "encode") and hasattr(sketcher, "d")):
+            raise ValueError("Baseline.search_sketched: sketcher must be a projection.SketchProjection")
+        if not 1 <= n_candidates <= self.MAX_K or not 1 <= k <= n_candidates:
+            raise ValueError(f"Baseline.search_sketched: n_candidates = {n_candidates} must be in [1, {self.MAX_K}] and k = {k} in [1, n_candidates]")
+        if np.ndim(queries) != 2 or np.ndim(data) != 2 or not np.shape(queries)[1] == np.shape(data)[1] == sketcher.d:
+            raise ValueError(f"Baseline.search_sketched: queries {np.shape(queries)}, data {np.shape(data)} and the sketcher's d = "
+                             f"{sketcher.d} do not fit")
+        t0 = time.time()
+        codes = [sketcher.encode(_unit(a), device=device) for a in (queries, data)]   # (the re-rank normalises the rows itself)
+        dists, ids, _ = self.search_sketch(queries, data, codes[0], codes[1], k=k, n_candidates=n_candidates, device=device)
+        return dists, ids, time.time() - t0
+
     def range_search(self, queries, data, radius, sort: bool = False, max_total: int = 0, device: int = 0):
         """Every object within cosine distance `radius` (a number, or one per query) of each query, by brute force (`lmi_knn_range`
         on unit rows, like `search`): (lims i64[nq + 1], dists f32[total], ids 1-based [total], seconds); query q owns

@@ -78,3 +78,59 @@ class PcaProjection:
     def load(cls, path) -> "PcaProjection":
         with np.load(path) as z:
             return cls(z["mean"], z["basis"], z["explained_variance"])
+
+
+class SketchProjection:
+    """Hyperplanes that turn vectors into bit-packed Hamming codes on the device (`_capi.sketch`): `basis` f32 [bits, d], `mean`
+    f32 [d] or None, `thresh` f32 [bits] or None (+0).  Bit j of a row is `((x - mean) . basis[j]) > thresh[j]`, with the arithmetic
+    of `_capi.project`; the codes are reproducible to the bit for a given (basis, mean, thresh).  `bits` is a multiple of 32 in
+    [32, SKETCH_MAX_BITS], the range of `_capi.knn_hamming`."""
+
+    def __init__(self, basis, mean=None, thresh=None):
+        self.basis = np.ascontiguousarray(basis, dtype=np.float32)
+        self.mean = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
+        self.thresh = None if thresh is None else np.ascontiguousarray(thresh, dtype=np.float32)
+        if self.basis.ndim != 2 or self.basis.shape[1] < 1:
+            raise ValueError(f"SketchProjection: basis {self.basis.shape} is not [bits, d]")
+        if self.bits < 32 or self.bits > _capi.SKETCH_MAX_BITS or self.bits % 32:
+            raise ValueError(f"SketchProjection: bits {self.bits} is not a multiple of 32 in [32, {_capi.SKETCH_MAX_BITS}]")
+        if (self.mean is not None and self.mean.shape != (self.d,)) or (self.thresh is not None and self.thresh.shape != (self.bits,)):
+            raise ValueError(f"SketchProjection: mean {getattr(self.mean, 'shape', None)} and thresh "
+                             f"{getattr(self.thresh, 'shape', None)} do not fit basis {self.basis.shape}: [d], [bits]")
+
+    @property
+    def bits(self) -> int:
+        return int(self.basis.shape[0])
+
+    @property
+    def d(self) -> int:
+        return int(self.basis.shape[1])
+
+    @classmethod
+    def random(cls, d: int, bits: int, seed: int, mean=None) -> "SketchProjection":
+        """Gaussian hyperplanes: `np.random.RandomState(seed).randn(bits, d)` as float32, a function of (d, bits, seed)."""
+        d, bits = int(d), int(bits)
+        if d < 1 or bits < 1:
+            raise ValueError(f"SketchProjection.random: d {d} and bits {bits} must be positive")
+        return cls(np.random.RandomState(seed).randn(bits, d).astype(np.float32), mean=mean)
+
+    @classmethod
+    def from_pca(cls, pca: PcaProjection, bits=None) -> "SketchProjection":
+        """The `bits` leading components of a fitted `PcaProjection` (default: all of them) and its mean."""
+        bits = pca.m if bits is None else int(bits)
+        if bits < 1 or bits > pca.m:
+            raise ValueError(f"SketchProjection.from_pca: bits {bits} outside [1, pca.m = {pca.m}]")
+        return cls(pca.basis[:bits], mean=pca.mean)
+
+    def encode(self, x, device: int = 0):
+        """uint8 [n, bits // 8]: numpy for a numpy `x`, a tensor on x's device for a device tensor (`_capi.sketch`)."""
+        return _capi.sketch(x, self.basis, mean=self.mean, thresh=self.thresh, device=device)
+
+    def save(self, path) -> None:
+        given = {k: v for k, v in (("mean", self.mean), ("thresh", self.thresh)) if v is not None}
+        np.savez(path, basis=self.basis, **given)
+
+    @classmethod
+    def load(cls, path) -> "SketchProjection":
+        with np.load(path) as z:
+            return cls(z["basis"], z["mean"] if "mean" in z else None, z["thresh"] if "thresh" in z else None)

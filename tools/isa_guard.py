@@ -9,7 +9,7 @@ For `pass2_kernel<true>` and `pass2_kernel<false>` of the gfx950 code object ins
   (b) every instruction that names v232..v255 is a `global_load_dwordx4` whose destination is a reserved set, or a
       `v_mfma_f32_16x16x32_f16` whose A operand is a reserved pair of registers (and whose other operands are not);
   (c) no `scratch_` instruction sits inside a tile body (a run of MFMAs less than 400 instructions apart).
-And (d), for the kernels of lmi_gram / lmi_project (PCA_KERNELS): no packed binary32 add, multiply or fma.
+And (d), for the kernels of lmi_gram / lmi_project / lmi_sketch (PCA_KERNELS): no packed binary32 add, multiply or fma.
 
   python3 tools/isa_guard.py [path/to/liblmi_hip.so]     exit code 0 = all checks pass
 """
@@ -133,7 +133,7 @@ def check_kernel(name: str, body, notes: dict) -> list:
 #: (d) the kernels of lmi_gram / lmi_project hold no packed binary32 arithmetic: the library is one translation unit built with
 #: packed-fp32-ops on, and these kernels' bit-for-bit contracts want every subtract and every fused multiply-add on its own
 PCA_KERNELS = ("_ZN3lmi11gram_kernel", "_ZN3lmi15gram_sum_kernel", "_ZN3lmi16gram_mean_kernel", "_ZN3lmi18gram_finish_kernel",
-               "_ZN3lmi14project_kernel", "_ZN3lmi19project_mean_kernel")
+               "_ZN3lmi14project_kernel", "_ZN3lmi19project_mean_kernel", "_ZN3lmi13sketch_kernel", "_ZN3lmi20sketch_thresh_kernel")
 _PACKED_F32 = re.compile(r"\bv_pk_(add|mul|fma)_f32\b")
 
 
